@@ -6,10 +6,22 @@ already resident in HBM as a prepared batched graph (CSR adjacencies + pooling i
 reference builds its graphs on the host before model.forward too, test_amazon_filterd.py:546-551):
 GNN embed (HeteroGGNN x2 -> positional-attention pooling -> L2-normalise, 6 launches) -> fused MFMA
 scoring + top-10 against this rank's corpus shard (2 launches) -> (N > 1) RCCL all-gather of the
-packed per-shard results -> merge.  `value_incl_graph_build` / `stage_ms.graph_build` additionally
+packed per-shard results -> merge.  `value_incl_graph_build` / `stage_ms.graph_build` (--full) additionally
 report the step that STARTS from the flat action table (native graph build, csrc/graphbuild.hip).
 
-The default run times TWO legs over the same corpus, weights and query batch, back to back, and
+A plain run does only what the headline figure needs: it builds the corpus and the query batch, warms up,
+times `--steps` steps of the reference-precision leg (below), writes that leg's outputs of its last timed
+step if `--dump-outputs DIR` is given, and prints the JSON line.  Everything else this file measures or
+checks -- the `fast_path` leg, the graph-build-inclusive step, the stage breakdown, the oracle checks
+(`recall_at_10`, `ids_bit_exact`, ...), the CPU baseline, `configs` and `reference_shapes` -- runs only
+with `--full`.
+
+`--dump-outputs DIR` writes what the caller of the timed step receives from its last timed step, as
+DIR/<name>.npy (floats as float32, ids / status as float64; at most 64 MB in all, larger outputs as a fixed
+seeded sample of query rows listed in DIR/sample_rows.npy).  The inputs are seeded, so two builds run with
+the same arguments can be compared output for output.
+
+The --full run times TWO legs over the same corpus, weights and query batch, back to back, and
 prints both in the one JSON line:
   * the top-level line is the REFERENCE-PRECISION leg: the candidate scan runs on the f32 MFMA over
     the float32 rows (`dtype: "f32"`, faiss IndexFlatIP scores in float32; test_amazon_filterd.py:578),
@@ -20,7 +32,7 @@ prints both in the one JSON line:
 Both legs return the SAME canonical results (float64 re-score of the candidates from the float32 rows
 + per-query proof); `--scan X` / `--dtype bf16` / `--workload c3` time that single configuration only.
 
-The default run (N = 1) also appends
+The --full run (N = 1) also appends
   * `configs`: BASELINE.json's other single-GPU-sized configurations, each timed in this same process
     with its own corpus (freed before the next), hipEvent `kernel_ms`, `roofline`, oracle-checked ids:
     `c4` = 10M random unit rows x 128, nq 1024, k 10, f32-MFMA leg (the `north_star` target: >= 0.70 of
@@ -35,7 +47,7 @@ result carries an on-device proof of exactness and unproven queries are COUNTED 
 the step did exactly the work of the synchronous `ShardedFlatIndex.search` minus one host sync;
 if it is not 0 the bench re-times with the synchronous API and reports that instead.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -55,7 +67,7 @@ Extra JSON objects (see DESIGN.md "measurement"):
                   "HBM"), printed only while the entry's `scan_hip_sha16` still equals the hash of
                   the csrc/scan.hip being run -- null otherwise (a stale figure is worse than none).
   cpu_baseline -- the oracle's restatement of the reference CPU path (torch CPU encoder +
-                  faiss-shaped blocked SGEMM/top-k search) on this host's cores, rank 0, N=1 only.
+                  faiss-shaped blocked SGEMM/top-k search) on this host's cores, rank 0, N=1, --full only.
 """
 from __future__ import annotations
 
@@ -178,12 +190,47 @@ def traffic_lookup(key, scan_sha):
     return None, None, None
 
 
+OUTPUT_NAMES = ("query_embeddings", "scores", "ids", "proof_status")     # search_async: emb, D, I, status (search: no status)
+C3_OUTPUT_NAMES = ("items", "item_status")                                  # knn_item_vote: top-k_items items, status
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(res, c3):
+    """{name: host array} of one step's results: floats as float32, ids / counts / status as float64 (exact)."""
+    out = {}
+    for name, t in zip(OUTPUT_NAMES + (C3_OUTPUT_NAMES if c3 else ()), res):
+        if t is None:
+            continue
+        t = t.detach()
+        out[name] = (t.float() if t.is_floating_point() else t.double()).cpu().numpy()
+    return out
+
+
+def write_outputs(path, outputs):
+    """DIR/<name>.npy for every output; above DUMP_LIMIT_BYTES in all, the same fixed seeded sample of query rows of
+    each (every output has one row per query), listed in DIR/sample_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    nq = next(iter(outputs.values())).shape[0]
+    total = sum(a.nbytes for a in outputs.values())
+    if total > DUMP_LIMIT_BYTES:
+        # + 8 B per row for sample_rows itself, 64 KiB for the .npy headers
+        keep = max(1, int((DUMP_LIMIT_BYTES - (64 << 10)) // (total / nq + 8)))
+        rows = np.sort(np.random.default_rng(20260000).choice(nq, keep, replace=False))
+        outputs = {name: a[rows] for name, a in outputs.items()}
+        outputs["sample_rows"] = rows.astype(np.float64)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(outputs)
+
+
 class Bench:
     def __init__(self, args, world, rank, device, dist):
         self.args, self.world, self.rank, self.device, self.dist = args, world, rank, device, dist
         self.L = _lib.lib()
-        from oracle import search_ref as sr, gnn_ref       # checker + CPU baseline only
-        self.sr, self.gnn_ref = sr, gnn_ref
+        self.sr = self.gnn_ref = None
+        if args.full:
+            from oracle import search_ref as sr, gnn_ref       # checker + CPU baseline only
+            self.sr, self.gnn_ref = sr, gnn_ref
         self.cores = max(1, min(len(os.sched_getaffinity(0)), 16))
         self.scan_sha = hashlib.sha256(open(os.path.join(ROOT, "sessionsimilaritysearch_amd", "csrc", "scan.hip"), "rb").read()).hexdigest()[:16]
         self.force = bool(args.force_collectives)
@@ -192,10 +239,13 @@ class Bench:
         log(self.rank, *a)
 
     # ---------------------------------------------------------------------------------------------
-    def run(self, sp: Spec, scans, steps, warmup, cpu_baseline=False, incl_graph=False):
+    def run(self, sp: Spec, scans, steps, warmup, cpu_baseline=False, incl_graph=False, keep_outputs=False):
         """Build the workload's corpus shard and query batch, time one leg per entry of `scans`, and return
-        {"legs": [...], "cpu": ..., "meta": ...}.  Everything the workload allocated is released on return."""
+        {"legs": [...], "cpu": ..., "meta": ...}.  Everything the workload allocated is released on return.
+        Without --full a leg is only timed (no oracle check, no stage breakdown); `keep_outputs`: the first leg
+        also returns the host copy of its last timed step's results as `outputs`."""
         args, world, rank, device, dist, L, sr = self.args, self.world, self.rank, self.device, self.dist, self.L, self.sr
+        full = bool(args.full)
         d, nq = sp.d, sp.nq
         c3 = sp.workload == "c3"
         cfg = EncoderConfig(d_in=d, h=d, n_layers=2, d_out=d, self_loop_rule="none")
@@ -266,7 +316,7 @@ class Bench:
                 self.say(f"[{sp.name}] oracle top-{k} of {nrq} queries over {hi - lo} rows in {time.time() - t1:.1f}s")
             return oracle_ref["Dr"], oracle_ref["Ir"]
 
-        def run_leg(scan):
+        def run_leg(scan, keep):
             """Time one configuration of the candidate scan over the shared corpus / weights / query batch."""
             index = FlatIndex(d, "ip", device, dtype=sp.dtype, scan=scan if sp.dtype == "f32" else None).adopt(xb, id_offset=lo)
             index.prepare(k)                         # images + norms now, not in the first timed search
@@ -320,6 +370,9 @@ class Bench:
                 api = "search (synchronous exact API; %d queries were unproven in the async run)" % unproven
                 step = step_sync
                 res, elapsed, _ = timed_region(step_sync, steps, warmup)
+            # the host copy of what the caller of the last timed step received (--dump-outputs), taken before anything
+            # below reuses the result buffers
+            outputs = step_outputs(res, c3) if keep else None
             # snapshot: D / I are the sharded index's own result buffers, which the stage timings below overwrite
             emb, D, I = res[0], res[1].clone(), res[2].clone()
             # waves whose bounded wait for the shared threshold ran out in the timed searches (sss.h: sss_scan_boot_expired):
@@ -335,38 +388,42 @@ class Bench:
             flop_per_launch = 2.0 * nq * (hi - lo) * d                 # 2*d FLOP per (query, corpus row) pair
             achieved = flop_per_launch / (kern_ms * 1e-3) / 1e12 if kern_ms > 0 else 0.0
 
-            # the same step STARTING FROM THE ACTION TABLE: native graph build (two kernel sweeps + one 5-integer
-            # read-back that sizes the outputs) -> embed -> search; (f)1 of SURVEY section 8 inside the timed step
-            incl = None
-            if incl_graph:
-                n_g = max(5, min(steps, 50))
-                _, el_g, _ = timed_region(lambda: step(enc.prepare_actions(q_table)), n_g, 2, profile=False)
-                incl = {"value": round(nq * n_g / el_g, 1), "ms_per_step": round(el_g / n_g * 1e3, 4), "steps": n_g}
+            incl = stage = coll = items_exact = None
+            checks = {}
+            if full:
+                # the same step STARTING FROM THE ACTION TABLE: native graph build (two kernel sweeps + one 5-integer
+                # read-back that sizes the outputs) -> embed -> search; (f)1 of SURVEY section 8 inside the timed step
+                if incl_graph:
+                    n_g = max(5, min(steps, 50))
+                    _, el_g, _ = timed_region(lambda: step(enc.prepare_actions(q_table)), n_g, 2, profile=False)
+                    incl = {"value": round(nq * n_g / el_g, 1), "ms_per_step": round(el_g / n_g * 1e3, 4), "steps": n_g}
 
-            # stage breakdown (outside the timed region)
-            embed_ms = timed(embed)
-            search_ms = timed(lambda: sharded.search_async(emb, k))
-            vote_ms = timed(lambda: knn_item_vote(D, I, session_items, k_items)) if c3 else None
-            graph_ms = timed(lambda: enc.prepare_actions(q_table)) if incl_graph else None
-            coll = None
-            if sharded.exchange:        # the two all-gathers + the merge on their own (hipEvent pair on the stream they run on)
-                chunk, pack, pack_all, _, _, _, Do, Io = sharded._buffers(nq, k)
-                mine = emb_all[q_lo:q_hi].clone()
-                coll = {"gather_embeddings": round(timed(lambda: gather_query_embeddings(mine, nq, emb_all, force_collective=self.force), 20), 4),
-                        "gather_results": round(timed(lambda: dist.all_gather_into_tensor(pack_all, pack), 20), 4),
-                        "merge": round(timed(lambda: engine.merge(pack_all, chunk, sharded.world, nq, k, Do, Io), 20), 4),
-                        "backend": dist.get_backend(), "ranks": sharded.world}
+                # stage breakdown (outside the timed region)
+                stage = {"embed_normalize": round(timed(embed), 4),
+                         "score_topk_merge": round(timed(lambda: sharded.search_async(emb, k)), 4)}
+                if c3:
+                    stage["item_vote"] = round(timed(lambda: knn_item_vote(D, I, session_items, k_items)), 4)
+                if incl_graph:
+                    stage["graph_build"] = round(timed(lambda: enc.prepare_actions(q_table)), 4)
+                if sharded.exchange:        # the two all-gathers + the merge on their own (hipEvent pair on the stream they run on)
+                    chunk, pack, pack_all, _, _, _, Do, Io = sharded._buffers(nq, k)
+                    mine = emb_all[q_lo:q_hi].clone()
+                    coll = {"gather_embeddings": round(timed(lambda: gather_query_embeddings(mine, nq, emb_all, force_collective=self.force), 20), 4),
+                            "gather_results": round(timed(lambda: dist.all_gather_into_tensor(pack_all, pack), 20), 4),
+                            "merge": round(timed(lambda: engine.merge(pack_all, chunk, sharded.world, nq, k, Do, Io), 20), 4),
+                            "backend": dist.get_backend(), "ranks": sharded.world}
 
-            # exactness: recall@10 / id equality against the oracle (canonical scores of the stored vectors)
-            Dr, Ir = oracle_topk(emb)
-            I_got, D_got = I[:nrq].cpu().numpy(), D[:nrq].cpu().numpy()
-            items_exact = None
-            if c3:      # aggregated top-10 items of the checked queries against the oracle's get_prediction_by_knn
-                ptr, its = session_items.ptr.cpu().numpy(), session_items.items.cpu().numpy()
-                lists = {int(s_): its[ptr[s_]:ptr[s_ + 1]] for s_ in np.unique(Ir[Ir >= 0])}
-                got_items = res[4][:nrq].cpu().numpy()
-                items_exact = all([int(v) for v in got_items[r] if v >= 0] == sr.knn_item_vote(Dr[r], Ir[r], lists, k_items)
-                                  for r in range(nrq))
+                # exactness: recall@10 / id equality against the oracle (canonical scores of the stored vectors)
+                Dr, Ir = oracle_topk(emb)
+                I_got, D_got = I[:nrq].cpu().numpy(), D[:nrq].cpu().numpy()
+                checks = {"recall_at_10": round(sr.recall_at_k(I_got, Ir, k), 6), "ids_bit_exact": bool(np.array_equal(I_got, Ir)),
+                          "max_score_err": float(np.abs(D_got - Dr).max()), "recall_queries_checked": nrq}
+                if c3:      # aggregated top-10 items of the checked queries against the oracle's get_prediction_by_knn
+                    ptr, its = session_items.ptr.cpu().numpy(), session_items.items.cpu().numpy()
+                    lists = {int(s_): its[ptr[s_]:ptr[s_ + 1]] for s_ in np.unique(Ir[Ir >= 0])}
+                    got_items = res[4][:nrq].cpu().numpy()
+                    items_exact = all([int(v) for v in got_items[r] if v >= 0] == sr.knn_item_vote(Dr[r], Ir[r], lists, k_items)
+                                      for r in range(nrq))
 
             mode = index.last_scan          # the scan the timed searches used
             split, f16 = mode == "split", mode == "f16"
@@ -384,16 +441,10 @@ class Bench:
                 peak = FP32_MFMA_PEAK_TFLOPS if sp.dtype == "f32" else BF16_MFMA_PEAK_TFLOPS
             scan_name = mode if (split or f16) else sp.dtype
             image_bytes = (hi - lo) * d * (2 if f16 else 4 if split else 0)
-            stage = {"embed_normalize": round(embed_ms, 4), "score_topk_merge": round(search_ms, 4)}
-            if c3:
-                stage["item_vote"] = round(vote_ms, 4)
-            if graph_ms is not None:
-                stage["graph_build"] = round(graph_ms, 4)
             return {
                 "value": round(nq * steps / elapsed, 1), "ms_per_step": round(elapsed / steps * 1e3, 4),
                 "dtype": "bf16x3" if split else "f16" if f16 else sp.dtype, "scan": mode, "timed_api": api,
-                "recall_at_10": round(sr.recall_at_k(I_got, Ir, k), 6), "ids_bit_exact": bool(np.array_equal(I_got, Ir)),
-                "max_score_err": float(np.abs(D_got - Dr).max()), "recall_queries_checked": nrq, "unproven_queries": unproven,
+                **checks, "unproven_queries": unproven, "outputs": outputs,
                 "bootstrap_wait_expired": boot_expired, "stage_ms": stage, "incl_graph_build": incl, "collectives_ms": coll,
                 "last_step_rung_queries": rung_q if step is step_sync else None,
                 "last_step_exhaustive_queries": exhaustive_q if step is step_sync else None,
@@ -423,7 +474,7 @@ class Bench:
                              "flop_per_launch": flop_per_launch},
             }
 
-        legs = [run_leg(s) for s in scans]
+        legs = [run_leg(s, keep_outputs and i == 0) for i, s in enumerate(scans)]
 
         # ---- CPU baseline (rank 0, N = 1): the reference path restated on the host cores
         cpu = None
@@ -594,7 +645,14 @@ def main():
                          "`configs` object uses 4 / 5 / 3 for C4 / C5 / C3")
     ap.add_argument("--force-collectives", action="store_true",
                     help="N = 1 only: create a one-rank RCCL group and run the all-gather + merge route of the multi-rank path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the results of the last timed step of the headline leg as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the fast_path leg, graph-build-inclusive step, stage "
+                         "breakdown, oracle checks, CPU baseline, `configs` and `reference_shapes`")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -625,14 +683,20 @@ def main():
               workload=args.workload, sample_size=args.sample_size,
               recall_queries=args.recall_queries if not c3 else min(8, args.recall_queries))
 
-    # Legs: the default run times the reference-precision scan (f32 MFMA) AND the production default
-    # (scan="auto") back to back; an explicit --scan / bf16 index / C3 times that one configuration.
-    two_legs = args.scan == "both" and args.dtype == "f32" and not c3
-    scans = ["f32", "auto"] if two_legs else [("auto" if args.scan == "both" else args.scan) if args.dtype == "f32" else "native"]
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and not c3
-    r = B.run(sp, scans, args.steps, args.warmup, cpu_baseline=want_cpu, incl_graph=not c3)
+    # Legs: the default run times the reference-precision scan (f32 MFMA), with --full followed by the production
+    # default (scan="auto") back to back; an explicit --scan / bf16 index / C3 times that one configuration.
+    both = args.scan == "both" and args.dtype == "f32" and not c3
+    two_legs = both and args.full
+    scans = (["f32", "auto"] if two_legs else ["f32"]) if both else \
+        [("auto" if args.scan == "both" else args.scan) if args.dtype == "f32" else "native"]
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not c3
+    r = B.run(sp, scans, args.steps, args.warmup, cpu_baseline=want_cpu, incl_graph=args.full and not c3,
+              keep_outputs=bool(args.dump_outputs) and rank == 0)
     main_leg, fast_leg = r["legs"][0], (r["legs"][1] if two_legs else None)
     meta, cpu = r["meta"], r["cpu"]
+    if main_leg["outputs"] is not None:
+        names = write_outputs(args.dump_outputs, main_leg.pop("outputs"))
+        log(rank, f"outputs of the last timed step written to {args.dump_outputs}: {', '.join(names)}")
     torch.cuda.empty_cache()
 
     extras = rank == 0 and world == 1 and two_legs
@@ -657,9 +721,9 @@ def main():
                                        "all-gather of results + merge") if world > 1 else
                                       ("single GPU, one-rank RCCL group: all-gather of embeddings, all-gather of results + merge executed"
                                        if args.force_collectives else "single GPU")},
-            "recall_at_10": m["recall_at_10"], "ids_bit_exact": m["ids_bit_exact"], "max_score_err": m["max_score_err"],
-            "recall_queries_checked": m["recall_queries_checked"], "unproven_queries": m["unproven_queries"],
-            "bootstrap_wait_expired": m["bootstrap_wait_expired"], "stage_ms": m["stage_ms"],
+            **{kk: m[kk] for kk in ("recall_at_10", "ids_bit_exact", "max_score_err", "recall_queries_checked") if kk in m},
+            "unproven_queries": m["unproven_queries"], "bootstrap_wait_expired": m["bootstrap_wait_expired"],
+            **({"stage_ms": m["stage_ms"]} if m["stage_ms"] else {}),
             **({"value_incl_graph_build": m["incl_graph_build"]["value"],
                 "ms_per_step_incl_graph_build": m["incl_graph_build"]["ms_per_step"],
                 "incl_graph_build_note": f"the same step started from the flat action table (native graph build on the device + its two small "
@@ -667,12 +731,12 @@ def main():
                if m["incl_graph_build"] else {}),
             **({"collectives_ms": m["collectives_ms"]} if m["collectives_ms"] else {}),
             **({"c3": {"sessions": meta["n_sessions"], "index_rows": meta["n_total"], "sample_size": meta["k"], "items_returned": meta["k_items"],
-                       "items_bit_exact": m["items_bit_exact"], "queries_checked": meta["nrq"],
+                       **({"items_bit_exact": m["items_bit_exact"], "queries_checked": meta["nrq"]} if args.full else {}),
                        "last_step_rung_queries": m["last_step_rung_queries"],
                        "last_step_exhaustive_queries": m["last_step_exhaustive_queries"]}} if c3 else {}),
             "arithmetic": m["arithmetic"],
             "roofline": m["roofline"],
-            "cpu_baseline": cpu,
+            **({"cpu_baseline": cpu} if args.full else {}),
         }
         if fast_leg is not None:
             f = B.leg_summary(fast_leg)
