@@ -69,7 +69,7 @@ __global__ __launch_bounds__(64) void k_exact_scores(const void* __restrict__ Qv
 // no LDS, no barrier.  Same canonical score: sequential float64 sum.
 // lb (optional, one float per selected query): a LOWER bound of the query's k-th best score (the fused
 // path's k-th re-scored candidate).  A cheap float32 pass first bounds every row's score from above
-// (float32 fma chain: error <= d 2^-24 |q||c|); rows that provably stay below lb -- almost all of them --
+// (float32 fma chain: error <= d 2^-24 |q||c| + d 2^-150); rows that provably stay below lb -- almost all of them --
 // skip the float64 chain and get -FLT_MAX, which the selection ignores.
 template <int D, int DT>
 __device__ __forceinline__ float q_elem(const void* qrow, int kx) {        // element kx of a (wave-uniform) query row
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void k_exact_scores_rows(const void* __restric
                                                            const void* __restrict__ Cv, long n, float* __restrict__ scores,
                                                            const float* __restrict__ lb) {
     constexpr int QB = 1024;                           // queries whose norms are kept in LDS at a time
-    __shared__ float qn[QB];
+    __shared__ double qn[QB];
     constexpr int EB = DT == DT_F32 ? 4 : 2;
     const char* C = reinterpret_cast<const char*>(Cv);
     const char* Q = reinterpret_cast<const char*>(Qv);
@@ -108,11 +108,13 @@ __global__ __launch_bounds__(256) void k_exact_scores_rows(const void* __restric
             }
         }
     }
-    float rnorm = 0.f;
+    // norms for the pre-test's margin in float64 (squares of float32 values are exact there): a float32 sum of squares
+    // is 0 for rows below ~1e-19 and inf above ~1.8e19, which would shrink the margin to nothing / widen it to everything
+    double rnorm = 0.0;
     if (lb) {
 #pragma unroll
-        for (int kx = 0; kx < D; ++kx) rnorm = fmaf(r[kx], r[kx], rnorm);
-        rnorm = sqrtf(rnorm) * 1.0001f;
+        for (int kx = 0; kx < D; ++kx) rnorm += (double)r[kx] * (double)r[kx];
+        rnorm = sqrt(rnorm) * 1.0001;
     }
     for (int f0 = 0; f0 < nsel; f0 += QB) {
         const int nf = nsel - f0 < QB ? nsel - f0 : QB;
@@ -120,9 +122,9 @@ __global__ __launch_bounds__(256) void k_exact_scores_rows(const void* __restric
             __syncthreads();
             for (int t = threadIdx.x; t < nf; t += 256) {
                 const char* qrow = Q + (size_t)qsel[f0 + t] * D * EB;
-                float s2 = 0.f;
-                for (int kx = 0; kx < D; ++kx) { const float v = q_elem<D, DT>(qrow, kx); s2 = fmaf(v, v, s2); }
-                qn[t] = sqrtf(s2) * 1.0001f;
+                double s2 = 0.0;
+                for (int kx = 0; kx < D; ++kx) { const double v = q_elem<D, DT>(qrow, kx); s2 += v * v; }
+                qn[t] = sqrt(s2) * 1.0001;
             }
             __syncthreads();
         }
@@ -133,8 +135,11 @@ __global__ __launch_bounds__(256) void k_exact_scores_rows(const void* __restric
                 float s0 = 0.f;
 #pragma unroll
                 for (int kx = 0; kx < D; ++kx) s0 = fmaf(q_elem<D, DT>(qrow, kx), r[kx], s0);
+                // margin in float64: the chain's relative error, its gradual underflow (D roundings of at most 2^-150 each
+                // below FLT_MIN) and one float32 ulp of l0 (2^-149 absolute in the subnormal range)
                 const float l0 = lb[f0 + f];
-                need = !(s0 + (float)D * 6.3e-8f * rnorm * qn[f] + 2.4e-7f * fabsf(l0) < l0);   // (NaN anywhere: keep the row)
+                need = !((double)s0 + (double)D * 6.3e-8 * rnorm * qn[f] + 2.4e-7 * fabs((double)l0) + (D + 8) * 1.4012984643248171e-45 <
+                         (double)l0);                      // (NaN anywhere: keep the row)
             }
             double acc = 0.0;
             if (need) {
@@ -530,10 +535,17 @@ int ip_topk_exhaustive(const void* q, const int* qsel, long nsel, const void* c,
         static bool head_attr[MAX_DEVICES] = {};
         const int hdev = current_device();
         if (!head_attr[hdev]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_threshold), hipFuncAttributeMaxDynamicSharedMemorySize, CP_HEAD * 4);
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_threshold), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    CP_HEAD * 4) != hipSuccess) {
+                (void)hipGetLastError();
+                set_error("k_head_threshold: opting in to %d bytes of LDS failed", CP_HEAD * 4);
+                return SSS_EHIP;
+            }
             head_attr[hdev] = true;
         }
         hipLaunchKernelGGL(k_head_threshold, dim3((unsigned)nsel), dim3(RS_THREADS), (size_t)CP_HEAD * 4, st, scores, n, k, metric, T0);
+        rc = check_launch("k_head_threshold");
+        if (rc) return rc;
         hipLaunchKernelGGL(k_count_ge, dim3((unsigned)nslabs, (unsigned)nsel), dim3(256), 0, st, scores, n, metric, T0, nslabs, cnt_gt, cnt_eq);
         hipLaunchKernelGGL(k_scan_slabs, dim3((unsigned)nsel), dim3(64), 0, st, cnt_gt, cnt_eq, nslabs, n, k, total);
         hipLaunchKernelGGL(k_compact_ge, dim3((unsigned)nslabs, (unsigned)nsel), dim3(RS_THREADS), 0, st, scores, n, k, metric, T0, nslabs,

@@ -42,55 +42,73 @@ __global__ __launch_bounds__(256) void k_normalize_rows(float* __restrict__ x, l
     }
 }
 
+// Largest row 2-norm, a true UPPER bound for any finite rows (it feeds every scan's error bound): the squares of
+// float32 values are exact in float64 and their sum stays finite and normal far beyond where a float32 sum of squares
+// under- or overflows (rows below ~1e-19 or above ~1.8e19); d <= 2^20 additions cost at most d 2^-53 relative, covered
+// by the 1e-12 headroom, and the float32 result is rounded UP (inf when the norm itself exceeds FLT_MAX).
+__device__ __forceinline__ float norm_up(double ss) {
+    const double r = sqrt(ss) * (1.0 + 1e-12);
+    float f = (float)r;
+    if ((double)f < r) f = nextafterf(f, INFINITY);
+    return f;
+}
+
+template <int LPR>
+__device__ __forceinline__ double group_sum_f64(double v) {
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
 template <int LPR>
 __global__ __launch_bounds__(256) void k_row_norm_max(const float* __restrict__ x, long n, int d,
                                                       float* __restrict__ out) {
     const int sub = threadIdx.x % LPR;
     const long rows_per_block = 256 / LPR;
     const int nv = d / 4;
-    float m = 0.f;
+    double m = 0.0;
     for (long row = (long)blockIdx.x * rows_per_block + threadIdx.x / LPR; row < n;
          row += (long)gridDim.x * rows_per_block) {
         const float4* p = reinterpret_cast<const float4*>(x + row * (long)d);
-        float ss = 0.f;
+        double ss = 0.0;
         for (int i = sub; i < nv; i += LPR) {
             const float4 v = p[i];
-            ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+            ss += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
         }
-        ss = group_sum<LPR>(ss);
-        m = fmaxf(m, ss);
+        ss = group_sum_f64<LPR>(ss);
+        m = fmax(m, ss);
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
     // non-negative floats order like their bit patterns
     if ((threadIdx.x & 63) == 0)
-        atomicMax(reinterpret_cast<unsigned int*>(out), __builtin_bit_cast(unsigned int, sqrtf(m) * 1.0000002f));
+        atomicMax(reinterpret_cast<unsigned int*>(out), __builtin_bit_cast(unsigned int, norm_up(m)));
 }
 
-// bf16 rows: max over rows of the 2-norm of the (exactly converted) float32 values
+// bf16 rows: max over rows of the 2-norm of the (exactly converted) float32 values, accumulated as above
 __global__ __launch_bounds__(256) void k_row_norm_max_bf16(const unsigned short* __restrict__ x, long n, int d,
                                                            float* __restrict__ out) {
     const int lane = threadIdx.x & 63;
     const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-    float m = 0.f;
+    double m = 0.0;
     for (long row = wave; row < n; row += nwaves) {
         const u32x4* p = reinterpret_cast<const u32x4*>(x + row * (long)d);
-        float ss = 0.f;
+        double ss = 0.0;
         for (int i = lane; i < d / 8; i += 64) {
             const u32x4 v = p[i];
 #define SSS_SQ2(w)                                                                   \
-    { const float lo = __builtin_bit_cast(float, v.w << 16), hi = __builtin_bit_cast(float, v.w & 0xFFFF0000u); \
+    { const double lo = __builtin_bit_cast(float, v.w << 16), hi = __builtin_bit_cast(float, v.w & 0xFFFF0000u); \
       ss += lo * lo + hi * hi; }
             SSS_SQ2(x) SSS_SQ2(y) SSS_SQ2(z) SSS_SQ2(w)
 #undef SSS_SQ2
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-        m = fmaxf(m, ss);
+        m = fmax(m, ss);
     }
     if (lane == 0)
-        atomicMax(reinterpret_cast<unsigned int*>(out), __builtin_bit_cast(unsigned int, sqrtf(m) * 1.0000002f));
+        atomicMax(reinterpret_cast<unsigned int*>(out), __builtin_bit_cast(unsigned int, norm_up(m)));
 }
 
 // float32 -> bfloat16, round to nearest even (plain cast: v_cvt_pk_bf16_f32, NaN stays NaN);
@@ -166,12 +184,12 @@ __global__ __launch_bounds__(256) void k_f16_resid_max(const float* __restrict__
     for (long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += (long)gridDim.x * 4) {
         double s = 0.0;
         for (int kk = lane; kk < d; kk += 64) {
-            const double r = (double)ldexpf((float)y[row * d + kk], -shift) - (double)x[row * d + kk];
+            const double r = ldexp((double)(float)y[row * d + kk], -shift) - (double)x[row * d + kk];   // (float ldexpf would round a subnormal result)
             s += r * r;
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        const float f = (float)(sqrt(s) * (1.0 + 1e-6));       // rounded up
+        const float f = norm_up(s);                             // rounded up
         if (f == f) m = fmaxf(m, f);
     }
     if (lane == 0 && m > 0.f) atomicMax(reinterpret_cast<unsigned*>(out), __float_as_uint(m));

@@ -753,7 +753,18 @@ static ScanPlan make_plan_for(long nq, long n, int d, int k, int dtype, bool wan
     // (tau_skip = 16 - K2 words allowed below it; scan_dev.h: tau_select16)
     p.Ju = p.J;
     p.tau_skip = (p.cert == 1 && p.J == 16) ? 16 - p.K2 : 0;
-    if (p.J * p.cert < p.K2 || 2 * active_splits < p.Ju) { p.J = 0; p.Ju = 0; p.tau_skip = 0; }      // tiny corpus: no threshold
+    // cert == 1: a query's lane pairs publish per SPLIT, into class (split + split / 16) & 15 -- with fewer than 16 active
+    // splits only classes 0 .. active_splits - 1 ever publish.  The scan's rank pick (scan_dev.h tau_select16) takes,
+    // per half of the 16 slots, its (skip / 2 + 1)-th smallest word (half 0: + 1 more for an odd skip) and the min of
+    // the two: each half may hold no more unpublished (zero) words than that, or the threshold stays 0 for the whole
+    // scan and every wave sits out its bootstrap wait (8 splits: > 4096 queries per call, or a corpus of a few thousand
+    // rows).  cert > 1 lists publish per lane ((2 split + h) % Ju).  Too few classes, or a tiny corpus: no threshold.
+    bool classes_ok = 2 * active_splits >= p.Ju;
+    if (p.cert == 1 && p.J == 16 && active_splits < 16) {
+        const int zero0 = active_splits < 8 ? 8 - active_splits : 0, zero1 = active_splits < 8 ? 8 : 16 - active_splits;
+        classes_ok = zero0 <= (p.tau_skip >> 1) + (p.tau_skip & 1) && zero1 <= (p.tau_skip >> 1);
+    }
+    if (p.J * p.cert < p.K2 || !classes_ok) { p.J = 0; p.Ju = 0; p.tau_skip = 0; }
     p.boot = (p.J > 0 && p.cert == 1) ? 1 : 0;
     p.append = (want_append && p.boot) ? 1 : 0;
     if (want_append && !p.append) return p;               // (the caller falls back to the list plan)

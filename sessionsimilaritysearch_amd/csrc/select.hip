@@ -173,14 +173,28 @@ __device__ __forceinline__ float elem_to_f32(const void* row, int kk, int dtype)
 //            most 2^-25 sqrt(d) |q||c| even if the matrix unit flushed them; products of two f16 are
 //            exact in f32 and accumulate like the bf16 case:
 //                         Rc |q| + (|c| + Rc) Rq + (2^-25 sqrt(d) + d * 2^-23) |q| |c|
-// (each with 2 % headroom; |c| <= the corpus' largest row norm).
+// (each with 2 % headroom; |c| <= the corpus' largest row norm, an upper bound at any magnitude: rowops.hip).
+// The relative terms assume normal float32 arithmetic.  Where the f32 values of a chain fall below FLT_MIN = 2^-126
+// they lose up to half a subnormal spacing (2^-150) per rounding, or -- if a unit flushes subnormals -- the whole
+// value (< 2^-126).  Absolute floor, per chain of d products and d sums (the split scan's passes are three chains):
+//   DT_F32   the f32 MFMA keeps subnormals (kernel mode; ISA: C / D never flush): d * 2^-149
+//   DT_BF16, DT_SPLIT  (no assumption about the bf16 unit's subnormals): 2 d * 2^-126 per chain, and an input
+//            element below 2^-126 (flushed, or -- split -- a lo / hi part rounded in the bf16 subnormal range) misses
+//            at most 2^-126 |y_k| per element of the other side: sqrt(d) 2^-126 (|q| + |c|) per pass
+//   DT_F16   sums and products of the scaled f16 image live in [2^-48, 2^26] x d: no floor needed
+// A proof among subnormal-range scores thus holds whatever the unit did with them; where the floor is as wide as the
+// gaps between the scores the query stays unproven and is resolved exactly by the threshold rung or the exhaustive
+// kernels.
 __device__ __forceinline__ double err_bound(int d, int scan_dtype, double qnorm, double cmax, double c_resid, double q_resid) {
+    constexpr double U126 = 1.1754943508222875e-38, U149 = 1.4012984643248171e-45;   // 2^-126, 2^-149
+    const double rd = sqrt((double)d);
     double b;
-    if (scan_dtype == DT_F32) b = (double)d * 5.9604644775390625e-08 * qnorm * cmax;
-    else if (scan_dtype == DT_BF16) b = (double)d * 1.1920928955078125e-07 * qnorm * cmax;
-    else if (scan_dtype == DT_SPLIT) b = (3.03 * 1.52587890625e-05 + 3.0 * (double)d * 1.1920928955078125e-07 * 1.016) * qnorm * cmax;
+    if (scan_dtype == DT_F32) b = (double)d * 5.9604644775390625e-08 * qnorm * cmax + (double)d * U149;
+    else if (scan_dtype == DT_BF16) b = (double)d * 1.1920928955078125e-07 * qnorm * cmax + (2.0 * d + rd * (qnorm + cmax)) * U126;
+    else if (scan_dtype == DT_SPLIT) b = (3.03 * 1.52587890625e-05 + 3.0 * (double)d * 1.1920928955078125e-07 * 1.016) * qnorm * cmax +
+                                         3.0 * (2.0 * d + rd * (qnorm + cmax)) * U126;
     else b = c_resid * qnorm + (cmax + c_resid) * q_resid +
-             (2.98023223876953125e-08 * sqrt((double)d) + (double)d * 1.1920928955078125e-07) * qnorm * cmax;
+             (2.98023223876953125e-08 * rd + (double)d * 1.1920928955078125e-07) * qnorm * cmax;
     return b * 1.02;
 }
 
@@ -260,8 +274,8 @@ __device__ __forceinline__ int decide_status(unsigned long long edge, unsigned l
 
 // squared rounding residual of query element v under the DT_F16 scan's scaling + rounding (scan.hip)
 __device__ __forceinline__ double f16_resid2(float v, int sh) {
-    const float back = ldexpf((float)(_Float16)ldexpf(v, sh), -sh);
-    const double r = (double)back - (double)v;
+    const double back = ldexp((double)(float)(_Float16)ldexpf(v, sh), -sh);     // (in float the scale-back of a tiny row would round)
+    const double r = back - (double)v;
     return r * r;
 }
 
