@@ -169,6 +169,37 @@ int sss_ip_topk_exhaustive_lb(const void* q, const int32_t* qsel, int64_t nsel, 
                               const float* lower_bound, float* D_out, int64_t* I_out, void* workspace,
                               size_t workspace_bytes, void* stream);
 
+/* ---- RANGE SEARCH (faiss `range_search(x, radius) -> (lims, D, I)`): every row whose canonical score passes a
+ * per-query radius -- score > radius[i] (inner product) or squared distance < radius[i] (L2), strict, as faiss
+ * IndexFlatIP / IndexFlatL2 -- in ascending id order.  Scores are the canonical ones of sss_ip_topk (float64
+ * accumulation, one rounding to float32).  The output size is only known after counting, so each route has two
+ * calls: COUNT (per-query counts), then -- once the caller has built lims (int64 [nq + 1], lims[0] = 0, the prefix
+ * sums of the counts) and allocated D float32 / I int64 [lims[nq]] -- FILL from the same workspace, untouched in
+ * between.  radius: device float32, one per query row.  Writes stay inside [lims[i], lims[i + 1]) and below lims[nq].
+ *
+ * Fused route: the threshold rung's matrix-core scan (same shapes / scan codes / images as sss_ip_topk_threshold)
+ * with each query's threshold derived from its radius, then a canonical re-score of every row the scan kept.
+ * A query whose scan kept more than 8192 rows gets status 1 and count 0: run it through the exhaustive route.
+ * workspace (256-byte aligned): sss_range_search_workspace_bytes(nq, n, d, scan), ~64 KB per query. */
+size_t sss_range_search_workspace_bytes(int64_t nq, int64_t n, int d, int scan);
+int sss_range_search_count(const void* q, int64_t nq, const void* corpus, int dtype, const void* scan_image, int scan,
+                           int corpus_shift, float corpus_resid_norm, int64_t n, int d, const float* radius,
+                           float corpus_max_norm, int64_t* counts, int32_t* status, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int sss_range_search_fill(int64_t nq, const int64_t* lims, int64_t id_offset, float* D_out, int64_t* I_out,
+                          const void* workspace, size_t workspace_bytes, void* stream);
+/* Exhaustive route: any n, any d % 4 == 0 (dtype 0) / d % 8 == 0 (dtype 1), metric 0 = inner product, 1 = squared
+ * L2.  qsel [nsel] int32 (nsel <= 65535): the query rows to process; counts [nsel] and lims [nsel + 1] follow the
+ * order of qsel.  The scores of all nsel queries stay in the workspace between count and fill:
+ * sss_range_search_exhaustive_workspace_bytes(nsel, n), ~4 n bytes per query. */
+size_t sss_range_search_exhaustive_workspace_bytes(int64_t nsel, int64_t n);
+int sss_range_search_exhaustive_count(const void* q, const int32_t* qsel, int64_t nsel, const void* corpus, int64_t n,
+                                      int d, int dtype, int metric, const float* radius, int64_t* counts,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+int sss_range_search_exhaustive_fill(const int32_t* qsel, int64_t nsel, int64_t n, int metric, const float* radius,
+                                     const int64_t* lims, int64_t id_offset, float* D_out, int64_t* I_out,
+                                     const void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- multi-GPU: merge per-shard results after the all-gather (no reference equivalent; the
  * reference is single process).  Shard s's [nq, k] block starts at D_in + s * d_shard_stride
  * (floats) / I_in + s * i_shard_stride (int64s); output [nq, k] by (score desc, id asc). */

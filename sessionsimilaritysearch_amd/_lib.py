@@ -52,6 +52,15 @@ _SIGNATURES = {
                                        c_void_p]),
     "sss_ip_topk_exhaustive_lb": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int,
                                           c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "sss_range_search_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
+    "sss_range_search_count": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int64, c_int, c_void_p,
+                                       c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "sss_range_search_fill": (c_int, [c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "sss_range_search_exhaustive_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "sss_range_search_exhaustive_count": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
+                                                  c_void_p, c_void_p, c_size_t, c_void_p]),
+    "sss_range_search_exhaustive_fill": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                                 c_void_p, c_size_t, c_void_p]),
     "sss_topk_merge": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_int, c_void_p, c_void_p,
                                c_void_p]),
     "sss_scan_boot_expired": (c_int, [c_int]),

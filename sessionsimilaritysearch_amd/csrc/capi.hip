@@ -46,6 +46,13 @@ size_t ip_topk_threshold_workspace_bytes(long, long, int, int);
 int ip_topk_threshold(const void*, const int*, long, const void*, int, const void*, int, int, float, long, int, int, long, float,
                       float*, long*, int*, void*, size_t, hipStream_t);
 int abs_max(const float*, long, float*, hipStream_t);
+size_t range_search_workspace_bytes(long, long, int, int);
+int range_search_count(const void*, long, const void*, int, const void*, int, int, float, long, int, const float*, float, long*, int*, void*,
+                       size_t, hipStream_t);
+int range_search_fill(long, const long*, long, float*, long*, const void*, size_t, hipStream_t);
+size_t range_exhaustive_workspace_bytes(long, long);
+int range_exhaustive_count(const void*, const int*, long, const void*, long, int, int, int, const float*, long*, void*, size_t, hipStream_t);
+int range_exhaustive_fill(const int*, long, long, int, const float*, const long*, long, float*, long*, const void*, size_t, hipStream_t);
 int scale_f16(const float*, long, int, unsigned short*, hipStream_t);
 int topk_merge(const float*, long, const long*, long, int, long, int, float*, long*, hipStream_t);
 int scan_boot_expired(int);
@@ -100,7 +107,7 @@ int graph_fill(const long*, const unsigned char*, const long*, const long*, long
 
 extern "C" {
 
-int sss_version(void) { return 240; }
+int sss_version(void) { return 250; }
 const char* sss_last_error(void) { return sss::g_err; }
 
 int sss_normalize_rows(float* x, int64_t n, int d, int64_t ld, float eps, int rule, void* stream) {
@@ -189,6 +196,33 @@ int sss_ip_topk_exhaustive_lb(const void* q, const int32_t* qsel, int64_t nsel, 
                               int64_t* I_out, void* workspace, size_t workspace_bytes, void* stream) {
     return sss::ip_topk_exhaustive(q, qsel, nsel, corpus, n, d, k, dtype, id_offset, 0, lower_bound, D_out,
                                    reinterpret_cast<long*>(I_out), workspace, workspace_bytes, ST(stream));
+}
+size_t sss_range_search_workspace_bytes(int64_t nq, int64_t n, int d, int scan) {
+    return sss::range_search_workspace_bytes(nq, n, d, scan);
+}
+int sss_range_search_count(const void* q, int64_t nq, const void* corpus, int dtype, const void* scan_image, int scan, int corpus_shift,
+                           float corpus_resid_norm, int64_t n, int d, const float* radius, float corpus_max_norm, int64_t* counts,
+                           int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    return sss::range_search_count(q, nq, corpus, dtype, scan_image, scan, corpus_shift, corpus_resid_norm, n, d, radius, corpus_max_norm,
+                                   reinterpret_cast<long*>(counts), status, workspace, workspace_bytes, ST(stream));
+}
+int sss_range_search_fill(int64_t nq, const int64_t* lims, int64_t id_offset, float* D_out, int64_t* I_out, const void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    return sss::range_search_fill(nq, reinterpret_cast<const long*>(lims), id_offset, D_out, reinterpret_cast<long*>(I_out), workspace,
+                                  workspace_bytes, ST(stream));
+}
+size_t sss_range_search_exhaustive_workspace_bytes(int64_t nsel, int64_t n) { return sss::range_exhaustive_workspace_bytes(nsel, n); }
+int sss_range_search_exhaustive_count(const void* q, const int32_t* qsel, int64_t nsel, const void* corpus, int64_t n, int d, int dtype,
+                                      int metric, const float* radius, int64_t* counts, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    return sss::range_exhaustive_count(q, qsel, nsel, corpus, n, d, dtype, metric, radius, reinterpret_cast<long*>(counts), workspace,
+                                       workspace_bytes, ST(stream));
+}
+int sss_range_search_exhaustive_fill(const int32_t* qsel, int64_t nsel, int64_t n, int metric, const float* radius, const int64_t* lims,
+                                     int64_t id_offset, float* D_out, int64_t* I_out, const void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    return sss::range_exhaustive_fill(qsel, nsel, n, metric, radius, reinterpret_cast<const long*>(lims), id_offset, D_out,
+                                      reinterpret_cast<long*>(I_out), workspace, workspace_bytes, ST(stream));
 }
 int sss_topk_merge(const float* D_in, int64_t d_shard_stride, const int64_t* I_in, int64_t i_shard_stride,
                    int shards, int64_t nq, int k, float* D_out, int64_t* I_out, void* stream) {

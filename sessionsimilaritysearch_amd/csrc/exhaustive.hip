@@ -81,7 +81,7 @@ __device__ __forceinline__ float q_elem(const void* qrow, int kx) {        // el
 template <int D, int DT>
 __global__ __launch_bounds__(256) void k_exact_scores_rows(const void* __restrict__ Qv, const int* __restrict__ qsel, int nsel,
                                                            const void* __restrict__ Cv, long n, float* __restrict__ scores,
-                                                           const float* __restrict__ lb) {
+                                                           const float* __restrict__ lb, int lb_by_row) {
     constexpr int QB = 1024;                           // queries whose norms are kept in LDS at a time
     __shared__ double qn[QB];
     constexpr int EB = DT == DT_F32 ? 4 : 2;
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256) void k_exact_scores_rows(const void* __restric
                 for (int kx = 0; kx < D; ++kx) s0 = fmaf(q_elem<D, DT>(qrow, kx), r[kx], s0);
                 // margin in float64: the chain's relative error, its gradual underflow (D roundings of at most 2^-150 each
                 // below FLT_MIN) and one float32 ulp of l0 (2^-149 absolute in the subnormal range)
-                const float l0 = lb[f0 + f];
+                const float l0 = lb[lb_by_row ? qsel[f0 + f] : f0 + f];    // (per selected query, or per query row)
                 need = !((double)s0 + (double)D * 6.3e-8 * rnorm * qn[f] + 2.4e-7 * fabs((double)l0) + (D + 8) * 1.4012984643248171e-45 <
                          (double)l0);                      // (NaN anywhere: keep the row)
             }
@@ -488,6 +488,27 @@ static size_t compact_bytes(long nsel, long n) {
     return (size_t)nsel * ((size_t)CP_CAP * 8 + (size_t)nslabs * 8 + 8) + 1024;
 }
 
+// scores [nsel][n] of the selected queries against every row (k_exact_scores_rows where the shape has it, else
+// k_exact_scores); lb / lb_by_row: the optional pre-test bound of k_exact_scores_rows (inner product only).
+static int launch_exact_scores(const void* q, const int* qsel, long nsel, const void* c, long n, int d, int dtype, int metric,
+                               float* scores, const float* lb, int lb_by_row, hipStream_t st) {
+    long gx = (n + EX_ROWS - 1) / EX_ROWS;
+    if (gx > 8192) gx = 8192;
+    const unsigned rb = (unsigned)((n + 255) / 256);
+#define SSS_ROWS(D_, DT_) hipLaunchKernelGGL((k_exact_scores_rows<D_, DT_>), dim3(rb), dim3(256), 0, st, q, qsel, (int)nsel, c, n, scores, lb, lb_by_row)
+    if (metric == 0 && dtype == DT_F32 && d == 64) SSS_ROWS(64, DT_F32);
+    else if (metric == 0 && dtype == DT_F32 && d == 128) SSS_ROWS(128, DT_F32);
+    else if (metric == 0 && dtype == DT_F32 && d == 256) SSS_ROWS(256, DT_F32);
+    else if (metric == 0 && dtype == DT_BF16 && d == 128) SSS_ROWS(128, DT_BF16);
+    else if (metric == 0 && dtype == DT_BF16 && d == 256) SSS_ROWS(256, DT_BF16);
+    else if (dtype == DT_F32)
+        hipLaunchKernelGGL(k_exact_scores<DT_F32>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
+    else
+        hipLaunchKernelGGL(k_exact_scores<DT_BF16>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
+#undef SSS_ROWS
+    return check_launch("k_exact_scores");
+}
+
 size_t ip_topk_exhaustive_workspace_bytes(long nsel, long n) {
     return (((size_t)nsel * n * 4 + 255) & ~(size_t)255) + 256 + compact_bytes(nsel, n);
 }
@@ -506,21 +527,7 @@ int ip_topk_exhaustive(const void* q, const int* qsel, long nsel, const void* c,
         return SSS_EWORKSPACE;
     }
     float* scores = reinterpret_cast<float*>(ws);
-    long gx = (n + EX_ROWS - 1) / EX_ROWS;
-    if (gx > 8192) gx = 8192;
-    const unsigned rb = (unsigned)((n + 255) / 256);
-#define SSS_ROWS(D_, DT_) hipLaunchKernelGGL((k_exact_scores_rows<D_, DT_>), dim3(rb), dim3(256), 0, st, q, qsel, (int)nsel, c, n, scores, lower_bound)
-    if (metric == 0 && dtype == DT_F32 && d == 64) SSS_ROWS(64, DT_F32);
-    else if (metric == 0 && dtype == DT_F32 && d == 128) SSS_ROWS(128, DT_F32);
-    else if (metric == 0 && dtype == DT_F32 && d == 256) SSS_ROWS(256, DT_F32);
-    else if (metric == 0 && dtype == DT_BF16 && d == 128) SSS_ROWS(128, DT_BF16);
-    else if (metric == 0 && dtype == DT_BF16 && d == 256) SSS_ROWS(256, DT_BF16);
-    else if (dtype == DT_F32)
-        hipLaunchKernelGGL(k_exact_scores<DT_F32>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
-    else
-        hipLaunchKernelGGL(k_exact_scores<DT_BF16>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
-#undef SSS_ROWS
-    int rc = check_launch("k_exact_scores");
+    int rc = launch_exact_scores(q, qsel, nsel, c, n, d, dtype, metric, scores, lower_bound, 0, st);
     if (rc) return rc;
     const float* cs = nullptr; const int* cids = nullptr; const unsigned* ctotal = nullptr;
     if (n >= CP_MIN_N) {
@@ -557,6 +564,153 @@ int ip_topk_exhaustive(const void* q, const int* qsel, long nsel, const void* c,
     hipLaunchKernelGGL(k_topk_radix, dim3((unsigned)nsel), dim3(RS_THREADS), 0, st, scores, qsel, n, k, id_offset, metric, D_out, I_out,
                        cs, cids, ctotal, CP_CAP);
     return check_launch("k_topk_radix");
+}
+
+// ------------------------------------------------------------------------------------------
+// RANGE SEARCH, exhaustive route: the canonical scores of the selected queries against every row (as above), then, per
+// query, the rows that pass -- score > radius (metric 0) or distance < radius (metric 1), strict -- counted per slab and
+// compacted in id order.  The count and the fill are two calls (the caller sizes the output in between); the scores
+// stay in the workspace from one to the other.  (k_count_ge / k_scan_slabs / k_compact_ge above keep their >= T top-k
+// semantics; these are their range counterparts.)
+// Workspace: scores f32 [nsel][n] | (256-byte aligned) slab offsets u32 [nsel][nslabs].
+constexpr int RG_SLAB = 16384;        // rows per counting / compaction workgroup
+constexpr int RG_THREADS = 256;
+
+__device__ __forceinline__ bool range_pass(float s, float r, int metric) { return metric == 0 ? s > r : s < r; }
+
+static long rg_slabs(long n) { return (n + RG_SLAB - 1) / RG_SLAB; }
+static size_t rg_scores_bytes(long nsel, long n) { return ((size_t)nsel * n * 4 + 255) & ~(size_t)255; }
+
+// grid (slabs, nsel): rows of one slab of one query that pass
+__global__ __launch_bounds__(RG_THREADS) void k_range_count(const float* __restrict__ scores, long n, int metric,
+                                                            const float* __restrict__ radius, const int* __restrict__ qsel, int nslabs,
+                                                            unsigned* __restrict__ cnt) {
+    __shared__ unsigned s_c[RG_THREADS / 64];
+    const int f = blockIdx.y, slab = blockIdx.x, tid = threadIdx.x;
+    const float* s = scores + (size_t)f * n;
+    const float r = radius[qsel[f]];
+    const long lo = (long)slab * RG_SLAB, hi = lo + RG_SLAB < n ? lo + RG_SLAB : n;
+    unsigned c = 0;
+    for (long i = lo + tid; i < hi; i += RG_THREADS) c += range_pass(s[i], r, metric) ? 1u : 0u;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((tid & 63) == 0) s_c[tid >> 6] = c;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned t = 0;
+        for (int w = 0; w < RG_THREADS / 64; ++w) t += s_c[w];
+        cnt[(size_t)f * nslabs + slab] = t;
+    }
+}
+
+// one thread per query: exclusive scan of its slab counts (in place) and its total
+__global__ __launch_bounds__(64) void k_range_scan(unsigned* __restrict__ cnt, int nslabs, int nsel, long* __restrict__ counts) {
+    const int f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= nsel) return;
+    unsigned run = 0;
+    for (int j = 0; j < nslabs; ++j) {
+        const unsigned c = cnt[(size_t)f * nslabs + j];
+        cnt[(size_t)f * nslabs + j] = run;
+        run += c;
+    }
+    counts[f] = (long)run;
+}
+
+// grid (slabs, nsel): ordered write of the slab's passing rows at lims[f] + (passing rows of the earlier slabs) + rank.
+// Every write stays inside [lims[f], lims[f + 1]) and below lims[nsel] (the size of D / I) whatever lims holds.
+__global__ __launch_bounds__(RG_THREADS) void k_range_compact(const float* __restrict__ scores, long n, int metric,
+                                                              const float* __restrict__ radius, const int* __restrict__ qsel, int nslabs,
+                                                              const unsigned* __restrict__ off, int nsel, const long* __restrict__ lims,
+                                                              long id_offset, float* __restrict__ D, long* __restrict__ I) {
+    __shared__ unsigned s_w[RG_THREADS / 64];
+    __shared__ unsigned s_base;
+    const int f = blockIdx.y, slab = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const float* s = scores + (size_t)f * n;
+    const float r = radius[qsel[f]];
+    const long total = lims[nsel], q_lo = lims[f];
+    long q_hi = lims[f + 1];
+    if (q_hi > total) q_hi = total;
+    if (q_lo < 0 || q_lo >= q_hi) return;                                // (workgroup-uniform)
+    const long lo = (long)slab * RG_SLAB, hi = lo + RG_SLAB < n ? lo + RG_SLAB : n;
+    if (tid == 0) s_base = off[(size_t)f * nslabs + slab];
+    __syncthreads();
+    for (long base = lo; base < hi; base += RG_THREADS) {
+        const long i = base + tid;
+        float v = 0.f;
+        bool pass = false;
+        if (i < hi) { v = s[i]; pass = range_pass(v, r, metric); }
+        const unsigned long long b = __builtin_amdgcn_ballot_w64(pass);
+        if (lane == 0) s_w[wv] = (unsigned)__builtin_popcountll(b);
+        __syncthreads();
+        unsigned before = s_base, tot = 0;
+        for (int w = 0; w < RG_THREADS / 64; ++w) {
+            const unsigned c = s_w[w];
+            if (w < wv) before += c;
+            tot += c;
+        }
+        before += (unsigned)__builtin_popcountll(b & ((1ull << lane) - 1ull));
+        const long pos = q_lo + (long)before;
+        if (pass && pos < q_hi) { D[pos] = v; I[pos] = i + id_offset; }
+        __syncthreads();
+        if (tid == 0) s_base += tot;
+        __syncthreads();
+    }
+}
+
+size_t range_exhaustive_workspace_bytes(long nsel, long n) {
+    if (nsel <= 0 || n <= 0) return 0;
+    return rg_scores_bytes(nsel, n) + (((size_t)nsel * rg_slabs(n) * 4 + 255) & ~(size_t)255);
+}
+
+static int range_exhaustive_check(const char* what, const int* qsel, long nsel, long n, int metric, const float* radius, const void* ws,
+                                  size_t ws_bytes) {
+    if (nsel <= 0 || n <= 0 || (metric != 0 && metric != 1) || !qsel || !radius) {
+        set_error("%s: need nsel, n > 0, metric in {0,1}, qsel and radius", what);
+        return SSS_EINVAL;
+    }
+    if (n >= (1L << 31) || nsel > 65535) { set_error("%s: n < 2^31, nsel <= 65535", what); return SSS_EINVAL; }
+    if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("%s: workspace must be 256-byte aligned", what); return SSS_EINVAL; }
+    if (!ws || ws_bytes < range_exhaustive_workspace_bytes(nsel, n)) {
+        set_error("%s: workspace %zu < %zu", what, ws_bytes, range_exhaustive_workspace_bytes(nsel, n));
+        return SSS_EWORKSPACE;
+    }
+    return SSS_OK;
+}
+
+int range_exhaustive_count(const void* q, const int* qsel, long nsel, const void* c, long n, int d, int dtype, int metric, const float* radius,
+                           long* counts, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (d <= 0 || (dtype != DT_F32 && dtype != DT_BF16) || d % (dtype == DT_F32 ? 4 : 8) || !q || !c || !counts) {
+        set_error("range_exhaustive_count: need d %% 4 == 0 (f32) / d %% 8 == 0 (bf16), q, corpus and counts");
+        return SSS_EINVAL;
+    }
+    int rc = range_exhaustive_check("range_exhaustive_count", qsel, nsel, n, metric, radius, ws, ws_bytes);
+    if (rc) return rc;
+    float* scores = reinterpret_cast<float*>(ws);
+    unsigned* cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + rg_scores_bytes(nsel, n));
+    const int nslabs = (int)rg_slabs(n);
+    // inner product: the radius is a valid pre-test bound -- a row k_exact_scores_rows skips (score -FLT_MAX) provably
+    // rounds to at most the radius, so it fails "> radius" either way
+    rc = launch_exact_scores(q, qsel, nsel, c, n, d, dtype, metric, scores, metric == 0 ? radius : nullptr, 1, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_range_count, dim3((unsigned)nslabs, (unsigned)nsel), dim3(RG_THREADS), 0, st, scores, n, metric, radius, qsel,
+                       nslabs, cnt);
+    rc = check_launch("k_range_count");
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_range_scan, dim3((unsigned)((nsel + 63) / 64)), dim3(64), 0, st, cnt, nslabs, (int)nsel, counts);
+    return check_launch("k_range_scan");
+}
+
+int range_exhaustive_fill(const int* qsel, long nsel, long n, int metric, const float* radius, const long* lims, long id_offset, float* D_out,
+                          long* I_out, const void* ws, size_t ws_bytes, hipStream_t st) {
+    int rc = range_exhaustive_check("range_exhaustive_fill", qsel, nsel, n, metric, radius, ws, ws_bytes);
+    if (rc) return rc;
+    if (!lims) { set_error("range_exhaustive_fill: lims is required"); return SSS_EINVAL; }
+    const float* scores = reinterpret_cast<const float*>(ws);
+    const unsigned* off = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(ws) + rg_scores_bytes(nsel, n));
+    const int nslabs = (int)rg_slabs(n);
+    hipLaunchKernelGGL(k_range_compact, dim3((unsigned)nslabs, (unsigned)nsel), dim3(RG_THREADS), 0, st, scores, n, metric, radius, qsel,
+                       nslabs, off, (int)nsel, lims, id_offset, D_out, I_out);
+    return check_launch("k_range_compact");
 }
 
 }  // namespace sss

@@ -165,6 +165,75 @@ int ip_topk_threshold(const void* q, const int* qsel, long nsel, const void* c_e
     return launch_select_all(t, st);
 }
 
+// RANGE SEARCH, fused route (select.hip: RANGE SEARCH): the threshold rung's scan with thresholds from per-query radii.
+// Workspace: thr f32 [nq] | cnt u32 [nq] | (256-byte aligned) qsel i32 [nq] | (256-byte aligned) cand u64 [nq][THR_CAP].
+// range_search_count leaves each resolved query's entries in its candidate row; range_search_fill copies them out.
+static size_t range_head_bytes(long nq) { return thr_head_bytes(nq) + (((size_t)nq * 4 + 255) & ~(size_t)255); }
+static size_t range_cand_bytes(long nq) { return ((size_t)nq * THR_CAP * 8 + 255) & ~(size_t)255; }
+
+size_t range_search_workspace_bytes(long nq, long n, int d, int scan_dtype) {
+    if (nq <= 0 || n <= 0 || !fused_shape_ok(d, scan_dtype)) return 0;
+    return range_head_bytes(nq) + make_thr_plan(nq, n, d, scan_dtype, THR_CAP).total_bytes;
+}
+
+int range_search_count(const void* q, long nq, const void* c_exact, int exact_dtype, const void* c_scan, int scan_dtype, int corpus_shift,
+                       float corpus_resid, long n, int d, const float* radius, float corpus_max_norm, long* counts, int* status, void* ws,
+                       size_t ws_bytes, hipStream_t st) {
+    if (nq <= 0 || n <= 0) { set_error("range_search_count: nq, n must be positive"); return SSS_EINVAL; }
+    if (exact_dtype != DT_F32 && exact_dtype != DT_BF16) { set_error("range_search_count: dtype must be 0 (f32) or 1 (bf16)"); return SSS_EINVAL; }
+    const bool native = scan_dtype == exact_dtype;
+    if (!fused_shape_ok(d, scan_dtype) || (!native && (exact_dtype != DT_F32 || (scan_dtype != DT_SPLIT && scan_dtype != DT_F16)))) {
+        set_error("range_search_count: no scan of type %d for dtype %d, d %d", scan_dtype, exact_dtype, d);
+        return SSS_EINVAL;
+    }
+    if (!c_scan || (reinterpret_cast<uintptr_t>(c_scan) & 15)) { set_error("range_search_count: scan image missing or not 16-byte aligned"); return SSS_EINVAL; }
+    if (!q || !c_exact || !radius || !counts || !status) { set_error("range_search_count: q, corpus, radius, counts and status are required"); return SSS_EINVAL; }
+    if (scan_dtype == DT_F16 && (corpus_shift < -160 || corpus_shift > 160 || !(corpus_resid >= 0.f))) {
+        set_error("range_search_count: corpus_shift out of range or corpus_resid_norm < 0");
+        return SSS_EINVAL;
+    }
+    if (n >= (1L << 31) - 1024 || nq >= (1L << 31)) { set_error("range_search_count: n and nq must be < 2^31"); return SSS_EINVAL; }
+    if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("range_search_count: workspace must be 256-byte aligned"); return SSS_EINVAL; }
+    const ScanPlan p = make_thr_plan(nq, n, d, scan_dtype, THR_CAP);
+    const size_t need = range_head_bytes(nq) + p.total_bytes;
+    if (!ws || ws_bytes < need) { set_error("range_search_count: workspace %zu < %zu", ws_bytes, need); return SSS_EWORKSPACE; }
+    char* w = reinterpret_cast<char*>(ws);
+    int* qsel = reinterpret_cast<int*>(w + thr_head_bytes(nq));
+    ThrArgs t;
+    t.Q = q; t.C = c_exact; t.qsel = qsel; t.nsel = (int)nq; t.d = d; t.dtype = exact_dtype; t.k = 1; t.cap = p.cap; t.n = n;
+    t.scan_dtype = scan_dtype; t.corpus_shift = corpus_shift; t.corpus_resid = corpus_resid; t.corpus_max_norm = corpus_max_norm;
+    t.id_offset = 0;
+    t.thr = reinterpret_cast<float*>(w);
+    t.cnt = reinterpret_cast<unsigned*>(w + (size_t)nq * 4);
+    t.cand = reinterpret_cast<unsigned long long*>(w + range_head_bytes(nq));
+    t.D_out = nullptr; t.I_out = nullptr; t.status = nullptr;
+    int rc = launch_range_prepare(t, radius, qsel, st);
+    if (rc) return rc;
+    ScanArgs a = {};
+    a.Q = q; a.C = c_scan; a.nq = (int)nq; a.n = (int)n;
+    a.tiles_per_split = p.tiles_per_split; a.total_tiles = p.total_tiles;
+    a.S = p.S; a.G = p.G; a.J = 0; a.Ju = 0; a.cert = 1; a.boot = 0; a.append = 0; a.cap = p.cap;
+    a.slots = nullptr; a.cnt = t.cnt; a.maxlast = nullptr;
+    a.cand = const_cast<unsigned long long*>(t.cand);
+    a.qsel = qsel; a.thr = t.thr;
+    rc = launch_scan(scan_dtype, d, p.tile_rows, a, st);
+    if (rc) return rc;
+    return launch_range_select(t, radius, counts, status, st);
+}
+
+int range_search_fill(long nq, const long* lims, long id_offset, float* D_out, long* I_out, const void* ws, size_t ws_bytes,
+                      hipStream_t st) {
+    if (nq <= 0 || nq >= (1L << 31)) { set_error("range_search_fill: nq must be in [1, 2^31)"); return SSS_EINVAL; }
+    if (!lims) { set_error("range_search_fill: lims is required"); return SSS_EINVAL; }
+    if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("range_search_fill: workspace must be 256-byte aligned"); return SSS_EINVAL; }
+    const size_t need = range_head_bytes(nq) + range_cand_bytes(nq);
+    if (!ws || ws_bytes < need) { set_error("range_search_fill: workspace %zu < %zu", ws_bytes, need); return SSS_EWORKSPACE; }
+    const char* w = reinterpret_cast<const char*>(ws);
+    return launch_range_fill(reinterpret_cast<const unsigned*>(w + (size_t)nq * 4),
+                             reinterpret_cast<const unsigned long long*>(w + range_head_bytes(nq)), THR_CAP, nq, lims, id_offset, D_out,
+                             I_out, st);
+}
+
 int ip_topk(const void* q, long nq, const void* c, long n, int d, int k, int dtype, long id_offset,
             float corpus_max_norm, float* D_out, long* I_out, int* status, int* unproven_count, void* state,
             size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st) {

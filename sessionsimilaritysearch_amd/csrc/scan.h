@@ -134,5 +134,12 @@ int launch_select_all(const ThrArgs& a, hipStream_t st);
 // column k-1 of D_out -> the next level's threshold; counters zeroed, or -- a.keep -- the kept rows pruned in place).
 int launch_long_setup(const ThrArgs& a, int* qsel, void* qimg, hipStream_t st);
 int launch_bound_prepare(const ThrArgs& a, hipStream_t st);
+// Range search, fused route (select.hip): scan thresholds from per-query radii (identity selection written to `qsel`,
+// counters zeroed); the canonical re-score + keep (> radius) + sort by id of the kept rows (counts / status per query,
+// the entries left in the candidate rows); the copy of those entries to D / I at lims.
+int launch_range_prepare(const ThrArgs& a, const float* radius, int* qsel, hipStream_t st);
+int launch_range_select(const ThrArgs& a, const float* radius, long* counts, int* status, hipStream_t st);
+int launch_range_fill(const unsigned* cnt, const unsigned long long* cand, int cap, long nq, const long* lims, long id_offset, float* D,
+                      long* I, hipStream_t st);
 
 }  // namespace sss

@@ -804,6 +804,66 @@ __global__ __launch_bounds__(SORT_THREADS) void k_bound_prepare(const ThrArgs A)
     prune_kept(A, i, thr, tid);
 }
 
+// Canonical re-score of the kept rows surv[0 .. keep) (scan keys: only their ids are read) by a workgroup of SORT_THREADS,
+// one thread per row for the strictly sequential float64 chain -- but rows of 1024 bytes and more come in through LDS:
+// the workgroup fetches 128 contiguous bytes of each of a group's SA_ROWS rows per step (coalesced: eight lanes a row)
+// and every thread then reads its own row's chunks from the staging tile `stage` ([SA_ROWS][SA_BYTES + 16]).  (A thread
+// walking its own 6400-byte row 16 bytes at a time -- round 3's first form -- turned every load into 64 separate line
+// requests per wave: 0.53 ms of a 5.7 ms search at D = 1600, K = 100.)  emit(c, valid, score, id) is called once for
+// every c < K2 (K2 >= keep) by the thread that owns it; valid == c < keep.  qrow: the query row in LDS.
+template <int SA_ROWS, typename Emit>
+__device__ __forceinline__ void rescore_kept(const unsigned long long* surv, int keep, int K2, const void* C, int rb, int dtype,
+                                             const char* qrow, char* stage, int tid, Emit emit) {
+    const int nchunks = rb / 16;
+    if (rb < 1024 || keep <= 0) {                                       // short rows (a few lines each): a thread per row, all 256 busy
+                                                                        // (nothing kept: the tile's clamped fetches would have no row)
+        for (int c = tid; c < K2; c += SORT_THREADS) {
+            if (c < keep) {
+                const int id = key_id(surv[c]);
+                emit(c, true, rescore_row(qrow, reinterpret_cast<const char*>(C) + (size_t)id * rb, nchunks, dtype), id);
+            } else {
+                emit(c, false, 0.0, -1);
+            }
+        }
+        return;
+    }
+    for (int c0 = 0; c0 < K2; c0 += SA_ROWS) {
+        constexpr int PER = SA_ROWS * (SA_BYTES / 16) / SORT_THREADS;   // 16-byte pieces a thread fetches per step
+        f32x4 pre[PER];
+        auto fetch = [&](int b) __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < PER; ++j) {
+                const int idx = tid + SORT_THREADS * j, r = idx / (SA_BYTES / 16), ch = idx % (SA_BYTES / 16);
+                const int cs = min(c0 + r, keep - 1), vs = min(b + ch, nchunks - 1);      // (clamped: unused copies of valid bytes)
+                pre[j] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(C) + (size_t)key_id(surv[cs]) * rb + (size_t)vs * 16);
+            }
+        };
+        double acc = 0.0;
+        fetch(0);
+        for (int b = 0; b < nchunks; b += SA_BYTES / 16) {
+            __syncthreads();                                            // the previous step's tile has been consumed
+#pragma unroll
+            for (int j = 0; j < PER; ++j) {
+                const int idx = tid + SORT_THREADS * j, r = idx / (SA_BYTES / 16), ch = idx % (SA_BYTES / 16);
+                *reinterpret_cast<f32x4*>(stage + r * (SA_BYTES + 16) + ch * 16) = pre[j];
+            }
+            __syncthreads();
+            if (b + SA_BYTES / 16 < nchunks) fetch(b + SA_BYTES / 16);  // in flight under this step's chain
+            if (tid < SA_ROWS && c0 + tid < keep) {
+#pragma unroll
+                for (int i = 0; i < SA_BYTES / 16; ++i)
+                    if (b + i < nchunks)
+                        acc = dot_chunk(acc, qrow, b + i, *reinterpret_cast<const f32x4*>(stage + tid * (SA_BYTES + 16) + i * 16), dtype);
+            }
+        }
+        __syncthreads();                                                // (surv is read by every fetch; what emit writes aliases nothing)
+        if (tid < SA_ROWS && c0 + tid < K2) {
+            if (c0 + tid < keep) emit(c0 + tid, true, acc, key_id(surv[c0 + tid]));
+            else emit(c0 + tid, false, 0.0, -1);
+        }
+    }
+}
+
 // k_select_all: one workgroup per selected query.  The kept rows are first pruned by SCAN score, before any row is
 // read: with s_k the k-th largest kept scan score, at least k rows have an exact score >= s_k * unscale - B, and a
 // row whose scan score lies more than 2 B (+ one float32 ulp) below s_k cannot reach that -- the survivors are a
@@ -860,59 +920,12 @@ __global__ __launch_bounds__(SORT_THREADS) void k_select_all(const ThrArgs A, in
     const int keep = (int)s_keep;                                       // >= k: the k-th largest itself passes the cut
     int K2 = 64;
     while (K2 < keep) K2 <<= 1;
-    // Canonical re-score of the survivors, SA_ROWS of them at a time, one thread per row for the strictly sequential
-    // float64 chain -- but the rows come in through LDS: the workgroup fetches 128 contiguous bytes of each of the
-    // group's rows per step (coalesced: eight lanes a row) and every thread then reads its own row's chunks from the
-    // staging tile.  (A thread walking its own 6400-byte row 16 bytes at a time -- round 3's first form -- turned
-    // every load into 64 separate line requests per wave: 0.53 ms of a 5.7 ms search at D = 1600, K = 100.)
+    // canonical re-score of the survivors (rescore_kept: SA_ROWS rows at a time through the staging tile for long rows)
     char* stage = qrow + ((rb + 15) & ~15);                             // [SA_ROWS][SA_BYTES + 16]
-    const int nchunks = rb / 16;
-    if (rb < 1024) {                                                    // short rows (a few lines each): a thread per row, all 256 busy
-        for (int c = tid; c < K2; c += SORT_THREADS) {
-            unsigned long long key = 0ull;
-            if (c < keep) {
-                const int id = key_id(surv[c]);
-                key = make_key((float)rescore_row(qrow, reinterpret_cast<const char*>(A.C) + (size_t)id * rb, nchunks, A.dtype), id);
-            }
-            keys[c] = key;
-        }
-    } else
-    for (int c0 = 0; c0 < K2; c0 += SA_ROWS) {
-        constexpr int PER = SA_ROWS * (SA_BYTES / 16) / SORT_THREADS;   // 16-byte pieces a thread fetches per step
-        f32x4 pre[PER];
-        auto fetch = [&](int b) __attribute__((always_inline)) {
-#pragma unroll
-            for (int j = 0; j < PER; ++j) {
-                const int idx = tid + SORT_THREADS * j, r = idx / (SA_BYTES / 16), ch = idx % (SA_BYTES / 16);
-                const int cs = min(c0 + r, keep - 1), vs = min(b + ch, nchunks - 1);      // (clamped: unused copies of valid bytes)
-                pre[j] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(A.C) + (size_t)key_id(surv[cs]) * rb + (size_t)vs * 16);
-            }
-        };
-        double acc = 0.0;
-        fetch(0);
-        for (int b = 0; b < nchunks; b += SA_BYTES / 16) {
-            __syncthreads();                                            // the previous step's tile has been consumed
-#pragma unroll
-            for (int j = 0; j < PER; ++j) {
-                const int idx = tid + SORT_THREADS * j, r = idx / (SA_BYTES / 16), ch = idx % (SA_BYTES / 16);
-                *reinterpret_cast<f32x4*>(stage + r * (SA_BYTES + 16) + ch * 16) = pre[j];
-            }
-            __syncthreads();
-            if (b + SA_BYTES / 16 < nchunks) fetch(b + SA_BYTES / 16);  // in flight under this step's chain
-            if (tid < SA_ROWS && c0 + tid < keep) {
-#pragma unroll
-                for (int i = 0; i < SA_BYTES / 16; ++i)
-                    if (b + i < nchunks)
-                        acc = dot_chunk(acc, qrow, b + i, *reinterpret_cast<const f32x4*>(stage + tid * (SA_BYTES + 16) + i * 16), A.dtype);
-            }
-        }
-        __syncthreads();                                                // (surv is read by every fetch; keys below aliases nothing)
-        if (tid < SA_ROWS && c0 + tid < K2) {
-            unsigned long long key = 0ull;
-            if (c0 + tid < keep) key = make_key((float)acc, key_id(surv[c0 + tid]));
-            keys[c0 + tid] = key;                                       // (the scan keys are no longer needed)
-        }
-    }
+    rescore_kept<SA_ROWS>(surv, keep, K2, A.C, rb, A.dtype, qrow, stage, tid,
+                          [&](int c, bool valid, double acc, int id) __attribute__((always_inline)) {
+                              keys[c] = valid ? make_key((float)acc, id) : 0ull;     // (the scan keys are no longer needed)
+                          });
     __syncthreads();
     // Many more survivors than results (a query whose k-th neighbour sits in a group of thousands of identical rows: config
     // C3's one-click prefix sessions): a bitonic sort of all K2 exact keys -- 91 barrier stages at K2 = 8192 -- was 0.3 of
@@ -946,6 +959,102 @@ __global__ __launch_bounds__(SORT_THREADS) void k_select_all(const ThrArgs A, in
         else { Dq[j] = -3.4028234663852886e38f; Iq[j] = -1; }
     }
     if (tid == 0) A.status[q] = 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// RANGE SEARCH, fused route (ip_topk.hip: range_search_count / range_search_fill).  The threshold rung with the caller's
+// radius r in place of a known k-th score: a row the scan does NOT keep has scan score <= thr_from_bound(r), hence an
+// exact score below r - one float32 ulp of r, which rounds to at most r -- never "> r".  So the rows kept are a superset
+// of the answer, and re-scoring all of them canonically decides it exactly (when they fit the capacity).
+//
+// k_range_prepare: one wave per query (identity selection): its scan threshold from its radius, counter zeroed.
+__global__ __launch_bounds__(256) void k_range_prepare(const ThrArgs A, const float* __restrict__ radius, int* __restrict__ qsel) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= A.nsel) return;
+    double B, unscale;
+    query_bound(A, i, i, lane, B, unscale);                                 // (every lane ends up with the same B / unscale)
+    const float thr = thr_from_bound((double)radius[i], B, unscale);        // -inf for r <= -3e38 (and NaN): keep every row
+    if (lane == 0) { qsel[i] = i; A.thr[i] = thr; A.cnt[i] = 0u; }
+}
+
+// Range output entry of a kept row: (~id) in the high word, the float32 score's bits in the low one.  A DESCENDING sort
+// of these orders by ASCENDING id (ids < 2^31: ~id >= 2^31), and 0 -- the padding -- sorts last.
+__device__ __forceinline__ unsigned long long range_entry(float s, int id) {
+    return ((unsigned long long)(~(unsigned)id) << 32) | (unsigned long long)__builtin_bit_cast(unsigned, s);
+}
+
+// k_range_select: one workgroup per query.  A query whose scan kept more rows than the capacity gets status 1 and count
+// 0 (the exhaustive route resolves it).  Otherwise its M kept rows are re-scored canonically (rescore_kept), those with
+// float32 score > radius are compacted in LDS, sorted by ascending id and written back over the query's candidate row
+// of the workspace (for k_range_fill); cnt[i] and counts[i] = their number, status 0.
+// Launched twice, as k_select_all: queries with m_lo < M <= cap_pow2 are this launch's share (the first launch, m_lo < 0,
+// a small LDS footprint for the common case of a few hundred kept rows; it also flags the overflowed queries).
+// LDS: keys[cap_pow2] scan keys | out[cap_pow2] entries | query row | staging tile (rows of 1024 bytes and more).
+template <int SA_ROWS>
+__global__ __launch_bounds__(SORT_THREADS) void k_range_select(const ThrArgs A, const float* __restrict__ radius, int cap_pow2, int m_lo,
+                                                               long* __restrict__ counts, int* __restrict__ status) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);
+    unsigned long long* out = keys + cap_pow2;
+    char* qrow = reinterpret_cast<char*>(out + cap_pow2);
+    char* stage = qrow + ((A.d * (A.dtype == DT_F32 ? 4 : 2) + 15) & ~15);
+    __shared__ unsigned s_keep;
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const int rb = A.d * (A.dtype == DT_F32 ? 4 : 2);
+    const unsigned M = A.cnt[i];
+    if (M > (unsigned)A.cap) {                                          // overflow: the exhaustive route's
+        if (m_lo < 0 && tid == 0) { counts[i] = 0; status[i] = 1; }
+        return;
+    }
+    if ((int)M <= m_lo || M > (unsigned)cap_pow2) return;               // the other launch's share
+    const float r = radius[i];
+    for (int v = tid; v < rb / 16; v += SORT_THREADS)
+        reinterpret_cast<f32x4*>(qrow)[v] = reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(A.Q) + (size_t)i * rb)[v];
+    unsigned long long* ck = const_cast<unsigned long long*>(A.cand) + (size_t)i * A.cap;
+    for (int c = tid; c < (int)M; c += SORT_THREADS) keys[c] = ck[c];
+    if (tid == 0) s_keep = 0u;
+    __syncthreads();
+    int K2 = 64;
+    while (K2 < (int)M) K2 <<= 1;                                       // <= cap_pow2
+    rescore_kept<SA_ROWS>(keys, (int)M, K2, A.C, rb, A.dtype, qrow, stage, tid,
+                          [&](int, bool valid, double acc, int id) __attribute__((always_inline)) {
+                              const float s = (float)acc;
+                              if (valid && s > r) {
+                                  const unsigned pos = atomicAdd(&s_keep, 1u);
+                                  if (pos < (unsigned)cap_pow2) out[pos] = range_entry(s, id);
+                              }
+                          });
+    __syncthreads();
+    const int keep = (int)min(s_keep, (unsigned)cap_pow2);              // (<= M: every kept row once)
+    int Ks = 64;
+    while (Ks < keep) Ks <<= 1;
+    for (int x = keep + tid; x < Ks; x += SORT_THREADS) out[x] = 0ull;
+    __syncthreads();
+    sort_desc(out, Ks, tid);                                            // ascending id
+    for (int x = tid; x < keep; x += SORT_THREADS) ck[x] = out[x];      // (the row's scan keys were read above)
+    if (tid == 0) { A.cnt[i] = (unsigned)keep; counts[i] = keep; status[i] = 0; }
+}
+
+// k_range_fill: one workgroup per query: its resolved entries (cnt[i] <= cap) to D / I at lims[i], ids + id_offset.
+// Writes stay inside [lims[i], lims[i+1]) and below lims[nq] (the size of D / I) whatever lims holds.
+__global__ __launch_bounds__(256) void k_range_fill(const unsigned* __restrict__ cnt, const unsigned long long* __restrict__ cand,
+                                                    int cap, int nq, const long* __restrict__ lims, long id_offset,
+                                                    float* __restrict__ D, long* __restrict__ I) {
+    const int i = blockIdx.x;
+    const unsigned m = cnt[i];
+    if (m > (unsigned)cap) return;                                      // overflowed: filled by the exhaustive route
+    const long total = lims[nq], lo = lims[i], hi = lims[i + 1];
+    if (lo < 0 || lo > total) return;
+    long len = (long)m;
+    if (hi - lo < len) len = hi - lo;
+    if (total - lo < len) len = total - lo;
+    const unsigned long long* row = cand + (size_t)i * cap;
+    for (long j = threadIdx.x; j < len; j += 256) {
+        const unsigned long long e = row[j];
+        D[lo + j] = __builtin_bit_cast(float, (unsigned)e);
+        I[lo + j] = (long)(int)~(unsigned)(e >> 32) + id_offset;
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1044,6 +1153,46 @@ int launch_select_all(const ThrArgs& a, hipStream_t st) {
     else hipLaunchKernelGGL(k_select_all<SA_ROWS_FULL>, dim3((unsigned)a.nsel), dim3(SORT_THREADS), 2 * (size_t)small * 8 + ((rb + 15) & ~15) + stage, st, a, small, 0);
     if (small < cap_pow2) hipLaunchKernelGGL(k_select_all<SA_ROWS_FULL>, dim3((unsigned)a.nsel), dim3(SORT_THREADS), lds, st, a, cap_pow2, 1);
     return check_launch("k_select_all");
+}
+
+int launch_range_prepare(const ThrArgs& a, const float* radius, int* qsel, hipStream_t st) {
+    hipLaunchKernelGGL(k_range_prepare, dim3((unsigned)((a.nsel + 3) / 4)), dim3(256), 0, st, a, radius, qsel);
+    return check_launch("k_range_prepare");
+}
+
+int launch_range_select(const ThrArgs& a, const float* radius, long* counts, int* status, hipStream_t st) {
+    const int rb = a.d * elem_bytes(a.dtype);
+    int cap_pow2 = 64;
+    while (cap_pow2 < a.cap) cap_pow2 <<= 1;
+    const size_t stage = rb < 1024 ? 0 : (size_t)SA_ROWS_FULL * (SA_BYTES + 16);
+    const size_t fixed = ((rb + 15) & ~15) + stage;                    // the query row + the tile
+    const size_t lds = 2 * (size_t)cap_pow2 * 8 + fixed;
+    if (lds > 156 * 1024) { set_error("range_select: candidate capacity %d / row of %d bytes too large", a.cap, rb); return SSS_EINVAL; }
+    static bool done[MAX_DEVICES] = {};
+    const int dev = current_device();
+    if (!done[dev]) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_range_select<SA_ROWS_FULL>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                160 * 1024 - 4096) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("k_range_select: opting in to %d bytes of LDS failed", 160 * 1024 - 4096);
+            return SSS_EHIP;
+        }
+        done[dev] = true;
+    }
+    const int small = cap_pow2 < 2048 ? cap_pow2 : 2048;
+    hipLaunchKernelGGL(k_range_select<SA_ROWS_FULL>, dim3((unsigned)a.nsel), dim3(SORT_THREADS), 2 * (size_t)small * 8 + fixed, st, a, radius,
+                       small, -1, counts, status);
+    int rc = check_launch("k_range_select");
+    if (rc || small == cap_pow2) return rc;
+    hipLaunchKernelGGL(k_range_select<SA_ROWS_FULL>, dim3((unsigned)a.nsel), dim3(SORT_THREADS), lds, st, a, radius, cap_pow2, small,
+                       counts, status);
+    return check_launch("k_range_select");
+}
+
+int launch_range_fill(const unsigned* cnt, const unsigned long long* cand, int cap, long nq, const long* lims, long id_offset, float* D,
+                      long* I, hipStream_t st) {
+    hipLaunchKernelGGL(k_range_fill, dim3((unsigned)nq), dim3(256), 0, st, cnt, cand, cap, (int)nq, lims, id_offset, D, I);
+    return check_launch("k_range_fill");
 }
 
 int topk_merge(const float* D_in, long d_stride, const long* I_in, long i_stride, int shards, long nq, int k,

@@ -41,6 +41,8 @@ DTYPE_CODE = {"f32": 0, "bf16": 1}                               # include/sss.h
 _EXHAUSTIVE_WS_BYTES = 1 << 30
 SEARCH_CHUNK = 65536             # queries per fused call of search_device (workspace 16 KB per query)
 SEARCH_CHUNK_LONG = 16384        # ... on the long-row path (64 KB per query)
+RANGE_CHUNK = 4096               # queries per fused range_search count / fill (workspace 64 KB per query)
+_SCAN_CODE = {"split": 2, "f16": 3}                              # include/sss.h: scan image codes (else the dtype's own)
 
 
 def _dev(device=None):
@@ -175,6 +177,8 @@ class FlatIndex:
         self.id_offset = 0              # global id of row 0 (row-sharded corpora)
         self.last_fallback_queries = 0  # queries of the last search() re-run exhaustively
         self.last_rescan_queries = 0    # queries of the last search() the fused scan left unproven (threshold rung first)
+        self.last_range_scan = None     # the scan the last range_search used ("" = exhaustive route only)
+        self.last_range_overflow_queries = 0    # queries of the last range_search the fused route sent to the exhaustive one
 
     @property
     def ntotal(self) -> int:
@@ -577,6 +581,136 @@ class FlatIndex:
         if is_np:
             return D.cpu().numpy(), I.cpu().numpy()
         return D, I
+
+    # ------------------------------------------------------------------ range search
+    def _radius(self, radius, nq: int) -> torch.Tensor:
+        """The radius as a device float32 [nq] tensor (a scalar for every query, or one per query); NaN raises."""
+        if isinstance(radius, torch.Tensor):
+            r = radius.detach().to(device=self.device, dtype=torch.float32).reshape(-1)
+        else:
+            r = torch.from_numpy(np.asarray(radius, dtype=np.float32).reshape(-1)).to(self.device)
+        if r.numel() == 1:
+            r = r.expand(nq)
+        elif r.numel() != nq:
+            raise ValueError(f"range_search: radius must be a scalar or have {nq} entries, got {r.numel()}")
+        if bool(torch.isnan(r).any()):
+            raise ValueError("range_search: radius is NaN")
+        return r.contiguous()
+
+    def range_search_device(self, q: torch.Tensor, radius):
+        """Exact range search, CUDA tensors in and out: (lims int64 [nq + 1], D float32 [lims[nq]], I int64 [lims[nq]]).
+        Query i's results are D[lims[i]:lims[i+1]] / I[...], in ascending id order: every row with canonical score
+        > radius (inner product) or squared distance < radius (L2), radius converted to float32.  Syncs once per chunk
+        of queries (to size the output)."""
+        if q.dtype != self._tdtype:
+            q = self._rows(q, "range_search")
+        nq, n = q.shape[0], self.ntotal
+        rad = self._radius(radius, nq)
+        self.last_range_scan, self.last_range_overflow_queries = "", 0
+        lims = torch.zeros(nq + 1, dtype=torch.int64, device=self.device)
+        if nq == 0 or n == 0:
+            return lims, torch.empty(0, dtype=torch.float32, device=self.device), torch.empty(0, dtype=torch.int64, device=self.device)
+        if self.d % (4 if self.dtype == "f32" else 8):
+            raise _lib.SssError("d must be a multiple of 4 (f32) / 8 (bf16)")
+        L, st = _lib.lib(), _lib.stream_ptr(self.device)
+        pieces = []                     # (query rows [host int64], their counts [host int64], D, I) in the order they were produced
+        mode = self.last_range_scan = self.rung_scan()
+        left = []                       # query rows for the exhaustive route
+        if mode:
+            if mode == "f16":
+                self._ensure_f16()
+                image, code, shift, resid = self._f16, _SCAN_CODE["f16"], self._c_shift, self.corpus_resid_norm()
+            elif mode == "split":
+                self._ensure_split()
+                image, code, shift, resid = self._split, _SCAN_CODE["split"], 0, 0.0
+            else:
+                image, code, shift, resid = self._xb, DTYPE_CODE[self.dtype], 0, 0.0
+            cmax = self.corpus_max_norm()
+            for lo in range(0, nq, RANGE_CHUNK):
+                m = min(nq, lo + RANGE_CHUNK) - lo
+                ws = self._workspace(L.sss_range_search_workspace_bytes(m, n, self.d, code))
+                cs = torch.empty(2 * m, dtype=torch.int64, device=self.device)           # counts | status (one copy to the host)
+                status = torch.empty(m, dtype=torch.int32, device=self.device)
+                rc = L.sss_range_search_count(q[lo:].data_ptr(), m, self._xb.data_ptr(), DTYPE_CODE[self.dtype], image.data_ptr(),
+                                              code, shift, resid, n, self.d, rad[lo:].data_ptr(), cmax, cs.data_ptr(),
+                                              status.data_ptr(), ws.data_ptr(), ws.numel(), st)
+                _lib.check(rc, "sss_range_search_count")
+                cs[m:] = status
+                host = cs.cpu().numpy()
+                counts, bad = host[:m], np.flatnonzero(host[m:])
+                D, I = self._range_fill(m, counts, lambda lims, D, I: L.sss_range_search_fill(
+                    m, lims.data_ptr(), self.id_offset, D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), st),
+                    "sss_range_search_fill")
+                pieces.append((np.arange(lo, lo + m, dtype=np.int64), counts, D, I))
+                left.extend((bad + lo).tolist())
+            self.last_range_overflow_queries = len(left)
+        else:
+            left = range(nq)
+        if len(left):
+            metric = 0 if self.metric == "ip" else 1
+            rows = torch.as_tensor(np.asarray(left, dtype=np.int32), device=self.device)
+            per = max(1, min(65535, _EXHAUSTIVE_WS_BYTES // max(1, 4 * n)))
+            for lo in range(0, rows.numel(), per):
+                sel = rows[lo:lo + per].contiguous()
+                m = sel.numel()
+                ws = self._workspace(L.sss_range_search_exhaustive_workspace_bytes(m, n))
+                counts_t = torch.empty(m, dtype=torch.int64, device=self.device)
+                rc = L.sss_range_search_exhaustive_count(q.data_ptr(), sel.data_ptr(), m, self._xb.data_ptr(), n, self.d,
+                                                         DTYPE_CODE[self.dtype], metric, rad.data_ptr(), counts_t.data_ptr(),
+                                                         ws.data_ptr(), ws.numel(), st)
+                _lib.check(rc, "sss_range_search_exhaustive_count")
+                counts = counts_t.cpu().numpy()
+                D, I = self._range_fill(m, counts, lambda lims, D, I: L.sss_range_search_exhaustive_fill(
+                    sel.data_ptr(), m, n, metric, rad.data_ptr(), lims.data_ptr(), self.id_offset, D.data_ptr(), I.data_ptr(),
+                    ws.data_ptr(), ws.numel(), st), "sss_range_search_exhaustive_fill")
+                pieces.append((np.asarray(left[lo:lo + m], dtype=np.int64), counts, D, I))
+        return self._range_merge(nq, pieces)
+
+    def _range_fill(self, m, counts, fill, what):
+        """Allocate one piece's output from its host counts and run its fill call (no-op when it is empty)."""
+        lims_h = np.zeros(m + 1, dtype=np.int64)
+        np.cumsum(counts, out=lims_h[1:])
+        total = int(lims_h[-1])
+        D = torch.empty(total, dtype=torch.float32, device=self.device)
+        I = torch.empty(total, dtype=torch.int64, device=self.device)
+        if total:
+            lims = torch.from_numpy(lims_h).to(self.device)
+            _lib.check(fill(lims, D, I), what)
+        return D, I
+
+    def _range_merge(self, nq, pieces):
+        """One (lims, D, I) in query order from the pieces of the two routes."""
+        counts = np.zeros(nq, dtype=np.int64)
+        for rows, cnt, _, _ in pieces:
+            counts[rows] = cnt
+        lims_h = np.zeros(nq + 1, dtype=np.int64)
+        np.cumsum(counts, out=lims_h[1:])
+        lims = torch.from_numpy(lims_h).to(self.device)
+        total = int(lims_h[-1])
+        live = [p for p in pieces if p[2].numel()]
+        if len(live) == 1 and len(live[0][0]) == nq:        # one piece holds every query, in order: it IS the result
+            return lims, live[0][2], live[0][3]
+        D = torch.empty(total, dtype=torch.float32, device=self.device)
+        I = torch.empty(total, dtype=torch.int64, device=self.device)
+        for rows, cnt, Dp, Ip in live:
+            own = np.zeros(len(rows) + 1, dtype=np.int64)
+            np.cumsum(cnt, out=own[1:])
+            # destination of entry j of the piece's query t: lims[rows[t]] + (j - own[t])
+            shift = torch.from_numpy(np.repeat(lims_h[rows] - own[:-1], cnt)).to(self.device)
+            dest = shift + torch.arange(Dp.numel(), dtype=torch.int64, device=self.device)
+            D[dest] = Dp
+            I[dest] = Ip
+        return lims, D, I
+
+    def range_search(self, x, radius):
+        """``index.range_search(x, radius) -> (lims, D, I)`` (faiss): numpy in -> numpy out, tensor in -> tensors.
+        ``radius``: a scalar (faiss) or one value per query."""
+        is_np = isinstance(x, np.ndarray)
+        q = self._rows(x, "range_search")
+        lims, D, I = self.range_search_device(q, radius)
+        if is_np:
+            return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
+        return lims, D, I
 
 
 def build_index(emb, metric: str, device=None) -> FlatIndex:
