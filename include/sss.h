@@ -51,8 +51,9 @@ int sss_f32_to_bf16(const float* x, int64_t count, uint16_t* y, void* stream);
  * k <= 500.  Writes D_out [nq, k] fp32 (descending) and I_out [nq, k] int64 = row + id_offset,
  * ordered by (score desc, id asc); missing results: I = -1, D = -FLT_MAX (faiss convention).
  * Scores are the canonical ones of DESIGN.md (float64 sequential dot of the stored elements,
- * rounded to float32).  status [nq] int32: 0 = proven exact, 1 = not proven (caller re-runs those
- * queries through sss_ip_topk_exhaustive); unproven_count (may be NULL): device int32 that is
+ * rounded to float32).  status [nq] int32: 0 = proven exact, != 0 = not proven, a mask of the reasons
+ * (1, 2, 4: csrc/select.hip) -- the caller re-runs those queries through sss_ip_topk_threshold /
+ * sss_ip_topk_exhaustive; unproven_count (may be NULL): device int32 that is
  * incremented once per unproven query (never reset here), so a caller can run many batches
  * without a host sync and check once.  corpus_max_norm = max row 2-norm of the corpus (for
  * the error bound).  workspace: 256-byte aligned, sss_ip_topk_workspace_bytes() bytes (0 = shape
