@@ -101,7 +101,10 @@ int sss_ip_topk_split(const float* q, int64_t nq, const float* corpus, const uin
  * (any upper bound is valid; the worst case is 2^-11 * corpus_max_norm).  Coarser than the other
  * scans (~4e-4 |q||c| at d = 128), so more near-ties are left unproven (status != 0) and go to
  * sss_ip_topk_exhaustive; results for status 0 are identical.
- * q float32 [nq, d]; workspace: sss_ip_topk_f16_workspace_bytes(nq, n, d, k); state as above. */
+ * q float32 [nq, d]; workspace: sss_ip_topk_f16_workspace_bytes(nq, n, d, k); state as above.
+ * Every search entry point checks what it scans the same way, before its workspace: a missing or not 16-byte aligned
+ * image (the corpus itself for sss_ip_topk), corpus_shift outside [-160, 160] or a negative / NaN corpus_resid_norm
+ * for an f16 image: -1. */
 int sss_abs_max(const float* x, int64_t count, float* out, void* stream);   /* max |x_i| -> *out (device, caller zeroes); count % 4 == 0 */
 int sss_f16_shift(float amax);                                              /* host helper: the shift for a largest magnitude */
 int sss_scale_f16(const float* x, int64_t count, int shift, uint16_t* y, void* stream);   /* count % 8 == 0 */

@@ -2,6 +2,10 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <mutex>
+#include <set>
+#include <utility>
+
 #include "../../include/sss.h"
 #include "sss_common.h"
 #include "scan.h"
@@ -27,40 +31,28 @@ int check_launch(const char* what) {
     return SSS_OK;
 }
 
-// implemented in the kernel translation units
-size_t ip_topk_workspace_bytes(long nq, long n, int d, int k, int dtype);
-size_t ip_topk_state_bytes(long nq);
-int ip_topk(const void*, long, const void*, long, int, int, int, long, float, float*, long*, int*, int*, void*, size_t, void*,
-            size_t, hipStream_t);
-int ip_topk_split(const float*, long, const float*, const void*, long, int, int, long, float, float*, long*, int*, int*, void*,
-                  size_t, void*, size_t, hipStream_t);
+int opt_in_lds(const void* kernel, const char* name, size_t bytes) {
+    static std::mutex mu;
+    static std::set<std::pair<const void*, int>> done;          // (kernel, device) pairs opted in
+    const std::pair<const void*, int> key(kernel, current_device());
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.count(key)) return SSS_OK;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: opting in to %zu bytes of LDS failed: %s", name, bytes, hipGetErrorString(e));
+        return SSS_EHIP;
+    }
+    done.insert(key);
+    return SSS_OK;
+}
+
+// implemented in the kernel translation units (the search family: scan.h)
 int split_bf16(const float*, long, int, unsigned short*, hipStream_t);
-int ip_topk_f16(const float*, long, const float*, const void*, int, float, long, int, int, long, float, float*, long*, int*, int*,
-                void*, size_t, void*, size_t, hipStream_t);
 int f16_resid_max(const float*, const unsigned short*, long, int, int, float*, hipStream_t);
-size_t ip_topk_scan_workspace_bytes(long, long, int, int, int);
-size_t ip_topk_long_workspace_bytes(long, long, int, int);
-int ip_topk_long(const void*, long, const void*, int, const void*, int, float, long, int, int, long, float, float*, long*, int*, void*,
-                 size_t, hipStream_t);
-size_t ip_topk_threshold_workspace_bytes(long, long, int, int);
-int ip_topk_threshold(const void*, const int*, long, const void*, int, const void*, int, int, float, long, int, int, long, float,
-                      float*, long*, int*, void*, size_t, hipStream_t);
 int abs_max(const float*, long, float*, hipStream_t);
-size_t range_search_workspace_bytes(long, long, int, int);
-int range_search_count(const void*, long, const void*, int, const void*, int, int, float, long, int, const float*, float, long*, int*, void*,
-                       size_t, hipStream_t);
-int range_search_fill(long, const long*, long, float*, long*, const void*, size_t, hipStream_t);
-size_t range_exhaustive_workspace_bytes(long, long);
-int range_exhaustive_count(const void*, const int*, long, const void*, long, int, int, int, const float*, long*, void*, size_t, hipStream_t);
-int range_exhaustive_fill(const int*, long, long, int, const float*, const long*, long, float*, long*, const void*, size_t, hipStream_t);
 int scale_f16(const float*, long, int, unsigned short*, hipStream_t);
 int topk_merge(const float*, long, const long*, long, int, long, int, float*, long*, hipStream_t);
-int scan_boot_expired(int);
-int profile_enable(int);
-int profile_read(double*, int*);
-size_t ip_topk_exhaustive_workspace_bytes(long nsel, long n);
-int ip_topk_exhaustive(const void*, const int*, long, const void*, long, int, int, int, long, int, const float*, float*, long*,
-                       void*, size_t, hipStream_t);
 int normalize_rows(float*, long, int, long, float, int, hipStream_t);
 int row_norm_max(const void*, long, int, int, float*, hipStream_t);
 int f32_to_bf16(const float*, long, unsigned short*, hipStream_t);
@@ -166,7 +158,6 @@ size_t sss_ip_topk_long_workspace_bytes(int64_t nq, int64_t n, int d, int dtype)
 int sss_ip_topk_long(const void* q, int64_t nq, const void* corpus, int dtype, const void* scan_image, int corpus_shift,
                      float corpus_resid_norm, int64_t n, int d, int k, int64_t id_offset, float corpus_max_norm, float* D_out,
                      int64_t* I_out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
-    if (dtype != 0 && dtype != 1) { sss::set_error("ip_topk_long: dtype must be 0 (f32) or 1 (bf16)"); return SSS_EINVAL; }
     return sss::ip_topk_long(q, nq, corpus, dtype, scan_image, corpus_shift, corpus_resid_norm, n, d, k, id_offset,
                              corpus_max_norm, D_out, reinterpret_cast<long*>(I_out), status, workspace, workspace_bytes,
                              ST(stream));

@@ -539,17 +539,8 @@ int ip_topk_exhaustive(const void* q, const int* qsel, long nsel, const void* c,
         unsigned* cnt_eq = reinterpret_cast<unsigned*>(p);               p += (size_t)nsel * nslabs * 4;
         unsigned* T0 = reinterpret_cast<unsigned*>(p);                   p += (size_t)nsel * 4;
         unsigned* total = reinterpret_cast<unsigned*>(p);
-        static bool head_attr[MAX_DEVICES] = {};
-        const int hdev = current_device();
-        if (!head_attr[hdev]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_threshold), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    CP_HEAD * 4) != hipSuccess) {
-                (void)hipGetLastError();
-                set_error("k_head_threshold: opting in to %d bytes of LDS failed", CP_HEAD * 4);
-                return SSS_EHIP;
-            }
-            head_attr[hdev] = true;
-        }
+        rc = opt_in_lds(reinterpret_cast<const void*>(&k_head_threshold), "k_head_threshold", (size_t)CP_HEAD * 4);
+        if (rc) return rc;
         hipLaunchKernelGGL(k_head_threshold, dim3((unsigned)nsel), dim3(RS_THREADS), (size_t)CP_HEAD * 4, st, scores, n, k, metric, T0);
         rc = check_launch("k_head_threshold");
         if (rc) return rc;

@@ -52,6 +52,38 @@ static bool fused_shape_ok(int d, int dtype) {
     return (dtype == DT_F32 || dtype == DT_BF16 || dtype == DT_SPLIT || dtype == DT_F16) && (rb == 256 || rb == 512 || rb == 1024);
 }
 
+// scan_dtype: what k_scan reads for rows of exact_dtype -- f32 rows: themselves, their split or their f16 image; bf16
+// rows: themselves.
+int check_scan_source(const char* what, int exact_dtype, int scan_dtype, int d, bool long_rows, const void* c_scan, int corpus_shift,
+                      float corpus_resid, long n, long nq) {
+    static const char* const image[] = {"f32 corpus", "bf16 corpus", "split image", "f16 image"};
+    const bool paired = exact_dtype == DT_F32 ? (scan_dtype == DT_F32 || scan_dtype == DT_SPLIT || scan_dtype == DT_F16)
+                                              : exact_dtype == DT_BF16 && scan_dtype == DT_BF16;
+    if (!paired || !(long_rows ? long_shape_ok(d, exact_dtype, scan_dtype) : fused_shape_ok(d, scan_dtype))) {
+        set_error("%s: no scan of type %d for dtype %d, d %d", what, scan_dtype, exact_dtype, d);
+        return SSS_EINVAL;
+    }
+    if (!c_scan || (reinterpret_cast<uintptr_t>(c_scan) & 15)) {
+        set_error("%s: scan image (the %s) missing or not 16-byte aligned", what, image[scan_dtype]);
+        return SSS_EINVAL;
+    }
+    if (scan_dtype == DT_F16 && (corpus_shift < -160 || corpus_shift > 160 || !(corpus_resid >= 0.f))) {
+        set_error("%s: corpus_shift %d outside [-160, 160] or corpus_resid_norm %g not >= 0", what, corpus_shift, (double)corpus_resid);
+        return SSS_EINVAL;
+    }
+    if (n >= (1L << 31) - 1024 || nq >= (1L << 31)) { set_error("%s: n and nq must be < 2^31", what); return SSS_EINVAL; }
+    return SSS_OK;
+}
+
+ThrArgs thr_args(const void* q, const void* c_exact, int exact_dtype, int scan_dtype, int corpus_shift, float corpus_resid,
+                 float corpus_max_norm, const int* qsel, long nsel, long n, int d, int k, int cap, long id_offset) {
+    ThrArgs t = {};
+    t.Q = q; t.C = c_exact; t.qsel = qsel; t.nsel = (int)nsel; t.d = d; t.dtype = exact_dtype; t.k = k; t.cap = cap; t.n = n;
+    t.scan_dtype = scan_dtype; t.corpus_shift = corpus_shift; t.corpus_resid = corpus_resid; t.corpus_max_norm = corpus_max_norm;
+    t.id_offset = id_offset;
+    return t;
+}
+
 size_t ip_topk_state_bytes(long nq) { return nq > 0 ? state_words(nq) * 4 : 0; }
 
 size_t ip_topk_workspace_bytes(long nq, long n, int d, int k, int dtype) {      // dtype: the C ABI's (0 / 1)
@@ -67,25 +99,22 @@ size_t ip_topk_scan_workspace_bytes(long nq, long n, int d, int k, int scan_dtyp
 // scan_dtype: what k_scan reads at c_scan (DT_F32 / DT_BF16: the corpus itself; DT_SPLIT: the
 // [hi | lo] bf16 image of an f32 corpus; DT_F16: its scaled f16 image, corpus * 2^corpus_shift);
 // c_exact / exact_dtype: the rows the candidates are re-scored from (and the element type of q).
-static int ip_topk_impl(const void* q, long nq, const void* c_scan, int scan_dtype, int corpus_shift, float corpus_resid,
-                        const void* c_exact,
+static int ip_topk_impl(const char* what, const void* q, long nq, const void* c_scan, int scan_dtype, int corpus_shift,
+                        float corpus_resid, const void* c_exact,
                         int exact_dtype, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out,
                         int* status, int* unproven_count, void* state, size_t state_bytes, void* ws, size_t ws_bytes,
                         hipStream_t st) {
-    if (nq <= 0 || n <= 0 || k <= 0) { set_error("ip_topk: nq, n, k must be positive"); return SSS_EINVAL; }
-    if (!fused_shape_ok(d, scan_dtype)) {
-        set_error("ip_topk: need dtype 0 (f32, d in {64,128,256}) or 1 (bf16, d in {128,256,512}); got dtype %d d %d", exact_dtype, d);
-        return SSS_EINVAL;
-    }
-    if (n >= (1L << 31) - 1024 || nq >= (1L << 31)) { set_error("ip_topk: n and nq must be < 2^31 per shard"); return SSS_EINVAL; }
-    if (k > 500) { set_error("ip_topk: k too large (max 500)"); return SSS_EINVAL; }
+    if (nq <= 0 || n <= 0 || k <= 0) { set_error("%s: nq, n, k must be positive", what); return SSS_EINVAL; }
+    int rc = check_scan_source(what, exact_dtype, scan_dtype, d, false, c_scan, corpus_shift, corpus_resid, n, nq);
+    if (rc) return rc;
+    if (k > 500) { set_error("%s: k too large (max 500)", what); return SSS_EINVAL; }
     if ((reinterpret_cast<uintptr_t>(ws) & 255) || (reinterpret_cast<uintptr_t>(state) & 15)) {
-        set_error("ip_topk: workspace must be 256-byte aligned, state 16-byte aligned");
+        set_error("%s: workspace must be 256-byte aligned, state 16-byte aligned", what);
         return SSS_EINVAL;
     }
-    if (!state || state_bytes < ip_topk_state_bytes(nq)) { set_error("ip_topk: state %zu < %zu bytes", state_bytes, ip_topk_state_bytes(nq)); return SSS_EWORKSPACE; }
+    if (!state || state_bytes < ip_topk_state_bytes(nq)) { set_error("%s: state %zu < %zu bytes", what, state_bytes, ip_topk_state_bytes(nq)); return SSS_EWORKSPACE; }
     const ScanPlan p = make_plan(nq, n, d, k, scan_dtype);
-    if (ws_bytes < p.total_bytes) { set_error("ip_topk: workspace %zu < %zu", ws_bytes, p.total_bytes); return SSS_EWORKSPACE; }
+    if (ws_bytes < p.total_bytes) { set_error("%s: workspace %zu < %zu", what, ws_bytes, p.total_bytes); return SSS_EWORKSPACE; }
     char* w = reinterpret_cast<char*>(ws);
 
     ScanArgs a;
@@ -101,7 +130,7 @@ static int ip_topk_impl(const void* q, long nq, const void* c_scan, int scan_dty
     Prof& pr = g_prof[current_device()];
     const bool prof = pr.on && pr.n < PROF_RING;
     if (prof) (void)hipEventRecord(pr.ev[2 * pr.n], st);
-    int rc = launch_scan(scan_dtype, d, p.tile_rows, a, st);
+    rc = launch_scan(scan_dtype, d, p.tile_rows, a, st);
     if (prof) { (void)hipEventRecord(pr.ev[2 * pr.n + 1], st); ++pr.n; }
     if (rc) return rc;                 // nothing ran: the state is still clean
 
@@ -114,6 +143,25 @@ static int ip_topk_impl(const void* q, long nq, const void* c_scan, int scan_dty
     rc = launch_select(s, st);
     if (rc) (void)hipMemsetAsync(state, 0, ip_topk_state_bytes(nq), st);   // the scan dirtied it and nobody will clear it
     return rc;
+}
+
+// Threshold form of k_scan (sss_ip_topk_threshold, sss_range_search_count): `prepare` writes the thresholds t.thr and
+// zeroes the counters t.cnt of the t.nsel queries t.qsel, the scan keeps every row above its query's threshold in
+// t.cand, `select` re-scores them.
+template <class Prepare, class Select>
+static int run_threshold_form(const ThrArgs& t, const void* c_scan, const ScanPlan& p, Prepare prepare, Select select, hipStream_t st) {
+    int rc = prepare();
+    if (rc) return rc;
+    ScanArgs a = {};
+    a.Q = t.Q; a.C = c_scan; a.nq = t.nsel; a.n = (int)t.n;
+    a.tiles_per_split = p.tiles_per_split; a.total_tiles = p.total_tiles;
+    a.S = p.S; a.G = p.G; a.J = 0; a.Ju = 0; a.cert = 1; a.boot = 0; a.append = 0; a.cap = p.cap;
+    a.slots = nullptr; a.cnt = t.cnt; a.maxlast = nullptr;
+    a.cand = const_cast<unsigned long long*>(t.cand);
+    a.qsel = t.qsel; a.thr = t.thr;
+    rc = launch_scan(t.scan_dtype, t.d, p.tile_rows, a, st);
+    if (rc) return rc;
+    return select();
 }
 
 // Threshold rung for the queries `qsel` a fused search left unproven (select.hip: THRESHOLD RUNG).
@@ -130,39 +178,20 @@ int ip_topk_threshold(const void* q, const int* qsel, long nsel, const void* c_e
                       int scan_dtype, int corpus_shift, float corpus_resid, long n, int d, int k, long id_offset,
                       float corpus_max_norm, float* D_out, long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st) {
     if (nsel <= 0 || n <= 0 || k <= 0 || !qsel) { set_error("ip_topk_threshold: nsel, n, k must be positive"); return SSS_EINVAL; }
-    if (exact_dtype != DT_F32 && exact_dtype != DT_BF16) { set_error("ip_topk_threshold: dtype must be 0 (f32) or 1 (bf16)"); return SSS_EINVAL; }
-    const bool native = scan_dtype == exact_dtype;
-    if (!fused_shape_ok(d, scan_dtype) || (!native && (exact_dtype != DT_F32 || (scan_dtype != DT_SPLIT && scan_dtype != DT_F16)))) {
-        set_error("ip_topk_threshold: no scan of type %d for dtype %d, d %d", scan_dtype, exact_dtype, d);
-        return SSS_EINVAL;
-    }
-    if (!c_scan || (reinterpret_cast<uintptr_t>(c_scan) & 15)) { set_error("ip_topk_threshold: scan image missing or not 16-byte aligned"); return SSS_EINVAL; }
-    if (n >= (1L << 31) - 1024 || nsel >= (1L << 31)) { set_error("ip_topk_threshold: n and nsel must be < 2^31"); return SSS_EINVAL; }
+    const int rc = check_scan_source("ip_topk_threshold", exact_dtype, scan_dtype, d, false, c_scan, corpus_shift, corpus_resid, n, nsel);
+    if (rc) return rc;
     if (k > THR_CAP) { set_error("ip_topk_threshold: k too large (max %d)", THR_CAP); return SSS_EINVAL; }
     if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("ip_topk_threshold: workspace must be 256-byte aligned"); return SSS_EINVAL; }
     const ScanPlan p = make_thr_plan(nsel, n, d, scan_dtype, THR_CAP);
     if (ws_bytes < thr_head_bytes(nsel) + p.total_bytes) { set_error("ip_topk_threshold: workspace %zu < %zu", ws_bytes, thr_head_bytes(nsel) + p.total_bytes); return SSS_EWORKSPACE; }
     char* w = reinterpret_cast<char*>(ws);
-    ThrArgs t;
-    t.Q = q; t.C = c_exact; t.qsel = qsel; t.nsel = (int)nsel; t.d = d; t.dtype = exact_dtype; t.k = k; t.cap = p.cap; t.n = n;
-    t.scan_dtype = scan_dtype; t.corpus_shift = corpus_shift; t.corpus_resid = corpus_resid; t.corpus_max_norm = corpus_max_norm;
-    t.id_offset = id_offset;
+    ThrArgs t = thr_args(q, c_exact, exact_dtype, scan_dtype, corpus_shift, corpus_resid, corpus_max_norm, qsel, nsel, n, d, k, p.cap,
+                         id_offset);
     t.thr = reinterpret_cast<float*>(w);
     t.cnt = reinterpret_cast<unsigned*>(w + (size_t)nsel * 4);
     t.cand = reinterpret_cast<unsigned long long*>(w + thr_head_bytes(nsel));
     t.D_out = D_out; t.I_out = I_out; t.status = status;
-    int rc = launch_thr_prepare(t, st);
-    if (rc) return rc;
-    ScanArgs a = {};
-    a.Q = q; a.C = c_scan; a.nq = (int)nsel; a.n = (int)n;
-    a.tiles_per_split = p.tiles_per_split; a.total_tiles = p.total_tiles;
-    a.S = p.S; a.G = p.G; a.J = 0; a.Ju = 0; a.cert = 1; a.boot = 0; a.append = 0; a.cap = p.cap;
-    a.slots = nullptr; a.cnt = t.cnt; a.maxlast = nullptr;
-    a.cand = const_cast<unsigned long long*>(t.cand);
-    a.qsel = qsel; a.thr = t.thr;
-    rc = launch_scan(scan_dtype, d, p.tile_rows, a, st);
-    if (rc) return rc;
-    return launch_select_all(t, st);
+    return run_threshold_form(t, c_scan, p, [&] { return launch_thr_prepare(t, st); }, [&] { return launch_select_all(t, st); }, st);
 }
 
 // RANGE SEARCH, fused route (select.hip: RANGE SEARCH): the threshold rung's scan with thresholds from per-query radii.
@@ -180,45 +209,21 @@ int range_search_count(const void* q, long nq, const void* c_exact, int exact_dt
                        float corpus_resid, long n, int d, const float* radius, float corpus_max_norm, long* counts, int* status, void* ws,
                        size_t ws_bytes, hipStream_t st) {
     if (nq <= 0 || n <= 0) { set_error("range_search_count: nq, n must be positive"); return SSS_EINVAL; }
-    if (exact_dtype != DT_F32 && exact_dtype != DT_BF16) { set_error("range_search_count: dtype must be 0 (f32) or 1 (bf16)"); return SSS_EINVAL; }
-    const bool native = scan_dtype == exact_dtype;
-    if (!fused_shape_ok(d, scan_dtype) || (!native && (exact_dtype != DT_F32 || (scan_dtype != DT_SPLIT && scan_dtype != DT_F16)))) {
-        set_error("range_search_count: no scan of type %d for dtype %d, d %d", scan_dtype, exact_dtype, d);
-        return SSS_EINVAL;
-    }
-    if (!c_scan || (reinterpret_cast<uintptr_t>(c_scan) & 15)) { set_error("range_search_count: scan image missing or not 16-byte aligned"); return SSS_EINVAL; }
+    const int rc = check_scan_source("range_search_count", exact_dtype, scan_dtype, d, false, c_scan, corpus_shift, corpus_resid, n, nq);
+    if (rc) return rc;
     if (!q || !c_exact || !radius || !counts || !status) { set_error("range_search_count: q, corpus, radius, counts and status are required"); return SSS_EINVAL; }
-    if (scan_dtype == DT_F16 && (corpus_shift < -160 || corpus_shift > 160 || !(corpus_resid >= 0.f))) {
-        set_error("range_search_count: corpus_shift out of range or corpus_resid_norm < 0");
-        return SSS_EINVAL;
-    }
-    if (n >= (1L << 31) - 1024 || nq >= (1L << 31)) { set_error("range_search_count: n and nq must be < 2^31"); return SSS_EINVAL; }
     if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("range_search_count: workspace must be 256-byte aligned"); return SSS_EINVAL; }
     const ScanPlan p = make_thr_plan(nq, n, d, scan_dtype, THR_CAP);
     const size_t need = range_head_bytes(nq) + p.total_bytes;
     if (!ws || ws_bytes < need) { set_error("range_search_count: workspace %zu < %zu", ws_bytes, need); return SSS_EWORKSPACE; }
     char* w = reinterpret_cast<char*>(ws);
     int* qsel = reinterpret_cast<int*>(w + thr_head_bytes(nq));
-    ThrArgs t;
-    t.Q = q; t.C = c_exact; t.qsel = qsel; t.nsel = (int)nq; t.d = d; t.dtype = exact_dtype; t.k = 1; t.cap = p.cap; t.n = n;
-    t.scan_dtype = scan_dtype; t.corpus_shift = corpus_shift; t.corpus_resid = corpus_resid; t.corpus_max_norm = corpus_max_norm;
-    t.id_offset = 0;
+    ThrArgs t = thr_args(q, c_exact, exact_dtype, scan_dtype, corpus_shift, corpus_resid, corpus_max_norm, qsel, nq, n, d, 1, p.cap, 0);
     t.thr = reinterpret_cast<float*>(w);
     t.cnt = reinterpret_cast<unsigned*>(w + (size_t)nq * 4);
     t.cand = reinterpret_cast<unsigned long long*>(w + range_head_bytes(nq));
-    t.D_out = nullptr; t.I_out = nullptr; t.status = nullptr;
-    int rc = launch_range_prepare(t, radius, qsel, st);
-    if (rc) return rc;
-    ScanArgs a = {};
-    a.Q = q; a.C = c_scan; a.nq = (int)nq; a.n = (int)n;
-    a.tiles_per_split = p.tiles_per_split; a.total_tiles = p.total_tiles;
-    a.S = p.S; a.G = p.G; a.J = 0; a.Ju = 0; a.cert = 1; a.boot = 0; a.append = 0; a.cap = p.cap;
-    a.slots = nullptr; a.cnt = t.cnt; a.maxlast = nullptr;
-    a.cand = const_cast<unsigned long long*>(t.cand);
-    a.qsel = qsel; a.thr = t.thr;
-    rc = launch_scan(scan_dtype, d, p.tile_rows, a, st);
-    if (rc) return rc;
-    return launch_range_select(t, radius, counts, status, st);
+    return run_threshold_form(t, c_scan, p, [&] { return launch_range_prepare(t, radius, qsel, st); },
+                              [&] { return launch_range_select(t, radius, counts, status, st); }, st);
 }
 
 int range_search_fill(long nq, const long* lims, long id_offset, float* D_out, long* I_out, const void* ws, size_t ws_bytes,
@@ -237,27 +242,22 @@ int range_search_fill(long nq, const long* lims, long id_offset, float* D_out, l
 int ip_topk(const void* q, long nq, const void* c, long n, int d, int k, int dtype, long id_offset,
             float corpus_max_norm, float* D_out, long* I_out, int* status, int* unproven_count, void* state,
             size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (dtype != DT_F32 && dtype != DT_BF16) { set_error("ip_topk: dtype must be 0 (f32) or 1 (bf16), got %d", dtype); return SSS_EINVAL; }
-    return ip_topk_impl(q, nq, c, dtype, 0, 0.f, c, dtype, n, d, k, id_offset, corpus_max_norm, D_out, I_out, status,
+    return ip_topk_impl("ip_topk", q, nq, c, dtype, 0, 0.f, c, dtype, n, d, k, id_offset, corpus_max_norm, D_out, I_out, status,
                         unproven_count, state, state_bytes, ws, ws_bytes, st);
 }
 
 int ip_topk_split(const float* q, long nq, const float* c, const void* c_split, long n, int d, int k, long id_offset,
                   float corpus_max_norm, float* D_out, long* I_out, int* status, int* unproven_count, void* state,
                   size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (!c_split || (reinterpret_cast<uintptr_t>(c_split) & 15)) { set_error("ip_topk_split: split image missing or not 16-byte aligned"); return SSS_EINVAL; }
-    return ip_topk_impl(q, nq, c_split, DT_SPLIT, 0, 0.f, c, DT_F32, n, d, k, id_offset, corpus_max_norm, D_out, I_out, status,
-                        unproven_count, state, state_bytes, ws, ws_bytes, st);
+    return ip_topk_impl("ip_topk_split", q, nq, c_split, DT_SPLIT, 0, 0.f, c, DT_F32, n, d, k, id_offset, corpus_max_norm, D_out,
+                        I_out, status, unproven_count, state, state_bytes, ws, ws_bytes, st);
 }
 
 int ip_topk_f16(const float* q, long nq, const float* c, const void* c_f16, int corpus_shift, float corpus_resid, long n, int d, int k,
                 long id_offset, float corpus_max_norm, float* D_out, long* I_out, int* status, int* unproven_count,
                 void* state, size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (!c_f16 || (reinterpret_cast<uintptr_t>(c_f16) & 15)) { set_error("ip_topk_f16: f16 image missing or not 16-byte aligned"); return SSS_EINVAL; }
-    if (corpus_shift < -160 || corpus_shift > 160) { set_error("ip_topk_f16: corpus_shift out of range"); return SSS_EINVAL; }
-    if (!(corpus_resid >= 0.f)) { set_error("ip_topk_f16: corpus_resid_norm must be >= 0"); return SSS_EINVAL; }
-    return ip_topk_impl(q, nq, c_f16, DT_F16, corpus_shift, corpus_resid, c, DT_F32, n, d, k, id_offset, corpus_max_norm, D_out, I_out,
-                        status, unproven_count, state, state_bytes, ws, ws_bytes, st);
+    return ip_topk_impl("ip_topk_f16", q, nq, c_f16, DT_F16, corpus_shift, corpus_resid, c, DT_F32, n, d, k, id_offset, corpus_max_norm,
+                        D_out, I_out, status, unproven_count, state, state_bytes, ws, ws_bytes, st);
 }
 
 }  // namespace sss

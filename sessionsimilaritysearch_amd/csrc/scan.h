@@ -37,13 +37,17 @@ constexpr int MAX_SLOTS = 128;  // admission-threshold slots per query (J <= MAX
 // A query's slot words start SLOT_STRIDE words apart whatever J is: the 1024 lines of a 1024-query batch then spread
 // over 512 KB of address space -- and with it over the memory channels -- instead of sitting in 64 contiguous KB that
 // every workgroup of the launch polls, fetches and hits with agent-scope atomics at the same moment (the bootstrap).
-#ifndef SSS_SLOT_STRIDE
-#define SSS_SLOT_STRIDE MAX_SLOTS
-#endif
-constexpr int SLOT_STRIDE = SSS_SLOT_STRIDE;
+constexpr int SLOT_STRIDE = MAX_SLOTS;
 constexpr unsigned ORD_NEG_INF = 0x007FFFFFu;   // f2ord(-inf); slot value 0 = "never written"
 
 static inline int elem_bytes(int dtype) { return (dtype == DT_BF16 || dtype == DT_F16) ? 2 : 4; }
+
+// Row shapes of sss_ip_topk_long: d % 64 == 0 and exact rows of at most 16384 bytes (k_select_all keeps the query row in
+// LDS); f32 rows are scanned through their f16 image, bf16 rows directly.
+static inline bool long_shape_ok(int d, int exact_dtype, int scan_dtype) {
+    if (d <= 0 || d % 64 || d * elem_bytes(exact_dtype) > 16384) return false;
+    return (exact_dtype == DT_F32 && scan_dtype == DT_F16) || (exact_dtype == DT_BF16 && scan_dtype == DT_BF16);
+}
 
 // STATE words (caller-owned, zero before the first call; every call leaves them zero: the select
 // kernel, their last reader, clears what the call used -- no per-call memset launch).  Because the
@@ -141,5 +145,54 @@ int launch_range_prepare(const ThrArgs& a, const float* radius, int* qsel, hipSt
 int launch_range_select(const ThrArgs& a, const float* radius, long* counts, int* status, hipStream_t st);
 int launch_range_fill(const unsigned* cnt, const unsigned long long* cand, int cap, long nq, const long* lims, long id_offset, float* D,
                       long* I, hipStream_t st);
+
+// What every scanning search entry point checks about its scan source (ip_topk.hip), in this order: the (exact, scan)
+// element-type pairing and row shape (long_rows: long_shape_ok, else the fused scans' shapes), the image pointer and
+// its 16-byte alignment, a DT_F16 image's corpus_shift in [-160, 160] and corpus_resid >= 0, n and nq below 2^31.
+// SSS_EINVAL with a message that starts with `what` on the first failure.
+int check_scan_source(const char* what, int exact_dtype, int scan_dtype, int d, bool long_rows, const void* c_scan, int corpus_shift,
+                      float corpus_resid, long n, long nq);
+// The ThrArgs fields of a threshold-form search that do not depend on its workspace layout (ip_topk.hip); the rest is
+// null / zero until the caller sets thr / cnt / cand, the outputs it writes and the long-row extras.
+ThrArgs thr_args(const void* q, const void* c_exact, int exact_dtype, int scan_dtype, int corpus_shift, float corpus_resid,
+                 float corpus_max_norm, const int* qsel, long nsel, long n, int d, int k, int cap, long id_offset);
+
+// The search family behind the C ABI (capi.hip): ip_topk.hip, scan_long.hip, exhaustive.hip.
+size_t ip_topk_state_bytes(long nq);
+size_t ip_topk_workspace_bytes(long nq, long n, int d, int k, int dtype);
+size_t ip_topk_scan_workspace_bytes(long nq, long n, int d, int k, int scan_dtype);
+int ip_topk(const void* q, long nq, const void* c, long n, int d, int k, int dtype, long id_offset, float corpus_max_norm,
+            float* D_out, long* I_out, int* status, int* unproven_count, void* state, size_t state_bytes, void* ws, size_t ws_bytes,
+            hipStream_t st);
+int ip_topk_split(const float* q, long nq, const float* c, const void* c_split, long n, int d, int k, long id_offset,
+                  float corpus_max_norm, float* D_out, long* I_out, int* status, int* unproven_count, void* state,
+                  size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st);
+int ip_topk_f16(const float* q, long nq, const float* c, const void* c_f16, int corpus_shift, float corpus_resid, long n, int d, int k,
+                long id_offset, float corpus_max_norm, float* D_out, long* I_out, int* status, int* unproven_count,
+                void* state, size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st);
+size_t ip_topk_threshold_workspace_bytes(long nsel, long n, int d, int scan_dtype);
+int ip_topk_threshold(const void* q, const int* qsel, long nsel, const void* c_exact, int exact_dtype, const void* c_scan,
+                      int scan_dtype, int corpus_shift, float corpus_resid, long n, int d, int k, long id_offset,
+                      float corpus_max_norm, float* D_out, long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st);
+size_t range_search_workspace_bytes(long nq, long n, int d, int scan_dtype);
+int range_search_count(const void* q, long nq, const void* c_exact, int exact_dtype, const void* c_scan, int scan_dtype, int corpus_shift,
+                       float corpus_resid, long n, int d, const float* radius, float corpus_max_norm, long* counts, int* status, void* ws,
+                       size_t ws_bytes, hipStream_t st);
+int range_search_fill(long nq, const long* lims, long id_offset, float* D_out, long* I_out, const void* ws, size_t ws_bytes,
+                      hipStream_t st);
+size_t ip_topk_long_workspace_bytes(long nq, long n, int d, int dtype);
+int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, const void* c_scan, int corpus_shift,
+                 float corpus_resid, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out,
+                 int* status, void* ws, size_t ws_bytes, hipStream_t st);
+size_t ip_topk_exhaustive_workspace_bytes(long nsel, long n);
+int ip_topk_exhaustive(const void* q, const int* qsel, long nsel, const void* c, long n, int d, int k, int dtype, long id_offset,
+                       int metric, const float* lower_bound, float* D_out, long* I_out, void* ws, size_t ws_bytes, hipStream_t st);
+size_t range_exhaustive_workspace_bytes(long nsel, long n);
+int range_exhaustive_count(const void* q, const int* qsel, long nsel, const void* c, long n, int d, int dtype, int metric,
+                           const float* radius, long* counts, void* ws, size_t ws_bytes, hipStream_t st);
+int range_exhaustive_fill(const int* qsel, long nsel, long n, int metric, const float* radius, const long* lims, long id_offset,
+                          float* D_out, long* I_out, const void* ws, size_t ws_bytes, hipStream_t st);
+int profile_enable(int on);
+int profile_read(double* total_ms, int* launches);
 
 }  // namespace sss

@@ -49,7 +49,6 @@
 //     workgroups per CU (four waves per SIMD) on twice the splits.
 #include "scan.h"
 #include "scan_dev.h"
-#include <cstdlib>
 
 #ifndef SSS_STAGGER
 #define SSS_STAGGER 1
@@ -697,9 +696,8 @@ ScanPlan make_plan(long nq, long n, int d, int k, int dtype) {
     // The append form (k <= 16 on 256-byte rows of a 16-bit scan: no lane lists, half the registers) runs TWO
     // workgroups per CU on twice the splits; it needs the bootstrap (a shared threshold from the first live row on) and
     // splits long enough to be worth it -- otherwise the plan with lane lists.
-    static const int ap_off = getenv("SSS_SCAN_AP_OFF") ? 1 : 0;       // (dev A/B switch)
     const int rb = d * elem_bytes(dtype);
-    if (!ap_off && rb == 256 && dtype != DT_F32 && k <= KP && append_form_fits()) {
+    if (rb == 256 && dtype != DT_F32 && k <= KP && append_form_fits()) {
         const ScanPlan a = make_plan_for(nq, n, d, k, dtype, true);
         if (a.append) return a;
     }
@@ -793,13 +791,8 @@ ScanPlan make_thr_plan(long nsel, long n, int d, int scan_dtype, int cap) {
 template <int RB, int TR, int DT, int NW, bool THR, bool AP = false>
 static int launch_form(const ScanArgs& a, hipStream_t st) {
     const size_t lds = 2 * (size_t)TR * RB + NW * 2048;      // two tile buffers + the threshold-slot staging
-    static bool attr_done[MAX_DEVICES] = {};
-    const int dev = current_device();
-    if (!attr_done[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan<RB, TR, DT, NW, THR, AP>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done[dev] = true;
-    }
+    const int rc = opt_in_lds(reinterpret_cast<const void*>(&k_scan<RB, TR, DT, NW, THR, AP>), "k_scan", lds);
+    if (rc) return rc;
     hipLaunchKernelGGL((k_scan<RB, TR, DT, NW, THR, AP>), dim3(a.S * a.G), dim3(NW * 64), lds, st, a);
     return check_launch("k_scan");
 }

@@ -26,7 +26,6 @@
 // Two to three passes, the last one dominant; no per-lane list, no shared threshold slots, no bootstrap.
 #include "scan.h"
 #include <cmath>
-#include <cstdlib>
 #include "scan_dev.h"
 
 namespace sss {
@@ -321,11 +320,6 @@ constexpr int LONG_MAX_K = 1024;    // what the exhaustive kernels -- the path o
 static int long_cap(int d, int exact_dtype) { return d * elem_bytes(exact_dtype) > 10240 ? LONG_CAP / 2 : LONG_CAP; }
 static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-static bool long_shape_ok(int d, int exact_dtype, int scan_dtype) {
-    if (d <= 0 || d % 64 || d * elem_bytes(exact_dtype) > 16384) return false;     // (k_select_all keeps the query row in LDS)
-    return (exact_dtype == DT_F32 && scan_dtype == DT_F16) || (exact_dtype == DT_BF16 && scan_dtype == DT_BF16);
-}
-
 size_t ip_topk_long_workspace_bytes(long nq, long n, int d, int dtype) {
     const int scan = dtype == DT_F32 ? DT_F16 : DT_BF16;
     if (nq <= 0 || n <= 0 || !long_shape_ok(d, dtype, scan)) return 0;
@@ -338,9 +332,8 @@ int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, c
                  int* status, void* ws, size_t ws_bytes, hipStream_t st) {
     const int scan_dtype = exact_dtype == DT_F32 ? DT_F16 : DT_BF16;
     if (nq <= 0 || n <= 0 || k <= 0) { set_error("ip_topk_long: nq, n, k must be positive"); return SSS_EINVAL; }
-    if (!long_shape_ok(d, exact_dtype, scan_dtype)) { set_error("ip_topk_long: need dtype 0 / 1, d %% 64 == 0 and rows of at most 16384 bytes (got dtype %d d %d)", exact_dtype, d); return SSS_EINVAL; }
-    if (!c_scan || (reinterpret_cast<uintptr_t>(c_scan) & 15)) { set_error("ip_topk_long: scan image missing or not 16-byte aligned"); return SSS_EINVAL; }
-    if (n >= (1L << 31) - 1024 || nq >= (1L << 31)) { set_error("ip_topk_long: n and nq must be < 2^31"); return SSS_EINVAL; }
+    int rc = check_scan_source("ip_topk_long", exact_dtype, scan_dtype, d, true, c_scan, corpus_shift, corpus_resid, n, nq);
+    if (rc) return rc;
     if (k > LONG_MAX_K) { set_error("ip_topk_long: k too large (max %d)", LONG_MAX_K); return SSS_EINVAL; }
     const int cap = long_cap(d, exact_dtype);
     if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("ip_topk_long: workspace must be 256-byte aligned"); return SSS_EINVAL; }
@@ -357,7 +350,6 @@ int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, c
     // (the f16 query image, the identity selection, D_out at "no bound known", thresholds, counters, status and the
     //  per-query bound cache are written by ONE launch below, once the ThrArgs are filled: launch_long_setup)
     const void* q_scan = scan_dtype == DT_F16 ? qimg : q;
-    int rc = SSS_OK;
 
     // ---- levels (descending in level_tiles, run in reverse).  The first sample is as large as the capacity allows with
     // the threshold at -inf (cap rows: every sampled row is kept) -- a 32-tile level costs the time of ONE tile, the chip
@@ -386,26 +378,21 @@ int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, c
         }
         level_tiles[levels++] = first;
     }
-    ThrArgs t;
-    t.Q = q; t.C = c_exact; t.qsel = qsel; t.nsel = (int)nq; t.d = d; t.dtype = exact_dtype; t.k = k; t.cap = cap;
-    t.scan_dtype = scan_dtype; t.corpus_shift = corpus_shift; t.corpus_resid = corpus_resid; t.corpus_max_norm = corpus_max_norm;
-    t.id_offset = id_offset; t.thr = thr; t.cnt = cnt; t.cand = cand; t.D_out = D_out; t.I_out = I_out; t.status = status;
-    t.qb = qb; t.qb_ready = 0;
+    const size_t lds = LT_LDS_BYTES;
+    rc = scan_dtype == DT_F16 ? opt_in_lds(reinterpret_cast<const void*>(&k_scan_long<DT_F16>), "k_scan_long", lds)
+                              : opt_in_lds(reinterpret_cast<const void*>(&k_scan_long<DT_BF16>), "k_scan_long", lds);
+    if (rc) return rc;
+    ThrArgs t = thr_args(q, c_exact, exact_dtype, scan_dtype, corpus_shift, corpus_resid, corpus_max_norm, qsel, nq, n, d, k, cap,
+                         id_offset);
+    t.thr = thr; t.cnt = cnt; t.cand = cand; t.D_out = D_out; t.I_out = I_out; t.status = status;
+    t.qb = qb;
     rc = launch_long_setup(t, qsel, scan_dtype == DT_F16 ? qimg : nullptr, st);
     if (rc) return rc;
     t.qb_ready = 1;
     LongArgs a;
     a.Qimg = q_scan; a.C = c_scan; a.nq = (int)nq; a.n = (int)n; a.d = d; a.G = (int)((nq + LT_Q - 1) / LT_Q);
     a.total_tiles = total_tiles; a.cap = cap; a.thr = thr; a.cnt = cnt; a.cand = cand;
-    // groups per XCD (block map of k_scan_long): all of them (fewer measured slower, see the kernel); the switch stays
-    // for A/B runs
-    a.gpx = a.G;
-    if (a.G == 2 || a.G == 4 || a.G == 8) {
-        static const int gpx_env = getenv("SSS_LONG_GPX") ? atoi(getenv("SSS_LONG_GPX")) : 0;
-        if (gpx_env > 0 && a.G % gpx_env == 0 && 8 % (a.G / gpx_env) == 0) a.gpx = gpx_env;
-    }
-    static bool attr_done[MAX_DEVICES][2] = {};
-    const int dev = current_device();
+    a.gpx = a.G;                    // groups per XCD (block map of k_scan_long): all of them (fewer measured slower, see the kernel)
     // DISJOINT LEVELS (three levels and more).  The last sample used to be scanned twice: once as a sample, once more as
     // part of the whole corpus -- 9 % of the matrix work at 1M x 1600, K = 100.  Now the last sample takes EVERY R-th
     // tile (R = the planned ratio, rounded, >= 2) and the final level only the tiles in between: the rows the sample kept
@@ -437,17 +424,9 @@ int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, c
         while (S > 8 && S > tiles) S -= 8;
         a.S = S;
         a.tiles_per_split = (tiles + S - 1) / S;
-        t.n = n;
         // (thresholds and counters of this level: written by launch_long_setup -- first level -- or by the previous level's
         //  launch_bound_prepare)
-        const size_t lds = LT_LDS_BYTES;
-        const int ti = scan_dtype == DT_F16 ? 0 : 1;
-        if (!attr_done[dev][ti]) {
-            if (ti == 0) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan_long<DT_F16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            else (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan_long<DT_BF16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_done[dev][ti] = true;
-        }
-        if (ti == 0) hipLaunchKernelGGL(k_scan_long<DT_F16>, dim3(a.S * a.G), dim3(LT_THREADS), lds, st, a);
+        if (scan_dtype == DT_F16) hipLaunchKernelGGL(k_scan_long<DT_F16>, dim3(a.S * a.G), dim3(LT_THREADS), lds, st, a);
         else hipLaunchKernelGGL(k_scan_long<DT_BF16>, dim3(a.S * a.G), dim3(LT_THREADS), lds, st, a);
         rc = check_launch("k_scan_long");
         if (rc) return rc;

@@ -1085,19 +1085,14 @@ __global__ void k_topk_merge(const float* __restrict__ D_in, long d_stride, cons
 // ------------------------------------------------------------------------------ host side
 int launch_select(const SelectArgs& a, hipStream_t st) {
     const int rb = a.d * elem_bytes(a.dtype);
-    const int dev = current_device();
     // the wave-per-query kernel serves the K2 <= 16 regime (class maxima + bootstrap: a few hundred
     // candidates per query); beyond it the lists run without the bootstrap and fill up (thousands of
     // candidates, more than a wave stages), which is the sort kernel's job
     if (a.K2 <= KP) {
         const size_t per_wave = (((size_t)FS_CAP * 8 + FS_K2 * 16 + 16 + rb) + 15) & ~(size_t)15;
         const size_t lds = 4 * per_wave;
-        static bool done[MAX_DEVICES] = {};
-        if (!done[dev]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_select_fast),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-            done[dev] = true;
-        }
+        const int rc = opt_in_lds(reinterpret_cast<const void*>(&k_select_fast), "k_select_fast", 160 * 1024 - 1024);
+        if (rc) return rc;
         hipLaunchKernelGGL(k_select_fast, dim3((unsigned)((a.nq + 3) / 4)), dim3(256), lds, st, a);
         return check_launch("k_select_fast");
     }
@@ -1106,12 +1101,8 @@ int launch_select(const SelectArgs& a, hipStream_t st) {
     while (cap_pow2 < a.cap || cap_pow2 < a.K2) cap_pow2 <<= 1;
     const size_t lds = (size_t)cap_pow2 * 8 + SEL_MAX_K2 * 8 + rb;
     if (lds > 150 * 1024) { set_error("select: candidate capacity %d too large", a.cap); return SSS_EINVAL; }
-    static bool done2[MAX_DEVICES] = {};
-    if (!done2[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_select_sort),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);     // (its static words take ~1.1 KB)
-        done2[dev] = true;
-    }
+    const int rc = opt_in_lds(reinterpret_cast<const void*>(&k_select_sort), "k_select_sort", 160 * 1024 - 4096);   // (its static words take ~1.1 KB)
+    if (rc) return rc;
     hipLaunchKernelGGL(k_select_sort, dim3((unsigned)a.nq), dim3(SORT_THREADS), lds, st, a, cap_pow2);
     return check_launch("k_select_sort");
 }
@@ -1140,13 +1131,9 @@ int launch_select_all(const ThrArgs& a, hipStream_t st) {
     const size_t stage_small = rb < 1024 ? 0 : (size_t)SA_ROWS_SMALL * (SA_BYTES + 16);
     const size_t lds = 2 * (size_t)cap_pow2 * 8 + ((rb + 15) & ~15) + stage;   // kept keys + survivors + the query row + the tile
     if (lds > 156 * 1024) { set_error("select_all: candidate capacity %d / row of %d bytes too large", a.cap, rb); return SSS_EINVAL; }
-    static bool done[MAX_DEVICES] = {};
-    const int dev = current_device();
-    if (!done[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_select_all<SA_ROWS_SMALL>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_select_all<SA_ROWS_FULL>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-        done[dev] = true;
-    }
+    int rc = opt_in_lds(reinterpret_cast<const void*>(&k_select_all<SA_ROWS_SMALL>), "k_select_all", 160 * 1024 - 4096);
+    if (!rc) rc = opt_in_lds(reinterpret_cast<const void*>(&k_select_all<SA_ROWS_FULL>), "k_select_all", 160 * 1024 - 4096);
+    if (rc) return rc;
     const int small = cap_pow2 < 2048 ? cap_pow2 : 2048;
     // (k <= 64: k + a few dozen survivors fit one 128-row group, and a 256-row group would fetch twice the clamped copies)
     if (a.k > 64) hipLaunchKernelGGL(k_select_all<SA_ROWS_SMALL>, dim3((unsigned)a.nsel), dim3(SORT_THREADS), 2 * (size_t)small * 8 + ((rb + 15) & ~15) + stage_small, st, a, small, 0);
@@ -1168,21 +1155,12 @@ int launch_range_select(const ThrArgs& a, const float* radius, long* counts, int
     const size_t fixed = ((rb + 15) & ~15) + stage;                    // the query row + the tile
     const size_t lds = 2 * (size_t)cap_pow2 * 8 + fixed;
     if (lds > 156 * 1024) { set_error("range_select: candidate capacity %d / row of %d bytes too large", a.cap, rb); return SSS_EINVAL; }
-    static bool done[MAX_DEVICES] = {};
-    const int dev = current_device();
-    if (!done[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_range_select<SA_ROWS_FULL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024 - 4096) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("k_range_select: opting in to %d bytes of LDS failed", 160 * 1024 - 4096);
-            return SSS_EHIP;
-        }
-        done[dev] = true;
-    }
+    int rc = opt_in_lds(reinterpret_cast<const void*>(&k_range_select<SA_ROWS_FULL>), "k_range_select", 160 * 1024 - 4096);
+    if (rc) return rc;
     const int small = cap_pow2 < 2048 ? cap_pow2 : 2048;
     hipLaunchKernelGGL(k_range_select<SA_ROWS_FULL>, dim3((unsigned)a.nsel), dim3(SORT_THREADS), 2 * (size_t)small * 8 + fixed, st, a, radius,
                        small, -1, counts, status);
-    int rc = check_launch("k_range_select");
+    rc = check_launch("k_range_select");
     if (rc || small == cap_pow2) return rc;
     hipLaunchKernelGGL(k_range_select<SA_ROWS_FULL>, dim3((unsigned)a.nsel), dim3(SORT_THREADS), lds, st, a, radius, cap_pow2, small,
                        counts, status);

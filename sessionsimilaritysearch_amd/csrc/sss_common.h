@@ -15,8 +15,11 @@ namespace sss {
 
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+// Opt `kernel` in to `bytes` of dynamic LDS on the current device, once per (device, kernel); SSS_EHIP, with the HIP
+// error cleared and a message naming `name` and the bytes, when the runtime refuses.
+int opt_in_lds(const void* kernel, const char* name, size_t bytes);
 
-// per-device one-time setup flags (hipFuncSetAttribute is per device); defined in scan.hip
+// per-device host state is indexed by current_device() (defined in scan.hip)
 constexpr int MAX_DEVICES = 64;
 int current_device();
 

@@ -163,13 +163,8 @@ int item_vote(const float* D, const long* I, long nq, int S, const long* items_p
     // 1024 queries ran in four rounds: 1.0 ms of config C3's step), then with the full capacity for the queries the first
     // launch had to leave (status 2; the others return at once).
     const int cap = VOTE_MAX_ENTRIES, cap_small = VOTE_SMALL_ENTRIES;
-    static bool done[64] = {};
-    int dev = 0; (void)hipGetDevice(&dev); if (dev < 0 || dev >= 64) dev = 0;
-    if (!done[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_item_vote), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)item_vote_lds_bytes(cap));
-        done[dev] = true;
-    }
+    const int rc = opt_in_lds(reinterpret_cast<const void*>(&k_item_vote), "k_item_vote", item_vote_lds_bytes(cap));
+    if (rc) return rc;
     hipLaunchKernelGGL(k_item_vote, dim3((unsigned)nq), dim3(VT), item_vote_lds_bytes(cap_small), st, D, I, S, items_ptr, items,
                        id_offset, n_sessions, K, cap_small, out_items, out_w, status, cap, 0);
     hipLaunchKernelGGL(k_item_vote, dim3((unsigned)nq), dim3(VT), item_vote_lds_bytes(cap), st, D, I, S, items_ptr, items,

@@ -339,6 +339,32 @@ class FlatIndex:
         self.corpus_max_norm()
         return mode
 
+    def _scan_image(self, mode: str):
+        """(image, scan code, corpus_shift, corpus_resid_norm) of what scan `mode` reads, the image brought up to date:
+        the scaled float16 image ("f16", and "long" for a float32 index), the bf16 hi|lo image ("split"), else the
+        index's own rows."""
+        if mode == "f16" or (mode == "long" and self.dtype == "f32"):
+            self._ensure_f16()
+            return self._f16, _SCAN_CODE["f16"], self._c_shift, self.corpus_resid_norm()
+        if mode == "split":
+            self._ensure_split()
+            return self._split, _SCAN_CODE["split"], 0, 0.0
+        return self._xb, DTYPE_CODE[self.dtype], 0, 0.0
+
+    def _require_d_aligned(self):
+        """The exhaustive kernels read rows in 16-byte pieces."""
+        if self.d % (4 if self.dtype == "f32" else 8):
+            raise _lib.SssError("d must be a multiple of 4 (f32) / 8 (bf16)")
+
+    def _exhaustive_chunks(self, rows: torch.Tensor, ws_bytes):
+        """(offset, query rows, workspace) per chunk of the device int32 `rows` whose [chunk, n] scores fit the exhaustive
+        workspace budget; ``ws_bytes(nsel, n)`` sizes a chunk's workspace."""
+        n = self.ntotal
+        per = max(1, min(65535, _EXHAUSTIVE_WS_BYTES // max(1, 4 * n)))
+        for lo in range(0, rows.numel(), per):
+            sel = rows[lo:lo + per].contiguous()
+            yield lo, sel, self._workspace(ws_bytes(sel.numel(), n))
+
     def _rows(self, x, what):
         """Input rows as a contiguous device tensor of the index's element type."""
         if isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16 and self.dtype == "bf16":
@@ -407,13 +433,12 @@ class FlatIndex:
         mode = self.last_scan = self.prepare(k)
         if mode == "":
             raise _lib.SssError("search_fused: this index / k has no fused path (use search)")
+        image, _, shift, resid = self._scan_image(mode)
         if mode == "long":
             ws = self._workspace(L.sss_ip_topk_long_workspace_bytes(nq, n, self.d, DTYPE_CODE[self.dtype]))
-            image = self._f16 if self.dtype == "f32" else self._xb
-            rc = L.sss_ip_topk_long(q.data_ptr(), nq, self._xb.data_ptr(), DTYPE_CODE[self.dtype], image.data_ptr(), self._c_shift,
-                                    self.corpus_resid_norm() if self.dtype == "f32" else 0.0, n, self.d, k, self.id_offset,
-                                    self.corpus_max_norm(), D.data_ptr(), I.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                                    ws.numel(), _lib.stream_ptr(self.device))
+            rc = L.sss_ip_topk_long(q.data_ptr(), nq, self._xb.data_ptr(), DTYPE_CODE[self.dtype], image.data_ptr(), shift, resid,
+                                    n, self.d, k, self.id_offset, self.corpus_max_norm(), D.data_ptr(), I.data_ptr(),
+                                    status.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
             _lib.check(rc, "sss_ip_topk_long")
             if unproven_count is not None:
                 unproven_count += (status != 0).sum().to(torch.int32)
@@ -430,11 +455,11 @@ class FlatIndex:
                 0 if unproven_count is None else unproven_count.data_ptr(),
                 self._state.data_ptr(), self._state.numel(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
         if mode == "f16":
-            rc = L.sss_ip_topk_f16(q.data_ptr(), nq, self._xb.data_ptr(), self._f16.data_ptr(), self._c_shift,
-                                   self.corpus_resid_norm(), n, self.d, k, self.id_offset, *tail)
+            rc = L.sss_ip_topk_f16(q.data_ptr(), nq, self._xb.data_ptr(), image.data_ptr(), shift, resid, n, self.d, k,
+                                   self.id_offset, *tail)
         elif mode == "split":
-            rc = L.sss_ip_topk_split(q.data_ptr(), nq, self._xb.data_ptr(), self._split.data_ptr(), n, self.d, k,
-                                     self.id_offset, *tail)
+            rc = L.sss_ip_topk_split(q.data_ptr(), nq, self._xb.data_ptr(), image.data_ptr(), n, self.d, k, self.id_offset,
+                                     *tail)
         else:
             rc = L.sss_ip_topk(q.data_ptr(), nq, self._xb.data_ptr(), n, self.d, k, DTYPE_CODE[self.dtype],
                                self.id_offset, *tail)
@@ -476,14 +501,7 @@ class FlatIndex:
         if mode == "" or rows.numel() == 0 or k > 8192:
             return rows
         L = _lib.lib()
-        if mode == "f16":
-            self._ensure_f16()
-            image, code, shift, resid = self._f16, 3, self._c_shift, self.corpus_resid_norm()
-        elif mode == "split":
-            self._ensure_split()
-            image, code, shift, resid = self._split, 2, 0, 0.0
-        else:
-            image, code, shift, resid = self._xb, DTYPE_CODE[self.dtype], 0, 0.0
+        image, code, shift, resid = self._scan_image(mode)
         sel = rows.to(device=self.device, dtype=torch.int32).contiguous()
         n = self.ntotal
         ws = self._workspace(L.sss_ip_topk_threshold_workspace_bytes(sel.numel(), n, self.d, code))
@@ -520,12 +538,8 @@ class FlatIndex:
         if rows is None:
             rows = torch.arange(q.shape[0], dtype=torch.int32, device=self.device)
         rows = rows.to(device=self.device, dtype=torch.int32).contiguous()
-        per = max(1, min(65535, _EXHAUSTIVE_WS_BYTES // max(1, 4 * n)))
         metric = 0 if self.metric == "ip" else 1
-        for lo in range(0, rows.numel(), per):
-            sel = rows[lo:lo + per].contiguous()
-            nbytes = L.sss_ip_topk_exhaustive_workspace_bytes(sel.numel(), n)
-            ws = self._workspace(nbytes)
+        for _, sel, ws in self._exhaustive_chunks(rows, L.sss_ip_topk_exhaustive_workspace_bytes):
             if bounded and metric == 0:
                 lb = D[sel.long(), k - 1].contiguous()
                 rc = L.sss_ip_topk_exhaustive_lb(q.data_ptr(), sel.data_ptr(), sel.numel(), self._xb.data_ptr(), n,
@@ -552,8 +566,7 @@ class FlatIndex:
             D.fill_(-3.4028234663852886e38 if self.metric == "ip" else 3.4028234663852886e38)
             I.fill_(-1)
             return D, I
-        if self.d % (4 if self.dtype == "f32" else 8):
-            raise _lib.SssError("d must be a multiple of 4 (f32) / 8 (bf16)")
+        self._require_d_aligned()
         if self.fused_ok(k):
             # the per-query workspace is 16 KB (fused scans) to 64 KB (long rows, threshold rung): the reference hands
             # `index.search` its whole test set at once (test_amazon_filterd.py:578), so large batches go in chunks
@@ -610,21 +623,13 @@ class FlatIndex:
         lims = torch.zeros(nq + 1, dtype=torch.int64, device=self.device)
         if nq == 0 or n == 0:
             return lims, torch.empty(0, dtype=torch.float32, device=self.device), torch.empty(0, dtype=torch.int64, device=self.device)
-        if self.d % (4 if self.dtype == "f32" else 8):
-            raise _lib.SssError("d must be a multiple of 4 (f32) / 8 (bf16)")
+        self._require_d_aligned()
         L, st = _lib.lib(), _lib.stream_ptr(self.device)
         pieces = []                     # (query rows [host int64], their counts [host int64], D, I) in the order they were produced
         mode = self.last_range_scan = self.rung_scan()
         left = []                       # query rows for the exhaustive route
         if mode:
-            if mode == "f16":
-                self._ensure_f16()
-                image, code, shift, resid = self._f16, _SCAN_CODE["f16"], self._c_shift, self.corpus_resid_norm()
-            elif mode == "split":
-                self._ensure_split()
-                image, code, shift, resid = self._split, _SCAN_CODE["split"], 0, 0.0
-            else:
-                image, code, shift, resid = self._xb, DTYPE_CODE[self.dtype], 0, 0.0
+            image, code, shift, resid = self._scan_image(mode)
             cmax = self.corpus_max_norm()
             for lo in range(0, nq, RANGE_CHUNK):
                 m = min(nq, lo + RANGE_CHUNK) - lo
@@ -649,11 +654,8 @@ class FlatIndex:
         if len(left):
             metric = 0 if self.metric == "ip" else 1
             rows = torch.as_tensor(np.asarray(left, dtype=np.int32), device=self.device)
-            per = max(1, min(65535, _EXHAUSTIVE_WS_BYTES // max(1, 4 * n)))
-            for lo in range(0, rows.numel(), per):
-                sel = rows[lo:lo + per].contiguous()
+            for lo, sel, ws in self._exhaustive_chunks(rows, L.sss_range_search_exhaustive_workspace_bytes):
                 m = sel.numel()
-                ws = self._workspace(L.sss_range_search_exhaustive_workspace_bytes(m, n))
                 counts_t = torch.empty(m, dtype=torch.int64, device=self.device)
                 rc = L.sss_range_search_exhaustive_count(q.data_ptr(), sel.data_ptr(), m, self._xb.data_ptr(), n, self.d,
                                                          DTYPE_CODE[self.dtype], metric, rad.data_ptr(), counts_t.data_ptr(),
