@@ -94,7 +94,60 @@ def _load_c():
         _lib.oracle_search_exact.restype = ctypes.c_int
         _lib.oracle_search_fp32.argtypes = _lib.oracle_search_exact.argtypes
         _lib.oracle_search_fp32.restype = ctypes.c_int
+        _lib.oracle_linear_chain.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                             ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_void_p, ctypes.c_int64]
+        _lib.oracle_linear_chain.restype = ctypes.c_int
+        _lib.oracle_fmaf.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int64]
+        _lib.oracle_fmaf.restype = None
     return _lib
+
+
+def linear_chain(x, w, bias=None):
+    """``x @ w.T + bias`` as the gfx950 grouped GEMM computes it, bit for bit (``oracle_linear_chain`` of
+    ``oracle/search_exact.c``): per element one correctly rounded float32 fma per k in the kernel's k order,
+    then the bias as a separate float32 add.  x [n, K], w [m, K], K a multiple of 32; returns float32 [n, m]."""
+    lib = _load_c()
+    x = np.ascontiguousarray(x, np.float32)
+    w = np.ascontiguousarray(w, np.float32)
+    n, K = x.shape
+    m = w.shape[0]
+    assert w.shape[1] == K and K % 32 == 0
+    b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+    assert b is None or b.shape == (m,)
+    out = np.empty((n, m), np.float32)
+    rc = lib.oracle_linear_chain(x.ctypes.data, K, w.ctypes.data, K, None if b is None else b.ctypes.data, n, m, K,
+                                 out.ctypes.data, m)
+    assert rc == 0
+    return out
+
+
+def fmaf(a, b, c):
+    """Element-wise C ``fmaf`` (one correct rounding of a*b + c) on float32 arrays of one shape."""
+    lib = _load_c()
+    a, b, c = (np.ascontiguousarray(v, np.float32) for v in (a, b, c))
+    assert a.shape == b.shape == c.shape
+    out = np.empty_like(a)
+    lib.oracle_fmaf(a.ctypes.data, b.ctypes.data, c.ctypes.data, out.ctypes.data, a.size)
+    return out
+
+
+# float32 epilogues of k_linear_grouped (act 1 and 3, and the post BatchNorm stage), each step one float32 rounding
+def relu32(v):
+    return np.maximum(np.asarray(v, np.float32), np.float32(0))
+
+
+def sign32(v):
+    """torch.sign: +-1, with 0 and NaN passing through unchanged."""
+    v = np.asarray(v, np.float32)
+    return np.where(v > 0, np.float32(1), np.where(v < 0, np.float32(-1), v)).astype(np.float32)
+
+
+def post32(v, scale, shift):
+    """relu(fl(fl(v * scale) + shift)): multiply, round, add, round -- no fused fma."""
+    v = np.asarray(v, np.float32)
+    p = (v * np.asarray(scale, np.float32)).astype(np.float32)
+    return relu32((p + np.asarray(shift, np.float32)).astype(np.float32))
 
 
 def search_exact(q, c, k, id_offset=0, threads=0):

@@ -32,7 +32,9 @@ __global__ __launch_bounds__(256) void k_csr_mean(const float* __restrict__ x, l
     }
 }
 
-// mode 0 mean, 1 add, 2 max over rows [ptr[g], ptr[g+1]); w (may be null) multiplies row r first.
+// mode 0 mean, 1 add, 2 max over rows [ptr[g], ptr[g+1]); w (may be null) multiplies row r first.  Empty segments give
+// zeros.  Inputs are finite by contract: a max over rows that are all -inf gives -inf (the oracle's isinf -> 0 does not
+// apply here; tests/test_variant_kernels_edges_gpu.py pins this).
 template <int LPR>
 __global__ __launch_bounds__(256) void k_segment_reduce(const float* __restrict__ x, long ld_x, const float* __restrict__ w,
                                                         const int* __restrict__ ptr, long n_graphs, int d, int mode,
