@@ -14,7 +14,7 @@ constexpr int EX_LD = EX_KC + 4;
 
 // scores[f][row] = float32( sum_k q[qsel[f]][k] * c[row][k] ) accumulated sequentially in
 // float64 (metric 0), or sum_k (q_k - c_k)^2 with one rounding per multiply and per add (1).
-// DT_BF16: q and c hold bf16; every element converts exactly to float32 on the way into LDS.
+// DT_BF16 / DT_H16: q and c hold bf16 / float16; every element converts exactly to float32 on the way into LDS.
 template <int DT>
 __global__ __launch_bounds__(64) void k_exact_scores(const void* __restrict__ Qv,
                                                      const int* __restrict__ qsel,
@@ -30,6 +30,7 @@ __global__ __launch_bounds__(64) void k_exact_scores(const void* __restrict__ Qv
     const char* q = reinterpret_cast<const char*>(Qv) + (size_t)qsel[f] * d * EB;
     auto to_f32 = [](const char* p, int i) -> float {
         if (DT == DT_F32) return reinterpret_cast<const float*>(p)[i];
+        if (DT == DT_H16) return (float)reinterpret_cast<const _Float16*>(p)[i];
         return __builtin_bit_cast(float, (unsigned)reinterpret_cast<const unsigned short*>(p)[i] << 16);
     };
     for (long row0 = (long)blockIdx.x * EX_ROWS; row0 < n; row0 += (long)gridDim.x * EX_ROWS) {
@@ -75,6 +76,7 @@ template <int D, int DT>
 __device__ __forceinline__ float q_elem(const void* qrow, int kx) {        // element kx of a (wave-uniform) query row
     if (DT == DT_F32) return reinterpret_cast<const float*>(qrow)[kx];
     const unsigned w = reinterpret_cast<const unsigned*>(qrow)[kx >> 1];
+    if (DT == DT_H16) return (float)__builtin_bit_cast(_Float16, (unsigned short)((kx & 1) ? w >> 16 : w & 0xFFFFu));
     return __builtin_bit_cast(float, (kx & 1) ? (w & 0xFFFF0000u) : (w << 16));
 }
 
@@ -103,8 +105,13 @@ __global__ __launch_bounds__(256) void k_exact_scores_rows(const void* __restric
             const unsigned u[4] = {c4.x, c4.y, c4.z, c4.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                r[8 * v + 2 * e] = __builtin_bit_cast(float, u[e] << 16);
-                r[8 * v + 2 * e + 1] = __builtin_bit_cast(float, u[e] & 0xFFFF0000u);
+                if (DT == DT_H16) {
+                    r[8 * v + 2 * e] = (float)__builtin_bit_cast(_Float16, (unsigned short)(u[e] & 0xFFFFu));
+                    r[8 * v + 2 * e + 1] = (float)__builtin_bit_cast(_Float16, (unsigned short)(u[e] >> 16));
+                } else {
+                    r[8 * v + 2 * e] = __builtin_bit_cast(float, u[e] << 16);
+                    r[8 * v + 2 * e + 1] = __builtin_bit_cast(float, u[e] & 0xFFFF0000u);
+                }
             }
         }
     }
@@ -501,8 +508,12 @@ static int launch_exact_scores(const void* q, const int* qsel, long nsel, const 
     else if (metric == 0 && dtype == DT_F32 && d == 256) SSS_ROWS(256, DT_F32);
     else if (metric == 0 && dtype == DT_BF16 && d == 128) SSS_ROWS(128, DT_BF16);
     else if (metric == 0 && dtype == DT_BF16 && d == 256) SSS_ROWS(256, DT_BF16);
+    else if (metric == 0 && dtype == DT_H16 && d == 128) SSS_ROWS(128, DT_H16);
+    else if (metric == 0 && dtype == DT_H16 && d == 256) SSS_ROWS(256, DT_H16);
     else if (dtype == DT_F32)
         hipLaunchKernelGGL(k_exact_scores<DT_F32>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
+    else if (dtype == DT_H16)
+        hipLaunchKernelGGL(k_exact_scores<DT_H16>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
     else
         hipLaunchKernelGGL(k_exact_scores<DT_BF16>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
 #undef SSS_ROWS
@@ -516,9 +527,9 @@ size_t ip_topk_exhaustive_workspace_bytes(long nsel, long n) {
 int ip_topk_exhaustive(const void* q, const int* qsel, long nsel, const void* c, long n, int d,
                        int k, int dtype, long id_offset, int metric, const float* lower_bound, float* D_out, long* I_out,
                        void* ws, size_t ws_bytes, hipStream_t st) {
-    if (nsel <= 0 || n <= 0 || k <= 0 || d <= 0 || (dtype != DT_F32 && dtype != DT_BF16) ||
+    if (nsel <= 0 || n <= 0 || k <= 0 || d <= 0 || !corpus_dtype_ok(dtype) ||
         d % (dtype == DT_F32 ? 4 : 8) || (metric != 0 && metric != 1)) {
-        set_error("ip_topk_exhaustive: need nsel, n, k > 0, d %% 4 == 0 (f32) / d %% 8 == 0 (bf16), metric in {0,1}");
+        set_error("ip_topk_exhaustive: need nsel, n, k > 0, d %% 4 == 0 (f32) / d %% 8 == 0 (bf16, f16), metric in {0,1}");
         return SSS_EINVAL;
     }
     if (n >= (1L << 31) || nsel > 65535 || k > RS_MAX_K) { set_error("ip_topk_exhaustive: n < 2^31, nsel <= 65535, k <= 1024"); return SSS_EINVAL; }
@@ -670,8 +681,8 @@ static int range_exhaustive_check(const char* what, const int* qsel, long nsel, 
 
 int range_exhaustive_count(const void* q, const int* qsel, long nsel, const void* c, long n, int d, int dtype, int metric, const float* radius,
                            long* counts, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (d <= 0 || (dtype != DT_F32 && dtype != DT_BF16) || d % (dtype == DT_F32 ? 4 : 8) || !q || !c || !counts) {
-        set_error("range_exhaustive_count: need d %% 4 == 0 (f32) / d %% 8 == 0 (bf16), q, corpus and counts");
+    if (d <= 0 || !corpus_dtype_ok(dtype) || d % (dtype == DT_F32 ? 4 : 8) || !q || !c || !counts) {
+        set_error("range_exhaustive_count: need d %% 4 == 0 (f32) / d %% 8 == 0 (bf16, f16), q, corpus and counts");
         return SSS_EINVAL;
     }
     int rc = range_exhaustive_check("range_exhaustive_count", qsel, nsel, n, metric, radius, ws, ws_bytes);

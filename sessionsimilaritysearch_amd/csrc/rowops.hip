@@ -111,6 +111,37 @@ __global__ __launch_bounds__(256) void k_row_norm_max_bf16(const unsigned short*
         atomicMax(reinterpret_cast<unsigned int*>(out), __builtin_bit_cast(unsigned int, norm_up(m)));
 }
 
+// float16 rows: the same maximum, squares of the (exactly converted) values summed in float64.  A row holding an inf or
+// a NaN reads as +inf, so one reduction also tells a caller that a conversion to float16 overflowed (FlatIndex.add).
+__global__ __launch_bounds__(256) void k_row_norm_max_f16(const unsigned short* __restrict__ x, long n, int d,
+                                                          float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
+    double m = 0.0;
+    for (long row = wave; row < n; row += nwaves) {
+        const u32x4* p = reinterpret_cast<const u32x4*>(x + row * (long)d);
+        double ss = 0.0;
+        bool bad = false;
+        for (int i = lane; i < d / 8; i += 64) {
+            const u32x4 v = p[i];
+#define SSS_SQ2(w)                                                                                        \
+    { const double lo = (double)__builtin_bit_cast(_Float16, (unsigned short)(v.w & 0xFFFFu)),          \
+                   hi = (double)__builtin_bit_cast(_Float16, (unsigned short)(v.w >> 16));              \
+      ss += lo * lo + hi * hi;                                                                            \
+      bad |= (v.w & 0x7C00u) == 0x7C00u || (v.w & 0x7C000000u) == 0x7C000000u; }
+            SSS_SQ2(x) SSS_SQ2(y) SSS_SQ2(z) SSS_SQ2(w)
+#undef SSS_SQ2
+        }
+        if (bad) ss = INFINITY;                         // (NaN would be dropped by fmax below)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+        m = fmax(m, ss);
+    }
+    if (lane == 0)
+        atomicMax(reinterpret_cast<unsigned int*>(out), __builtin_bit_cast(unsigned int, norm_up(m)));
+}
+
 // float32 -> bfloat16, round to nearest even (plain cast: v_cvt_pk_bf16_f32, NaN stays NaN);
 // 8 elements per thread, 32-byte loads / 16-byte stores.
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -274,17 +305,21 @@ int normalize_rows(float* x, long n, int d, long ld, float eps, int rule, hipStr
 }
 
 int row_norm_max(const void* xv, long n, int d, int dtype, float* out, hipStream_t st) {
-    if (dtype == 1) {
-        if (n < 0 || d <= 0 || d % 8) { set_error("row_norm_max: bf16 needs d %% 8 == 0"); return SSS_EINVAL; }
+    if (dtype == 1 || dtype == 4) {                     // include/sss.h: bfloat16 / float16 rows
+        if (n < 0 || d <= 0 || d % 8) { set_error("row_norm_max: bf16 / f16 need d %% 8 == 0"); return SSS_EINVAL; }
         if (n == 0) return SSS_OK;
         long blocks = (n + 3) / 4;
         if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(k_row_norm_max_bf16, dim3((unsigned)blocks), dim3(256), 0, st,
-                           reinterpret_cast<const unsigned short*>(xv), n, d, out);
-        return check_launch("k_row_norm_max_bf16");
+        if (dtype == 1)
+            hipLaunchKernelGGL(k_row_norm_max_bf16, dim3((unsigned)blocks), dim3(256), 0, st,
+                               reinterpret_cast<const unsigned short*>(xv), n, d, out);
+        else
+            hipLaunchKernelGGL(k_row_norm_max_f16, dim3((unsigned)blocks), dim3(256), 0, st,
+                               reinterpret_cast<const unsigned short*>(xv), n, d, out);
+        return check_launch("k_row_norm_max_16");
     }
     const float* x = reinterpret_cast<const float*>(xv);
-    if (dtype != 0 || n < 0 || d <= 0 || d % 4) { set_error("row_norm_max: need dtype in {0,1}, n >= 0, d %% 4 == 0"); return SSS_EINVAL; }
+    if (dtype != 0 || n < 0 || d <= 0 || d % 4) { set_error("row_norm_max: need dtype in {0,1,4}, n >= 0, d %% 4 == 0"); return SSS_EINVAL; }
     if (n == 0) return SSS_OK;
     const int lpr = lanes_per_row(d);
     SSS_DISPATCH_LPR(lpr, hipLaunchKernelGGL(k_row_norm_max<L>, dim3(grid_for(n, L)), dim3(256), 0, st, x, n, d, out));

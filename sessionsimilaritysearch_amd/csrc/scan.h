@@ -22,6 +22,11 @@ constexpr int DT_SPLIT = 2;
 // proof.  One f16 MFMA pass (1/3 of DT_SPLIT's matrix work, half its bytes) with a coarser bound
 // (select.hip: err_bound ~ 2^-10 |q||c|), still proven per query and re-scored from the f32 rows.
 constexpr int DT_F16 = 3;
+// Corpus dtype of the C ABI (include/sss.h: dtype 4) and its own scan type: rows STORED as IEEE float16 (round to
+// nearest even of whatever the caller had), queries float16 too.  Rows and queries go into v_mfma_f32_32x32x16_f16 as
+// they are -- no scaling, no residual, scan scores are scores -- and the candidates are re-scored from the same rows.
+// (3 stays the scaled image of an f32 corpus: the two share the MFMA and the operand layout, not the bound.)
+constexpr int DT_H16 = 4;
 
 // shift that maps a largest magnitude `amax` into [2^12, 2^13); 0 for an all-zero / non-finite row
 __host__ __device__ inline int f16_shift(float amax) {
@@ -40,13 +45,15 @@ constexpr int MAX_SLOTS = 128;  // admission-threshold slots per query (J <= MAX
 constexpr int SLOT_STRIDE = MAX_SLOTS;
 constexpr unsigned ORD_NEG_INF = 0x007FFFFFu;   // f2ord(-inf); slot value 0 = "never written"
 
-static inline int elem_bytes(int dtype) { return (dtype == DT_BF16 || dtype == DT_F16) ? 2 : 4; }
+static inline int elem_bytes(int dtype) { return (dtype == DT_BF16 || dtype == DT_F16 || dtype == DT_H16) ? 2 : 4; }
+static inline bool corpus_dtype_ok(int dtype) { return dtype == DT_F32 || dtype == DT_BF16 || dtype == DT_H16; }   // what crosses the C ABI as `dtype`
 
 // Row shapes of sss_ip_topk_long: d % 64 == 0 and exact rows of at most 16384 bytes (k_select_all keeps the query row in
-// LDS); f32 rows are scanned through their f16 image, bf16 rows directly.
+// LDS); f32 rows are scanned through their f16 image, bf16 and f16 rows directly.
 static inline bool long_shape_ok(int d, int exact_dtype, int scan_dtype) {
     if (d <= 0 || d % 64 || d * elem_bytes(exact_dtype) > 16384) return false;
-    return (exact_dtype == DT_F32 && scan_dtype == DT_F16) || (exact_dtype == DT_BF16 && scan_dtype == DT_BF16);
+    return (exact_dtype == DT_F32 && scan_dtype == DT_F16) || (exact_dtype == DT_BF16 && scan_dtype == DT_BF16) ||
+           (exact_dtype == DT_H16 && scan_dtype == DT_H16);
 }
 
 // STATE words (caller-owned, zero before the first call; every call leaves them zero: the select
@@ -92,7 +99,7 @@ struct SelectArgs {
     const void* C;
     int nq, d, dtype, k, K2, J, cap;
     int tau_skip = 0;               // the scan's rank-selected threshold: (tau_skip + 1)-th smallest of the 16 slots
-    int scan_dtype;                 // what produced the candidates (DT_F32 / DT_BF16 / DT_SPLIT / DT_F16): picks the error bound
+    int scan_dtype;                 // what produced the candidates (DT_F32 / DT_BF16 / DT_SPLIT / DT_F16 / DT_H16): picks the error bound
     int corpus_shift;               // DT_F16: the corpus image is corpus * 2^corpus_shift (else 0)
     float corpus_resid;             // DT_F16: largest row norm of (image * 2^-corpus_shift - corpus)
     const unsigned long long* cand;

@@ -1,4 +1,4 @@
-// Query x corpus inner-product CANDIDATE scan with fused running top-k (gfx950 / CDNA4): f32, bf16,
+// Query x corpus inner-product CANDIDATE scan with fused running top-k (gfx950 / CDNA4): f32, bf16, f16 rows,
 // split-bf16 (three passes over an f32 corpus) and scaled f16 (one pass over an f32 corpus).
 //
 // Replaces what the reference asks of faiss at test_amazon_filterd.py:578
@@ -15,8 +15,8 @@
 //   * each wave keeps its 32 queries resident in RB/8 VGPRs as the B operand of
 //     v_mfma_f32_32x32x2_f32 (DT_F32: an exact k-ordered f32 fma chain), v_mfma_f32_32x32x16_bf16
 //     (DT_BF16; DT_SPLIT: hi*hi + hi*lo + lo*hi of rows stored [hi | lo]) or v_mfma_f32_32x32x16_f16
-//     (DT_F16: f32 queries scaled by their own power of two and rounded in the prologue), so the
-//     query tile is read from HBM once;
+//     (DT_F16: f32 queries scaled by their own power of two and rounded in the prologue; DT_H16: stored f16 rows
+//     and f16 queries as they are), so the query tile is read from HBM once;
 //   * corpus rows stream HBM -> LDS with global_load_lds_dwordx4 (no VGPR staging), double
 //     buffered, one burst per tile, 16-byte chunks XOR-swizzled on the SOURCE address so the
 //     ds_read_b128 fragment reads are bank-conflict free.  Rows of equal BYTES stage and read
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
                 const bf16x8 qb = __builtin_bit_cast(bf16x8, qc[u]);
                 acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a0), qb, acc0, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a1), qb, acc1, 0, 0, 0);
-            } else if constexpr (DT == DT_F16) {
+            } else if constexpr (DT == DT_F16 || DT == DT_H16) {
                 const f16x8 qb = __builtin_bit_cast(f16x8, qc[u]);
                 acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a0), qb, acc0, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a1), qb, acc1, 0, 0, 0);
@@ -545,7 +545,8 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
     // live across the barrier): after every barrier one partner starts with matrix work, the other with vector work.
     // Measured (same device, alternating builds): split scan -3.5 %, bf16 C5 -1.3 % time; f16 and f32 scans unchanged
     // to +1 % (their partners drift apart by themselves), so those keep the plain order.
-    const bool defer = SSS_STAGGER && NW == 8 && (DT == DT_SPLIT || DT == DT_BF16) && wave >= 4;
+    // (DT_H16 -- stored f16 rows -- is the bf16 kernel with the other MFMA: it takes the bf16 order)
+    const bool defer = SSS_STAGGER && NW == 8 && (DT == DT_SPLIT || DT == DT_BF16 || DT == DT_H16) && wave >= 4;
     int t = 0;
     if constexpr (AP || THR) {
         // The forms WITHOUT lane lists (append, threshold) have no list state to keep out of the hot loop, so theirs is the
@@ -826,6 +827,10 @@ int launch_scan(int dtype, int d, int tile_rows, const ScanArgs& a, hipStream_t 
         if (rb == 256) return tile_rows == 256 ? launch_one<256, 256, DT_F16>(a, st) : launch_one<256, 128, DT_F16>(a, st);
         if (rb == 512) return tile_rows == 128 ? launch_one<512, 128, DT_F16>(a, st) : launch_one<512, 64, DT_F16>(a, st);
         if (rb == 1024) return launch_one<1024, 64, DT_F16, 4>(a, st);
+    } else if (dtype == DT_H16) {
+        if (rb == 256) return tile_rows == 256 ? launch_one<256, 256, DT_H16>(a, st) : launch_one<256, 128, DT_H16>(a, st);
+        if (rb == 512) return tile_rows == 128 ? launch_one<512, 128, DT_H16>(a, st) : launch_one<512, 64, DT_H16>(a, st);
+        if (rb == 1024) return launch_one<1024, 64, DT_H16, 4>(a, st);
     } else if (dtype == DT_SPLIT) {
         if (rb == 256) return tile_rows == 256 ? launch_one<256, 256, DT_SPLIT>(a, st) : launch_one<256, 128, DT_SPLIT>(a, st);
         if (rb == 512) return tile_rows == 128 ? launch_one<512, 128, DT_SPLIT>(a, st) : launch_one<512, 64, DT_SPLIT>(a, st);

@@ -92,7 +92,8 @@ __device__ __forceinline__ void load8_sc1(const unsigned* p, unsigned (&v)[8]) {
 
 // Resident queries of one 32-query MFMA B operand: lane (r, h) ends up with the 16-byte chunks of query row
 // q_ld it meets in the k-groups (qc[u]: k = 16u + 8h .. + 7 for the 16-bit types, chunk 2u + h for f32).
-// DT_SPLIT / DT_F16 take float32 queries and split / scale + round them here (scan.h).
+// DT_SPLIT / DT_F16 take float32 queries and split / scale + round them here (scan.h); the others (DT_H16: float16
+// queries against float16 rows) load the row as it is stored.
 template <int RB, int DT>
 __device__ __forceinline__ void load_queries(const char* __restrict__ Qb, int q_ld, int h, f32x4 (&qc)[RB / 32]) {
     constexpr int NU = RB / 32;

@@ -43,8 +43,8 @@ constexpr int LT_LDS_BYTES = 5 * LT_HALF;
 static_assert(LT_ROWS == LT_Q, "the two operand slabs have one size");
 
 struct LongArgs {
-    const void* Qimg;               // [nq][d] 16-bit queries (f16: scaled image, bf16: the queries themselves)
-    const void* C;                  // [n][d] 16-bit rows (f16 image / bf16 rows)
+    const void* Qimg;               // [nq][d] 16-bit queries (f16 image of f32 queries; bf16 / f16 index: the queries themselves)
+    const void* C;                  // [n][d] 16-bit rows (f16 image of f32 rows; bf16 / f16 rows)
     int nq, n, d, G, S;
     int gpx;                        // query groups that share an XCD (block map below); divides G, G / gpx divides 8
     int dense;                      // sample level (many rows kept per lane and tile): aggregated appends
@@ -313,6 +313,9 @@ __global__ __launch_bounds__(LT_THREADS, (LT_THREADS + 255) / 256) void k_scan_l
 }
 
 // ------------------------------------------------------------------------------ host side
+// What the scan reads for rows of `exact_dtype`: f32 rows their scaled f16 image, bf16 and f16 rows themselves (an f16
+// index is its own image: shift 0, no residual, the f16 kernel as it is).
+static int long_scan_dtype(int exact_dtype) { return exact_dtype == DT_F32 ? DT_F16 : exact_dtype; }
 constexpr int LONG_CAP = 8192;      // rows kept per query (k_select_all sorts them in 64 KB of LDS)
 constexpr int LONG_MAX_K = 1024;    // what the exhaustive kernels -- the path of a query left at status 1 -- can resolve
 // k_select_all keeps 2 x cap keys + the exact query row + its staging tile in LDS: rows beyond 10240 bytes
@@ -321,8 +324,7 @@ static int long_cap(int d, int exact_dtype) { return d * elem_bytes(exact_dtype)
 static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 size_t ip_topk_long_workspace_bytes(long nq, long n, int d, int dtype) {
-    const int scan = dtype == DT_F32 ? DT_F16 : DT_BF16;
-    if (nq <= 0 || n <= 0 || !long_shape_ok(d, dtype, scan)) return 0;
+    if (nq <= 0 || n <= 0 || !long_shape_ok(d, dtype, long_scan_dtype(dtype))) return 0;
     return al256((size_t)nq * d * 2) + al256((size_t)nq * 4) * 3 + al256((size_t)nq * 16) + (size_t)nq * LONG_CAP * 8;
 }
 
@@ -330,7 +332,8 @@ size_t ip_topk_long_workspace_bytes(long nq, long n, int d, int dtype) {
 int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, const void* c_scan, int corpus_shift,
                  float corpus_resid, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out,
                  int* status, void* ws, size_t ws_bytes, hipStream_t st) {
-    const int scan_dtype = exact_dtype == DT_F32 ? DT_F16 : DT_BF16;
+    const int scan_dtype = long_scan_dtype(exact_dtype);
+    const bool f16_mfma = scan_dtype != DT_BF16;        // the scaled image and stored f16 rows share k_scan_long<DT_F16>
     if (nq <= 0 || n <= 0 || k <= 0) { set_error("ip_topk_long: nq, n, k must be positive"); return SSS_EINVAL; }
     int rc = check_scan_source("ip_topk_long", exact_dtype, scan_dtype, d, true, c_scan, corpus_shift, corpus_resid, n, nq);
     if (rc) return rc;
@@ -379,7 +382,7 @@ int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, c
         level_tiles[levels++] = first;
     }
     const size_t lds = LT_LDS_BYTES;
-    rc = scan_dtype == DT_F16 ? opt_in_lds(reinterpret_cast<const void*>(&k_scan_long<DT_F16>), "k_scan_long", lds)
+    rc = f16_mfma ? opt_in_lds(reinterpret_cast<const void*>(&k_scan_long<DT_F16>), "k_scan_long", lds)
                               : opt_in_lds(reinterpret_cast<const void*>(&k_scan_long<DT_BF16>), "k_scan_long", lds);
     if (rc) return rc;
     ThrArgs t = thr_args(q, c_exact, exact_dtype, scan_dtype, corpus_shift, corpus_resid, corpus_max_norm, qsel, nq, n, d, k, cap,
@@ -426,7 +429,7 @@ int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, c
         a.tiles_per_split = (tiles + S - 1) / S;
         // (thresholds and counters of this level: written by launch_long_setup -- first level -- or by the previous level's
         //  launch_bound_prepare)
-        if (scan_dtype == DT_F16) hipLaunchKernelGGL(k_scan_long<DT_F16>, dim3(a.S * a.G), dim3(LT_THREADS), lds, st, a);
+        if (f16_mfma) hipLaunchKernelGGL(k_scan_long<DT_F16>, dim3(a.S * a.G), dim3(LT_THREADS), lds, st, a);
         else hipLaunchKernelGGL(k_scan_long<DT_BF16>, dim3(a.S * a.G), dim3(LT_THREADS), lds, st, a);
         rc = check_launch("k_scan_long");
         if (rc) return rc;

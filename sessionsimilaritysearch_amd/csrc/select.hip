@@ -75,8 +75,12 @@ __device__ __forceinline__ void wave_sync() {
 // four), and the strictly sequential float64 chain runs part after part, handed from lane to lane --
 // the same additions in the same order as one lane walking the row.  Candidates [c0, c0 + 16) of `sel`.
 __device__ __forceinline__ double dot_chunk(double acc, const char* qrow, int v, f32x4 c, int dtype);
-__device__ __forceinline__ void rescore16(const unsigned long long* sel, double* resc, int c0, int c1, const void* C, int rb,
-                                          const char* qrow, int dtype, int lane) {
+// (DT: the element type as a compile-time constant -- with the three-way choice inside the unrolled chain the 32 chunk
+//  registers of a part went to scratch)
+template <int DT>
+__device__ __forceinline__ void rescore16_t(const unsigned long long* sel, double* resc, int c0, int c1, const void* C, int rb,
+                                            const char* qrow, int lane) {
+    constexpr int dtype = DT;
     const int c = c0 + (lane >> 2), p = lane & 3;
     const int per = rb / 64;                                       // chunks per part: 4 / 8 / 16 / 32 (rows of 256 .. 2048 bytes)
     const unsigned long long key = c < c1 ? sel[c] : 0ull;
@@ -102,8 +106,18 @@ __device__ __forceinline__ void rescore16(const unsigned long long* sel, double*
     }
     if (c < c1 && p == 3) resc[c] = live ? acc : 0.0;
 }
+__device__ __forceinline__ void rescore16(const unsigned long long* sel, double* resc, int c0, int c1, const void* C, int rb,
+                                          const char* qrow, int dtype, int lane) {
+    if (dtype == DT_F32) rescore16_t<DT_F32>(sel, resc, c0, c1, C, rb, qrow, lane);
+    else if (dtype == DT_H16) rescore16_t<DT_H16>(sel, resc, c0, c1, C, rb, qrow, lane);
+    else rescore16_t<DT_BF16>(sel, resc, c0, c1, C, rb, qrow, lane);
+}
 
-// acc += sum over the elements of one 16-byte chunk (4 f32 or 8 bf16), sequential in k
+// the two float16 values of a 32-bit word (element 2i in the low half)
+__device__ __forceinline__ _Float16 h16_lo(unsigned w) { return __builtin_bit_cast(_Float16, (unsigned short)(w & 0xFFFFu)); }
+__device__ __forceinline__ _Float16 h16_hi(unsigned w) { return __builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+
+// acc += sum over the elements of one 16-byte chunk (4 f32, 8 bf16 or 8 f16), sequential in k
 __device__ __forceinline__ double dot_chunk(double acc, const char* qrow, int v, f32x4 c, int dtype) {
     if (dtype == DT_F32) {
         const f32x4 qv = *reinterpret_cast<const f32x4*>(qrow + v * 16);
@@ -115,6 +129,14 @@ __device__ __forceinline__ double dot_chunk(double acc, const char* qrow, int v,
     }
     const u32x4 cu = __builtin_bit_cast(u32x4, c);
     const u32x4 qu = *reinterpret_cast<const u32x4*>(qrow + v * 16);
+    if (dtype == DT_H16) {                                        // f16 -> f64 is exact (subnormals included)
+#define SSS_H2(w)                                                                                     \
+    acc += (double)h16_lo(qu.w) * (double)h16_lo(cu.w);                                               \
+    acc += (double)h16_hi(qu.w) * (double)h16_hi(cu.w);
+        SSS_H2(x) SSS_H2(y) SSS_H2(z) SSS_H2(w)
+#undef SSS_H2
+        return acc;
+    }
 #define SSS_BF2(w)                                                                                              \
     acc += (double)__builtin_bit_cast(float, qu.w << 16) * (double)__builtin_bit_cast(float, cu.w << 16);      \
     acc += (double)__builtin_bit_cast(float, qu.w & 0xFFFF0000u) * (double)__builtin_bit_cast(float, cu.w & 0xFFFF0000u);
@@ -152,6 +174,7 @@ __device__ __forceinline__ double rescore_row(const char* qrow, const char* row,
 __device__ __forceinline__ float elem_to_f32(const void* row, int kk, int dtype) {
     if (dtype == DT_F32) return reinterpret_cast<const float*>(row)[kk];
     const unsigned short b = reinterpret_cast<const unsigned short*>(row)[kk];
+    if (dtype == DT_H16) return (float)__builtin_bit_cast(_Float16, b);   // f16 -> f32 is exact
     return __builtin_bit_cast(float, (unsigned)b << 16);          // bf16 -> f32 is exact
 }
 
@@ -173,6 +196,10 @@ __device__ __forceinline__ float elem_to_f32(const void* row, int kk, int dtype)
 //            most 2^-25 sqrt(d) |q||c| even if the matrix unit flushed them; products of two f16 are
 //            exact in f32 and accumulate like the bf16 case:
 //                         Rc |q| + (|c| + Rc) Rq + (2^-25 sqrt(d) + d * 2^-23) |q| |c|
+//   DT_H16   rows and queries STORED as float16 and fed to the f16 MFMA as they are: no rounding of inputs at all.
+//            A product of two f16 values has 22 significant bits and lies in [2^-48, 2^32): exact in f32, and so
+//            is every partial sum's grid (multiples of 2^-48); what remains is the f32 accumulation, as for bf16:
+//                                                                  d * 2^-23 * |q| |c|
 // (each with 2 % headroom; |c| <= the corpus' largest row norm, an upper bound at any magnitude: rowops.hip).
 // The relative terms assume normal float32 arithmetic.  Where the f32 values of a chain fall below FLT_MIN = 2^-126
 // they lose up to half a subnormal spacing (2^-150) per rounding, or -- if a unit flushes subnormals -- the whole
@@ -182,6 +209,11 @@ __device__ __forceinline__ float elem_to_f32(const void* row, int kk, int dtype)
 //            element below 2^-126 (flushed, or -- split -- a lo / hi part rounded in the bf16 subnormal range) misses
 //            at most 2^-126 |y_k| per element of the other side: sqrt(d) 2^-126 (|q| + |c|) per pass
 //   DT_F16   sums and products of the scaled f16 image live in [2^-48, 2^26] x d: no floor needed
+//   DT_H16   products are multiples of 2^-48 below 2^32 and sums stay below d * 2^32: nothing in the chain comes near
+//            FLT_MIN or FLT_MAX whatever the stored magnitudes (f16 subnormals, 65504), so no floor here either --
+//            where bf16 rows, with float32's exponent range, need one.  f16 subnormal INPUTS are kept by the matrix
+//            unit: its A / B operands follow the kernel's f16 denormal mode, which hipcc leaves at "keep"
+//            (tests/test_f16_index_gpu.py scans a corpus of nothing but f16 subnormals)
 // A proof among subnormal-range scores thus holds whatever the unit did with them; where the floor is as wide as the
 // gaps between the scores the query stays unproven and is resolved exactly by the threshold rung or the exhaustive
 // kernels.
@@ -191,6 +223,7 @@ __device__ __forceinline__ double err_bound(int d, int scan_dtype, double qnorm,
     double b;
     if (scan_dtype == DT_F32) b = (double)d * 5.9604644775390625e-08 * qnorm * cmax + (double)d * U149;
     else if (scan_dtype == DT_BF16) b = (double)d * 1.1920928955078125e-07 * qnorm * cmax + (2.0 * d + rd * (qnorm + cmax)) * U126;
+    else if (scan_dtype == DT_H16) b = (double)d * 1.1920928955078125e-07 * qnorm * cmax;
     else if (scan_dtype == DT_SPLIT) b = (3.03 * 1.52587890625e-05 + 3.0 * (double)d * 1.1920928955078125e-07 * 1.016) * qnorm * cmax +
                                          3.0 * (2.0 * d + rd * (qnorm + cmax)) * U126;
     else b = c_resid * qnorm + (cmax + c_resid) * q_resid +

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 
-FUSED_DIMS = {"f32": (64, 128, 256), "bf16": (128, 256, 512)}   # row bytes 256 / 512 / 1024
+FUSED_DIMS = {"f32": (64, 128, 256), "bf16": (128, 256, 512), "f16": (128, 256, 512)}   # row bytes 256 / 512 / 1024
 F16_SCAN_DIMS = (128, 256, 512)                                  # scaled-f16 image: 2 bytes per element
 # scan="auto": the fastest scan whose error bound is still small against the spacing of the scores
 # around rank k (the spacing shrinks as k grows): one-pass f16 up to k = 128, bf16 split up to k = 500
@@ -37,7 +37,8 @@ _LADDER = ("f16", "split", "f32")
 FUSED_MAX_K = 500
 LONG_MAX_K = 1024                                                # sss_ip_topk_long: what its exhaustive fallback resolves
 LONG_MAX_ROW_BYTES = 16384
-DTYPE_CODE = {"f32": 0, "bf16": 1}                               # include/sss.h: dtype
+DTYPE_CODE = {"f32": 0, "bf16": 1, "f16": 4}                     # include/sss.h: dtype (2, 3 are scan images, below)
+_TORCH_DTYPE = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 _EXHAUSTIVE_WS_BYTES = 1 << 30
 SEARCH_CHUNK = 65536             # queries per fused call of search_device (workspace 16 KB per query)
 SEARCH_CHUNK_LONG = 16384        # ... on the long-row path (64 KB per query)
@@ -73,6 +74,13 @@ def to_bf16(x: torch.Tensor) -> torch.Tensor:
     rc = _lib.lib().sss_f32_to_bf16(x.data_ptr(), x.numel(), y.data_ptr(), _lib.stream_ptr(x.device))
     _lib.check(rc, "sss_f32_to_bf16")
     return y
+
+
+def to_f16(x: torch.Tensor) -> torch.Tensor:
+    """float32 CUDA tensor -> IEEE float16 (round to nearest even): what an f16 index stores.  Values beyond
+    +-65504 become inf; ``FlatIndex.add`` refuses such rows."""
+    _lib.require_cuda(x, "x", torch.float32)
+    return x.to(torch.float16)
 
 
 def normalize_(x: torch.Tensor, eps: float = 1e-6, rule: int = 0) -> torch.Tensor:
@@ -118,6 +126,11 @@ class FlatIndex:
     bfloat16 and scores on the bf16 MFMA; the contract is then defined on the ROUNDED vectors
     (float64 dot of the stored bf16 values).
 
+    ``dtype="f16"`` stores the corpus -- and rounds every query -- to IEEE float16 (11 significant bits against
+    bfloat16's 8, the same 2 bytes per element; the format of faiss ``useFloat16`` and of a half-precision
+    encoder's output) and scores on the f16 MFMA, with the same contract on the rounded vectors.  Float16 ends at
+    65504: ``add`` raises ``ValueError`` for rows that do not stay finite, and stores nothing.
+
     ``scan`` picks how a float32 index finds its candidates (the results are the same, they are
     re-scored from the float32 rows and proven per query either way; what differs is speed and how
     many near-tied queries are left to the exhaustive fallback):
@@ -142,9 +155,9 @@ class FlatIndex:
         if metric not in ("ip", "l2"):
             raise ValueError("metric must be 'ip' or 'l2'")
         if dtype not in DTYPE_CODE:
-            raise ValueError("dtype must be 'f32' or 'bf16'")
-        if dtype == "bf16" and d % 8:
-            raise ValueError("bf16 index needs d % 8 == 0")
+            raise ValueError("dtype must be 'f32', 'bf16' or 'f16'")
+        if dtype != "f32" and d % 8:
+            raise ValueError(f"{dtype} index needs d % 8 == 0")
         if scan is None:
             scan = "auto" if dtype == "f32" else "native"
         if scan not in (("auto", "f16", "split", "f32") if dtype == "f32" else ("native",)):
@@ -157,7 +170,7 @@ class FlatIndex:
         self.d = int(d)
         self.metric = metric
         self.dtype = dtype
-        self._tdtype = torch.float32 if dtype == "f32" else torch.bfloat16
+        self._tdtype = _TORCH_DTYPE[dtype]
         self.device = _dev(device)
         # derived corpus images, built on first use and extended as rows are added
         self._split = None              # [cap, 2d] bf16 hi|lo image of the rows        ("split" scan)
@@ -187,6 +200,7 @@ class FlatIndex:
     def add(self, x):
         """Append rows (copied, ids = insertion order) -- ``IndexFlatIP.add``."""
         x = self._rows(x, "add")
+        new_max = self._checked_norm_max(x)
         n_old = self.ntotal
         if n_old + x.shape[0] > self._store.shape[0]:          # amortised growth: no re-copy per add()
             cap = max(n_old + x.shape[0], 2 * self._store.shape[0])
@@ -195,7 +209,11 @@ class FlatIndex:
             self._store = store
         self._store[n_old:n_old + x.shape[0]] = x
         self._xb = self._store[:n_old + x.shape[0]]
-        self._norm_max(x)
+        if new_max is None:
+            self._norm_max(x)
+        else:
+            torch.maximum(self._cmax_t, new_max, out=self._cmax_t)
+            self._cmax = None
         # streaming adds keep what the searches have learned about this corpus; only once it has doubled since
         # an escalation was earned is that treated as a different corpus (adopt() always resets)
         if self._auto_level and self.ntotal > 2 * max(1, self._auto_rows):
@@ -354,7 +372,7 @@ class FlatIndex:
     def _require_d_aligned(self):
         """The exhaustive kernels read rows in 16-byte pieces."""
         if self.d % (4 if self.dtype == "f32" else 8):
-            raise _lib.SssError("d must be a multiple of 4 (f32) / 8 (bf16)")
+            raise _lib.SssError("d must be a multiple of 4 (f32) / 8 (bf16, f16)")
 
     def _exhaustive_chunks(self, rows: torch.Tensor, ws_bytes):
         """(offset, query rows, workspace) per chunk of the device int32 `rows` whose [chunk, n] scores fit the exhaustive
@@ -367,12 +385,16 @@ class FlatIndex:
 
     def _rows(self, x, what):
         """Input rows as a contiguous device tensor of the index's element type."""
-        if isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16 and self.dtype == "bf16":
+        if isinstance(x, torch.Tensor) and x.dtype == self._tdtype and self.dtype != "f32":
             x = x.to(self.device).contiguous()
+        elif self.dtype == "f16" and isinstance(x, np.ndarray) and x.dtype == np.float16:
+            x = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
         else:
             x = _as_device_f32(x, self.device)
             if self.dtype == "bf16":
                 x = to_bf16(x)
+            elif self.dtype == "f16":
+                x = to_f16(x)
         if x.dim() != 2 or x.shape[1] != self.d:
             raise ValueError(f"{what}: expected [n, {self.d}], got {tuple(x.shape)}")
         return x
@@ -384,16 +406,36 @@ class FlatIndex:
             _lib.check(rc, "sss_row_norm_max")
         self._cmax = None
 
+    def _checked_norm_max(self, x):
+        """f16 index: the largest row norm of the new rows as a device float32 [1] tensor, after checking that the
+        rows are finite (a float32 value beyond 65504 became inf in ``to_f16``): ``sss_row_norm_max`` reads +inf
+        for a row holding an inf or a NaN, so one reduction (and one host sync) serves both.  None for the other
+        dtypes and for rows the reduction does not take: the caller runs ``_norm_max``."""
+        if self.dtype != "f16" or not x.shape[0]:
+            return None
+        t = torch.zeros(1, dtype=torch.float32, device=self.device)
+        rc = _lib.lib().sss_row_norm_max(x.data_ptr(), x.shape[0], self.d, DTYPE_CODE[self.dtype], t.data_ptr(),
+                                         _lib.stream_ptr(self.device))
+        _lib.check(rc, "sss_row_norm_max")
+        if not np.isfinite(float(t.item())):
+            raise ValueError("f16 index: rows hold values that are not finite in float16 (|x| > 65504, inf or NaN)")
+        return t
+
     def adopt(self, xb: torch.Tensor, id_offset: int = 0):
         """Use an existing CUDA [n, d] tensor of the index's element type as the corpus without
         copying it."""
         _lib.require_cuda(xb, "xb", self._tdtype)
         if xb.dim() != 2 or xb.shape[1] != self.d:
             raise ValueError("adopt: wrong shape")
+        new_max = self._checked_norm_max(xb)
         self._xb = self._store = xb
         self.id_offset = int(id_offset)
         self._cmax_t.zero_()
-        self._norm_max(xb)
+        if new_max is None:
+            self._norm_max(xb)
+        else:
+            self._cmax_t.copy_(new_max)
+            self._cmax = None
         self._split, self._split_done = None, 0
         self._f16, self._f16_done = None, 0
         self._amax_t.zero_()
