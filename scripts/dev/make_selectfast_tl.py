@@ -3,7 +3,7 @@
 end; word 7 = candidate count).  Build:
   cd sessionsimilaritysearch_amd/csrc && hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -c select_tl.hip -o /tmp/select_tl.o &&
   hipcc --offload-arch=gfx950 -shared -o ../../scripts/dev/libsss_sftl.so capi.o ip_topk.o scan.o scan_long.o /tmp/select_tl.o \
-        exhaustive.o rowops.o gnn.o vote.o graphbuild.o hamming.o variants.o"""
+        select_thr.o topk_merge.o exhaustive.o rowops.o gnn.o vote.o graphbuild.o hamming.o variants.o"""
 import os
 root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 src = open(os.path.join(root, "sessionsimilaritysearch_amd/csrc/select.hip")).read()
@@ -18,15 +18,15 @@ body = sub1(body, "    if (q >= A.nq) return;                                   
 body = sub1(body, "    if (M > FS_CAP) {", "    SF(1);\n    if (lane == 0 && q < 1024) g_sf[q * 8 + 7] = (unsigned long long)M;\n    if (M > FS_CAP) {")
 body = sub1(body, "    // ---- K2 rounds: wave-wide arg-max, the owner lane retires its key\n", "    SF(2);\n")
 body = sub1(body, "    wave_sync();\n    // ---- float64 re-score: one lane per candidate", "    wave_sync();\n    SF(3);\n    // ---- float64 re-score: one lane per candidate")
-body = sub1(body, "    for (int c0 = 0; c0 < K2; c0 += 16) rescore16(sel, resc, c0, K2, A.C, rb, qrow, A.dtype, lane);\n    double qn2 = 0.0;",
-            "    for (int c0 = 0; c0 < K2; c0 += 16) rescore16(sel, resc, c0, K2, A.C, rb, qrow, A.dtype, lane);\n    SF(4);\n    double qn2 = 0.0;")
+body = sub1(body, "    for (int c0 = 0; c0 < K2; c0 += 16) rescore16(sel, resc, c0, K2, A.C, rb, qrow, A.dtype, lane);\n    double B, unscale;",
+            "    for (int c0 = 0; c0 < K2; c0 += 16) rescore16(sel, resc, c0, K2, A.C, rb, qrow, A.dtype, lane);\n    SF(4);\n    double B, unscale;")
 body = sub1(body, "    const int nvalid = *s_nvalid;\n", "    const int nvalid = *s_nvalid;\n    SF(5);\n")
 body = sub1(body, "    if (lane == 0) {\n        A.status[q] = st;", "    SF(6);\n    if (lane == 0) {\n        A.status[q] = st;")
 body = ("__device__ unsigned long long g_sf[1024 * 8];\n"
         "#define SF(slot) do { if (lane == 0 && q < 1024) g_sf[q * 8 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)\n") + body
 src = src[:a] + body + src[b:]
-src = sub1(src, "// ------------------------------------------------------------------------------------------\n// k-way merge",
+src = sub1(src, "// ------------------------------------------------------------------------------ host side\nint launch_select(",
            "extern \"C\" int sss_debug_selfast(unsigned long long* host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(sss::g_sf), 1024 * 8 * 8); }\n\n"
-           "// ------------------------------------------------------------------------------------------\n// k-way merge")
+           "// ------------------------------------------------------------------------------ host side\nint launch_select(")
 open(os.path.join(root, "sessionsimilaritysearch_amd/csrc/select_tl.hip"), "w").write(src)
 print("wrote csrc/select_tl.hip")

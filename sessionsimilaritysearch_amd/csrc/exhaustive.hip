@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void k_exact_scores_rows(const void* __restric
                 // margin in float64: the chain's relative error, its gradual underflow (D roundings of at most 2^-150 each
                 // below FLT_MIN) and one float32 ulp of l0 (2^-149 absolute in the subnormal range)
                 const float l0 = lb[lb_by_row ? qsel[f0 + f] : f0 + f];    // (per selected query, or per query row)
-                need = !((double)s0 + (double)D * 6.3e-8 * rnorm * qn[f] + 2.4e-7 * fabs((double)l0) + (D + 8) * 1.4012984643248171e-45 <
+                need = !((double)s0 + (double)D * 6.3e-8 * rnorm * qn[f] + ULP32_REL * fabs((double)l0) + (D + 8) * 1.4012984643248171e-45 <
                          (double)l0);                      // (NaN anywhere: keep the row)
             }
             double acc = 0.0;

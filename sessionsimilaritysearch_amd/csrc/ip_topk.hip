@@ -165,7 +165,7 @@ static int run_threshold_form(const ThrArgs& t, const void* c_scan, const ScanPl
     return select();
 }
 
-// Threshold rung for the queries `qsel` a fused search left unproven (select.hip: THRESHOLD RUNG).
+// Threshold rung for the queries `qsel` a fused search left unproven (select_thr.hip: THRESHOLD RUNG).
 // Workspace: thr f32 [nsel] | cnt u32 [nsel] | (256-byte aligned) cand u64 [nsel][cap].
 constexpr int THR_CAP = 8192;       // rows kept per query (64 KB of keys in LDS for the sort)
 static size_t thr_head_bytes(long nsel) { return ((size_t)nsel * 8 + 255) & ~(size_t)255; }
@@ -195,7 +195,7 @@ int ip_topk_threshold(const void* q, const int* qsel, long nsel, const void* c_e
     return run_threshold_form(t, c_scan, p, [&] { return launch_thr_prepare(t, st); }, [&] { return launch_select_all(t, st); }, st);
 }
 
-// RANGE SEARCH, fused route (select.hip: RANGE SEARCH): the threshold rung's scan with thresholds from per-query radii.
+// RANGE SEARCH, fused route (select_thr.hip: RANGE SEARCH): the threshold rung's scan with thresholds from per-query radii.
 // Workspace: thr f32 [nq] | cnt u32 [nq] | (256-byte aligned) qsel i32 [nq] | (256-byte aligned) cand u64 [nq][THR_CAP].
 // range_search_count leaves each resolved query's entries in its candidate row; range_search_fill copies them out.
 static size_t range_head_bytes(long nq) { return thr_head_bytes(nq) + (((size_t)nq * 4 + 255) & ~(size_t)255); }

@@ -1,5 +1,5 @@
 // Internal interface between the scan kernel (scan.hip), the select / re-score kernels
-// (select.hip) and the host orchestration of sss_ip_topk (ip_topk.hip).  gfx950 only.
+// (select.hip, select_thr.hip) and the host orchestration of sss_ip_topk (ip_topk.hip).  gfx950 only.
 #pragma once
 #include "sss_common.h"
 
@@ -11,7 +11,7 @@ constexpr int DT_BF16 = 1;
 // elements stored as [hi(d) | lo(d)] bfloat16, hi = rne_bf16(x), lo = rne_bf16(x - hi) -- 4 bytes
 // per element like f32.  The scan scores hi*hi + hi*lo + lo*hi on the bf16 MFMA (three passes at
 // 16x the f32 MFMA rate); queries are f32 and are split by the kernel.  Candidates are re-scored
-// from the f32 rows, and the proof uses the split's own error bound (select.hip: err_bound).
+// from the f32 rows, and the proof uses the split's own error bound (select_dev.h: err_bound).
 constexpr int DT_SPLIT = 2;
 // Scan-only element type: an f32 corpus stored as float16 after an exact power-of-two scaling,
 // x * 2^shift with ONE shift for the whole corpus chosen so that the largest |element| lies in
@@ -20,7 +20,7 @@ constexpr int DT_SPLIT = 2;
 // score times 2^(corpus shift + query shift): thresholds and candidate selection work in that
 // domain (per query it is a fixed positive factor), and the select kernel divides it out for the
 // proof.  One f16 MFMA pass (1/3 of DT_SPLIT's matrix work, half its bytes) with a coarser bound
-// (select.hip: err_bound ~ 2^-10 |q||c|), still proven per query and re-scored from the f32 rows.
+// (select_dev.h: err_bound ~ 2^-10 |q||c|), still proven per query and re-scored from the f32 rows.
 constexpr int DT_F16 = 3;
 // Corpus dtype of the C ABI (include/sss.h: dtype 4) and its own scan type: rows STORED as IEEE float16 (round to
 // nearest even of whatever the caller had), queries float16 too.  Rows and queries go into v_mfma_f32_32x32x16_f16 as
@@ -44,8 +44,13 @@ constexpr int MAX_SLOTS = 128;  // admission-threshold slots per query (J <= MAX
 // every workgroup of the launch polls, fetches and hits with agent-scope atomics at the same moment (the bootstrap).
 constexpr int SLOT_STRIDE = MAX_SLOTS;
 constexpr unsigned ORD_NEG_INF = 0x007FFFFFu;   // f2ord(-inf); slot value 0 = "never written"
+// One float32 ulp, as every proof of exactness allows for the final rounding of a score to float32 (select_dev.h: the
+// proof window; exhaustive.hip: the bounded pre-test): relative to the score, with headroom over 2^-23 = 1.19e-7 ...
+constexpr double ULP32_REL = 2.4e-7;
+constexpr double ULP32_MIN = 1e-44;             // ... and its floor in the subnormal range (the spacing there is 2^-149 = 1.4e-45)
 
 static inline int elem_bytes(int dtype) { return (dtype == DT_BF16 || dtype == DT_F16 || dtype == DT_H16) ? 2 : 4; }
+static inline int pow2_at_least(int x) { int p = 64; while (p < x) p <<= 1; return p; }   // smallest power of two >= max(x, 64): LDS key arrays
 static inline bool corpus_dtype_ok(int dtype) { return dtype == DT_F32 || dtype == DT_BF16 || dtype == DT_H16; }   // what crosses the C ABI as `dtype`
 
 // Row shapes of sss_ip_topk_long: d % 64 == 0 and exact rows of at most 16384 bytes (k_select_all keeps the query row in
@@ -116,7 +121,7 @@ struct SelectArgs {
 
 int launch_select(const SelectArgs& a, hipStream_t st);
 
-// Threshold rung (select.hip: k_thr_prepare, k_select_all; scan.hip: k_scan<..., THR = true>)
+// Threshold rung (select_thr.hip: k_thr_prepare, k_select_all; scan.hip: k_scan<..., THR = true>)
 struct ThrArgs {
     const void* Q;                  // all queries [*, d] of the exact element type
     const void* C;                  // the stored rows (re-score)
@@ -145,7 +150,7 @@ int launch_select_all(const ThrArgs& a, hipStream_t st);
 // column k-1 of D_out -> the next level's threshold; counters zeroed, or -- a.keep -- the kept rows pruned in place).
 int launch_long_setup(const ThrArgs& a, int* qsel, void* qimg, hipStream_t st);
 int launch_bound_prepare(const ThrArgs& a, hipStream_t st);
-// Range search, fused route (select.hip): scan thresholds from per-query radii (identity selection written to `qsel`,
+// Range search, fused route (select_thr.hip): scan thresholds from per-query radii (identity selection written to `qsel`,
 // counters zeroed); the canonical re-score + keep (> radius) + sort by id of the kept rows (counts / status per query,
 // the entries left in the candidate rows); the copy of those entries to D / I at lims.
 int launch_range_prepare(const ThrArgs& a, const float* radius, int* qsel, hipStream_t st);

@@ -8,7 +8,7 @@
 // address), v_mfma_f32_32x32x16_{f16,bf16} accumulating the full dot products in 8 accumulators per wave
 // (a wave = 64 queries x 128 rows: two B operands x four row blocks; a lane owns one query column per operand).
 //
-// The top-k rides on the THRESHOLD machinery of the rung (select.hip: THRESHOLD RUNG) instead of running lists:
+// The top-k rides on the THRESHOLD machinery of the rung (select_thr.hip: THRESHOLD RUNG) instead of running lists:
 // the epilogue of a tile only compares its 128 scores per lane with the lane's fixed threshold and appends what
 // passes.  The threshold comes from LEVELS of evenly spread row samples:
 //   level 1   a sample of up to `cap` rows (>= 2k), threshold -inf: every sampled row is kept; at least k of them have a scan
@@ -58,7 +58,7 @@ struct LongArgs {
 };
 
 // (the f16 image of f32 queries -- scaled by the query's own power of two, scan.h: f16_shift -- is written by
-//  select.hip: k_long_setup; the select side, err_bound / k_thr_prepare, re-derives the same shift)
+//  select_thr.hip: k_long_setup; the select side, query_bound / k_thr_prepare, re-derives the same shift)
 
 #ifndef SSS_LT_LOADERS
 #define SSS_LT_LOADERS 4
