@@ -414,11 +414,14 @@ int sss_graph_fill(const int64_t* sess_ptr, const uint8_t* is_search, const int6
  * faiss.IndexBinaryFlat(nbits).add / .search (fine_tune_ours.py:839-843,871-876).
  * sss_pack_sign_bits: x [n, c] fp32 (row stride ldx) -> out [n, nbytes] uint8, bit = ((int)((x+1)/2) != 0),
  *   first column in the most significant bit of byte 0, zero padded (numpy packbits).
- * sss_hamming_topk: q [nq, nbytes], codes [n, nbytes] uint8, nbytes in {16, 32, 64}; D_out [nq, k]
+ * sss_hamming_topk: q [nq, nbytes], codes [n, nbytes] uint8, nbytes in {16, 32, 64, 128, 256} (128 to 2048 bits;
+ *   any other value returns -1: pad shorter codes with zero bytes, which add no distance); D_out [nq, k]
  *   int32 Hamming distances ascending, I_out [nq, k] int64 ids ordered by (distance asc, id asc),
  *   -1 / INT_MAX padded; status 0 = proven exact, 1 = re-run through the exhaustive entry point.
  *   k <= sss_hamming_topk_capacity(nq, n) (16 * splits, typically 1024); returns -1 for larger k (use
- *   the exhaustive entry point). */
+ *   the exhaustive entry point).  Workspace and capacity depend on (nq, n) only, not on nbytes.
+ * sss_hamming_topk_exhaustive: the same rows and widths (nbytes in {16, 32, 64, 128, 256}) for the nsel queries
+ *   listed in qsel, exact for any k and any amount of ties. */
 int sss_pack_sign_bits(const float* x, int64_t n, int c, int64_t ldx, uint8_t* out, int nbytes, void* stream);
 size_t sss_hamming_topk_workspace_bytes(int64_t nq, int64_t n);
 int sss_hamming_topk_capacity(int64_t nq, int64_t n);

@@ -13,6 +13,21 @@
 // (distance, id) in registers; k_hamming_select sorts a query's S x 16 candidates and proves
 // the result exact (every FULL list's tail is no better than the k-th result) or flags the query
 // for the exhaustive path.
+//
+// Codes of 1024 / 2048 bits (NW = 32 / 64) run k_hamming_scan_wide.  k_hamming_scan's tile is
+// 2 x 256 rows x NW words of static LDS: 64 KiB at NW = 32 (the static limit) and 128 KiB at NW = 64, and its
+// staging registers grow with NW.  The wide kernel takes the first of the three ways out, FEWER ROWS PER LDS
+// TILE WITH SEVERAL THREADS SHARING A ROW'S FETCH: a 256-row tile is walked as NW / 16 sub-tiles of 4096 / NW rows
+// (128 / 64), so a sub-tile is 16 KiB whatever the width, the double buffer is 32 KiB of static LDS
+// (no dynamic-LDS opt-in to fail, several workgroups per CU still fit), and a thread stages 64 contiguous bytes
+// -- its share of a row, NW / 16 threads to a row -- in 16 registers exactly as a thread of the 512-bit kernel
+// does, with the same coalesced 64-byte-per-lane loads and 16-byte LDS stores.  A word-chunked loop over all 256
+// rows would need 256 partial distances per thread; this needs none, and the inner loop stays the 512-bit
+// kernel's: broadcast ds_read_b128, v_xor + v_bcnt, four rows per trip.
+// THE TILE-TO-SPLIT RULE IS UNCHANGED: what is dealt round-robin is still the 256-row tile, so row id belongs to
+// split (id / 256) % S at every width, S = hamming_capacity / 16; sub-tiles of one tile stay in one list.
+// Registers per thread at NW = 64: query 64 + stage 16 + list 32 + the row words in flight; no scratch (see
+// DESIGN.md for the compiler's figures and the occupancy).
 #include "sss_common.h"
 
 namespace sss {
@@ -40,7 +55,7 @@ __device__ __forceinline__ void hlist_insert(unsigned (&ld)[N], int (&li)[N], un
     }
 }
 
-template <int NW>       // 32-bit words per code (4, 8, 16 -> 128, 256, 512 bits)
+template <int NW>       // 32-bit words per code (4, 8, 16 -> 128, 256, 512 bits; 32 and 64: k_hamming_scan_wide)
 __global__ __launch_bounds__(256) void k_hamming_scan(const unsigned* __restrict__ Q, int nq, const unsigned* __restrict__ C,
                                                       int n, int S, unsigned long long* __restrict__ cand) {
     __shared__ __attribute__((aligned(16))) unsigned tile[2][HT_ROWS * NW];
@@ -111,6 +126,88 @@ __global__ __launch_bounds__(256) void k_hamming_scan(const unsigned* __restrict
     }
 }
 
+// Rows of 128 / 256 bytes (NW = 32 / 64): the same scan over sub-tiles of SUB_ROWS rows (file header).  Thread tid
+// stages words [tid * 16, tid * 16 + 16) of the sub-tile's SUB_ROWS * NW contiguous words: row tid / NSUB, 64-byte
+// piece tid % NSUB.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+template <int NW>
+__global__ __launch_bounds__(256) void k_hamming_scan_wide(const unsigned* __restrict__ Q, int nq, const unsigned* __restrict__ C,
+                                                           int n, int S, unsigned long long* __restrict__ cand) {
+    constexpr int PIECE = 16;                        // words a thread stages: 64 bytes, a whole row of the 512-bit kernel
+    constexpr int NSUB = NW / PIECE;                 // sub-tiles per 256-row tile = threads sharing a row's fetch
+    constexpr int SUB_ROWS = HT_ROWS / NSUB;         // 128 / 64 rows: SUB_ROWS * NW = 4096 words = 16 KiB at every width
+    static_assert(NW % PIECE == 0 && SUB_ROWS * NSUB == HT_ROWS && SUB_ROWS % 4 == 0 && SUB_ROWS * NW == 256 * PIECE, "sub-tile shape");
+    __shared__ __attribute__((aligned(16))) unsigned tile[2][SUB_ROWS * NW];
+    const int tid = threadIdx.x;
+    const int split = blockIdx.x % S, g = blockIdx.x / S;
+    const int q = g * 256 + tid;
+    const int q_ld = q < nq ? q : nq - 1;
+    unsigned qw[NW];
+#pragma unroll
+    for (int w = 0; w < NW; ++w) qw[w] = Q[(size_t)q_ld * NW + w];
+    unsigned ld[HK];
+    int li[HK];
+#pragma unroll
+    for (int i = 0; i < HK; ++i) { ld[i] = 0xFFFFFFFFu; li[i] = -1; }
+    const int total_tiles = (n + HT_ROWS - 1) / HT_ROWS;
+    u32x4 stage[PIECE / 4];                          // (native vectors, not words cast to uint4: those park the array in scratch)
+    auto fetch = [&](int t, int s) {                 // rows past the end re-read row n - 1 (never scored: nrows below)
+        long row = (long)t * HT_ROWS + s * SUB_ROWS + tid / NSUB;
+        if (row > n - 1) row = n - 1;
+        const u32x4* src = reinterpret_cast<const u32x4*>(C + (size_t)row * NW + (tid % NSUB) * PIECE);
+#pragma unroll
+        for (int w = 0; w < PIECE / 4; ++w) stage[w] = src[w];
+    };
+    int t = split;                                   // tiles split, split + S, ...: round-robin over the splits, as above
+    if (t < total_tiles) fetch(t, 0);
+    int buf = 0;
+    for (; t < total_tiles; t += S) {
+#pragma unroll 1
+        for (int s = 0; s < NSUB; ++s) {
+#pragma unroll
+            for (int w = 0; w < PIECE / 4; ++w) *reinterpret_cast<u32x4*>(&tile[buf][tid * PIECE + w * 4]) = stage[w];
+            __syncthreads();                         // (double buffered: the previous sub-tile's readers are past their loop)
+            if (s + 1 < NSUB) fetch(t, s + 1);       // the next sub-tile's loads fly under this one's popcounts
+            else if (t + S < total_tiles) fetch(t + S, 0);
+            const int row0 = t * HT_ROWS + s * SUB_ROWS;
+            const int nrows = min(SUB_ROWS, n - row0);       // <= 0 in the sub-tiles past a ragged last tile's end
+            const unsigned* tl = tile[buf];
+            auto dist_of = [&](int r) {
+                unsigned d = 0;
+#pragma unroll
+                for (int w = 0; w < NW; w += 4) {
+                    const uint4 c4 = *reinterpret_cast<const uint4*>(tl + r * NW + w);   // same address in every lane: broadcast
+                    d += __builtin_popcount(c4.x ^ qw[w]) + __builtin_popcount(c4.y ^ qw[w + 1]) +
+                         __builtin_popcount(c4.z ^ qw[w + 2]) + __builtin_popcount(c4.w ^ qw[w + 3]);
+                }
+                return d;
+            };
+            int r = 0;
+            for (; r + 4 <= nrows; r += 4) {
+                const unsigned d0 = dist_of(r), d1 = dist_of(r + 1), d2 = dist_of(r + 2), d3 = dist_of(r + 3);
+                const unsigned dm = min(min(d0, d1), min(d2, d3));
+                if (__builtin_amdgcn_ballot_w64(dm < ld[HK - 1]) != 0) {
+                    if (d0 < ld[HK - 1]) hlist_insert<HK>(ld, li, d0, row0 + r);
+                    if (d1 < ld[HK - 1]) hlist_insert<HK>(ld, li, d1, row0 + r + 1);
+                    if (d2 < ld[HK - 1]) hlist_insert<HK>(ld, li, d2, row0 + r + 2);
+                    if (d3 < ld[HK - 1]) hlist_insert<HK>(ld, li, d3, row0 + r + 3);
+                }
+            }
+            for (; r < nrows; ++r) {
+                const unsigned d = dist_of(r);
+                if (d < ld[HK - 1]) hlist_insert<HK>(ld, li, d, row0 + r);
+            }
+            buf ^= 1;
+        }
+    }
+    if (q < nq) {
+        unsigned long long* dst = cand + ((size_t)q * S + split) * HK;
+#pragma unroll
+        for (int i = 0; i < HK; ++i)
+            dst[i] = li[i] >= 0 ? (((unsigned long long)ld[i] << 32) | (unsigned)li[i]) : ~0ull;
+    }
+}
+
 // One workgroup per query: bitonic sort (ascending) of its S * HK candidate keys, write the first
 // k, and prove exactness: a FULL list may have dropped rows, all of them worse than its tail, so
 // the result is exact iff no full list's tail beats the k-th result.
@@ -157,7 +254,8 @@ __global__ __launch_bounds__(HSEL_THREADS) void k_hamming_select(const unsigned 
 
 // ---- exhaustive backstop: distances of selected queries against every row, then k rounds of
 // "smallest key above the previous one" (correct for any amount of ties; slow; rare)
-template <int NW>
+// dist is unsigned short: the largest distance is the code length, 2048 bits at NW = 64, far below 65535.
+template <int NW>       // 4 ... 64: one thread per row at every width (NW / 4 16-byte loads; no LDS, nothing to re-tile)
 __global__ __launch_bounds__(256) void k_hamming_dists(const unsigned* __restrict__ Q, const int* __restrict__ qsel,
                                                        const unsigned* __restrict__ C, long n, unsigned short* __restrict__ dist) {
     const int f = blockIdx.y;
@@ -249,11 +347,17 @@ static void launch_hscan(const unsigned* q, int nq, const unsigned* c, int n, in
     const int G = (nq + 255) / 256;
     hipLaunchKernelGGL(k_hamming_scan<NW>, dim3((unsigned)(G * S)), dim3(256), 0, st, q, nq, c, n, S, cand);
 }
+template <int NW>       // the same grid, split count and candidate layout: workspace and capacity do not depend on the width
+static void launch_hscan_wide(const unsigned* q, int nq, const unsigned* c, int n, int S, unsigned long long* cand, hipStream_t st) {
+    const int G = (nq + 255) / 256;
+    hipLaunchKernelGGL(k_hamming_scan_wide<NW>, dim3((unsigned)(G * S)), dim3(256), 0, st, q, nq, c, n, S, cand);
+}
+static bool hwidth_ok(int nbytes) { return nbytes == 16 || nbytes == 32 || nbytes == 64 || nbytes == 128 || nbytes == 256; }
 
 int hamming_topk(const unsigned char* q, long nq, const unsigned char* codes, long n, int nbytes, int k, long id_offset,
                  int* D_out, long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (nq <= 0 || n <= 0 || k <= 0 || (nbytes != 16 && nbytes != 32 && nbytes != 64)) {
-        set_error("hamming_topk: need nq, n, k > 0 and 16, 32 or 64 code bytes (got %d)", nbytes);
+    if (nq <= 0 || n <= 0 || k <= 0 || !hwidth_ok(nbytes)) {
+        set_error("hamming_topk: need nq, n, k > 0 and 16, 32, 64, 128 or 256 code bytes (got %d)", nbytes);
         return SSS_EINVAL;
     }
     if (n >= (1L << 31) || nq >= (1L << 31)) { set_error("hamming_topk: n and nq must be < 2^31"); return SSS_EINVAL; }
@@ -266,7 +370,9 @@ int hamming_topk(const unsigned char* q, long nq, const unsigned char* codes, lo
     const unsigned* cu = reinterpret_cast<const unsigned*>(codes);
     if (nbytes == 16) launch_hscan<4>(qu, (int)nq, cu, (int)n, S, cand, st);
     else if (nbytes == 32) launch_hscan<8>(qu, (int)nq, cu, (int)n, S, cand, st);
-    else launch_hscan<16>(qu, (int)nq, cu, (int)n, S, cand, st);
+    else if (nbytes == 64) launch_hscan<16>(qu, (int)nq, cu, (int)n, S, cand, st);
+    else if (nbytes == 128) launch_hscan_wide<32>(qu, (int)nq, cu, (int)n, S, cand, st);
+    else launch_hscan_wide<64>(qu, (int)nq, cu, (int)n, S, cand, st);
     int rc = check_launch("k_hamming_scan");
     if (rc) return rc;
     int M2 = 64;
@@ -280,8 +386,8 @@ size_t hamming_exhaustive_workspace_bytes(long nsel, long n) { return (size_t)ns
 
 int hamming_topk_exhaustive(const unsigned char* q, const int* qsel, long nsel, const unsigned char* codes, long n, int nbytes,
                             int k, long id_offset, int* D_out, long* I_out, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (nsel <= 0 || n <= 0 || k <= 0 || nsel > 65535 || (nbytes != 16 && nbytes != 32 && nbytes != 64)) {
-        set_error("hamming_topk_exhaustive: need 0 < nsel <= 65535, n, k > 0 and 16, 32 or 64 code bytes");
+    if (nsel <= 0 || n <= 0 || k <= 0 || nsel > 65535 || !hwidth_ok(nbytes)) {
+        set_error("hamming_topk_exhaustive: need 0 < nsel <= 65535, n, k > 0 and 16, 32, 64, 128 or 256 code bytes (got %d)", nbytes);
         return SSS_EINVAL;
     }
     if (ws_bytes < hamming_exhaustive_workspace_bytes(nsel, n)) { set_error("hamming_topk_exhaustive: workspace too small"); return SSS_EWORKSPACE; }
@@ -293,7 +399,9 @@ int hamming_topk_exhaustive(const unsigned char* q, const int* qsel, long nsel, 
     const dim3 grid((unsigned)gx, (unsigned)nsel);
     if (nbytes == 16) hipLaunchKernelGGL(k_hamming_dists<4>, grid, dim3(256), 0, st, qu, qsel, cu, n, dist);
     else if (nbytes == 32) hipLaunchKernelGGL(k_hamming_dists<8>, grid, dim3(256), 0, st, qu, qsel, cu, n, dist);
-    else hipLaunchKernelGGL(k_hamming_dists<16>, grid, dim3(256), 0, st, qu, qsel, cu, n, dist);
+    else if (nbytes == 64) hipLaunchKernelGGL(k_hamming_dists<16>, grid, dim3(256), 0, st, qu, qsel, cu, n, dist);
+    else if (nbytes == 128) hipLaunchKernelGGL(k_hamming_dists<32>, grid, dim3(256), 0, st, qu, qsel, cu, n, dist);
+    else hipLaunchKernelGGL(k_hamming_dists<64>, grid, dim3(256), 0, st, qu, qsel, cu, n, dist);
     int rc = check_launch("k_hamming_dists");
     if (rc) return rc;
     hipLaunchKernelGGL(k_hamming_topk_full, dim3((unsigned)nsel), dim3(1024), 0, st, dist, qsel, n, k, id_offset, D_out, I_out);

@@ -791,20 +791,26 @@ def pack_sign_bits(emb, code_bytes: int | None = None) -> torch.Tensor:
 class BinaryFlatIndex:
     """``faiss.IndexBinaryFlat(nbits)`` as the reference uses it (fine_tune_ours.py:841-843,876):
     ``add(codes)`` with uint8 [n, nbits / 8] rows, ``search(codes, k) -> (D int32, I int64)`` by
-    Hamming distance ascending, ties by ascending id.  Codes of 128 / 256 / 512 bits run on the
-    fused scan; other widths (and unproven queries) go through the exhaustive kernels after the
-    codes are zero padded to the next supported width (padding adds no distance)."""
+    Hamming distance ascending, ties by ascending id.  Codes are stored in rows of 128 / 256 / 512 / 1024 / 2048 bits,
+    zero padded to the next of these widths (padding adds no distance; 1600 bits, the sign code of the session
+    vector, is stored in 2048), and every stored width runs on the fused scan; queries it cannot prove go through
+    the exhaustive kernels."""
 
-    WIDTHS = (16, 32, 64)
+    WIDTHS = (16, 32, 64, 128, 256)     # stored row bytes
 
-    def __init__(self, nbits: int, device=None):
+    @classmethod
+    def stored_bytes(cls, nbits: int) -> int:
+        """Row bytes a code of `nbits` bits is stored in: the next of WIDTHS."""
         if nbits % 8:
             raise ValueError("nbits must be a multiple of 8")
+        if nbits > 8 * cls.WIDTHS[-1]:
+            raise ValueError(f"codes longer than {8 * cls.WIDTHS[-1]} bits are not supported")
+        return next(w for w in cls.WIDTHS if w >= nbits // 8)
+
+    def __init__(self, nbits: int, device=None):
+        self._w = self.stored_bytes(nbits)                                  # stored (padded) row bytes
         self.d = int(nbits)
         self.code_bytes = nbits // 8
-        if self.code_bytes > 64:
-            raise ValueError("codes longer than 512 bits are not supported")
-        self._w = next(w for w in self.WIDTHS if w >= self.code_bytes)     # stored (padded) row bytes
         self.device = _dev(device)
         self._codes = torch.empty((0, self._w), dtype=torch.uint8, device=self.device)
         self._store = self._codes       # backing storage of _codes (grown geometrically by add())
