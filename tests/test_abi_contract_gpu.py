@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from oracle import gnn_ref
+from oracle.encoder_kernels_ref import gat_ref as _gat_ref, gru_ref as _gru_ref
 from oracle import search_ref as sr
 from sessionsimilaritysearch_amd import _lib
 from sessionsimilaritysearch_amd import sessions as S
@@ -768,25 +769,6 @@ def _csr(rng, n_src, n_dst, e):
     return rowptr, src[order].astype(np.int32)
 
 
-def _edges(rowptr, col, i, n_self_loop):
-    js = [int(j) for j in col[rowptr[i]:rowptr[i + 1]]]
-    if n_self_loop:
-        js = [j for j in js if j != i] + ([i] if i < n_self_loop else [])
-    return js
-
-
-def _gat_ref(xs, a_src, a_dst, rowptr, col, n_dst, bias, n_self_loop):
-    out = torch.zeros((n_dst, xs.shape[1]), dtype=torch.float64)
-    for i in range(n_dst):
-        js = _edges(rowptr, col, i, n_self_loop)
-        if js:
-            e = torch.nn.functional.leaky_relu(a_src[js] + a_dst[i], 0.2)
-            w = torch.exp(e - e.max())
-            w = w / (w.sum() + 1e-16)
-            out[i] = (w[:, None] * xs[js]).sum(0)
-    return out + bias
-
-
 @pytest.mark.parametrize("n_self_loop", [0, 29])
 def test_gat_aggregate(cuda, n_self_loop):
     rng = np.random.default_rng(53)
@@ -803,16 +785,6 @@ def test_gat_aggregate(cuda, n_self_loop):
                                             out.ptr, h + 8, _st()), [out], written=[_cols_mask((nd, h + 8), h)])
     ref = _gat_ref(xs.double(), a_s.double(), a_d.double(), rowptr, col, nd, b.double(), n_self_loop)
     assert (out.t[:, :h].cpu().double() - ref).abs().max() < 2e-5
-
-
-def _gru_ref(gi, gh, x, add):
-    h = gh.shape[1] // 3
-    r = torch.sigmoid(gi[:, :h] + gh[:, :h])
-    z = torch.sigmoid(gi[:, h:2 * h] + gh[:, h:2 * h])
-    nn_ = torch.tanh(gi[:, 2 * h:] + r * gh[:, 2 * h:])
-    xp = torch.zeros((x.shape[0], h), dtype=torch.float64)
-    xp[:, :x.shape[1]] = x
-    return torch.relu((0 if add is None else add) + (1 - z) * nn_ + z * xp)
 
 
 def test_csr_weighted_sum_and_gru(cuda):
