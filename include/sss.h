@@ -39,7 +39,8 @@ int sss_normalize_rows(float* x, int64_t n, int d, int64_t ld, float eps, int ru
 
 /* max over rows of ||x_i||_2 -> *out (device float, caller zeroes).  dtype 0: x is float32
  * (d % 4 == 0); dtype 1: x is bfloat16 (d % 8 == 0); dtype 4: x is IEEE float16 (d % 8 == 0) -- a row holding an inf
- * or a NaN makes *out +inf, so the same reduction tells whether a conversion to float16 overflowed. */
+ * or a NaN makes *out +inf, so the same reduction tells whether a conversion to float16 overflowed; dtype 6: x is int8
+ * (d % 16 == 0). */
 int sss_row_norm_max(const void* x, int64_t n, int d, int dtype, float* out, void* stream);
 
 /* float32 -> bfloat16 (round to nearest even) of `count` contiguous elements (count % 8 == 0):
@@ -50,9 +51,11 @@ int sss_f32_to_bf16(const float* x, int64_t count, uint16_t* y, void* stream);
  * dtype 0: q [nq, d] and corpus [n, d] float32 (row-major, as IndexFlatIP.add stored it), d in
  * {64,128,256}; dtype 1: both bfloat16, d in {128,256,512} (f32 accumulate on the bf16 MFMA); dtype 4: both IEEE
  * float16, d in {128,256,512} (f32 accumulate on the f16 MFMA; the stored float16 values are the rows of record: no
- * scaling, no float32 copy; error bound of a scan score d 2^-23 |q| |c|, finite rows only).  The corpus dtype codes
- * are 0, 1 and 4 wherever a `dtype` is taken; 2 and 3 name scan images of a float32 corpus (`scan` below), never a
- * corpus: -1.
+ * scaling, no float32 copy; error bound of a scan score d 2^-23 |q| |c|, finite rows only); dtype 6: both int8 (queries
+ * are int8 like the rows, as the 16-bit dtypes put queries in the stored type), d in {256,512,1024} (int32 accumulate on
+ * v_mfma_i32_32x32x32_i8; the stored int8 values are the rows of record and a scan score is the canonical score: error
+ * bound 0, as |score| <= d 2^14 <= 2^24 is exact in float32).  The corpus dtype codes are 0, 1, 4 and 6 wherever a `dtype`
+ * is taken; 2 and 3 name scan images of a float32 corpus (`scan` below), never a corpus, and 5 is unassigned: -1.
  * k <= 500.  Writes D_out [nq, k] fp32 (descending) and I_out [nq, k] int64 = row + id_offset,
  * ordered by (score desc, id asc); missing results: I = -1, D = -FLT_MAX (faiss convention).
  * Scores are the canonical ones of DESIGN.md (float64 sequential dot of the stored elements,
@@ -127,8 +130,8 @@ int sss_ip_topk_f16(const float* q, int64_t nq, const float* corpus, const uint1
  * lies above (bound - scan error bound - one float32 ulp) and re-scores them all canonically (float64, from
  * `corpus`): exact for near ties and for exact ties (duplicate rows) alike.  Resolved queries get their rows of
  * D_out / I_out rewritten and status 0; a query with more than 8192 such rows (or NaNs) keeps its status and goes
- * to sss_ip_topk_exhaustive.  scan: 0 / 1 / 4 = the corpus itself (f32 / bf16 / f16 index: scan = dtype, pass
- * scan_image = corpus),
+ * to sss_ip_topk_exhaustive.  scan: 0 / 1 / 4 / 6 = the corpus itself (f32 / bf16 / f16 / int8 index: scan = dtype,
+ * pass scan_image = corpus),
  * 2 = the [hi | lo] bf16 image (sss_split_bf16), 3 = the scaled float16 image (corpus_shift / corpus_resid_norm
  * as for sss_ip_topk_f16; ignored otherwise).  Serves the same result contract as the reference's
  * `index.search` (test_amazon_filterd.py:578).  workspace (256-byte aligned):
@@ -152,6 +155,7 @@ int sss_ip_topk_threshold(const void* q, const int32_t* qsel, int64_t nsel, cons
  * corpus_resid_norm as for sss_ip_topk_f16; the queries are scaled + rounded to float16 internally).
  * dtype 1: q / corpus bfloat16, scan_image = corpus (shift / residual ignored).
  * dtype 4: q / corpus float16, scan_image = corpus: float16 rows are their own scan image (shift / residual ignored).
+ * dtype 6 (int8 rows) has no long-row scan: -1, and a workspace size of 0; such rows go to sss_ip_topk_exhaustive.
  * workspace (256-byte aligned): sss_ip_topk_long_workspace_bytes(nq, n, d, dtype). */
 size_t sss_ip_topk_long_workspace_bytes(int64_t nq, int64_t n, int d, int dtype);
 int sss_ip_topk_long(const void* q, int64_t nq, const void* corpus, int dtype, const void* scan_image,
@@ -161,7 +165,7 @@ int sss_ip_topk_long(const void* q, int64_t nq, const void* corpus, int dtype, c
 
 /* Exhaustive exact search for a (small) set of queries: qsel [nsel] int32 are the query rows of
  * q to process; results are written to rows qsel[i] of D_out / I_out.  Any n, any d % 4 == 0
- * (dtype 0) or d % 8 == 0 (dtype 1, 4), k <= 1024.  metric: 0 = inner product, 1 = squared L2
+ * (dtype 0), d % 8 == 0 (dtype 1, 4) or d % 16 == 0 (dtype 6), k <= 1024.  metric: 0 = inner product, 1 = squared L2
  * (IndexFlatL2, test_amazon_filterd.py:215-217; D ascending).
  * workspace: sss_ip_topk_exhaustive_workspace_bytes(nsel, n). */
 size_t sss_ip_topk_exhaustive_workspace_bytes(int64_t nsel, int64_t n);
@@ -173,7 +177,8 @@ int sss_ip_topk_exhaustive(const void* q, const int32_t* qsel, int64_t nsel, con
 /* The same (inner-product metric) with a per-query LOWER bound of the k-th best score, lower_bound [nsel]
  * float32 -- e.g. D_out[q][k-1] of a fused search that returned status != 0: its k-th re-scored candidate
  * is a real row's canonical score.  A float32 pre-test then skips the float64 chain for every row that
- * provably scores below the bound (d in {64,128,256} float32 / {128,256} bfloat16 or float16; other shapes ignore it).
+ * provably scores below the bound (d in {64,128,256} float32 / {128,256} bfloat16 or float16; other shapes, and int8
+ * rows at every d, ignore it).
  * Results are identical to sss_ip_topk_exhaustive; pass -FLT_MAX where no bound is known. */
 int sss_ip_topk_exhaustive_lb(const void* q, const int32_t* qsel, int64_t nsel, const void* corpus,
                               int64_t n, int d, int k, int dtype, int64_t id_offset,
@@ -199,7 +204,7 @@ int sss_range_search_count(const void* q, int64_t nq, const void* corpus, int dt
                            size_t workspace_bytes, void* stream);
 int sss_range_search_fill(int64_t nq, const int64_t* lims, int64_t id_offset, float* D_out, int64_t* I_out,
                           const void* workspace, size_t workspace_bytes, void* stream);
-/* Exhaustive route: any n, any d % 4 == 0 (dtype 0) / d % 8 == 0 (dtype 1, 4), metric 0 = inner product, 1 = squared
+/* Exhaustive route: any n, any d % 4 == 0 (dtype 0) / d % 8 == 0 (dtype 1, 4) / d % 16 == 0 (dtype 6), metric 0 = inner product, 1 = squared
  * L2.  qsel [nsel] int32 (nsel <= 65535): the query rows to process; counts [nsel] and lims [nsel + 1] follow the
  * order of qsel.  The scores of all nsel queries stay in the workspace between count and fill:
  * sss_range_search_exhaustive_workspace_bytes(nsel, n), ~4 n bytes per query. */

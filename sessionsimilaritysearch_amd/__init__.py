@@ -1,7 +1,8 @@
 """MI355X-native session-similarity retrieval hot path.
 
 Drop-in surface of the reference's path:
-  normalize, build_index, FlatIndex (f32 / bf16 / f16)  (index.py <- test_amazon_filterd.py / util_amazon_filtered.py)
+  normalize, build_index, FlatIndex (f32 / bf16 / f16 / i8), quantize_i8
+                                                  (index.py     <- test_amazon_filterd.py / util_amazon_filtered.py)
   BinaryFlatIndex, pack_sign_bits                 (index.py     <- fine_tune_ours.py IndexBinaryFlat branch)
   SessionEncoder (+ prepare_actions)              (encoder.py   <- model/model.py UnifyPoolingGraphLevelEncoder,
                                                                   util_amazon_filtered.sequence_to_graph)

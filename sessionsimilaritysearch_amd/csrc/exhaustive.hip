@@ -14,7 +14,8 @@ constexpr int EX_LD = EX_KC + 4;
 
 // scores[f][row] = float32( sum_k q[qsel[f]][k] * c[row][k] ) accumulated sequentially in
 // float64 (metric 0), or sum_k (q_k - c_k)^2 with one rounding per multiply and per add (1).
-// DT_BF16 / DT_H16: q and c hold bf16 / float16; every element converts exactly to float32 on the way into LDS.
+// DT_BF16 / DT_H16 / DT_I8: q and c hold bf16 / float16 / int8; every element converts exactly to float32 on the way into
+// LDS (int8: every partial sum of either metric is an integer below 2^53, so the chain rounds nowhere).
 template <int DT>
 __global__ __launch_bounds__(64) void k_exact_scores(const void* __restrict__ Qv,
                                                      const int* __restrict__ qsel,
@@ -22,7 +23,7 @@ __global__ __launch_bounds__(64) void k_exact_scores(const void* __restrict__ Qv
                                                      int metric, float* __restrict__ scores) {
     __shared__ __attribute__((aligned(16))) float tile[EX_ROWS * EX_LD];
     __shared__ __attribute__((aligned(16))) float qs[EX_KC];
-    constexpr int EB = DT == DT_F32 ? 4 : 2;          // bytes per element
+    constexpr int EB = DT == DT_F32 ? 4 : DT == DT_I8 ? 1 : 2;   // bytes per element
     constexpr int EPV = 16 / EB;                      // elements per 16-byte load
     const int lane = threadIdx.x;
     const int f = blockIdx.y;
@@ -31,6 +32,7 @@ __global__ __launch_bounds__(64) void k_exact_scores(const void* __restrict__ Qv
     auto to_f32 = [](const char* p, int i) -> float {
         if (DT == DT_F32) return reinterpret_cast<const float*>(p)[i];
         if (DT == DT_H16) return (float)reinterpret_cast<const _Float16*>(p)[i];
+        if (DT == DT_I8) return (float)reinterpret_cast<const signed char*>(p)[i];
         return __builtin_bit_cast(float, (unsigned)reinterpret_cast<const unsigned short*>(p)[i] << 16);
     };
     for (long row0 = (long)blockIdx.x * EX_ROWS; row0 < n; row0 += (long)gridDim.x * EX_ROWS) {
@@ -514,6 +516,8 @@ static int launch_exact_scores(const void* q, const int* qsel, long nsel, const 
         hipLaunchKernelGGL(k_exact_scores<DT_F32>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
     else if (dtype == DT_H16)
         hipLaunchKernelGGL(k_exact_scores<DT_H16>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
+    else if (dtype == DT_I8)                            // (no row-resident form: every int8 shape ignores the bound)
+        hipLaunchKernelGGL(k_exact_scores<DT_I8>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
     else
         hipLaunchKernelGGL(k_exact_scores<DT_BF16>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
 #undef SSS_ROWS
@@ -528,8 +532,8 @@ int ip_topk_exhaustive(const void* q, const int* qsel, long nsel, const void* c,
                        int k, int dtype, long id_offset, int metric, const float* lower_bound, float* D_out, long* I_out,
                        void* ws, size_t ws_bytes, hipStream_t st) {
     if (nsel <= 0 || n <= 0 || k <= 0 || d <= 0 || !corpus_dtype_ok(dtype) ||
-        d % (dtype == DT_F32 ? 4 : 8) || (metric != 0 && metric != 1)) {
-        set_error("ip_topk_exhaustive: need nsel, n, k > 0, d %% 4 == 0 (f32) / d %% 8 == 0 (bf16, f16), metric in {0,1}");
+        d % elems_per_chunk(dtype) || (metric != 0 && metric != 1)) {
+        set_error("ip_topk_exhaustive: need nsel, n, k > 0, d %% 4 == 0 (f32) / d %% 8 == 0 (bf16, f16) / d %% 16 == 0 (int8), metric in {0,1}");
         return SSS_EINVAL;
     }
     if (n >= (1L << 31) || nsel > 65535 || k > RS_MAX_K) { set_error("ip_topk_exhaustive: n < 2^31, nsel <= 65535, k <= 1024"); return SSS_EINVAL; }
@@ -681,8 +685,8 @@ static int range_exhaustive_check(const char* what, const int* qsel, long nsel, 
 
 int range_exhaustive_count(const void* q, const int* qsel, long nsel, const void* c, long n, int d, int dtype, int metric, const float* radius,
                            long* counts, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (d <= 0 || !corpus_dtype_ok(dtype) || d % (dtype == DT_F32 ? 4 : 8) || !q || !c || !counts) {
-        set_error("range_exhaustive_count: need d %% 4 == 0 (f32) / d %% 8 == 0 (bf16, f16), q, corpus and counts");
+    if (d <= 0 || !corpus_dtype_ok(dtype) || d % elems_per_chunk(dtype) || !q || !c || !counts) {
+        set_error("range_exhaustive_count: need d %% 4 == 0 (f32) / d %% 8 == 0 (bf16, f16) / d %% 16 == 0 (int8), q, corpus and counts");
         return SSS_EINVAL;
     }
     int rc = range_exhaustive_check("range_exhaustive_count", qsel, nsel, n, metric, radius, ws, ws_bytes);

@@ -49,17 +49,22 @@ int profile_read(double* total_ms, int* launches) {
 
 static bool fused_shape_ok(int d, int dtype) {
     const int rb = d * elem_bytes(dtype);
-    return (dtype == DT_F32 || dtype == DT_BF16 || dtype == DT_SPLIT || dtype == DT_F16 || dtype == DT_H16) &&
+    // (DT_I8: d = 256 / 512 / 1024 -- the d <= 1024 that keeps an int8 score exact in float32, select_dev.h: err_bound)
+    return (dtype == DT_F32 || dtype == DT_BF16 || dtype == DT_SPLIT || dtype == DT_F16 || dtype == DT_H16 || dtype == DT_I8) &&
            (rb == 256 || rb == 512 || rb == 1024);
 }
 
 // scan_dtype: what k_scan reads for rows of exact_dtype -- f32 rows: themselves, their split or their f16 image; bf16
-// and f16 rows: themselves.
+// f16 and int8 rows: themselves.
 int check_scan_source(const char* what, int exact_dtype, int scan_dtype, int d, bool long_rows, const void* c_scan, int corpus_shift,
                       float corpus_resid, long n, long nq) {
-    static const char* const image[] = {"f32 corpus", "bf16 corpus", "split image", "f16 image", "f16 corpus"};
+    static const char* const image[] = {"f32 corpus", "bf16 corpus", "split image", "f16 image", "f16 corpus", "", "int8 corpus"};
     const bool paired = exact_dtype == DT_F32 ? (scan_dtype == DT_F32 || scan_dtype == DT_SPLIT || scan_dtype == DT_F16)
-                                              : (exact_dtype == DT_BF16 || exact_dtype == DT_H16) && scan_dtype == exact_dtype;
+                                              : (exact_dtype == DT_BF16 || exact_dtype == DT_H16 || exact_dtype == DT_I8) && scan_dtype == exact_dtype;
+    if (long_rows && exact_dtype == DT_I8) {
+        set_error("%s: int8 rows (dtype %d) have no long-row scan: d in {256,512,1024} on the fused scan, else the exhaustive kernels", what, DT_I8);
+        return SSS_EINVAL;
+    }
     if (!paired || !(long_rows ? long_shape_ok(d, exact_dtype, scan_dtype) : fused_shape_ok(d, scan_dtype))) {
         set_error("%s: no scan of type %d for dtype %d, d %d", what, scan_dtype, exact_dtype, d);
         return SSS_EINVAL;
@@ -87,17 +92,17 @@ ThrArgs thr_args(const void* q, const void* c_exact, int exact_dtype, int scan_d
 
 size_t ip_topk_state_bytes(long nq) { return nq > 0 ? state_words(nq) * 4 : 0; }
 
-size_t ip_topk_workspace_bytes(long nq, long n, int d, int k, int dtype) {      // dtype: the C ABI's (0 / 1 / 4)
+size_t ip_topk_workspace_bytes(long nq, long n, int d, int k, int dtype) {      // dtype: the C ABI's (0 / 1 / 4 / 6)
     if (nq <= 0 || n <= 0 || k <= 0 || !corpus_dtype_ok(dtype) || !fused_shape_ok(d, dtype)) return 0;
     return make_plan(nq, n, d, k, dtype).total_bytes;
 }
 
-size_t ip_topk_scan_workspace_bytes(long nq, long n, int d, int k, int scan_dtype) {   // scan.h codes (0..4)
+size_t ip_topk_scan_workspace_bytes(long nq, long n, int d, int k, int scan_dtype) {   // scan.h codes (0..4, 6)
     if (nq <= 0 || n <= 0 || k <= 0 || !fused_shape_ok(d, scan_dtype)) return 0;
     return make_plan(nq, n, d, k, scan_dtype).total_bytes;
 }
 
-// scan_dtype: what k_scan reads at c_scan (DT_F32 / DT_BF16 / DT_H16: the corpus itself; DT_SPLIT: the
+// scan_dtype: what k_scan reads at c_scan (DT_F32 / DT_BF16 / DT_H16 / DT_I8: the corpus itself; DT_SPLIT: the
 // [hi | lo] bf16 image of an f32 corpus; DT_F16: its scaled f16 image, corpus * 2^corpus_shift);
 // c_exact / exact_dtype: the rows the candidates are re-scored from (and the element type of q).
 static int ip_topk_impl(const char* what, const void* q, long nq, const void* c_scan, int scan_dtype, int corpus_shift,

@@ -142,6 +142,32 @@ __global__ __launch_bounds__(256) void k_row_norm_max_f16(const unsigned short* 
         atomicMax(reinterpret_cast<unsigned int*>(out), __builtin_bit_cast(unsigned int, norm_up(m)));
 }
 
+// int8 rows (include/sss.h: dtype 6): the same maximum; a row's sum of squares is an integer (exact in int64, then in
+// float64), so the value is the exact norm rounded up by norm_up.
+__global__ __launch_bounds__(256) void k_row_norm_max_i8(const signed char* __restrict__ x, long n, int d, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
+    double m = 0.0;
+    for (long row = wave; row < n; row += nwaves) {
+        const u32x4* p = reinterpret_cast<const u32x4*>(x + row * (long)d);
+        long ss = 0;
+        for (int i = lane; i < d / 16; i += 64) {
+            const u32x4 v = p[i];
+            const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) { const int t = (int)(signed char)(w[e] >> (8 * b)); ss += t * t; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+        m = fmax(m, (double)ss);
+    }
+    if (lane == 0)
+        atomicMax(reinterpret_cast<unsigned int*>(out), __builtin_bit_cast(unsigned int, norm_up(m)));
+}
+
 // float32 -> bfloat16, round to nearest even (plain cast: v_cvt_pk_bf16_f32, NaN stays NaN);
 // 8 elements per thread, 32-byte loads / 16-byte stores.
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -318,8 +344,16 @@ int row_norm_max(const void* xv, long n, int d, int dtype, float* out, hipStream
                                reinterpret_cast<const unsigned short*>(xv), n, d, out);
         return check_launch("k_row_norm_max_16");
     }
+    if (dtype == 6) {                                   // include/sss.h: int8 rows
+        if (n < 0 || d <= 0 || d % 16) { set_error("row_norm_max: int8 needs d %% 16 == 0"); return SSS_EINVAL; }
+        if (n == 0) return SSS_OK;
+        long blocks = (n + 3) / 4;
+        if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL(k_row_norm_max_i8, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const signed char*>(xv), n, d, out);
+        return check_launch("k_row_norm_max_i8");
+    }
     const float* x = reinterpret_cast<const float*>(xv);
-    if (dtype != 0 || n < 0 || d <= 0 || d % 4) { set_error("row_norm_max: need dtype in {0,1,4}, n >= 0, d %% 4 == 0"); return SSS_EINVAL; }
+    if (dtype != 0 || n < 0 || d <= 0 || d % 4) { set_error("row_norm_max: need dtype in {0,1,4,6}, n >= 0, d %% 4 == 0"); return SSS_EINVAL; }
     if (n == 0) return SSS_OK;
     const int lpr = lanes_per_row(d);
     SSS_DISPATCH_LPR(lpr, hipLaunchKernelGGL(k_row_norm_max<L>, dim3(grid_for(n, L)), dim3(256), 0, st, x, n, d, out));

@@ -27,6 +27,11 @@ constexpr int DT_F16 = 3;
 // they are -- no scaling, no residual, scan scores are scores -- and the candidates are re-scored from the same rows.
 // (3 stays the scaled image of an f32 corpus: the two share the MFMA and the operand layout, not the bound.)
 constexpr int DT_H16 = 4;
+// Corpus dtype of the C ABI (include/sss.h: dtype 6; 5 stays unassigned) and its own scan type: rows STORED as int8,
+// queries int8 too, 1 byte per element.  Rows and queries go into v_mfma_i32_32x32x32_i8 as they are, 16 elements per
+// 16-byte chunk; products and sums are exact in int32, and for the fused shapes (d <= 1024) |score| <= d * 2^14 <= 2^24
+// is exact in float32 as well: the scan score IS the canonical score (select_dev.h: err_bound = 0).
+constexpr int DT_I8 = 6;
 
 // shift that maps a largest magnitude `amax` into [2^12, 2^13); 0 for an all-zero / non-finite row
 __host__ __device__ inline int f16_shift(float amax) {
@@ -49,12 +54,13 @@ constexpr unsigned ORD_NEG_INF = 0x007FFFFFu;   // f2ord(-inf); slot value 0 = "
 constexpr double ULP32_REL = 2.4e-7;
 constexpr double ULP32_MIN = 1e-44;             // ... and its floor in the subnormal range (the spacing there is 2^-149 = 1.4e-45)
 
-static inline int elem_bytes(int dtype) { return (dtype == DT_BF16 || dtype == DT_F16 || dtype == DT_H16) ? 2 : 4; }
+static inline int elem_bytes(int dtype) { return dtype == DT_I8 ? 1 : (dtype == DT_BF16 || dtype == DT_F16 || dtype == DT_H16) ? 2 : 4; }
+static inline int elems_per_chunk(int dtype) { return 16 / elem_bytes(dtype); }   // a stored row is read in 16-byte pieces: d % this == 0
 static inline int pow2_at_least(int x) { int p = 64; while (p < x) p <<= 1; return p; }   // smallest power of two >= max(x, 64): LDS key arrays
-static inline bool corpus_dtype_ok(int dtype) { return dtype == DT_F32 || dtype == DT_BF16 || dtype == DT_H16; }   // what crosses the C ABI as `dtype`
+static inline bool corpus_dtype_ok(int dtype) { return dtype == DT_F32 || dtype == DT_BF16 || dtype == DT_H16 || dtype == DT_I8; }   // what crosses the C ABI as `dtype`
 
 // Row shapes of sss_ip_topk_long: d % 64 == 0 and exact rows of at most 16384 bytes (k_select_all keeps the query row in
-// LDS); f32 rows are scanned through their f16 image, bf16 and f16 rows directly.
+// LDS); f32 rows are scanned through their f16 image, bf16 and f16 rows directly.  int8 rows have no long-row scan.
 static inline bool long_shape_ok(int d, int exact_dtype, int scan_dtype) {
     if (d <= 0 || d % 64 || d * elem_bytes(exact_dtype) > 16384) return false;
     return (exact_dtype == DT_F32 && scan_dtype == DT_F16) || (exact_dtype == DT_BF16 && scan_dtype == DT_BF16) ||
@@ -104,7 +110,7 @@ struct SelectArgs {
     const void* C;
     int nq, d, dtype, k, K2, J, cap;
     int tau_skip = 0;               // the scan's rank-selected threshold: (tau_skip + 1)-th smallest of the 16 slots
-    int scan_dtype;                 // what produced the candidates (DT_F32 / DT_BF16 / DT_SPLIT / DT_F16 / DT_H16): picks the error bound
+    int scan_dtype;                 // what produced the candidates (DT_F32 / DT_BF16 / DT_SPLIT / DT_F16 / DT_H16 / DT_I8): picks the error bound
     int corpus_shift;               // DT_F16: the corpus image is corpus * 2^corpus_shift (else 0)
     float corpus_resid;             // DT_F16: largest row norm of (image * 2^-corpus_shift - corpus)
     const unsigned long long* cand;

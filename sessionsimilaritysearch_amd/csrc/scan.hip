@@ -1,4 +1,4 @@
-// Query x corpus inner-product CANDIDATE scan with fused running top-k (gfx950 / CDNA4): f32, bf16, f16 rows,
+// Query x corpus inner-product CANDIDATE scan with fused running top-k (gfx950 / CDNA4): f32, bf16, f16, int8 rows,
 // split-bf16 (three passes over an f32 corpus) and scaled f16 (one pass over an f32 corpus).
 //
 // Replaces what the reference asks of faiss at test_amazon_filterd.py:578
@@ -16,7 +16,9 @@
 //     v_mfma_f32_32x32x2_f32 (DT_F32: an exact k-ordered f32 fma chain), v_mfma_f32_32x32x16_bf16
 //     (DT_BF16; DT_SPLIT: hi*hi + hi*lo + lo*hi of rows stored [hi | lo]) or v_mfma_f32_32x32x16_f16
 //     (DT_F16: f32 queries scaled by their own power of two and rounded in the prologue; DT_H16: stored f16 rows
-//     and f16 queries as they are), so the query tile is read from HBM once;
+//     and f16 queries as they are) or v_mfma_i32_32x32x32_i8 (DT_I8: stored int8 rows and int8 queries, 16 elements
+//     per 16-byte chunk, exact int32 sums converted to float32 keys once per 64-row step), so the query tile is read
+//     from HBM once;
 //   * corpus rows stream HBM -> LDS with global_load_lds_dwordx4 (no VGPR staging), double
 //     buffered, one burst per tile, 16-byte chunks XOR-swizzled on the SOURCE address so the
 //     ds_read_b128 fragment reads are bank-conflict free.  Rows of equal BYTES stage and read
@@ -302,6 +304,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
         for (int u = 0; u < PF && u < NU; ++u) { const f32x4* p = lda(u); as0[u] = p[0]; as1[u] = p[32 * CH]; }
         const f32x16 zero = {0};
         acc0 = zero; acc1 = zero;
+        [[maybe_unused]] i32x16 ia0 = {0}, ia1 = {0};       // DT_I8: the step's int32 accumulators
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
             if (u + PF < NU) { const f32x4* p = lda(u + PF); as0[u + PF] = p[0]; as1[u + PF] = p[32 * CH]; }
@@ -324,6 +327,12 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
                 const f16x8 qb = __builtin_bit_cast(f16x8, qc[u]);
                 acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a0), qb, acc0, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a1), qb, acc1, 0, 0, 0);
+            } else if constexpr (DT == DT_I8) {
+                // (lane half h holds the same 16 k values of chunk 2u + h on the A and on the B side: whatever order the
+                //  unit gives the 16 bytes of a lane, a row's byte j meets the query's byte j)
+                const i32x4 qb = __builtin_bit_cast(i32x4, qc[u]);
+                ia0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, a0), qb, ia0, 0, 0, 0);
+                ia1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, a1), qb, ia1, 0, 0, 0);
             } else {
                 // split f32: chunks of the hi half meet q_hi and q_lo, chunks of the lo half meet q_hi
                 const bf16x8 A0 = __builtin_bit_cast(bf16x8, a0), A1 = __builtin_bit_cast(bf16x8, a1);
@@ -337,6 +346,11 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (DT == DT_I8) {
+            // |sum| <= RB * 2^14 <= 2^24: the conversion is exact, the float32 key is the score itself
+            acc0 = __builtin_convertvector(ia0, f32x16);
+            acc1 = __builtin_convertvector(ia1, f32x16);
         }
         if constexpr (H > 1) { if (sub == 0 && next_tile >= 0) stage(buf ^ 1, next_tile); }
     };
@@ -545,8 +559,9 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
     // live across the barrier): after every barrier one partner starts with matrix work, the other with vector work.
     // Measured (same device, alternating builds): split scan -3.5 %, bf16 C5 -1.3 % time; f16 and f32 scans unchanged
     // to +1 % (their partners drift apart by themselves), so those keep the plain order.
-    // (DT_H16 -- stored f16 rows -- is the bf16 kernel with the other MFMA: it takes the bf16 order)
-    const bool defer = SSS_STAGGER && NW == 8 && (DT == DT_SPLIT || DT == DT_BF16 || DT == DT_H16) && wave >= 4;
+    // (DT_H16 -- stored f16 rows -- and DT_I8 -- stored int8 rows -- are the bf16 kernel with another MFMA: they take the
+    //  bf16 order)
+    const bool defer = SSS_STAGGER && NW == 8 && (DT == DT_SPLIT || DT == DT_BF16 || DT == DT_H16 || DT == DT_I8) && wave >= 4;
     int t = 0;
     if constexpr (AP || THR) {
         // The forms WITHOUT lane lists (append, threshold) have no list state to keep out of the hot loop, so theirs is the
@@ -831,6 +846,10 @@ int launch_scan(int dtype, int d, int tile_rows, const ScanArgs& a, hipStream_t 
         if (rb == 256) return tile_rows == 256 ? launch_one<256, 256, DT_H16>(a, st) : launch_one<256, 128, DT_H16>(a, st);
         if (rb == 512) return tile_rows == 128 ? launch_one<512, 128, DT_H16>(a, st) : launch_one<512, 64, DT_H16>(a, st);
         if (rb == 1024) return launch_one<1024, 64, DT_H16, 4>(a, st);
+    } else if (dtype == DT_I8) {
+        if (rb == 256) return tile_rows == 256 ? launch_one<256, 256, DT_I8>(a, st) : launch_one<256, 128, DT_I8>(a, st);
+        if (rb == 512) return tile_rows == 128 ? launch_one<512, 128, DT_I8>(a, st) : launch_one<512, 64, DT_I8>(a, st);
+        if (rb == 1024) return launch_one<1024, 64, DT_I8, 4>(a, st);
     } else if (dtype == DT_SPLIT) {
         if (rb == 256) return tile_rows == 256 ? launch_one<256, 256, DT_SPLIT>(a, st) : launch_one<256, 128, DT_SPLIT>(a, st);
         if (rb == 512) return tile_rows == 128 ? launch_one<512, 128, DT_SPLIT>(a, st) : launch_one<512, 64, DT_SPLIT>(a, st);

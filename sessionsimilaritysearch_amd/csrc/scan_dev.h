@@ -8,6 +8,8 @@ typedef char __attribute__((address_space(3)))* lptr_c;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));       // 16 int8 values: one A / B operand of v_mfma_i32_32x32x32_i8
+typedef int i32x16 __attribute__((ext_vector_type(16)));     // its int32 accumulators (the C / D layout of the 16-bit forms)
 
 // Sorted (descending) insert of (x, id) into a register list; lanes whose x does not beat
 // their list tail fall through untouched.
@@ -91,9 +93,9 @@ __device__ __forceinline__ void load8_sc1(const unsigned* p, unsigned (&v)[8]) {
 }
 
 // Resident queries of one 32-query MFMA B operand: lane (r, h) ends up with the 16-byte chunks of query row
-// q_ld it meets in the k-groups (qc[u]: k = 16u + 8h .. + 7 for the 16-bit types, chunk 2u + h for f32).
-// DT_SPLIT / DT_F16 take float32 queries and split / scale + round them here (scan.h); the others (DT_H16: float16
-// queries against float16 rows) load the row as it is stored.
+// q_ld it meets in the k-groups (qc[u]: k = 16u + 8h .. + 7 for the 16-bit types, k = 32u + 16h .. + 15 for int8, chunk
+// 2u + h for f32).  DT_SPLIT / DT_F16 take float32 queries and split / scale + round them here (scan.h); the others
+// (DT_H16: float16 queries against float16 rows, DT_I8: int8 against int8) load the row as it is stored.
 template <int RB, int DT>
 __device__ __forceinline__ void load_queries(const char* __restrict__ Qb, int q_ld, int h, f32x4 (&qc)[RB / 32]) {
     constexpr int NU = RB / 32;

@@ -83,6 +83,7 @@ __device__ __forceinline__ void rescore16(const unsigned long long* sel, double*
                                           const char* qrow, int dtype, int lane) {
     if (dtype == DT_F32) rescore16_t<DT_F32>(sel, resc, c0, c1, C, rb, qrow, lane);
     else if (dtype == DT_H16) rescore16_t<DT_H16>(sel, resc, c0, c1, C, rb, qrow, lane);
+    else if (dtype == DT_I8) rescore16_t<DT_I8>(sel, resc, c0, c1, C, rb, qrow, lane);
     else rescore16_t<DT_BF16>(sel, resc, c0, c1, C, rb, qrow, lane);
 }
 
@@ -90,7 +91,15 @@ __device__ __forceinline__ void rescore16(const unsigned long long* sel, double*
 __device__ __forceinline__ _Float16 h16_lo(unsigned w) { return __builtin_bit_cast(_Float16, (unsigned short)(w & 0xFFFFu)); }
 __device__ __forceinline__ _Float16 h16_hi(unsigned w) { return __builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
 
-// acc += sum over the elements of one 16-byte chunk (4 f32, 8 bf16 or 8 f16), sequential in k
+// sum of the four int8 products of two 32-bit words (at most 4 * 2^14: exact in int32)
+__device__ __forceinline__ int i8_dot4(unsigned q, unsigned c) {
+    int s = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) s += (int)(signed char)(q >> (8 * b)) * (int)(signed char)(c >> (8 * b));
+    return s;
+}
+
+// acc += sum over the elements of one 16-byte chunk (4 f32, 8 bf16, 8 f16 or 16 int8), sequential in k
 __device__ __forceinline__ double dot_chunk(double acc, const char* qrow, int v, f32x4 c, int dtype) {
     if (dtype == DT_F32) {
         const f32x4 qv = *reinterpret_cast<const f32x4*>(qrow + v * 16);
@@ -102,6 +111,12 @@ __device__ __forceinline__ double dot_chunk(double acc, const char* qrow, int v,
     }
     const u32x4 cu = __builtin_bit_cast(u32x4, c);
     const u32x4 qu = *reinterpret_cast<const u32x4*>(qrow + v * 16);
+    if (dtype == DT_I8) {
+        // Every product and every partial sum of the float64 chain is an integer below 2^53, so the chain rounds nowhere
+        // and equals the integer sum in any order: the chunk's 16 products are summed in int32 and added once.
+        acc += (double)(i8_dot4(qu.x, cu.x) + i8_dot4(qu.y, cu.y) + i8_dot4(qu.z, cu.z) + i8_dot4(qu.w, cu.w));
+        return acc;
+    }
     if (dtype == DT_H16) {                                        // f16 -> f64 is exact (subnormals included)
 #define SSS_H2(w)                                                                                     \
     acc += (double)h16_lo(qu.w) * (double)h16_lo(cu.w);                                               \
@@ -146,6 +161,7 @@ __device__ __forceinline__ double rescore_row(const char* qrow, const char* row,
 
 __device__ __forceinline__ float elem_to_f32(const void* row, int kk, int dtype) {
     if (dtype == DT_F32) return reinterpret_cast<const float*>(row)[kk];
+    if (dtype == DT_I8) return (float)reinterpret_cast<const signed char*>(row)[kk];
     const unsigned short b = reinterpret_cast<const unsigned short*>(row)[kk];
     if (dtype == DT_H16) return (float)__builtin_bit_cast(_Float16, b);   // f16 -> f32 is exact
     return __builtin_bit_cast(float, (unsigned)b << 16);          // bf16 -> f32 is exact
@@ -173,6 +189,13 @@ __device__ __forceinline__ float elem_to_f32(const void* row, int kk, int dtype)
 //            A product of two f16 values has 22 significant bits and lies in [2^-48, 2^32): exact in f32, and so
 //            is every partial sum's grid (multiples of 2^-48); what remains is the f32 accumulation, as for bf16:
 //                                                                  d * 2^-23 * |q| |c|
+//   DT_I8    rows and queries STORED as int8 and fed to the i8 MFMA as they are, int32 accumulators: products and sums
+//            of integers, exact in any order.  The scan key is that int32 converted to float32, exact while
+//            |score| <= d * 2^14 <= 2^24 -- the premise d <= 1024, which the fused shapes' row sizes enforce
+//            (ip_topk.hip: fused_shape_ok; 1 byte per element, rows of at most 1024 bytes).  The scan score IS the
+//            canonical score:                                               0
+//            (what is left of the proof window is its float32 ulp term: a proof fails on exact ties at rank k and,
+//             near |score| = 2^24 where that term reaches 4, on scores within 4 of the k-th)
 // (each with 2 % headroom; |c| <= the corpus' largest row norm, an upper bound at any magnitude: rowops.hip).
 // The relative terms assume normal float32 arithmetic.  Where the f32 values of a chain fall below FLT_MIN = 2^-126
 // they lose up to half a subnormal spacing (2^-150) per rounding, or -- if a unit flushes subnormals -- the whole
@@ -197,6 +220,7 @@ __device__ __forceinline__ double err_bound(int d, int scan_dtype, double qnorm,
     if (scan_dtype == DT_F32) b = (double)d * 5.9604644775390625e-08 * qnorm * cmax + (double)d * U149;
     else if (scan_dtype == DT_BF16) b = (double)d * 1.1920928955078125e-07 * qnorm * cmax + (2.0 * d + rd * (qnorm + cmax)) * U126;
     else if (scan_dtype == DT_H16) b = (double)d * 1.1920928955078125e-07 * qnorm * cmax;
+    else if (scan_dtype == DT_I8) b = 0.0;
     else if (scan_dtype == DT_SPLIT) b = (3.03 * 1.52587890625e-05 + 3.0 * (double)d * 1.1920928955078125e-07 * 1.016) * qnorm * cmax +
                                          3.0 * (2.0 * d + rd * (qnorm + cmax)) * U126;
     else b = c_resid * qnorm + (cmax + c_resid) * q_resid +
@@ -404,9 +428,9 @@ __device__ __forceinline__ void rescore_kept(const unsigned long long* surv, int
     }
 }
 
-// bytes of a STORED row of d elements (the exact element types: DT_F32, else DT_BF16 / DT_H16; the host's elem_bytes,
-// scan.h, also knows the scan-only images)
-__device__ __forceinline__ int row_bytes(int d, int dtype) { return d * (dtype == DT_F32 ? 4 : 2); }
+// bytes of a STORED row of d elements (the exact element types: DT_F32, DT_I8, else DT_BF16 / DT_H16; the host's
+// elem_bytes, scan.h, also knows the scan-only images)
+__device__ __forceinline__ int row_bytes(int d, int dtype) { return d * (dtype == DT_F32 ? 4 : dtype == DT_I8 ? 1 : 2); }
 
 // the query row q of Q (rb bytes) into LDS, by the NT threads t of its wave or workgroup
 template <int NT>

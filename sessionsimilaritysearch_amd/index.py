@@ -19,7 +19,8 @@ import torch
 
 from . import _lib
 
-FUSED_DIMS = {"f32": (64, 128, 256), "bf16": (128, 256, 512), "f16": (128, 256, 512)}   # row bytes 256 / 512 / 1024
+FUSED_DIMS = {"f32": (64, 128, 256), "bf16": (128, 256, 512), "f16": (128, 256, 512),
+              "i8": (256, 512, 1024)}                            # row bytes 256 / 512 / 1024
 F16_SCAN_DIMS = (128, 256, 512)                                  # scaled-f16 image: 2 bytes per element
 # scan="auto": the fastest scan whose error bound is still small against the spacing of the scores
 # around rank k (the spacing shrinks as k grows): one-pass f16 up to k = 128, bf16 split up to k = 500
@@ -37,8 +38,14 @@ _LADDER = ("f16", "split", "f32")
 FUSED_MAX_K = 500
 LONG_MAX_K = 1024                                                # sss_ip_topk_long: what its exhaustive fallback resolves
 LONG_MAX_ROW_BYTES = 16384
-DTYPE_CODE = {"f32": 0, "bf16": 1, "f16": 4}                     # include/sss.h: dtype (2, 3 are scan images, below)
-_TORCH_DTYPE = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
+DTYPE_CODE = {"f32": 0, "bf16": 1, "f16": 4}                     # include/sss.h: dtype of the float formats (2, 3 are scan images, below)
+# ... and of the integer format.  Kept beside DTYPE_CODE, not in it: tests/test_f16_index_cpu.py pins that dict to the
+# three float formats and passes 5 to every entry point as a value that must stay invalid -- so int8 is code 6.
+INT_DTYPE_CODE = {"i8": 6}
+_CODE = {**DTYPE_CODE, **INT_DTYPE_CODE}                         # every storage format an index can have
+_TORCH_DTYPE = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "i8": torch.int8}
+_ROW_ALIGN = {"f32": 4, "bf16": 8, "f16": 8, "i8": 16}           # elements per 16-byte piece of a stored row: d % this == 0
+_ELEM_BYTES = {"f32": 4, "bf16": 2, "f16": 2, "i8": 1}
 _EXHAUSTIVE_WS_BYTES = 1 << 30
 SEARCH_CHUNK = 65536             # queries per fused call of search_device (workspace 16 KB per query)
 SEARCH_CHUNK_LONG = 16384        # ... on the long-row path (64 KB per query)
@@ -81,6 +88,27 @@ def to_f16(x: torch.Tensor) -> torch.Tensor:
     +-65504 become inf; ``FlatIndex.add`` refuses such rows."""
     _lib.require_cuda(x, "x", torch.float32)
     return x.to(torch.float16)
+
+
+def integer_valued_i8(x: torch.Tensor) -> torch.Tensor:
+    """Is every element of the float tensor ``x`` an integer in [-128, 127]?  A bool scalar tensor on x's device (no
+    sync; NaN and inf are not).  What an int8 index asks of float input before it casts it."""
+    return ((x == torch.round(x)) & (x >= -128.0) & (x <= 127.0)).all()
+
+
+def quantize_i8(x, scale=None):
+    """Symmetric int8 quantisation for an ``dtype="i8"`` index: ``codes = clip(rint(x * scale), -127, 127)`` as int8
+    (round half to even; -128 is never produced), ``scale`` defaulting to ``127 / max|x|`` (1.0 for an all-zero input).
+    numpy in -> numpy codes, tensor in -> tensor codes (on its device); returns ``(codes, scale)``.  Scores of the
+    codes are ``scale_q * scale_c`` times those of the vectors, up to the rounding."""
+    is_np = isinstance(x, np.ndarray)
+    t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if is_np else x.to(torch.float32)
+    if scale is None:
+        amax = float(t.abs().max().item()) if t.numel() else 0.0
+        scale = 127.0 / amax if amax > 0.0 else 1.0
+    scale = float(scale)
+    codes = torch.clamp(torch.round(t * scale), -127.0, 127.0).to(torch.int8)
+    return (codes.numpy() if is_np else codes), scale
 
 
 def normalize_(x: torch.Tensor, eps: float = 1e-6, rule: int = 0) -> torch.Tensor:
@@ -131,6 +159,15 @@ class FlatIndex:
     encoder's output) and scores on the f16 MFMA, with the same contract on the rounded vectors.  Float16 ends at
     65504: ``add`` raises ``ValueError`` for rows that do not stay finite, and stores nothing.
 
+    ``dtype="i8"`` stores the corpus as int8, one byte per element (faiss ``QT_8bit_direct``, any int8 embedding
+    export; ``quantize_i8`` makes such codes), with d % 16 == 0.  Queries are int8 as well.  ``add`` / ``search`` /
+    ``adopt`` take ``np.int8`` arrays and ``torch.int8`` tensors as they are; float input is accepted only if every
+    value is an integer in [-128, 127] -- anything else raises ``ValueError`` and ``add`` stores nothing.  The
+    contract is the same float64 dot (or sum of squared differences) of the stored values: every partial sum is an
+    integer, and the i8 MFMA scan (d = 256 / 512 / 1024, k <= 500) computes it exactly in int32, so a query stays
+    unproven only on an exact tie at rank k.  Every other d, larger k and the L2 metric run on the exhaustive
+    kernels; there is no long-row scan for int8 rows (d = 1600 is served exhaustively).
+
     ``scan`` picks how a float32 index finds its candidates (the results are the same, they are
     re-scored from the float32 rows and proven per query either way; what differs is speed and how
     many near-tied queries are left to the exhaustive fallback):
@@ -154,10 +191,10 @@ class FlatIndex:
     def __init__(self, d: int, metric: str = "ip", device=None, dtype: str = "f32", scan: str | None = None):
         if metric not in ("ip", "l2"):
             raise ValueError("metric must be 'ip' or 'l2'")
-        if dtype not in DTYPE_CODE:
-            raise ValueError("dtype must be 'f32', 'bf16' or 'f16'")
-        if dtype != "f32" and d % 8:
-            raise ValueError(f"{dtype} index needs d % 8 == 0")
+        if dtype not in _CODE:
+            raise ValueError("dtype must be 'f32', 'bf16', 'f16' or 'i8'")
+        if dtype != "f32" and d % _ROW_ALIGN[dtype]:
+            raise ValueError(f"{dtype} index needs d % {_ROW_ALIGN[dtype]} == 0")
         if scan is None:
             scan = "auto" if dtype == "f32" else "native"
         if scan not in (("auto", "f16", "split", "f32") if dtype == "f32" else ("native",)):
@@ -245,7 +282,9 @@ class FlatIndex:
 
     def _long_or_none(self, k: int) -> str:
         """"long": the K-tiled scan for rows beyond the register-resident kernels (``sss_ip_topk_long``)."""
-        row_bytes = self.d * (4 if self.dtype == "f32" else 2)
+        if self.dtype == "i8":
+            return ""                            # no long-row scan for int8 rows: the exhaustive kernels
+        row_bytes = self.d * _ELEM_BYTES[self.dtype]
         return "long" if (self.d % 64 == 0 and row_bytes <= LONG_MAX_ROW_BYTES and k <= LONG_MAX_K) else ""
 
     def _scan_served(self, scan: str) -> bool:
@@ -367,12 +406,12 @@ class FlatIndex:
         if mode == "split":
             self._ensure_split()
             return self._split, _SCAN_CODE["split"], 0, 0.0
-        return self._xb, DTYPE_CODE[self.dtype], 0, 0.0
+        return self._xb, _CODE[self.dtype], 0, 0.0
 
     def _require_d_aligned(self):
         """The exhaustive kernels read rows in 16-byte pieces."""
-        if self.d % (4 if self.dtype == "f32" else 8):
-            raise _lib.SssError("d must be a multiple of 4 (f32) / 8 (bf16, f16)")
+        if self.d % _ROW_ALIGN[self.dtype]:
+            raise _lib.SssError("d must be a multiple of 4 (f32) / 8 (bf16, f16) / 16 (i8)")
 
     def _exhaustive_chunks(self, rows: torch.Tensor, ws_bytes):
         """(offset, query rows, workspace) per chunk of the device int32 `rows` whose [chunk, n] scores fit the exhaustive
@@ -389,19 +428,27 @@ class FlatIndex:
             x = x.to(self.device).contiguous()
         elif self.dtype == "f16" and isinstance(x, np.ndarray) and x.dtype == np.float16:
             x = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
+        elif self.dtype == "i8" and isinstance(x, np.ndarray) and x.dtype == np.int8:
+            x = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
         else:
             x = _as_device_f32(x, self.device)
             if self.dtype == "bf16":
                 x = to_bf16(x)
             elif self.dtype == "f16":
                 x = to_f16(x)
+            elif self.dtype == "i8":
+                # one device reduction, one host read -- as the f16 index's "not finite" check
+                if not bool(integer_valued_i8(x).item()):
+                    raise ValueError(f"{what}: an i8 index takes int8 rows, or floats that are integers in [-128, 127] "
+                                     "(quantize_i8 makes them)")
+                x = x.to(torch.int8)
         if x.dim() != 2 or x.shape[1] != self.d:
             raise ValueError(f"{what}: expected [n, {self.d}], got {tuple(x.shape)}")
         return x
 
     def _norm_max(self, x):
-        if x.shape[0] and self.d % (4 if self.dtype == "f32" else 8) == 0:
-            rc = _lib.lib().sss_row_norm_max(x.data_ptr(), x.shape[0], self.d, DTYPE_CODE[self.dtype],
+        if x.shape[0] and self.d % _ROW_ALIGN[self.dtype] == 0:
+            rc = _lib.lib().sss_row_norm_max(x.data_ptr(), x.shape[0], self.d, _CODE[self.dtype],
                                              self._cmax_t.data_ptr(), _lib.stream_ptr(self.device))
             _lib.check(rc, "sss_row_norm_max")
         self._cmax = None
@@ -414,7 +461,7 @@ class FlatIndex:
         if self.dtype != "f16" or not x.shape[0]:
             return None
         t = torch.zeros(1, dtype=torch.float32, device=self.device)
-        rc = _lib.lib().sss_row_norm_max(x.data_ptr(), x.shape[0], self.d, DTYPE_CODE[self.dtype], t.data_ptr(),
+        rc = _lib.lib().sss_row_norm_max(x.data_ptr(), x.shape[0], self.d, _CODE[self.dtype], t.data_ptr(),
                                          _lib.stream_ptr(self.device))
         _lib.check(rc, "sss_row_norm_max")
         if not np.isfinite(float(t.item())):
@@ -477,8 +524,8 @@ class FlatIndex:
             raise _lib.SssError("search_fused: this index / k has no fused path (use search)")
         image, _, shift, resid = self._scan_image(mode)
         if mode == "long":
-            ws = self._workspace(L.sss_ip_topk_long_workspace_bytes(nq, n, self.d, DTYPE_CODE[self.dtype]))
-            rc = L.sss_ip_topk_long(q.data_ptr(), nq, self._xb.data_ptr(), DTYPE_CODE[self.dtype], image.data_ptr(), shift, resid,
+            ws = self._workspace(L.sss_ip_topk_long_workspace_bytes(nq, n, self.d, _CODE[self.dtype]))
+            rc = L.sss_ip_topk_long(q.data_ptr(), nq, self._xb.data_ptr(), _CODE[self.dtype], image.data_ptr(), shift, resid,
                                     n, self.d, k, self.id_offset, self.corpus_max_norm(), D.data_ptr(), I.data_ptr(),
                                     status.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
             _lib.check(rc, "sss_ip_topk_long")
@@ -488,7 +535,7 @@ class FlatIndex:
         if mode == "f16":
             nbytes = L.sss_ip_topk_f16_workspace_bytes(nq, n, self.d, k)
         else:
-            nbytes = L.sss_ip_topk_workspace_bytes(nq, n, self.d, k, DTYPE_CODE[self.dtype])
+            nbytes = L.sss_ip_topk_workspace_bytes(nq, n, self.d, k, _CODE[self.dtype])
         ws = self._workspace(nbytes)
         sbytes = L.sss_ip_topk_state_bytes(nq)
         if self._state is None or self._state.numel() < sbytes:
@@ -503,7 +550,7 @@ class FlatIndex:
             rc = L.sss_ip_topk_split(q.data_ptr(), nq, self._xb.data_ptr(), image.data_ptr(), n, self.d, k, self.id_offset,
                                      *tail)
         else:
-            rc = L.sss_ip_topk(q.data_ptr(), nq, self._xb.data_ptr(), n, self.d, k, DTYPE_CODE[self.dtype],
+            rc = L.sss_ip_topk(q.data_ptr(), nq, self._xb.data_ptr(), n, self.d, k, _CODE[self.dtype],
                                self.id_offset, *tail)
         if rc != 0:
             self._state = None          # re-made (zeroed) on the next call
@@ -547,7 +594,7 @@ class FlatIndex:
         sel = rows.to(device=self.device, dtype=torch.int32).contiguous()
         n = self.ntotal
         ws = self._workspace(L.sss_ip_topk_threshold_workspace_bytes(sel.numel(), n, self.d, code))
-        rc = L.sss_ip_topk_threshold(q.data_ptr(), sel.data_ptr(), sel.numel(), self._xb.data_ptr(), DTYPE_CODE[self.dtype],
+        rc = L.sss_ip_topk_threshold(q.data_ptr(), sel.data_ptr(), sel.numel(), self._xb.data_ptr(), _CODE[self.dtype],
                                      image.data_ptr(), code, shift, resid, n, self.d, k, self.id_offset,
                                      self.corpus_max_norm(), D.data_ptr(), I.data_ptr(), status.data_ptr(),
                                      ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
@@ -585,12 +632,12 @@ class FlatIndex:
             if bounded and metric == 0:
                 lb = D[sel.long(), k - 1].contiguous()
                 rc = L.sss_ip_topk_exhaustive_lb(q.data_ptr(), sel.data_ptr(), sel.numel(), self._xb.data_ptr(), n,
-                                                 self.d, k, DTYPE_CODE[self.dtype], self.id_offset, lb.data_ptr(),
+                                                 self.d, k, _CODE[self.dtype], self.id_offset, lb.data_ptr(),
                                                  D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(),
                                                  _lib.stream_ptr(self.device))
             else:
                 rc = L.sss_ip_topk_exhaustive(q.data_ptr(), sel.data_ptr(), sel.numel(), self._xb.data_ptr(), n,
-                                              self.d, k, DTYPE_CODE[self.dtype], self.id_offset, metric, D.data_ptr(),
+                                              self.d, k, _CODE[self.dtype], self.id_offset, metric, D.data_ptr(),
                                               I.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
             _lib.check(rc, "sss_ip_topk_exhaustive")
 
@@ -678,7 +725,7 @@ class FlatIndex:
                 ws = self._workspace(L.sss_range_search_workspace_bytes(m, n, self.d, code))
                 cs = torch.empty(2 * m, dtype=torch.int64, device=self.device)           # counts | status (one copy to the host)
                 status = torch.empty(m, dtype=torch.int32, device=self.device)
-                rc = L.sss_range_search_count(q[lo:].data_ptr(), m, self._xb.data_ptr(), DTYPE_CODE[self.dtype], image.data_ptr(),
+                rc = L.sss_range_search_count(q[lo:].data_ptr(), m, self._xb.data_ptr(), _CODE[self.dtype], image.data_ptr(),
                                               code, shift, resid, n, self.d, rad[lo:].data_ptr(), cmax, cs.data_ptr(),
                                               status.data_ptr(), ws.data_ptr(), ws.numel(), st)
                 _lib.check(rc, "sss_range_search_count")
@@ -700,7 +747,7 @@ class FlatIndex:
                 m = sel.numel()
                 counts_t = torch.empty(m, dtype=torch.int64, device=self.device)
                 rc = L.sss_range_search_exhaustive_count(q.data_ptr(), sel.data_ptr(), m, self._xb.data_ptr(), n, self.d,
-                                                         DTYPE_CODE[self.dtype], metric, rad.data_ptr(), counts_t.data_ptr(),
+                                                         _CODE[self.dtype], metric, rad.data_ptr(), counts_t.data_ptr(),
                                                          ws.data_ptr(), ws.numel(), st)
                 _lib.check(rc, "sss_range_search_exhaustive_count")
                 counts = counts_t.cpu().numpy()
