@@ -8,9 +8,21 @@ Drop-in surface of the reference's path:
                                                                   util_amazon_filtered.sequence_to_graph)
   get_prediction_by_knn, get_p_r, SessionItems    (retrieval.py <- test_amazon_filterd.py:59-85)
   HeteroSAGE, GraphPooling, AttentionPooling, ... (variants.py  <- model/gnn.py, model/model.py variants)
-  ShardedFlatIndex                                (distributed.py: corpus row-sharded over RCCL)
+  SparseSessionIndex, session_vectors, find_K_sparse_dense
+                                                  (sparse.py    <- test_amazon_filterd.py SKNN / STAN item-vector baselines)
+  ShardedFlatIndex, ShardedBinaryIndex, ShardedSparseIndex
+                                                  (distributed.py: corpus row-sharded over RCCL)
   SessionBatch, build_batch, synthetic_actions    (sessions.py  <- sequence_to_graph + Batch.from_data_list, host side)
 """
 from ._lib import SssError, build, exported_symbols, lib  # noqa: F401
 
-__all__ = ["SssError", "build", "exported_symbols", "lib"]
+__all__ = ["SssError", "build", "exported_symbols", "lib", "SessionVectors", "SparseSessionIndex", "session_vectors",
+           "find_K_sparse_dense"]
+
+
+def __getattr__(name):
+    # the sparse session index, re-exported lazily: importing it pulls in torch, which `build()` does not need
+    if name in ("SessionVectors", "SparseSessionIndex", "session_vectors", "find_K_sparse_dense"):
+        from . import sparse
+        return getattr(sparse, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

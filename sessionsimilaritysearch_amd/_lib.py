@@ -1,4 +1,4 @@
-"""ctypes binding of libsss.so (the C ABI declared in include/sss.h).
+"""ctypes binding of libsss.so (the C ABI declared in include/sss.h and include/sss_sparse.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails, this
 module raises.  ``build()`` compiles the library in-tree with hipcc for gfx950.
@@ -109,6 +109,16 @@ _SIGNATURES = {
     "sss_attention_dot_pool": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
 }
 
+# include/sss_sparse.h one to one (the sparse session index: its own header, bound from the same library)
+_SPARSE_SIGNATURES = {
+    "sss_session_vectors_count": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sss_session_vectors_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, ctypes.c_double, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p]),
+    "sss_sparse_topk_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "sss_sparse_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64,
+                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 
 class LinearProblem(ctypes.Structure):
     """``sss_linear_problem`` of include/sss.h."""
@@ -139,6 +149,11 @@ def exported_symbols():
     return sorted(_SIGNATURES)
 
 
+def sparse_symbols():
+    """The entry points of include/sss_sparse.h."""
+    return sorted(_SPARSE_SIGNATURES)
+
+
 def build(verbose: bool = False) -> str:
     """Compile libsss.so for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-C", CSRC, "-j4"]
@@ -160,7 +175,7 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C "
                 "sessionsimilaritysearch_amd/csrc`). There is no CPU fallback.")
         h = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in (*_SIGNATURES.items(), *_SPARSE_SIGNATURES.items()):
             fn = getattr(h, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = h

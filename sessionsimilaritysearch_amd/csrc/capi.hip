@@ -1,4 +1,4 @@
-// extern "C" surface of libsss (declared in include/sss.h) + error plumbing.
+// extern "C" surface of libsss (declared in include/sss.h and include/sss_sparse.h) + error plumbing.
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "../../include/sss.h"
+#include "../../include/sss_sparse.h"
 #include "sss_common.h"
 #include "scan.h"
 #include "kargs.h"
@@ -92,6 +93,12 @@ int pack_sign_bits(const float*, long, int, long, unsigned char*, int, hipStream
 size_t graph_scratch_ints(long S);
 int graph_counts(const long*, const unsigned char*, const long*, long, int*, int*, int*, hipStream_t);
 int graph_fill(const long*, const unsigned char*, const long*, const long*, long, const int*, const GraphOut&, hipStream_t);
+int session_vectors_count(const long*, const unsigned char*, const long*, long, long, int*, int*, hipStream_t);
+int session_vectors_fill(const long*, const unsigned char*, const long*, long, long, int, double, const long*, int*, float*, int*,
+                         hipStream_t);
+size_t sparse_topk_workspace_bytes(long nq, long n);
+int sparse_topk(const long*, const int*, const float*, long, const long*, const int*, const float*, long, int, long, float*, long*, void*,
+                size_t, hipStream_t);
 
 }  // namespace sss
 
@@ -371,6 +378,28 @@ int sss_knn_item_vote(const float* D, const int64_t* I, int64_t nq, int s, const
 }
 int sss_segment_ptr(const int64_t* batch, int64_t n, int64_t n_graphs, int32_t* ptr, void* stream) {
     return sss::segment_ptr(reinterpret_cast<const long*>(batch), n, n_graphs, ptr, ST(stream));
+}
+
+// ---- include/sss_sparse.h
+int sss_session_vectors_count(const int64_t* sess_ptr, const uint8_t* is_search, const int64_t* item_id, int64_t n_sessions,
+                              int64_t n_items, int32_t* counts, int32_t* err, void* stream) {
+    return sss::session_vectors_count(reinterpret_cast<const long*>(sess_ptr), is_search, reinterpret_cast<const long*>(item_id),
+                                      n_sessions, n_items, counts, err, ST(stream));
+}
+int sss_session_vectors_fill(const int64_t* sess_ptr, const uint8_t* is_search, const int64_t* item_id, int64_t n_sessions,
+                             int64_t n_items, int mode, double lammy, const int64_t* ptr, int32_t* items, float* weights,
+                             int32_t* err, void* stream) {
+    return sss::session_vectors_fill(reinterpret_cast<const long*>(sess_ptr), is_search, reinterpret_cast<const long*>(item_id),
+                                     n_sessions, n_items, mode, lammy, reinterpret_cast<const long*>(ptr), items, weights, err,
+                                     ST(stream));
+}
+size_t sss_sparse_topk_workspace_bytes(int64_t nq, int64_t n) { return sss::sparse_topk_workspace_bytes(nq, n); }
+int sss_sparse_topk(const int64_t* q_ptr, const int32_t* q_items, const float* q_weights, int64_t nq, const int64_t* c_ptr,
+                    const int32_t* c_items, const float* c_weights, int64_t n, int k, int64_t id_offset, float* D_out,
+                    int64_t* I_out, void* workspace, size_t workspace_bytes, void* stream) {
+    return sss::sparse_topk(reinterpret_cast<const long*>(q_ptr), q_items, q_weights, nq, reinterpret_cast<const long*>(c_ptr),
+                            c_items, c_weights, n, k, id_offset, D_out, reinterpret_cast<long*>(I_out), workspace, workspace_bytes,
+                            ST(stream));
 }
 
 }  // extern "C"

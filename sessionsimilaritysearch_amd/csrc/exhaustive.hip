@@ -497,6 +497,43 @@ static size_t compact_bytes(long nsel, long n) {
     return (size_t)nsel * ((size_t)CP_CAP * 8 + (size_t)nslabs * 8 + 8) + 1024;
 }
 
+size_t topk_of_scores_bytes(long nsel, long n) { return compact_bytes(nsel, n); }
+
+// The exact top-k of a finished score matrix: scores f32 [nsel][n] -> D_out / I_out rows qsel[f], by (score desc, id asc)
+// for metric 0 ((distance asc, id asc) for metric 1), ids = row + id_offset, padding beyond n.  Long rows are compacted
+// first (above).  `tail`: topk_of_scores_bytes(nsel, n) bytes, 256-byte aligned.  Shared by the dense exhaustive search
+// below and the sparse session index (sparse.hip).  nsel <= 65535, n < 2^31, k <= RS_MAX_K are the callers' to check.
+int topk_of_scores(const float* scores, const int* qsel, long nsel, long n, int k, long id_offset, int metric, float* D_out,
+                   long* I_out, void* tail, hipStream_t st) {
+    int rc;
+    const float* cs = nullptr; const int* cids = nullptr; const unsigned* ctotal = nullptr;
+    if (n >= CP_MIN_N) {
+        const int nslabs = (int)((n + CP_SLAB - 1) / CP_SLAB);
+        char* p = reinterpret_cast<char*>(tail);
+        float* cs_w = reinterpret_cast<float*>(p);                       p += (size_t)nsel * CP_CAP * 4;
+        int* cids_w = reinterpret_cast<int*>(p);                         p += (size_t)nsel * CP_CAP * 4;
+        unsigned* cnt_gt = reinterpret_cast<unsigned*>(p);               p += (size_t)nsel * nslabs * 4;
+        unsigned* cnt_eq = reinterpret_cast<unsigned*>(p);               p += (size_t)nsel * nslabs * 4;
+        unsigned* T0 = reinterpret_cast<unsigned*>(p);                   p += (size_t)nsel * 4;
+        unsigned* total = reinterpret_cast<unsigned*>(p);
+        rc = opt_in_lds(reinterpret_cast<const void*>(&k_head_threshold), "k_head_threshold", (size_t)CP_HEAD * 4);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_head_threshold, dim3((unsigned)nsel), dim3(RS_THREADS), (size_t)CP_HEAD * 4, st, scores, n, k, metric, T0);
+        rc = check_launch("k_head_threshold");
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_count_ge, dim3((unsigned)nslabs, (unsigned)nsel), dim3(256), 0, st, scores, n, metric, T0, nslabs, cnt_gt, cnt_eq);
+        hipLaunchKernelGGL(k_scan_slabs, dim3((unsigned)nsel), dim3(64), 0, st, cnt_gt, cnt_eq, nslabs, n, k, total);
+        hipLaunchKernelGGL(k_compact_ge, dim3((unsigned)nslabs, (unsigned)nsel), dim3(RS_THREADS), 0, st, scores, n, k, metric, T0, nslabs,
+                           cnt_gt, cnt_eq, total, CP_CAP, cs_w, cids_w);
+        rc = check_launch("k_compact_ge");
+        if (rc) return rc;
+        cs = cs_w; cids = cids_w; ctotal = total;
+    }
+    hipLaunchKernelGGL(k_topk_radix, dim3((unsigned)nsel), dim3(RS_THREADS), 0, st, scores, qsel, n, k, id_offset, metric, D_out, I_out,
+                       cs, cids, ctotal, CP_CAP);
+    return check_launch("k_topk_radix");
+}
+
 // scores [nsel][n] of the selected queries against every row (k_exact_scores_rows where the shape has it, else
 // k_exact_scores); lb / lb_by_row: the optional pre-test bound of k_exact_scores_rows (inner product only).
 static int launch_exact_scores(const void* q, const int* qsel, long nsel, const void* c, long n, int d, int dtype, int metric,
@@ -544,32 +581,8 @@ int ip_topk_exhaustive(const void* q, const int* qsel, long nsel, const void* c,
     float* scores = reinterpret_cast<float*>(ws);
     int rc = launch_exact_scores(q, qsel, nsel, c, n, d, dtype, metric, scores, lower_bound, 0, st);
     if (rc) return rc;
-    const float* cs = nullptr; const int* cids = nullptr; const unsigned* ctotal = nullptr;
-    if (n >= CP_MIN_N) {
-        const int nslabs = (int)((n + CP_SLAB - 1) / CP_SLAB);
-        char* p = reinterpret_cast<char*>(ws) + (((size_t)nsel * n * 4 + 255) & ~(size_t)255);
-        float* cs_w = reinterpret_cast<float*>(p);                       p += (size_t)nsel * CP_CAP * 4;
-        int* cids_w = reinterpret_cast<int*>(p);                         p += (size_t)nsel * CP_CAP * 4;
-        unsigned* cnt_gt = reinterpret_cast<unsigned*>(p);               p += (size_t)nsel * nslabs * 4;
-        unsigned* cnt_eq = reinterpret_cast<unsigned*>(p);               p += (size_t)nsel * nslabs * 4;
-        unsigned* T0 = reinterpret_cast<unsigned*>(p);                   p += (size_t)nsel * 4;
-        unsigned* total = reinterpret_cast<unsigned*>(p);
-        rc = opt_in_lds(reinterpret_cast<const void*>(&k_head_threshold), "k_head_threshold", (size_t)CP_HEAD * 4);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_head_threshold, dim3((unsigned)nsel), dim3(RS_THREADS), (size_t)CP_HEAD * 4, st, scores, n, k, metric, T0);
-        rc = check_launch("k_head_threshold");
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_count_ge, dim3((unsigned)nslabs, (unsigned)nsel), dim3(256), 0, st, scores, n, metric, T0, nslabs, cnt_gt, cnt_eq);
-        hipLaunchKernelGGL(k_scan_slabs, dim3((unsigned)nsel), dim3(64), 0, st, cnt_gt, cnt_eq, nslabs, n, k, total);
-        hipLaunchKernelGGL(k_compact_ge, dim3((unsigned)nslabs, (unsigned)nsel), dim3(RS_THREADS), 0, st, scores, n, k, metric, T0, nslabs,
-                           cnt_gt, cnt_eq, total, CP_CAP, cs_w, cids_w);
-        rc = check_launch("k_compact_ge");
-        if (rc) return rc;
-        cs = cs_w; cids = cids_w; ctotal = total;
-    }
-    hipLaunchKernelGGL(k_topk_radix, dim3((unsigned)nsel), dim3(RS_THREADS), 0, st, scores, qsel, n, k, id_offset, metric, D_out, I_out,
-                       cs, cids, ctotal, CP_CAP);
-    return check_launch("k_topk_radix");
+    return topk_of_scores(scores, qsel, nsel, n, k, id_offset, metric, D_out, I_out,
+                          reinterpret_cast<char*>(ws) + (((size_t)nsel * n * 4 + 255) & ~(size_t)255), st);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -205,6 +205,10 @@ int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, c
 size_t ip_topk_exhaustive_workspace_bytes(long nsel, long n);
 int ip_topk_exhaustive(const void* q, const int* qsel, long nsel, const void* c, long n, int d, int k, int dtype, long id_offset,
                        int metric, const float* lower_bound, float* D_out, long* I_out, void* ws, size_t ws_bytes, hipStream_t st);
+// the exact top-k of a finished [nsel][n] score matrix (exhaustive.hip): the tail of ip_topk_exhaustive, also sparse.hip's
+size_t topk_of_scores_bytes(long nsel, long n);
+int topk_of_scores(const float* scores, const int* qsel, long nsel, long n, int k, long id_offset, int metric, float* D_out,
+                   long* I_out, void* tail, hipStream_t st);
 size_t range_exhaustive_workspace_bytes(long nsel, long n);
 int range_exhaustive_count(const void* q, const int* qsel, long nsel, const void* c, long n, int d, int dtype, int metric,
                            const float* radius, long* counts, void* ws, size_t ws_bytes, hipStream_t st);

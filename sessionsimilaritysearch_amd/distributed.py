@@ -12,7 +12,7 @@ every rank would be the Amdahl term of strong scaling.
 
 Every index kind shards this way.  ``ShardedFlatIndex`` serves both metrics and every d / k of ``FlatIndex``
 (shapes without a fused scan run the shard's exhaustive kernels) and ``range_search``; ``ShardedBinaryIndex``
-serves ``BinaryFlatIndex``.  All of them merge through the one ``sss_topk_merge`` -- (score desc, id asc) --
+serves ``BinaryFlatIndex``; ``ShardedSparseIndex`` serves ``SparseSessionIndex``.  All of them merge through the one ``sss_topk_merge`` -- (score desc, id asc) --
 so a contract that orders ascending (L2, Hamming) crosses the exchange NEGATED: float negation is exact and
 ``(-dist desc, id asc)`` is ``(dist asc, id asc)``.
 
@@ -122,6 +122,21 @@ class HammingEngine:
         """This shard's (D int32, I int64) by (distance asc, id asc) with global ids, padding (0x7fffffff, -1);
         any k (beyond the fused capacity: the shard's exhaustive route)."""
         return self.index.search(codes, k)
+
+    def merge(self, pack_all, chunk, shards, nq, k, D_out, I_out):
+        _merge_packs(pack_all, chunk, shards, nq, k, D_out, I_out)
+
+
+class SparseEngine:
+    """Local search + merge of a ``SparseSessionIndex`` shard through libsss."""
+
+    def __init__(self, index):
+        self.index = index
+
+    def local_search(self, vectors, k, D, I):
+        """This shard's top-k by (score desc, id asc) with global ids (``index.id_offset`` = first row of the shard),
+        padding (-FLT_MAX, -1), into D / I; no host sync."""
+        self.index.search_device(vectors, k, D, I)
 
     def merge(self, pack_all, chunk, shards, nq, k, D_out, I_out):
         _merge_packs(pack_all, chunk, shards, nq, k, D_out, I_out)
@@ -306,3 +321,21 @@ class ShardedBinaryIndex(_Sharded):
         pack_all = self._buffers(nq, k)[2]
         dist.all_gather_into_tensor(pack_all, self._pack_local(codes, k), group=self.group)
         return self._merge(pack_all, self.world, nq, k)
+
+
+class ShardedSparseIndex(_Sharded):
+    """``SparseSessionIndex.search(vectors, k) -> (D float32, I int64)`` over session vectors row-sharded across ``dist``
+    ranks: (score desc, id asc), padding (-FLT_MAX, -1) -- already the order and the padding of ``sss_topk_merge``, so the
+    local result crosses the exchange as it is.  ``engine.local_search(vectors, k, D, I)`` writes this rank's result with
+    GLOBAL ids; every rank returns the full merged result."""
+
+    def search(self, vectors, k):
+        k = int(k)
+        nq = len(vectors)
+        chunk, pack, pack_all, D, I, _, Do, Io = self._buffers(nq, k)
+        self.engine.local_search(vectors, k, D, I)
+        if not self.exchange:
+            return D, I
+        dist.all_gather_into_tensor(pack_all, pack, group=self.group)
+        self.engine.merge(pack_all, chunk, self.world, nq, k, Do, Io)
+        return Do, Io
