@@ -390,6 +390,9 @@ int sss_attention_dot_pool(const float* x, int64_t ld_x, const int32_t* ptr, int
  * (test_amazon_filterd.py:485-488), straight into the CSR-by-target form the encoder kernels read.
  * Input: sessions stored contiguously, sess_ptr int64 [S+1]; per action is_search uint8, item_id
  * int64 (clicks), query_tok int64 (searches); at most 64 actions per session (*err != 0 otherwise).
+ * Item ids must fit int32 (0 <= id < 2^31): the kernels keep them in 32-bit lanes and an id beyond
+ * that would alias another one.  Neither entry point reads the ids back; the caller checks their
+ * range before sss_graph_fill (SessionEncoder.prepare_actions raises IndexError, as nn.Embedding does).
  * Step 1, sss_graph_counts: bases int32 [5][S+1] = exclusive scans over sessions of (query nodes,
  *   product nodes, expanded product rows, click edges, unique transitions), grand totals at [.][S]
  *   -- the caller reads the 5 totals to size the outputs; rows 2 and 0 double as the pooling's

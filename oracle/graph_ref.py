@@ -9,6 +9,12 @@ A session is a list of ``(is_search: bool, item_id: int, query_tok: int)``.
 
 Difference from the reference, on purpose: distinct items are kept in first-occurrence order
 (the reference's ``list(set(...))`` at ``util_amazon_filtered.py:128`` is hash-ordered).
+
+Reference-pinned: ``tests/golden/reference_graph.npz`` holds what the reference's own
+``sequence_to_graph`` returned for a grid of sessions (``tests/golden/make_golden_graph.py``), and
+``tests/test_graph_reference_cpu.py`` holds ``session_to_graph`` to it with ``==`` after relabelling
+the reference's products to first-occurrence order.  ``q_x`` is not pinned: the reference's query
+nodes carry token tensors, no id.
 """
 from __future__ import annotations
 
@@ -51,6 +57,7 @@ def session_to_graph(seq):
     # transitions -- :199-218
     item_seq = [it for is_s, it, _ in seq if not is_s]
     t_from, t_to, w, seen = [], [], [], {}
+    last_click = 0                          # :203-216: the last transition's target, node 0 when there is none
     for i in range(len(item_seq) - 1):
         k = (pos[item_seq[i]], pos[item_seq[i + 1]])
         if k not in seen:
@@ -58,8 +65,9 @@ def session_to_graph(seq):
             t_from.append(k[0]); t_to.append(k[1]); w.append(1)
         else:
             w[seen[k]] += 1
+        last_click = k[1]
     return dict(q_x=q_x, q_pos=q_pos_emb, p_x=distinct, p_cnt=cnt, p_pos=pos_ids,
-                qp=(e_from, e_to), pp=(t_from, t_to), pp_w=w)
+                qp=(e_from, e_to), pp=(t_from, t_to), pp_w=w, last_click=last_click)
 
 
 def collate(graphs):

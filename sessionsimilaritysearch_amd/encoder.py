@@ -385,13 +385,22 @@ class SessionEncoder:
         err = torch.empty(1, dtype=torch.int32, device=dev)
         _lib.check(L.sss_graph_counts(sess_ptr.data_ptr(), is_search.data_ptr(), item_id.data_ptr(), S_, bases.data_ptr(),
                                       scratch.data_ptr(), err.data_ptr(), st), "sss_graph_counts")
-        lows = torch.stack([item_id.min(), query_tok.min()]).to(torch.int32) if item_id.numel() else bases.new_zeros(2)
-        tot = torch.cat([bases[:, S_], err, lows]).tolist()        # the one host read-back of the build
-        Nq, Np, Xp, E, Epp, bad, item_lo, tok_lo = (int(v) for v in tot)
+        # id bounds ride along in the read-back AS INT64: the kernels keep an item id in a 32-bit lane, so an id
+        # that does not fit (2**32 + 7) would come out as another, valid one (7) and pass _check_ids below
+        if item_id.numel():
+            item_lo, item_hi = torch.aminmax(item_id)
+            ends = torch.stack([item_lo, query_tok.min(), item_hi])
+        else:
+            ends = torch.zeros(3, dtype=torch.int64, device=dev)
+        tot = torch.cat([bases[:, S_], err, ends.view(torch.int32)]).tolist()   # the one host read-back of the build
+        Nq, Np, Xp, E, Epp, bad = (int(v) for v in tot[:6])
+        # (the int64 bounds travel as int32 halves, low word first: no conversion kernel for the int32 totals)
+        item_lo, tok_lo, item_hi = ((int(hi) << 32) | (int(lo) & 0xFFFFFFFF) for lo, hi in zip(tot[6::2], tot[7::2]))
         if bad:
             raise _lib.SssError("prepare_actions: a session has more than 64 actions")
-        if item_lo < 0 or tok_lo < 0:
-            raise IndexError("index out of range in self")         # negative ids: what nn.Embedding raises upstream
+        item_rows = int(self.item_table.shape[0]) if self.item_table is not None else 2 ** 31
+        if item_lo < 0 or tok_lo < 0 or item_hi >= item_rows:
+            raise IndexError("index out of range in self")         # what nn.Embedding raises upstream
         i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
         i64 = lambda n: torch.empty(n, dtype=torch.int64, device=dev)
         pb = PreparedBatch()

@@ -4,10 +4,15 @@ Floating-point path: the tolerance is the one BASELINE.json's north_star states 
 1e-5 (absolute, on O(1) embeddings; relative 1e-5 on the L2-normalised vectors that reach the
 index).  Each kernel is also checked on its own against a float64 torch restatement.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from graph_np import csr_by_target  # noqa: E402
 from oracle import gnn_ref
 from oracle import search_ref as sr
 from sessionsimilaritysearch_amd import _lib
@@ -373,8 +378,10 @@ def test_encoder_matches_independent_float64_fixture(cuda, loops, tag):
 @pytest.mark.parametrize("loops", [False, True])
 def test_native_graph_builder_is_bit_exact(cuda, seed, n, vocab, loops):
     """csrc/graphbuild.hip (action table -> CSR batch on device) against the host builder +
-    torch CSR conversion it replaces -- itself checked against oracle/graph_ref.py on CPU --
-    array by array, and through the encoder."""
+    torch CSR conversion it replaces -- itself checked against oracle/graph_ref.py on CPU, and that
+    oracle is reference-pinned: tests/test_graph_reference_cpu.py holds it to what the reference's own
+    sequence_to_graph returned (tests/golden/reference_graph.npz) -- array by array, and through the
+    encoder."""
     cfg = EncoderConfig(d_in=32, h=32, n_layers=1, d_out=64, n_items=vocab, n_query=33,
                         self_loop_rule="pyg_bipartite_global" if loops else "none")
     enc = SessionEncoder(cfg, init_weights(cfg, 5, tables=vocab < 1000), cuda, use_edge_weight=True)
@@ -402,11 +409,7 @@ def test_native_graph_builder_is_bit_exact(cuda, seed, n, vocab, loops):
         Nq, Np = len(o["q_x"]), len(o["p_x"])
         assert (got.Nq, got.Np, got.B) == (Nq, Np, n)
 
-        def csr(src, dst, n_dst, w=None):
-            order = np.argsort(dst, kind="stable")
-            rowptr = np.zeros(n_dst + 1, np.int64)
-            np.cumsum(np.bincount(dst, minlength=n_dst), out=rowptr[1:])
-            return rowptr, src[order], None if w is None else w[order]
+        csr = csr_by_target
         npy = lambda t: t.cpu().numpy().astype(np.int64)
         for name, (rp, col, w) in (("csr_qp", csr(o["qp0"], o["qp1"], Np)), ("csr_pq", csr(o["qp1"], o["qp0"], Nq)),
                                    ("csr_pp", csr(o["pp0"], o["pp1"], Np, o["pp_w"]))):
