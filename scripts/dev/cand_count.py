@@ -17,10 +17,10 @@ idx.search_fused(q, k)                                  # builds images, sizes t
 L = _lib.lib()
 nbytes = L.sss_ip_topk_f16_workspace_bytes(nq, n, d, k) if scan == "f16" else L.sss_ip_topk_workspace_bytes(nq, n, d, k, 0)
 for rep in range(3):
-    idx._ws = torch.zeros(idx._ws.numel(), dtype=torch.uint8, device=dev)
+    idx._ws.buf = torch.zeros(idx._ws.buf.numel(), dtype=torch.uint8, device=dev)
     D, I, st = idx.search_fused(q, k)
     torch.cuda.synchronize()
     cap = nbytes // 8 // nq
-    keys = idx._ws[:nq * cap * 8].view(torch.int64).view(nq, cap)
+    keys = idx._ws.buf[:nq * cap * 8].view(torch.int64).view(nq, cap)
     m = (keys != 0).sum(1).float()
     print(f"n={n} scan={scan} cap={cap}: candidates per query mean {m.mean().item():.0f} min {m.min().item():.0f} max {m.max().item():.0f}; unproven {int((st != 0).sum())}", flush=True)

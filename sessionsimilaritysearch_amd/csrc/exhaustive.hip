@@ -23,18 +23,12 @@ __global__ __launch_bounds__(64) void k_exact_scores(const void* __restrict__ Qv
                                                      int metric, float* __restrict__ scores) {
     __shared__ __attribute__((aligned(16))) float tile[EX_ROWS * EX_LD];
     __shared__ __attribute__((aligned(16))) float qs[EX_KC];
-    constexpr int EB = DT == DT_F32 ? 4 : DT == DT_I8 ? 1 : 2;   // bytes per element
-    constexpr int EPV = 16 / EB;                      // elements per 16-byte load
+    constexpr int EB = Elem<DT>::bytes;               // bytes per element
+    constexpr int EPV = Elem<DT>::per_chunk;          // elements per 16-byte load
     const int lane = threadIdx.x;
     const int f = blockIdx.y;
     const char* C = reinterpret_cast<const char*>(Cv);
     const char* q = reinterpret_cast<const char*>(Qv) + (size_t)qsel[f] * d * EB;
-    auto to_f32 = [](const char* p, int i) -> float {
-        if (DT == DT_F32) return reinterpret_cast<const float*>(p)[i];
-        if (DT == DT_H16) return (float)reinterpret_cast<const _Float16*>(p)[i];
-        if (DT == DT_I8) return (float)reinterpret_cast<const signed char*>(p)[i];
-        return __builtin_bit_cast(float, (unsigned)reinterpret_cast<const unsigned short*>(p)[i] << 16);
-    };
     for (long row0 = (long)blockIdx.x * EX_ROWS; row0 < n; row0 += (long)gridDim.x * EX_ROWS) {
         double acc = 0.0;
         for (int k0 = 0; k0 < d; k0 += EX_KC) {
@@ -47,9 +41,9 @@ __global__ __launch_bounds__(64) void k_exact_scores(const void* __restrict__ Qv
                 if (grow > n - 1) grow = n - 1;
                 const f32x4 v = *reinterpret_cast<const f32x4*>(C + ((size_t)grow * d + k0) * EB + cc * 16);
 #pragma unroll
-                for (int e = 0; e < EPV; ++e) tile[rr * EX_LD + cc * EPV + e] = to_f32(reinterpret_cast<const char*>(&v), e);
+                for (int e = 0; e < EPV; ++e) tile[rr * EX_LD + cc * EPV + e] = Elem<DT>::to_f32(&v, e);
             }
-            for (int i = lane; i < kc; i += 64) qs[i] = to_f32(q, k0 + i);
+            for (int i = lane; i < kc; i += 64) qs[i] = Elem<DT>::to_f32(q, k0 + i);
             __syncthreads();
             const float* mine = &tile[lane * EX_LD];
             if (metric == 0) {
@@ -74,12 +68,10 @@ __global__ __launch_bounds__(64) void k_exact_scores(const void* __restrict__ Qv
 // path's k-th re-scored candidate).  A cheap float32 pass first bounds every row's score from above
 // (float32 fma chain: error <= d 2^-24 |q||c| + d 2^-150); rows that provably stay below lb -- almost all of them --
 // skip the float64 chain and get -FLT_MAX, which the selection ignores.
-template <int D, int DT>
-__device__ __forceinline__ float q_elem(const void* qrow, int kx) {        // element kx of a (wave-uniform) query row
-    if (DT == DT_F32) return reinterpret_cast<const float*>(qrow)[kx];
-    const unsigned w = reinterpret_cast<const unsigned*>(qrow)[kx >> 1];
-    if (DT == DT_H16) return (float)__builtin_bit_cast(_Float16, (unsigned short)((kx & 1) ? w >> 16 : w & 0xFFFFu));
-    return __builtin_bit_cast(float, (kx & 1) ? (w & 0xFFFF0000u) : (w << 16));
+template <int DT>
+__device__ __forceinline__ float q_elem(const void* qrow, int kx) {        // element kx of a (wave-uniform) query row: its 32-bit word
+    constexpr int PW = 4 / Elem<DT>::bytes;
+    return Elem<DT>::from_word(reinterpret_cast<const unsigned*>(qrow)[kx / PW], kx % PW);
 }
 
 template <int D, int DT>
@@ -88,34 +80,19 @@ __global__ __launch_bounds__(256) void k_exact_scores_rows(const void* __restric
                                                            const float* __restrict__ lb, int lb_by_row) {
     constexpr int QB = 1024;                           // queries whose norms are kept in LDS at a time
     __shared__ double qn[QB];
-    constexpr int EB = DT == DT_F32 ? 4 : 2;
+    constexpr int EB = Elem<DT>::bytes, EPV = Elem<DT>::per_chunk, PW = EPV / 4;   // PW: elements per 32-bit word
     const char* C = reinterpret_cast<const char*>(Cv);
     const char* Q = reinterpret_cast<const char*>(Qv);
     const long row = (long)blockIdx.x * 256 + threadIdx.x;
     const long rl = row < n ? row : n - 1;
     float r[D];
-    if (DT == DT_F32) {
 #pragma unroll
-        for (int v = 0; v < D / 4; ++v) {
-            const f32x4 c4 = *reinterpret_cast<const f32x4*>(C + ((size_t)rl * D + v * 4) * EB);
-            r[4 * v] = c4.x; r[4 * v + 1] = c4.y; r[4 * v + 2] = c4.z; r[4 * v + 3] = c4.w;
-        }
-    } else {
+    for (int v = 0; v < D / EPV; ++v) {
+        const u32x4 c4 = *reinterpret_cast<const u32x4*>(C + ((size_t)rl * D + v * EPV) * EB);
 #pragma unroll
-        for (int v = 0; v < D / 8; ++v) {
-            const uint4 c4 = *reinterpret_cast<const uint4*>(C + ((size_t)rl * D + v * 8) * EB);
-            const unsigned u[4] = {c4.x, c4.y, c4.z, c4.w};
+        for (int e = 0; e < 4; ++e)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (DT == DT_H16) {
-                    r[8 * v + 2 * e] = (float)__builtin_bit_cast(_Float16, (unsigned short)(u[e] & 0xFFFFu));
-                    r[8 * v + 2 * e + 1] = (float)__builtin_bit_cast(_Float16, (unsigned short)(u[e] >> 16));
-                } else {
-                    r[8 * v + 2 * e] = __builtin_bit_cast(float, u[e] << 16);
-                    r[8 * v + 2 * e + 1] = __builtin_bit_cast(float, u[e] & 0xFFFF0000u);
-                }
-            }
-        }
+            for (int j = 0; j < PW; ++j) r[EPV * v + PW * e + j] = Elem<DT>::from_word(c4[e], j);
     }
     // norms for the pre-test's margin in float64 (squares of float32 values are exact there): a float32 sum of squares
     // is 0 for rows below ~1e-19 and inf above ~1.8e19, which would shrink the margin to nothing / widen it to everything
@@ -132,7 +109,7 @@ __global__ __launch_bounds__(256) void k_exact_scores_rows(const void* __restric
             for (int t = threadIdx.x; t < nf; t += 256) {
                 const char* qrow = Q + (size_t)qsel[f0 + t] * D * EB;
                 double s2 = 0.0;
-                for (int kx = 0; kx < D; ++kx) { const double v = q_elem<D, DT>(qrow, kx); s2 += v * v; }
+                for (int kx = 0; kx < D; ++kx) { const double v = q_elem<DT>(qrow, kx); s2 += v * v; }
                 qn[t] = sqrt(s2) * 1.0001;
             }
             __syncthreads();
@@ -143,7 +120,7 @@ __global__ __launch_bounds__(256) void k_exact_scores_rows(const void* __restric
             if (lb) {                                      // float32 upper bound first
                 float s0 = 0.f;
 #pragma unroll
-                for (int kx = 0; kx < D; ++kx) s0 = fmaf(q_elem<D, DT>(qrow, kx), r[kx], s0);
+                for (int kx = 0; kx < D; ++kx) s0 = fmaf(q_elem<DT>(qrow, kx), r[kx], s0);
                 // margin in float64: the chain's relative error, its gradual underflow (D roundings of at most 2^-150 each
                 // below FLT_MIN) and one float32 ulp of l0 (2^-149 absolute in the subnormal range)
                 const float l0 = lb[lb_by_row ? qsel[f0 + f] : f0 + f];    // (per selected query, or per query row)
@@ -153,7 +130,7 @@ __global__ __launch_bounds__(256) void k_exact_scores_rows(const void* __restric
             double acc = 0.0;
             if (need) {
 #pragma unroll
-                for (int kx = 0; kx < D; ++kx) acc += (double)q_elem<D, DT>(qrow, kx) * (double)r[kx];
+                for (int kx = 0; kx < D; ++kx) acc += (double)q_elem<DT>(qrow, kx) * (double)r[kx];
             }
             if (row < n) scores[(size_t)(f0 + f) * n + row] = need ? (float)acc : -3.4028234663852886e38f;
         }
@@ -541,23 +518,23 @@ static int launch_exact_scores(const void* q, const int* qsel, long nsel, const 
     long gx = (n + EX_ROWS - 1) / EX_ROWS;
     if (gx > 8192) gx = 8192;
     const unsigned rb = (unsigned)((n + 255) / 256);
-#define SSS_ROWS(D_, DT_) hipLaunchKernelGGL((k_exact_scores_rows<D_, DT_>), dim3(rb), dim3(256), 0, st, q, qsel, (int)nsel, c, n, scores, lb, lb_by_row)
-    if (metric == 0 && dtype == DT_F32 && d == 64) SSS_ROWS(64, DT_F32);
-    else if (metric == 0 && dtype == DT_F32 && d == 128) SSS_ROWS(128, DT_F32);
-    else if (metric == 0 && dtype == DT_F32 && d == 256) SSS_ROWS(256, DT_F32);
-    else if (metric == 0 && dtype == DT_BF16 && d == 128) SSS_ROWS(128, DT_BF16);
-    else if (metric == 0 && dtype == DT_BF16 && d == 256) SSS_ROWS(256, DT_BF16);
-    else if (metric == 0 && dtype == DT_H16 && d == 128) SSS_ROWS(128, DT_H16);
-    else if (metric == 0 && dtype == DT_H16 && d == 256) SSS_ROWS(256, DT_H16);
-    else if (dtype == DT_F32)
-        hipLaunchKernelGGL(k_exact_scores<DT_F32>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
-    else if (dtype == DT_H16)
-        hipLaunchKernelGGL(k_exact_scores<DT_H16>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
-    else if (dtype == DT_I8)                            // (no row-resident form: every int8 shape ignores the bound)
-        hipLaunchKernelGGL(k_exact_scores<DT_I8>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
-    else
-        hipLaunchKernelGGL(k_exact_scores<DT_BF16>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
-#undef SSS_ROWS
+    // the row-resident form: inner product, rows of 256 / 512 bytes (float32: 1024 as well); none for int8 rows, whose
+    // every shape ignores the bound
+    const bool known = with_dtype(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        [[maybe_unused]] auto rows = [&](auto dd) {
+            hipLaunchKernelGGL((k_exact_scores_rows<decltype(dd)::value, DT>), dim3(rb), dim3(256), 0, st, q, qsel, (int)nsel, c, n, scores, lb, lb_by_row);
+        };
+        if constexpr (DT == DT_F32) {
+            if (metric == 0 && d == 64) return rows(std::integral_constant<int, 64>());
+        }
+        if constexpr (DT != DT_I8) {
+            if (metric == 0 && d == 128) return rows(std::integral_constant<int, 128>());
+            if (metric == 0 && d == 256) return rows(std::integral_constant<int, 256>());
+        }
+        hipLaunchKernelGGL(k_exact_scores<DT>, dim3((unsigned)gx, (unsigned)nsel), dim3(64), 0, st, q, qsel, c, n, d, metric, scores);
+    });
+    if (!known) { set_error("exact scores: dtype %d is not a corpus dtype", dtype); return SSS_EINVAL; }
     return check_launch("k_exact_scores");
 }
 
@@ -570,7 +547,7 @@ int ip_topk_exhaustive(const void* q, const int* qsel, long nsel, const void* c,
                        void* ws, size_t ws_bytes, hipStream_t st) {
     if (nsel <= 0 || n <= 0 || k <= 0 || d <= 0 || !corpus_dtype_ok(dtype) ||
         d % elems_per_chunk(dtype) || (metric != 0 && metric != 1)) {
-        set_error("ip_topk_exhaustive: need nsel, n, k > 0, d %% 4 == 0 (f32) / d %% 8 == 0 (bf16, f16) / d %% 16 == 0 (int8), metric in {0,1}");
+        set_error("ip_topk_exhaustive: need nsel, n, k > 0, %s, metric in {0,1}", row_align_text());
         return SSS_EINVAL;
     }
     if (n >= (1L << 31) || nsel > 65535 || k > RS_MAX_K) { set_error("ip_topk_exhaustive: n < 2^31, nsel <= 65535, k <= 1024"); return SSS_EINVAL; }
@@ -699,7 +676,7 @@ static int range_exhaustive_check(const char* what, const int* qsel, long nsel, 
 int range_exhaustive_count(const void* q, const int* qsel, long nsel, const void* c, long n, int d, int dtype, int metric, const float* radius,
                            long* counts, void* ws, size_t ws_bytes, hipStream_t st) {
     if (d <= 0 || !corpus_dtype_ok(dtype) || d % elems_per_chunk(dtype) || !q || !c || !counts) {
-        set_error("range_exhaustive_count: need d %% 4 == 0 (f32) / d %% 8 == 0 (bf16, f16) / d %% 16 == 0 (int8), q, corpus and counts");
+        set_error("range_exhaustive_count: need %s, q, corpus and counts", row_align_text());
         return SSS_EINVAL;
     }
     int rc = range_exhaustive_check("range_exhaustive_count", qsel, nsel, n, metric, radius, ws, ws_bytes);

@@ -50,27 +50,22 @@ int profile_read(double* total_ms, int* launches) {
 static bool fused_shape_ok(int d, int dtype) {
     const int rb = d * elem_bytes(dtype);
     // (DT_I8: d = 256 / 512 / 1024 -- the d <= 1024 that keeps an int8 score exact in float32, select_dev.h: err_bound)
-    return (dtype == DT_F32 || dtype == DT_BF16 || dtype == DT_SPLIT || dtype == DT_F16 || dtype == DT_H16 || dtype == DT_I8) &&
-           (rb == 256 || rb == 512 || rb == 1024);
+    return format_of(dtype) && (rb == 256 || rb == 512 || rb == 1024);
 }
 
-// scan_dtype: what k_scan reads for rows of exact_dtype -- f32 rows: themselves, their split or their f16 image; bf16
-// f16 and int8 rows: themselves.
+// scan_dtype: what k_scan reads for rows of exact_dtype (elem.h: scan_pair_ok).
 int check_scan_source(const char* what, int exact_dtype, int scan_dtype, int d, bool long_rows, const void* c_scan, int corpus_shift,
                       float corpus_resid, long n, long nq) {
-    static const char* const image[] = {"f32 corpus", "bf16 corpus", "split image", "f16 image", "f16 corpus", "", "int8 corpus"};
-    const bool paired = exact_dtype == DT_F32 ? (scan_dtype == DT_F32 || scan_dtype == DT_SPLIT || scan_dtype == DT_F16)
-                                              : (exact_dtype == DT_BF16 || exact_dtype == DT_H16 || exact_dtype == DT_I8) && scan_dtype == exact_dtype;
     if (long_rows && exact_dtype == DT_I8) {
         set_error("%s: int8 rows (dtype %d) have no long-row scan: d in {256,512,1024} on the fused scan, else the exhaustive kernels", what, DT_I8);
         return SSS_EINVAL;
     }
-    if (!paired || !(long_rows ? long_shape_ok(d, exact_dtype, scan_dtype) : fused_shape_ok(d, scan_dtype))) {
+    if (!(long_rows ? long_shape_ok(d, exact_dtype, scan_dtype) : scan_pair_ok(exact_dtype, scan_dtype, false) && fused_shape_ok(d, scan_dtype))) {
         set_error("%s: no scan of type %d for dtype %d, d %d", what, scan_dtype, exact_dtype, d);
         return SSS_EINVAL;
     }
     if (!c_scan || (reinterpret_cast<uintptr_t>(c_scan) & 15)) {
-        set_error("%s: scan image (the %s) missing or not 16-byte aligned", what, image[scan_dtype]);
+        set_error("%s: scan image (the %s) missing or not 16-byte aligned", what, format_of(scan_dtype)->name);
         return SSS_EINVAL;
     }
     if (scan_dtype == DT_F16 && (corpus_shift < -160 || corpus_shift > 160 || !(corpus_resid >= 0.f))) {

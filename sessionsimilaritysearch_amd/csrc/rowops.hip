@@ -5,14 +5,12 @@
 //   k_gather_rows     <- NodeAsinEmbedding.forward (reference model/NodeEmbedding.py:137-138)
 // Each row is owned by a group of LPR lanes that move 16 bytes per lane per access (coalesced
 // 16 B x LPR segments); reductions are butterflies inside the lane group.
-#include "sss_common.h"
+#include "elem.h"
 
 namespace sss {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
+template <int LPR, typename T>
+__device__ __forceinline__ T group_sum(T v) {
 #pragma unroll
     for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
@@ -53,118 +51,43 @@ __device__ __forceinline__ float norm_up(double ss) {
     return f;
 }
 
-template <int LPR>
-__device__ __forceinline__ double group_sum_f64(double v) {
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-template <int LPR>
-__global__ __launch_bounds__(256) void k_row_norm_max(const float* __restrict__ x, long n, int d,
-                                                      float* __restrict__ out) {
+// One group of LPR lanes per row (float32 rows: the smallest power of two that covers d / 4 chunks; the other formats a
+// whole wave), a lane folding the squares of the row's 16-byte chunks in the format's own accumulator (elem.h:
+// chunk_sumsq -- the squares of the exactly converted values in float64; int8: an integer sum, exact in int64, so the
+// value is the exact norm rounded up by norm_up).  float16 rows: a row holding an inf or a NaN reads as +inf, so one
+// reduction also tells a caller that a conversion to float16 overflowed (FlatIndex.add).
+template <int DT, int LPR>
+__global__ __launch_bounds__(256) void k_row_norm_max(const void* __restrict__ x, long n, int d, float* __restrict__ out) {
+    typedef Elem<DT> E;
     const int sub = threadIdx.x % LPR;
     const long rows_per_block = 256 / LPR;
-    const int nv = d / 4;
+    const int nv = d / E::per_chunk;
     double m = 0.0;
     for (long row = (long)blockIdx.x * rows_per_block + threadIdx.x / LPR; row < n;
          row += (long)gridDim.x * rows_per_block) {
-        const float4* p = reinterpret_cast<const float4*>(x + row * (long)d);
-        double ss = 0.0;
+        const u32x4* p = reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(x) + row * (long)d * E::bytes);
+        typename E::sum_t ss = 0;
+        [[maybe_unused]] bool bad = false;
         for (int i = sub; i < nv; i += LPR) {
-            const float4 v = p[i];
-            ss += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
-        }
-        ss = group_sum_f64<LPR>(ss);
-        m = fmax(m, ss);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
-    // non-negative floats order like their bit patterns
-    if ((threadIdx.x & 63) == 0)
-        atomicMax(reinterpret_cast<unsigned int*>(out), __builtin_bit_cast(unsigned int, norm_up(m)));
-}
-
-// bf16 rows: max over rows of the 2-norm of the (exactly converted) float32 values, accumulated as above
-__global__ __launch_bounds__(256) void k_row_norm_max_bf16(const unsigned short* __restrict__ x, long n, int d,
-                                                           float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-    double m = 0.0;
-    for (long row = wave; row < n; row += nwaves) {
-        const u32x4* p = reinterpret_cast<const u32x4*>(x + row * (long)d);
-        double ss = 0.0;
-        for (int i = lane; i < d / 8; i += 64) {
             const u32x4 v = p[i];
-#define SSS_SQ2(w)                                                                   \
-    { const double lo = __builtin_bit_cast(float, v.w << 16), hi = __builtin_bit_cast(float, v.w & 0xFFFF0000u); \
-      ss += lo * lo + hi * hi; }
-            SSS_SQ2(x) SSS_SQ2(y) SSS_SQ2(z) SSS_SQ2(w)
-#undef SSS_SQ2
+            ss = E::chunk_sumsq(ss, v);
+            if constexpr (DT == DT_H16) {
+#pragma unroll
+                for (int w = 0; w < 4; ++w) bad |= (v[w] & 0x7C00u) == 0x7C00u || (v[w] & 0x7C000000u) == 0x7C000000u;
+            }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-        m = fmax(m, ss);
-    }
-    if (lane == 0)
-        atomicMax(reinterpret_cast<unsigned int*>(out), __builtin_bit_cast(unsigned int, norm_up(m)));
-}
-
-// float16 rows: the same maximum, squares of the (exactly converted) values summed in float64.  A row holding an inf or
-// a NaN reads as +inf, so one reduction also tells a caller that a conversion to float16 overflowed (FlatIndex.add).
-__global__ __launch_bounds__(256) void k_row_norm_max_f16(const unsigned short* __restrict__ x, long n, int d,
-                                                          float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-    double m = 0.0;
-    for (long row = wave; row < n; row += nwaves) {
-        const u32x4* p = reinterpret_cast<const u32x4*>(x + row * (long)d);
-        double ss = 0.0;
-        bool bad = false;
-        for (int i = lane; i < d / 8; i += 64) {
-            const u32x4 v = p[i];
-#define SSS_SQ2(w)                                                                                        \
-    { const double lo = (double)__builtin_bit_cast(_Float16, (unsigned short)(v.w & 0xFFFFu)),          \
-                   hi = (double)__builtin_bit_cast(_Float16, (unsigned short)(v.w >> 16));              \
-      ss += lo * lo + hi * hi;                                                                            \
-      bad |= (v.w & 0x7C00u) == 0x7C00u || (v.w & 0x7C000000u) == 0x7C000000u; }
-            SSS_SQ2(x) SSS_SQ2(y) SSS_SQ2(z) SSS_SQ2(w)
-#undef SSS_SQ2
+        if constexpr (DT == DT_H16) {
+            if (bad) ss = INFINITY;                     // (NaN would be dropped by fmax below)
         }
-        if (bad) ss = INFINITY;                         // (NaN would be dropped by fmax below)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-        m = fmax(m, ss);
-    }
-    if (lane == 0)
-        atomicMax(reinterpret_cast<unsigned int*>(out), __builtin_bit_cast(unsigned int, norm_up(m)));
-}
-
-// int8 rows (include/sss.h: dtype 6): the same maximum; a row's sum of squares is an integer (exact in int64, then in
-// float64), so the value is the exact norm rounded up by norm_up.
-__global__ __launch_bounds__(256) void k_row_norm_max_i8(const signed char* __restrict__ x, long n, int d, float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-    double m = 0.0;
-    for (long row = wave; row < n; row += nwaves) {
-        const u32x4* p = reinterpret_cast<const u32x4*>(x + row * (long)d);
-        long ss = 0;
-        for (int i = lane; i < d / 16; i += 64) {
-            const u32x4 v = p[i];
-            const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) { const int t = (int)(signed char)(w[e] >> (8 * b)); ss += t * t; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+        ss = group_sum<LPR>(ss);
         m = fmax(m, (double)ss);
     }
-    if (lane == 0)
+    if constexpr (LPR < 64) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+    }
+    // non-negative floats order like their bit patterns
+    if ((threadIdx.x & 63) == 0)
         atomicMax(reinterpret_cast<unsigned int*>(out), __builtin_bit_cast(unsigned int, norm_up(m)));
 }
 
@@ -330,33 +253,20 @@ int normalize_rows(float* x, long n, int d, long ld, float eps, int rule, hipStr
     return check_launch("k_normalize_rows");
 }
 
-int row_norm_max(const void* xv, long n, int d, int dtype, float* out, hipStream_t st) {
-    if (dtype == 1 || dtype == 4) {                     // include/sss.h: bfloat16 / float16 rows
-        if (n < 0 || d <= 0 || d % 8) { set_error("row_norm_max: bf16 / f16 need d %% 8 == 0"); return SSS_EINVAL; }
-        if (n == 0) return SSS_OK;
-        long blocks = (n + 3) / 4;
-        if (blocks > 2048) blocks = 2048;
-        if (dtype == 1)
-            hipLaunchKernelGGL(k_row_norm_max_bf16, dim3((unsigned)blocks), dim3(256), 0, st,
-                               reinterpret_cast<const unsigned short*>(xv), n, d, out);
-        else
-            hipLaunchKernelGGL(k_row_norm_max_f16, dim3((unsigned)blocks), dim3(256), 0, st,
-                               reinterpret_cast<const unsigned short*>(xv), n, d, out);
-        return check_launch("k_row_norm_max_16");
+int row_norm_max(const void* x, long n, int d, int dtype, float* out, hipStream_t st) {
+    if (!corpus_dtype_ok(dtype) || n < 0 || d <= 0 || d % elems_per_chunk(dtype)) {
+        set_error("row_norm_max: need dtype in {0,1,4,6}, n >= 0, %s", row_align_text());
+        return SSS_EINVAL;
     }
-    if (dtype == 6) {                                   // include/sss.h: int8 rows
-        if (n < 0 || d <= 0 || d % 16) { set_error("row_norm_max: int8 needs d %% 16 == 0"); return SSS_EINVAL; }
-        if (n == 0) return SSS_OK;
-        long blocks = (n + 3) / 4;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(k_row_norm_max_i8, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const signed char*>(xv), n, d, out);
-        return check_launch("k_row_norm_max_i8");
-    }
-    const float* x = reinterpret_cast<const float*>(xv);
-    if (dtype != 0 || n < 0 || d <= 0 || d % 4) { set_error("row_norm_max: need dtype in {0,1,4,6}, n >= 0, d %% 4 == 0"); return SSS_EINVAL; }
     if (n == 0) return SSS_OK;
-    const int lpr = lanes_per_row(d);
-    SSS_DISPATCH_LPR(lpr, hipLaunchKernelGGL(k_row_norm_max<L>, dim3(grid_for(n, L)), dim3(256), 0, st, x, n, d, out));
+    with_dtype(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if constexpr (DT == DT_F32) {
+            SSS_DISPATCH_LPR(lanes_per_row(d), hipLaunchKernelGGL((k_row_norm_max<DT, L>), dim3(grid_for(n, L)), dim3(256), 0, st, x, n, d, out));
+        } else {
+            hipLaunchKernelGGL((k_row_norm_max<DT, 64>), dim3(grid_for(n, 64)), dim3(256), 0, st, x, n, d, out);
+        }
+    });
     return check_launch("k_row_norm_max");
 }
 

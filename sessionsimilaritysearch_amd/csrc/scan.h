@@ -1,37 +1,9 @@
 // Internal interface between the scan kernel (scan.hip), the select / re-score kernels
 // (select.hip, select_thr.hip) and the host orchestration of sss_ip_topk (ip_topk.hip).  gfx950 only.
 #pragma once
-#include "sss_common.h"
+#include "elem.h"
 
 namespace sss {
-
-constexpr int DT_F32 = 0;       // element type codes of the C ABI (include/sss.h: dtype)
-constexpr int DT_BF16 = 1;
-// Scan-only element type (never crosses the C ABI as a corpus dtype): an f32 corpus row of d
-// elements stored as [hi(d) | lo(d)] bfloat16, hi = rne_bf16(x), lo = rne_bf16(x - hi) -- 4 bytes
-// per element like f32.  The scan scores hi*hi + hi*lo + lo*hi on the bf16 MFMA (three passes at
-// 16x the f32 MFMA rate); queries are f32 and are split by the kernel.  Candidates are re-scored
-// from the f32 rows, and the proof uses the split's own error bound (select_dev.h: err_bound).
-constexpr int DT_SPLIT = 2;
-// Scan-only element type: an f32 corpus stored as float16 after an exact power-of-two scaling,
-// x * 2^shift with ONE shift for the whole corpus chosen so that the largest |element| lies in
-// [2^12, 2^13) (f16_shift below: far from both ends of the f16 range) -- 2 bytes per element.  The
-// kernel scales each f32 query by its own power of two the same way, so a scan score is the true
-// score times 2^(corpus shift + query shift): thresholds and candidate selection work in that
-// domain (per query it is a fixed positive factor), and the select kernel divides it out for the
-// proof.  One f16 MFMA pass (1/3 of DT_SPLIT's matrix work, half its bytes) with a coarser bound
-// (select_dev.h: err_bound ~ 2^-10 |q||c|), still proven per query and re-scored from the f32 rows.
-constexpr int DT_F16 = 3;
-// Corpus dtype of the C ABI (include/sss.h: dtype 4) and its own scan type: rows STORED as IEEE float16 (round to
-// nearest even of whatever the caller had), queries float16 too.  Rows and queries go into v_mfma_f32_32x32x16_f16 as
-// they are -- no scaling, no residual, scan scores are scores -- and the candidates are re-scored from the same rows.
-// (3 stays the scaled image of an f32 corpus: the two share the MFMA and the operand layout, not the bound.)
-constexpr int DT_H16 = 4;
-// Corpus dtype of the C ABI (include/sss.h: dtype 6; 5 stays unassigned) and its own scan type: rows STORED as int8,
-// queries int8 too, 1 byte per element.  Rows and queries go into v_mfma_i32_32x32x32_i8 as they are, 16 elements per
-// 16-byte chunk; products and sums are exact in int32, and for the fused shapes (d <= 1024) |score| <= d * 2^14 <= 2^24
-// is exact in float32 as well: the scan score IS the canonical score (select_dev.h: err_bound = 0).
-constexpr int DT_I8 = 6;
 
 // shift that maps a largest magnitude `amax` into [2^12, 2^13); 0 for an all-zero / non-finite row
 __host__ __device__ inline int f16_shift(float amax) {
@@ -54,17 +26,12 @@ constexpr unsigned ORD_NEG_INF = 0x007FFFFFu;   // f2ord(-inf); slot value 0 = "
 constexpr double ULP32_REL = 2.4e-7;
 constexpr double ULP32_MIN = 1e-44;             // ... and its floor in the subnormal range (the spacing there is 2^-149 = 1.4e-45)
 
-static inline int elem_bytes(int dtype) { return dtype == DT_I8 ? 1 : (dtype == DT_BF16 || dtype == DT_F16 || dtype == DT_H16) ? 2 : 4; }
-static inline int elems_per_chunk(int dtype) { return 16 / elem_bytes(dtype); }   // a stored row is read in 16-byte pieces: d % this == 0
 static inline int pow2_at_least(int x) { int p = 64; while (p < x) p <<= 1; return p; }   // smallest power of two >= max(x, 64): LDS key arrays
-static inline bool corpus_dtype_ok(int dtype) { return dtype == DT_F32 || dtype == DT_BF16 || dtype == DT_H16 || dtype == DT_I8; }   // what crosses the C ABI as `dtype`
 
 // Row shapes of sss_ip_topk_long: d % 64 == 0 and exact rows of at most 16384 bytes (k_select_all keeps the query row in
-// LDS); f32 rows are scanned through their f16 image, bf16 and f16 rows directly.  int8 rows have no long-row scan.
+// LDS), scanned by what scan_pair_ok (elem.h) pairs them with.
 static inline bool long_shape_ok(int d, int exact_dtype, int scan_dtype) {
-    if (d <= 0 || d % 64 || d * elem_bytes(exact_dtype) > 16384) return false;
-    return (exact_dtype == DT_F32 && scan_dtype == DT_F16) || (exact_dtype == DT_BF16 && scan_dtype == DT_BF16) ||
-           (exact_dtype == DT_H16 && scan_dtype == DT_H16);
+    return d > 0 && d % 64 == 0 && d * elem_bytes(exact_dtype) <= 16384 && scan_pair_ok(exact_dtype, scan_dtype, true);
 }
 
 // STATE words (caller-owned, zero before the first call; every call leaves them zero: the select

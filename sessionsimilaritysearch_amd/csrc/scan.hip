@@ -830,31 +830,14 @@ static int launch_one(const ScanArgs& a, hipStream_t st) {
 
 int launch_scan(int dtype, int d, int tile_rows, const ScanArgs& a, hipStream_t st) {
     const int rb = d * elem_bytes(dtype);
-    if (dtype == DT_F32) {
-        if (rb == 256) return tile_rows == 256 ? launch_one<256, 256, DT_F32>(a, st) : launch_one<256, 128, DT_F32>(a, st);
-        if (rb == 512) return tile_rows == 128 ? launch_one<512, 128, DT_F32>(a, st) : launch_one<512, 64, DT_F32>(a, st);
-        if (rb == 1024) return launch_one<1024, 64, DT_F32, 4>(a, st);
-    } else if (dtype == DT_BF16) {
-        if (rb == 256) return tile_rows == 256 ? launch_one<256, 256, DT_BF16>(a, st) : launch_one<256, 128, DT_BF16>(a, st);
-        if (rb == 512) return tile_rows == 128 ? launch_one<512, 128, DT_BF16>(a, st) : launch_one<512, 64, DT_BF16>(a, st);
-        if (rb == 1024) return launch_one<1024, 64, DT_BF16, 4>(a, st);
-    } else if (dtype == DT_F16) {
-        if (rb == 256) return tile_rows == 256 ? launch_one<256, 256, DT_F16>(a, st) : launch_one<256, 128, DT_F16>(a, st);
-        if (rb == 512) return tile_rows == 128 ? launch_one<512, 128, DT_F16>(a, st) : launch_one<512, 64, DT_F16>(a, st);
-        if (rb == 1024) return launch_one<1024, 64, DT_F16, 4>(a, st);
-    } else if (dtype == DT_H16) {
-        if (rb == 256) return tile_rows == 256 ? launch_one<256, 256, DT_H16>(a, st) : launch_one<256, 128, DT_H16>(a, st);
-        if (rb == 512) return tile_rows == 128 ? launch_one<512, 128, DT_H16>(a, st) : launch_one<512, 64, DT_H16>(a, st);
-        if (rb == 1024) return launch_one<1024, 64, DT_H16, 4>(a, st);
-    } else if (dtype == DT_I8) {
-        if (rb == 256) return tile_rows == 256 ? launch_one<256, 256, DT_I8>(a, st) : launch_one<256, 128, DT_I8>(a, st);
-        if (rb == 512) return tile_rows == 128 ? launch_one<512, 128, DT_I8>(a, st) : launch_one<512, 64, DT_I8>(a, st);
-        if (rb == 1024) return launch_one<1024, 64, DT_I8, 4>(a, st);
-    } else if (dtype == DT_SPLIT) {
-        if (rb == 256) return tile_rows == 256 ? launch_one<256, 256, DT_SPLIT>(a, st) : launch_one<256, 128, DT_SPLIT>(a, st);
-        if (rb == 512) return tile_rows == 128 ? launch_one<512, 128, DT_SPLIT>(a, st) : launch_one<512, 64, DT_SPLIT>(a, st);
-        if (rb == 1024) return launch_one<1024, 64, DT_SPLIT, 4>(a, st);
-    }
+    int rc = 1;                                                  // (1: nothing launched)
+    with_dtype<true>(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (rb == 256) rc = tile_rows == 256 ? launch_one<256, 256, DT>(a, st) : launch_one<256, 128, DT>(a, st);
+        else if (rb == 512) rc = tile_rows == 128 ? launch_one<512, 128, DT>(a, st) : launch_one<512, 64, DT>(a, st);
+        else if (rb == 1024) rc = launch_one<1024, 64, DT, 4>(a, st);
+    });
+    if (rc != 1) return rc;
     set_error("scan: unsupported row size %d bytes", rb);
     return SSS_EINVAL;
 }

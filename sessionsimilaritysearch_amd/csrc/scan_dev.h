@@ -7,7 +7,6 @@ namespace sss {
 typedef char __attribute__((address_space(3)))* lptr_c;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));       // 16 int8 values: one A / B operand of v_mfma_i32_32x32x32_i8
 typedef int i32x16 __attribute__((ext_vector_type(16)));     // its int32 accumulators (the C / D layout of the 16-bit forms)
 

@@ -8,7 +8,6 @@ namespace sss {
 
 constexpr int SORT_THREADS = 256;
 constexpr int SA_BYTES = 128;      // rescore_kept: bytes of every row staged through LDS per step
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Wave-wide maximum of a u32 on the DPP network (no LDS round trips): row_shr 1/2/4/8 leave each
 // 16-lane row's maximum in its last lane, row_bcast15 / row_bcast31 carry it across rows, lane 63
@@ -429,7 +428,7 @@ __device__ __forceinline__ void rescore_kept(const unsigned long long* surv, int
 }
 
 // bytes of a STORED row of d elements (the exact element types: DT_F32, DT_I8, else DT_BF16 / DT_H16; the host's
-// elem_bytes, scan.h, also knows the scan-only images)
+// elem_bytes, elem.h, also knows the scan-only images)
 __device__ __forceinline__ int row_bytes(int d, int dtype) { return d * (dtype == DT_F32 ? 4 : dtype == DT_I8 ? 1 : 2); }
 
 // the query row q of Q (rb bytes) into LDS, by the NT threads t of its wave or workgroup

@@ -14,13 +14,42 @@ stream.  There is no CPU fallback.
 """
 from __future__ import annotations
 
+import dataclasses
+from typing import Callable
+
 import numpy as np
 import torch
 
 from . import _lib
+from ._device import EXHAUSTIVE_WS_BYTES as _EXHAUSTIVE_WS_BYTES, Workspace, exhaustive_chunk, grow_rows
 
-FUSED_DIMS = {"f32": (64, 128, 256), "bf16": (128, 256, 512), "f16": (128, 256, 512),
-              "i8": (256, 512, 1024)}                            # row bytes 256 / 512 / 1024
+
+@dataclasses.dataclass(frozen=True)
+class _Format:
+    """One storage format of a FlatIndex (csrc/elem.h holds the kernels' side of the same table)."""
+    name: str
+    code: int                       # include/sss.h: dtype
+    torch_dtype: torch.dtype
+    numpy_dtype: type | None        # numpy arrays of this type are stored as they are (None: numpy has no such type)
+    elem_bytes: int
+    fused_dims: tuple               # d of the fused scans: rows of 256 / 512 / 1024 bytes
+    long_rows: bool                 # has a long-row scan (sss_ip_topk_long)
+    from_f32: Callable              # (float32 device tensor, what) -> tensor of the stored type; ValueError for what it cannot hold
+    checks_finite: bool = False     # add / adopt refuse rows that are not finite in the stored type
+
+    @property
+    def align(self) -> int:
+        """Elements per 16-byte piece of a stored row: d % this == 0."""
+        return 16 // self.elem_bytes
+
+
+_FORMATS = {f.name: f for f in (
+    _Format("f32", 0, torch.float32, np.float32, 4, (64, 128, 256), True, lambda x, what: x),
+    _Format("bf16", 1, torch.bfloat16, None, 2, (128, 256, 512), True, lambda x, what: to_bf16(x)),
+    _Format("f16", 4, torch.float16, np.float16, 2, (128, 256, 512), True, lambda x, what: to_f16(x), checks_finite=True),
+    _Format("i8", 6, torch.int8, np.int8, 1, (256, 512, 1024), False, lambda x, what: _i8_from_f32(x, what)),
+)}
+FUSED_DIMS = {f.name: f.fused_dims for f in _FORMATS.values()}
 F16_SCAN_DIMS = (128, 256, 512)                                  # scaled-f16 image: 2 bytes per element
 # scan="auto": the fastest scan whose error bound is still small against the spacing of the scores
 # around rank k (the spacing shrinks as k grows): one-pass f16 up to k = 128, bf16 split up to k = 500
@@ -38,15 +67,10 @@ _LADDER = ("f16", "split", "f32")
 FUSED_MAX_K = 500
 LONG_MAX_K = 1024                                                # sss_ip_topk_long: what its exhaustive fallback resolves
 LONG_MAX_ROW_BYTES = 16384
-DTYPE_CODE = {"f32": 0, "bf16": 1, "f16": 4}                     # include/sss.h: dtype of the float formats (2, 3 are scan images, below)
-# ... and of the integer format.  Kept beside DTYPE_CODE, not in it: tests/test_f16_index_cpu.py pins that dict to the
-# three float formats and passes 5 to every entry point as a value that must stay invalid -- so int8 is code 6.
-INT_DTYPE_CODE = {"i8": 6}
-_CODE = {**DTYPE_CODE, **INT_DTYPE_CODE}                         # every storage format an index can have
-_TORCH_DTYPE = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "i8": torch.int8}
-_ROW_ALIGN = {"f32": 4, "bf16": 8, "f16": 8, "i8": 16}           # elements per 16-byte piece of a stored row: d % this == 0
-_ELEM_BYTES = {"f32": 4, "bf16": 2, "f16": 2, "i8": 1}
-_EXHAUSTIVE_WS_BYTES = 1 << 30
+_CODE = {f.name: f.code for f in _FORMATS.values()}              # include/sss.h: dtype (2, 3 are scan images, below; 5 is unassigned)
+_TORCH_DTYPE = {f.name: f.torch_dtype for f in _FORMATS.values()}
+DTYPE_CODE = {n: c for n, c in _CODE.items() if _TORCH_DTYPE[n].is_floating_point}    # the public views: float formats ...
+INT_DTYPE_CODE = {n: c for n, c in _CODE.items() if n not in DTYPE_CODE}               # ... and integer ones
 SEARCH_CHUNK = 65536             # queries per fused call of search_device (workspace 16 KB per query)
 SEARCH_CHUNK_LONG = 16384        # ... on the long-row path (64 KB per query)
 RANGE_CHUNK = 4096               # queries per fused range_search count / fill (workspace 64 KB per query)
@@ -94,6 +118,14 @@ def integer_valued_i8(x: torch.Tensor) -> torch.Tensor:
     """Is every element of the float tensor ``x`` an integer in [-128, 127]?  A bool scalar tensor on x's device (no
     sync; NaN and inf are not).  What an int8 index asks of float input before it casts it."""
     return ((x == torch.round(x)) & (x >= -128.0) & (x <= 127.0)).all()
+
+
+def _i8_from_f32(x: torch.Tensor, what: str) -> torch.Tensor:
+    # one device reduction, one host read -- as the f16 index's "not finite" check
+    if not bool(integer_valued_i8(x).item()):
+        raise ValueError(f"{what}: an i8 index takes int8 rows, or floats that are integers in [-128, 127] "
+                         "(quantize_i8 makes them)")
+    return x.to(torch.int8)
 
 
 def quantize_i8(x, scale=None):
@@ -191,10 +223,12 @@ class FlatIndex:
     def __init__(self, d: int, metric: str = "ip", device=None, dtype: str = "f32", scan: str | None = None):
         if metric not in ("ip", "l2"):
             raise ValueError("metric must be 'ip' or 'l2'")
-        if dtype not in _CODE:
-            raise ValueError("dtype must be 'f32', 'bf16', 'f16' or 'i8'")
-        if dtype != "f32" and d % _ROW_ALIGN[dtype]:
-            raise ValueError(f"{dtype} index needs d % {_ROW_ALIGN[dtype]} == 0")
+        if dtype not in _FORMATS:
+            names = [repr(n) for n in _FORMATS]
+            raise ValueError(f"dtype must be {', '.join(names[:-1])} or {names[-1]}")
+        fmt = _FORMATS[dtype]
+        if dtype != "f32" and d % fmt.align:
+            raise ValueError(f"{dtype} index needs d % {fmt.align} == 0")
         if scan is None:
             scan = "auto" if dtype == "f32" else "native"
         if scan not in (("auto", "f16", "split", "f32") if dtype == "f32" else ("native",)):
@@ -207,7 +241,7 @@ class FlatIndex:
         self.d = int(d)
         self.metric = metric
         self.dtype = dtype
-        self._tdtype = _TORCH_DTYPE[dtype]
+        self._tdtype = fmt.torch_dtype
         self.device = _dev(device)
         # derived corpus images, built on first use and extended as rows are added
         self._split = None              # [cap, 2d] bf16 hi|lo image of the rows        ("split" scan)
@@ -222,7 +256,7 @@ class FlatIndex:
         self._store = self._xb          # backing storage of _xb (grown geometrically by add())
         self._cmax_t = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._cmax = None
-        self._ws = None
+        self._ws = Workspace(self.device)
         self._state = None              # per-query state words of sss_ip_topk: zeroed once, kept zero by the kernels
         self.id_offset = 0              # global id of row 0 (row-sharded corpora)
         self.last_fallback_queries = 0  # queries of the last search() re-run exhaustively
@@ -231,26 +265,19 @@ class FlatIndex:
         self.last_range_overflow_queries = 0    # queries of the last range_search the fused route sent to the exhaustive one
 
     @property
+    def _fmt(self) -> _Format:
+        """The record of this index's storage format (``dtype`` names it)."""
+        return _FORMATS[self.dtype]
+
+    @property
     def ntotal(self) -> int:
         return int(self._xb.shape[0])
 
     def add(self, x):
         """Append rows (copied, ids = insertion order) -- ``IndexFlatIP.add``."""
         x = self._rows(x, "add")
-        new_max = self._checked_norm_max(x)
-        n_old = self.ntotal
-        if n_old + x.shape[0] > self._store.shape[0]:          # amortised growth: no re-copy per add()
-            cap = max(n_old + x.shape[0], 2 * self._store.shape[0])
-            store = torch.empty((cap, self.d), dtype=self._tdtype, device=self.device)
-            store[:n_old] = self._xb
-            self._store = store
-        self._store[n_old:n_old + x.shape[0]] = x
-        self._xb = self._store[:n_old + x.shape[0]]
-        if new_max is None:
-            self._norm_max(x)
-        else:
-            torch.maximum(self._cmax_t, new_max, out=self._cmax_t)
-            self._cmax = None
+        self._take_norm_max(x)
+        self._store, self._xb = grow_rows(self._store, self._xb, x)
         # streaming adds keep what the searches have learned about this corpus; only once it has doubled since
         # an escalation was earned is that treated as a different corpus (adopt() always resets)
         if self._auto_level and self.ntotal > 2 * max(1, self._auto_rows):
@@ -261,7 +288,7 @@ class FlatIndex:
         """Which candidate scan a fused search for k results uses ("" = none: exhaustive path)."""
         if self.metric != "ip" or k <= 0 or self.ntotal == 0:
             return ""
-        fused_shape = self.d in FUSED_DIMS[self.dtype] or (self.dtype == "f32" and self.d in F16_SCAN_DIMS)
+        fused_shape = self.d in self._fmt.fused_dims or (self.dtype == "f32" and self.d in F16_SCAN_DIMS)
         if not fused_shape:
             return self._long_or_none(k)         # rows longer than the register-resident scans take (D = 1600 ...)
         if k > FUSED_MAX_K:
@@ -282,9 +309,9 @@ class FlatIndex:
 
     def _long_or_none(self, k: int) -> str:
         """"long": the K-tiled scan for rows beyond the register-resident kernels (``sss_ip_topk_long``)."""
-        if self.dtype == "i8":
-            return ""                            # no long-row scan for int8 rows: the exhaustive kernels
-        row_bytes = self.d * _ELEM_BYTES[self.dtype]
+        if not self._fmt.long_rows:
+            return ""                            # (int8 rows: the exhaustive kernels)
+        row_bytes = self.d * self._fmt.elem_bytes
         return "long" if (self.d % 64 == 0 and row_bytes <= LONG_MAX_ROW_BYTES and k <= LONG_MAX_K) else ""
 
     def _scan_served(self, scan: str) -> bool:
@@ -388,11 +415,7 @@ class FlatIndex:
         """Build whatever a fused search for k results needs (images, norms) now rather than on
         the first search; returns the scan that will be used."""
         mode = self.scan_for(k)
-        if mode == "f16" or (mode == "long" and self.dtype == "f32"):
-            self._ensure_f16()
-            self.corpus_resid_norm()
-        elif mode == "split":
-            self._ensure_split()
+        self._scan_image(mode)
         self.corpus_max_norm()
         return mode
 
@@ -406,67 +429,57 @@ class FlatIndex:
         if mode == "split":
             self._ensure_split()
             return self._split, _SCAN_CODE["split"], 0, 0.0
-        return self._xb, _CODE[self.dtype], 0, 0.0
+        return self._xb, self._fmt.code, 0, 0.0
 
     def _require_d_aligned(self):
         """The exhaustive kernels read rows in 16-byte pieces."""
-        if self.d % _ROW_ALIGN[self.dtype]:
-            raise _lib.SssError("d must be a multiple of 4 (f32) / 8 (bf16, f16) / 16 (i8)")
+        if self.d % self._fmt.align:
+            by_align = {}
+            for f in _FORMATS.values():
+                by_align.setdefault(f.align, []).append(f.name)
+            raise _lib.SssError("d must be a multiple of " + " / ".join(f"{a} ({', '.join(n)})" for a, n in sorted(by_align.items())))
 
     def _exhaustive_chunks(self, rows: torch.Tensor, ws_bytes):
         """(offset, query rows, workspace) per chunk of the device int32 `rows` whose [chunk, n] scores fit the exhaustive
         workspace budget; ``ws_bytes(nsel, n)`` sizes a chunk's workspace."""
         n = self.ntotal
-        per = max(1, min(65535, _EXHAUSTIVE_WS_BYTES // max(1, 4 * n)))
+        per = exhaustive_chunk(n, 4)
         for lo in range(0, rows.numel(), per):
             sel = rows[lo:lo + per].contiguous()
-            yield lo, sel, self._workspace(ws_bytes(sel.numel(), n))
+            yield lo, sel, self._ws.get(ws_bytes(sel.numel(), n))
 
     def _rows(self, x, what):
         """Input rows as a contiguous device tensor of the index's element type."""
-        if isinstance(x, torch.Tensor) and x.dtype == self._tdtype and self.dtype != "f32":
+        fmt = self._fmt
+        if self.dtype != "f32" and isinstance(x, torch.Tensor) and x.dtype == fmt.torch_dtype:
             x = x.to(self.device).contiguous()
-        elif self.dtype == "f16" and isinstance(x, np.ndarray) and x.dtype == np.float16:
-            x = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
-        elif self.dtype == "i8" and isinstance(x, np.ndarray) and x.dtype == np.int8:
+        elif self.dtype != "f32" and isinstance(x, np.ndarray) and fmt.numpy_dtype is not None and x.dtype == fmt.numpy_dtype:
             x = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
         else:
-            x = _as_device_f32(x, self.device)
-            if self.dtype == "bf16":
-                x = to_bf16(x)
-            elif self.dtype == "f16":
-                x = to_f16(x)
-            elif self.dtype == "i8":
-                # one device reduction, one host read -- as the f16 index's "not finite" check
-                if not bool(integer_valued_i8(x).item()):
-                    raise ValueError(f"{what}: an i8 index takes int8 rows, or floats that are integers in [-128, 127] "
-                                     "(quantize_i8 makes them)")
-                x = x.to(torch.int8)
+            x = fmt.from_f32(_as_device_f32(x, self.device), what)
         if x.dim() != 2 or x.shape[1] != self.d:
             raise ValueError(f"{what}: expected [n, {self.d}], got {tuple(x.shape)}")
         return x
 
-    def _norm_max(self, x):
-        if x.shape[0] and self.d % _ROW_ALIGN[self.dtype] == 0:
-            rc = _lib.lib().sss_row_norm_max(x.data_ptr(), x.shape[0], self.d, _CODE[self.dtype],
-                                             self._cmax_t.data_ptr(), _lib.stream_ptr(self.device))
+    def _take_norm_max(self, x, reset=False):
+        """Merge the largest row norm of the new rows ``x`` into ``_cmax_t`` (``reset``: start from zero -- the rows
+        replace the corpus): one ``sss_row_norm_max`` into a fresh device [1] tensor, no host sync.  A format that
+        checks its rows are finite (f16: a float32 value beyond 65504 became inf in ``to_f16``) reads the result
+        first -- the reduction gives +inf for a row holding an inf or a NaN, so it serves both at one host sync --
+        and raises before the index has changed.  Rows the reduction does not take (f32, d % 4 != 0) are skipped."""
+        new_max = None
+        if x.shape[0] and self.d % self._fmt.align == 0:
+            new_max = torch.zeros(1, dtype=torch.float32, device=self.device)
+            rc = _lib.lib().sss_row_norm_max(x.data_ptr(), x.shape[0], self.d, self._fmt.code, new_max.data_ptr(),
+                                             _lib.stream_ptr(self.device))
             _lib.check(rc, "sss_row_norm_max")
+            if self._fmt.checks_finite and not np.isfinite(float(new_max.item())):
+                raise ValueError("f16 index: rows hold values that are not finite in float16 (|x| > 65504, inf or NaN)")
+        if reset:
+            self._cmax_t.zero_()
+        if new_max is not None:
+            torch.maximum(self._cmax_t, new_max, out=self._cmax_t)
         self._cmax = None
-
-    def _checked_norm_max(self, x):
-        """f16 index: the largest row norm of the new rows as a device float32 [1] tensor, after checking that the
-        rows are finite (a float32 value beyond 65504 became inf in ``to_f16``): ``sss_row_norm_max`` reads +inf
-        for a row holding an inf or a NaN, so one reduction (and one host sync) serves both.  None for the other
-        dtypes and for rows the reduction does not take: the caller runs ``_norm_max``."""
-        if self.dtype != "f16" or not x.shape[0]:
-            return None
-        t = torch.zeros(1, dtype=torch.float32, device=self.device)
-        rc = _lib.lib().sss_row_norm_max(x.data_ptr(), x.shape[0], self.d, _CODE[self.dtype], t.data_ptr(),
-                                         _lib.stream_ptr(self.device))
-        _lib.check(rc, "sss_row_norm_max")
-        if not np.isfinite(float(t.item())):
-            raise ValueError("f16 index: rows hold values that are not finite in float16 (|x| > 65504, inf or NaN)")
-        return t
 
     def adopt(self, xb: torch.Tensor, id_offset: int = 0):
         """Use an existing CUDA [n, d] tensor of the index's element type as the corpus without
@@ -474,15 +487,9 @@ class FlatIndex:
         _lib.require_cuda(xb, "xb", self._tdtype)
         if xb.dim() != 2 or xb.shape[1] != self.d:
             raise ValueError("adopt: wrong shape")
-        new_max = self._checked_norm_max(xb)
+        self._take_norm_max(xb, reset=True)
         self._xb = self._store = xb
         self.id_offset = int(id_offset)
-        self._cmax_t.zero_()
-        if new_max is None:
-            self._norm_max(xb)
-        else:
-            self._cmax_t.copy_(new_max)
-            self._cmax = None
         self._split, self._split_done = None, 0
         self._f16, self._f16_done = None, 0
         self._amax_t.zero_()
@@ -497,11 +504,6 @@ class FlatIndex:
         return self._cmax
 
     # ------------------------------------------------------------------ device-level search
-    def _workspace(self, nbytes: int) -> torch.Tensor:
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
-
     def fused_ok(self, k: int) -> bool:
         return self.scan_for(k) != ""
 
@@ -524,8 +526,8 @@ class FlatIndex:
             raise _lib.SssError("search_fused: this index / k has no fused path (use search)")
         image, _, shift, resid = self._scan_image(mode)
         if mode == "long":
-            ws = self._workspace(L.sss_ip_topk_long_workspace_bytes(nq, n, self.d, _CODE[self.dtype]))
-            rc = L.sss_ip_topk_long(q.data_ptr(), nq, self._xb.data_ptr(), _CODE[self.dtype], image.data_ptr(), shift, resid,
+            ws = self._ws.get(L.sss_ip_topk_long_workspace_bytes(nq, n, self.d, self._fmt.code))
+            rc = L.sss_ip_topk_long(q.data_ptr(), nq, self._xb.data_ptr(), self._fmt.code, image.data_ptr(), shift, resid,
                                     n, self.d, k, self.id_offset, self.corpus_max_norm(), D.data_ptr(), I.data_ptr(),
                                     status.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
             _lib.check(rc, "sss_ip_topk_long")
@@ -535,8 +537,8 @@ class FlatIndex:
         if mode == "f16":
             nbytes = L.sss_ip_topk_f16_workspace_bytes(nq, n, self.d, k)
         else:
-            nbytes = L.sss_ip_topk_workspace_bytes(nq, n, self.d, k, _CODE[self.dtype])
-        ws = self._workspace(nbytes)
+            nbytes = L.sss_ip_topk_workspace_bytes(nq, n, self.d, k, self._fmt.code)
+        ws = self._ws.get(nbytes)
         sbytes = L.sss_ip_topk_state_bytes(nq)
         if self._state is None or self._state.numel() < sbytes:
             self._state = torch.zeros(sbytes, dtype=torch.uint8, device=self.device)
@@ -550,7 +552,7 @@ class FlatIndex:
             rc = L.sss_ip_topk_split(q.data_ptr(), nq, self._xb.data_ptr(), image.data_ptr(), n, self.d, k, self.id_offset,
                                      *tail)
         else:
-            rc = L.sss_ip_topk(q.data_ptr(), nq, self._xb.data_ptr(), n, self.d, k, _CODE[self.dtype],
+            rc = L.sss_ip_topk(q.data_ptr(), nq, self._xb.data_ptr(), n, self.d, k, self._fmt.code,
                                self.id_offset, *tail)
         if rc != 0:
             self._state = None          # re-made (zeroed) on the next call
@@ -564,7 +566,7 @@ class FlatIndex:
         if self.metric != "ip" or self.ntotal == 0:
             return ""
         if self.dtype != "f32":
-            return "native" if self.d in FUSED_DIMS[self.dtype] else ""
+            return "native" if self.d in self._fmt.fused_dims else ""
         if not any(self._scan_served(s) for s in _LADDER):
             return ""                            # long rows: their scan IS a threshold scan; what it leaves is mass ties
         if self.scan == "auto":
@@ -593,8 +595,8 @@ class FlatIndex:
         image, code, shift, resid = self._scan_image(mode)
         sel = rows.to(device=self.device, dtype=torch.int32).contiguous()
         n = self.ntotal
-        ws = self._workspace(L.sss_ip_topk_threshold_workspace_bytes(sel.numel(), n, self.d, code))
-        rc = L.sss_ip_topk_threshold(q.data_ptr(), sel.data_ptr(), sel.numel(), self._xb.data_ptr(), _CODE[self.dtype],
+        ws = self._ws.get(L.sss_ip_topk_threshold_workspace_bytes(sel.numel(), n, self.d, code))
+        rc = L.sss_ip_topk_threshold(q.data_ptr(), sel.data_ptr(), sel.numel(), self._xb.data_ptr(), self._fmt.code,
                                      image.data_ptr(), code, shift, resid, n, self.d, k, self.id_offset,
                                      self.corpus_max_norm(), D.data_ptr(), I.data_ptr(), status.data_ptr(),
                                      ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
@@ -632,12 +634,12 @@ class FlatIndex:
             if bounded and metric == 0:
                 lb = D[sel.long(), k - 1].contiguous()
                 rc = L.sss_ip_topk_exhaustive_lb(q.data_ptr(), sel.data_ptr(), sel.numel(), self._xb.data_ptr(), n,
-                                                 self.d, k, _CODE[self.dtype], self.id_offset, lb.data_ptr(),
+                                                 self.d, k, self._fmt.code, self.id_offset, lb.data_ptr(),
                                                  D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(),
                                                  _lib.stream_ptr(self.device))
             else:
                 rc = L.sss_ip_topk_exhaustive(q.data_ptr(), sel.data_ptr(), sel.numel(), self._xb.data_ptr(), n,
-                                              self.d, k, _CODE[self.dtype], self.id_offset, metric, D.data_ptr(),
+                                              self.d, k, self._fmt.code, self.id_offset, metric, D.data_ptr(),
                                               I.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
             _lib.check(rc, "sss_ip_topk_exhaustive")
 
@@ -722,10 +724,10 @@ class FlatIndex:
             cmax = self.corpus_max_norm()
             for lo in range(0, nq, RANGE_CHUNK):
                 m = min(nq, lo + RANGE_CHUNK) - lo
-                ws = self._workspace(L.sss_range_search_workspace_bytes(m, n, self.d, code))
+                ws = self._ws.get(L.sss_range_search_workspace_bytes(m, n, self.d, code))
                 cs = torch.empty(2 * m, dtype=torch.int64, device=self.device)           # counts | status (one copy to the host)
                 status = torch.empty(m, dtype=torch.int32, device=self.device)
-                rc = L.sss_range_search_count(q[lo:].data_ptr(), m, self._xb.data_ptr(), _CODE[self.dtype], image.data_ptr(),
+                rc = L.sss_range_search_count(q[lo:].data_ptr(), m, self._xb.data_ptr(), self._fmt.code, image.data_ptr(),
                                               code, shift, resid, n, self.d, rad[lo:].data_ptr(), cmax, cs.data_ptr(),
                                               status.data_ptr(), ws.data_ptr(), ws.numel(), st)
                 _lib.check(rc, "sss_range_search_count")
@@ -747,7 +749,7 @@ class FlatIndex:
                 m = sel.numel()
                 counts_t = torch.empty(m, dtype=torch.int64, device=self.device)
                 rc = L.sss_range_search_exhaustive_count(q.data_ptr(), sel.data_ptr(), m, self._xb.data_ptr(), n, self.d,
-                                                         _CODE[self.dtype], metric, rad.data_ptr(), counts_t.data_ptr(),
+                                                         self._fmt.code, metric, rad.data_ptr(), counts_t.data_ptr(),
                                                          ws.data_ptr(), ws.numel(), st)
                 _lib.check(rc, "sss_range_search_exhaustive_count")
                 counts = counts_t.cpu().numpy()
@@ -861,7 +863,7 @@ class BinaryFlatIndex:
         self.device = _dev(device)
         self._codes = torch.empty((0, self._w), dtype=torch.uint8, device=self.device)
         self._store = self._codes       # backing storage of _codes (grown geometrically by add())
-        self._ws = None
+        self._ws = Workspace(self.device)
         self.id_offset = 0
         self.last_fallback_queries = 0
 
@@ -882,20 +884,7 @@ class BinaryFlatIndex:
         return x.contiguous()
 
     def add(self, codes):
-        x = self._rows(codes)
-        n_old = self.ntotal
-        if n_old + x.shape[0] > self._store.shape[0]:          # amortised growth, as FlatIndex.add
-            cap = max(n_old + x.shape[0], 2 * self._store.shape[0])
-            store = torch.empty((cap, self._w), dtype=torch.uint8, device=self.device)
-            store[:n_old] = self._codes
-            self._store = store
-        self._store[n_old:n_old + x.shape[0]] = x
-        self._codes = self._store[:n_old + x.shape[0]]
-
-    def _workspace(self, nbytes):
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
+        self._store, self._codes = grow_rows(self._store, self._codes, self._rows(codes))
 
     def search(self, codes, k: int):
         is_np = isinstance(codes, np.ndarray)
@@ -908,7 +897,7 @@ class BinaryFlatIndex:
         if nq and n:
             st = _lib.stream_ptr(self.device)
             if k <= L.sss_hamming_topk_capacity(nq, n):
-                ws = self._workspace(L.sss_hamming_topk_workspace_bytes(nq, n))
+                ws = self._ws.get(L.sss_hamming_topk_workspace_bytes(nq, n))
                 status = torch.empty((nq,), dtype=torch.int32, device=self.device)
                 rc = L.sss_hamming_topk(q.data_ptr(), nq, self._codes.data_ptr(), n, self._w, k, self.id_offset, D.data_ptr(),
                                         I.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), st)
@@ -917,10 +906,10 @@ class BinaryFlatIndex:
             else:                               # k beyond the fused capacity: everything through the exhaustive path
                 bad = torch.arange(nq, dtype=torch.int32, device=self.device)
             self.last_fallback_queries = int(bad.numel())
-            per = max(1, min(65535, _EXHAUSTIVE_WS_BYTES // max(1, 2 * n)))
+            per = exhaustive_chunk(n, 2)
             for lo in range(0, bad.numel(), per):
                 sel = bad[lo:lo + per].contiguous()
-                ws = self._workspace(L.sss_hamming_topk_exhaustive_workspace_bytes(sel.numel(), n))
+                ws = self._ws.get(L.sss_hamming_topk_exhaustive_workspace_bytes(sel.numel(), n))
                 rc = L.sss_hamming_topk_exhaustive(q.data_ptr(), sel.data_ptr(), sel.numel(), self._codes.data_ptr(), n,
                                                    self._w, k, self.id_offset, D.data_ptr(), I.data_ptr(), ws.data_ptr(),
                                                    ws.numel(), st)

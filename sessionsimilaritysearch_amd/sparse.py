@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .index import _EXHAUSTIVE_WS_BYTES, _dev
+from ._device import Workspace, exhaustive_chunk
+from .index import _dev
 from .sessions import ActionTable
 
 FLT_MAX = 3.4028234663852886e38
@@ -162,7 +163,7 @@ class SparseSessionIndex:
         self.device = _dev(device)
         self.id_offset = 0
         self._v = _device_triple(np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float32), self.device)
-        self._ws = None
+        self._ws = Workspace(self.device)
         self.last_chunks = 0                             # query chunks of the last search
 
     @property
@@ -200,11 +201,6 @@ class SparseSessionIndex:
         self._v = SessionVectors(ptr, items[:nnz_old + nnz], weights[:nnz_old + nnz])
         return self
 
-    def _workspace(self, nbytes: int) -> torch.Tensor:
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
-
     def search_device(self, q: SessionVectors, k: int, D: torch.Tensor | None = None, I: torch.Tensor | None = None):
         """``search`` for device vectors, into ``D`` / ``I`` when given; no host sync."""
         k = int(k)
@@ -225,10 +221,10 @@ class SparseSessionIndex:
             return D, I
         L, st, c = _lib.lib(), _lib.stream_ptr(self.device), self._v
         # items / weights of an all-empty batch: zero entries, but sliced from a one-entry allocation (never NULL)
-        per = max(1, min(65535, _EXHAUSTIVE_WS_BYTES // max(1, 4 * n)))
+        per = exhaustive_chunk(n, 4)
         for lo in range(0, nq, per):
             m = min(per, nq - lo)
-            ws = self._workspace(L.sss_sparse_topk_workspace_bytes(m, n))
+            ws = self._ws.get(L.sss_sparse_topk_workspace_bytes(m, n))
             rc = L.sss_sparse_topk(q.ptr.data_ptr() + 8 * lo, _ptr_of(q.items), _ptr_of(q.weights), m, c.ptr.data_ptr(),
                                    _ptr_of(c.items), _ptr_of(c.weights), n, k, self.id_offset, D.data_ptr() + 4 * lo * k,
                                    I.data_ptr() + 8 * lo * k, ws.data_ptr(), ws.numel(), st)
