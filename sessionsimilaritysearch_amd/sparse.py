@@ -40,8 +40,9 @@ class SessionVectors:
         """Raise ValueError unless this is a well-formed batch: ``ptr`` non-decreasing inside ``items``, ``items`` and
         ``weights`` of one length, item ids strictly ascending inside every row (the search merges ascending lists; an
         unsorted row would silently score wrong) and inside ``[0, n_items)``.  Device reductions and one host read; the
-        result is remembered, so a batch is checked once."""
-        if getattr(self, "_checked", None) == n_items:
+        result is remembered per ``n_items`` (``_checked`` holds ``(n_items,)``, so "never checked" differs from
+        "checked with None"), and a batch is checked once."""
+        if getattr(self, "_checked", ()) == (n_items,):
             return self
         ptr, items = self.ptr, self.items
         if ptr.dim() != 1 or ptr.numel() < 1 or items.dim() != 1 or self.weights.shape != items.shape:
@@ -61,7 +62,7 @@ class SessionVectors:
         if bad:
             raise ValueError("SessionVectors: ptr must be non-decreasing inside items, and the item ids of a row strictly "
                              f"ascending and inside [0, {n_items if n_items is not None else 2 ** 31 - 1})")
-        object.__setattr__(self, "_checked", n_items)
+        object.__setattr__(self, "_checked", (n_items,))
         return self
 
     def require_contiguous(self):
