@@ -1,4 +1,4 @@
-"""ctypes binding of libsss.so (the C ABI declared in include/sss.h and include/sss_sparse.h).
+"""ctypes binding of libsss.so (the C ABI declared in include/sss.h, include/sss_sparse.h and include/sss_l2.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails, this
 module raises.  ``build()`` compiles the library in-tree with hipcc for gfx950.
@@ -119,6 +119,17 @@ _SPARSE_SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
+# include/sss_l2.h one to one (L2 top-k on the matrix-core scans)
+_L2_SIGNATURES = {
+    "sss_l2_row_bias": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "sss_l2_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int, c_int]),
+    "sss_l2_topk": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_int, c_int, c_int64,
+                            c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "sss_l2_topk_threshold_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
+    "sss_l2_topk_threshold": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_int,
+                                      c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 
 class LinearProblem(ctypes.Structure):
     """``sss_linear_problem`` of include/sss.h."""
@@ -154,6 +165,11 @@ def sparse_symbols():
     return sorted(_SPARSE_SIGNATURES)
 
 
+def l2_symbols():
+    """The entry points of include/sss_l2.h."""
+    return sorted(_L2_SIGNATURES)
+
+
 def build(verbose: bool = False) -> str:
     """Compile libsss.so for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-C", CSRC, "-j4"]
@@ -175,7 +191,7 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C "
                 "sessionsimilaritysearch_amd/csrc`). There is no CPU fallback.")
         h = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in (*_SIGNATURES.items(), *_SPARSE_SIGNATURES.items()):
+        for name, (res, args) in (*_SIGNATURES.items(), *_SPARSE_SIGNATURES.items(), *_L2_SIGNATURES.items()):
             fn = getattr(h, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = h

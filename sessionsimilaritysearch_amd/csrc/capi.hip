@@ -1,4 +1,4 @@
-// extern "C" surface of libsss (declared in include/sss.h and include/sss_sparse.h) + error plumbing.
+// extern "C" surface of libsss (declared in include/sss.h, include/sss_sparse.h and include/sss_l2.h) + error plumbing.
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -8,6 +8,7 @@
 
 #include "../../include/sss.h"
 #include "../../include/sss_sparse.h"
+#include "../../include/sss_l2.h"
 #include "sss_common.h"
 #include "scan.h"
 #include "kargs.h"
@@ -400,6 +401,31 @@ int sss_sparse_topk(const int64_t* q_ptr, const int32_t* q_items, const float* q
     return sss::sparse_topk(reinterpret_cast<const long*>(q_ptr), q_items, q_weights, nq, reinterpret_cast<const long*>(c_ptr),
                             c_items, c_weights, n, k, id_offset, D_out, reinterpret_cast<long*>(I_out), workspace, workspace_bytes,
                             ST(stream));
+}
+
+// ---- include/sss_l2.h
+int sss_l2_row_bias(const float* corpus, int64_t n, int d, float* bias, void* stream) { return sss::l2_row_bias(corpus, n, d, bias, ST(stream)); }
+size_t sss_l2_topk_workspace_bytes(int64_t nq, int64_t n, int d, int k, int scan_dtype) {
+    return sss::l2_topk_workspace_bytes(nq, n, d, k, scan_dtype);
+}
+int sss_l2_topk(const float* q, int64_t nq, const float* corpus, const void* scan_image, int scan_dtype, int corpus_shift,
+                float corpus_resid_norm, const float* bias, int64_t n, int d, int k, int64_t id_offset, float corpus_max_norm,
+                float* D_out, int64_t* I_out, int32_t* status, int32_t* unproven_count, void* state, size_t state_bytes,
+                void* workspace, size_t workspace_bytes, void* stream) {
+    return sss::l2_topk(q, nq, corpus, scan_image, scan_dtype, corpus_shift, corpus_resid_norm, bias, n, d, k, id_offset, corpus_max_norm,
+                        D_out, reinterpret_cast<long*>(I_out), status, unproven_count, state, state_bytes, workspace, workspace_bytes,
+                        ST(stream));
+}
+size_t sss_l2_topk_threshold_workspace_bytes(int64_t nsel, int64_t n, int d, int scan_dtype) {
+    return sss::l2_topk_threshold_workspace_bytes(nsel, n, d, scan_dtype);
+}
+int sss_l2_topk_threshold(const float* q, const int32_t* qsel, int64_t nsel, const float* corpus, const void* scan_image,
+                          int scan_dtype, int corpus_shift, float corpus_resid_norm, const float* bias, int64_t n, int d, int k,
+                          int64_t id_offset, float corpus_max_norm, float* D_out, int64_t* I_out, int32_t* status, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    return sss::l2_topk_threshold(q, qsel, nsel, corpus, scan_image, scan_dtype, corpus_shift, corpus_resid_norm, bias, n, d, k,
+                                  id_offset, corpus_max_norm, D_out, reinterpret_cast<long*>(I_out), status, workspace,
+                                  workspace_bytes, ST(stream));
 }
 
 }  // extern "C"

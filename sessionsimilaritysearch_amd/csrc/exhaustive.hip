@@ -49,10 +49,7 @@ __global__ __launch_bounds__(64) void k_exact_scores(const void* __restrict__ Qv
             if (metric == 0) {
                 for (int kk = 0; kk < kc; ++kk) acc += (double)qs[kk] * (double)mine[kk];
             } else {
-                for (int kk = 0; kk < kc; ++kk) {
-                    const double dl = __dsub_rn((double)qs[kk], (double)mine[kk]);
-                    acc = __dadd_rn(acc, __dmul_rn(dl, dl));
-                }
+                for (int kk = 0; kk < kc; ++kk) acc = l2_chain_step(acc, (double)qs[kk], (double)mine[kk]);
             }
         }
         if (row0 + lane < n) scores[(size_t)f * n + row0 + lane] = (float)acc;

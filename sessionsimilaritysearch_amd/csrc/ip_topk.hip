@@ -104,7 +104,9 @@ static int ip_topk_impl(const char* what, const void* q, long nq, const void* c_
                         float corpus_resid, const void* c_exact,
                         int exact_dtype, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out,
                         int* status, int* unproven_count, void* state, size_t state_bytes, void* ws, size_t ws_bytes,
-                        hipStream_t st) {
+                        hipStream_t st, const float* bias = nullptr) {
+    // bias: the L2 search (l2_topk below) -- the scan's keys are q.c + bias[row], the select's scores negated distances
+    const bool l2 = bias != nullptr;
     if (nq <= 0 || n <= 0 || k <= 0) { set_error("%s: nq, n, k must be positive", what); return SSS_EINVAL; }
     int rc = check_scan_source(what, exact_dtype, scan_dtype, d, false, c_scan, corpus_shift, corpus_resid, n, nq);
     if (rc) return rc;
@@ -128,6 +130,7 @@ static int ip_topk_impl(const char* what, const void* q, long nq, const void* c_
     a.cnt = sw + state_off_cnt(nq);
     a.maxlast = reinterpret_cast<unsigned long long*>(sw + state_off_maxlast(nq));
     a.cand = reinterpret_cast<unsigned long long*>(w);
+    a.bias = bias; a.corpus_shift = corpus_shift;
     Prof& pr = g_prof[current_device()];
     const bool prof = pr.on && pr.n < PROF_RING;
     if (prof) (void)hipEventRecord(pr.ev[2 * pr.n], st);
@@ -141,6 +144,7 @@ static int ip_topk_impl(const char* what, const void* q, long nq, const void* c_
     s.cand = a.cand; s.slots = a.slots; s.cnt = a.cnt; s.maxlast = a.maxlast;
     s.id_offset = id_offset; s.corpus_max_norm = corpus_max_norm;
     s.D_out = D_out; s.I_out = I_out; s.status = status; s.unproven_count = unproven_count;
+    s.metric = l2 ? 1 : 0;
     rc = launch_select(s, st);
     if (rc) (void)hipMemsetAsync(state, 0, ip_topk_state_bytes(nq), st);   // the scan dirtied it and nobody will clear it
     return rc;
@@ -150,7 +154,8 @@ static int ip_topk_impl(const char* what, const void* q, long nq, const void* c_
 // zeroes the counters t.cnt of the t.nsel queries t.qsel, the scan keeps every row above its query's threshold in
 // t.cand, `select` re-scores them.
 template <class Prepare, class Select>
-static int run_threshold_form(const ThrArgs& t, const void* c_scan, const ScanPlan& p, Prepare prepare, Select select, hipStream_t st) {
+static int run_threshold_form(const ThrArgs& t, const void* c_scan, const ScanPlan& p, Prepare prepare, Select select, hipStream_t st,
+                              const float* bias = nullptr) {
     int rc = prepare();
     if (rc) return rc;
     ScanArgs a = {};
@@ -160,6 +165,7 @@ static int run_threshold_form(const ThrArgs& t, const void* c_scan, const ScanPl
     a.slots = nullptr; a.cnt = t.cnt; a.maxlast = nullptr;
     a.cand = const_cast<unsigned long long*>(t.cand);
     a.qsel = t.qsel; a.thr = t.thr;
+    a.bias = bias; a.corpus_shift = t.corpus_shift;
     rc = launch_scan(t.scan_dtype, t.d, p.tile_rows, a, st);
     if (rc) return rc;
     return select();
@@ -175,16 +181,17 @@ size_t ip_topk_threshold_workspace_bytes(long nsel, long n, int d, int scan_dtyp
     return thr_head_bytes(nsel) + make_thr_plan(nsel, n, d, scan_dtype, THR_CAP).total_bytes;
 }
 
-int ip_topk_threshold(const void* q, const int* qsel, long nsel, const void* c_exact, int exact_dtype, const void* c_scan,
-                      int scan_dtype, int corpus_shift, float corpus_resid, long n, int d, int k, long id_offset,
-                      float corpus_max_norm, float* D_out, long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (nsel <= 0 || n <= 0 || k <= 0 || !qsel) { set_error("ip_topk_threshold: nsel, n, k must be positive"); return SSS_EINVAL; }
-    const int rc = check_scan_source("ip_topk_threshold", exact_dtype, scan_dtype, d, false, c_scan, corpus_shift, corpus_resid, n, nsel);
+static int topk_threshold_impl(const char* what, const void* q, const int* qsel, long nsel, const void* c_exact, int exact_dtype,
+                               const void* c_scan, int scan_dtype, int corpus_shift, float corpus_resid, long n, int d, int k,
+                               long id_offset, float corpus_max_norm, float* D_out, long* I_out, int* status, void* ws, size_t ws_bytes,
+                               hipStream_t st, const float* bias = nullptr) {
+    if (nsel <= 0 || n <= 0 || k <= 0 || !qsel) { set_error("%s: nsel, n, k must be positive", what); return SSS_EINVAL; }
+    const int rc = check_scan_source(what, exact_dtype, scan_dtype, d, false, c_scan, corpus_shift, corpus_resid, n, nsel);
     if (rc) return rc;
-    if (k > THR_CAP) { set_error("ip_topk_threshold: k too large (max %d)", THR_CAP); return SSS_EINVAL; }
-    if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("ip_topk_threshold: workspace must be 256-byte aligned"); return SSS_EINVAL; }
+    if (k > THR_CAP) { set_error("%s: k too large (max %d)", what, THR_CAP); return SSS_EINVAL; }
+    if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("%s: workspace must be 256-byte aligned", what); return SSS_EINVAL; }
     const ScanPlan p = make_thr_plan(nsel, n, d, scan_dtype, THR_CAP);
-    if (ws_bytes < thr_head_bytes(nsel) + p.total_bytes) { set_error("ip_topk_threshold: workspace %zu < %zu", ws_bytes, thr_head_bytes(nsel) + p.total_bytes); return SSS_EWORKSPACE; }
+    if (ws_bytes < thr_head_bytes(nsel) + p.total_bytes) { set_error("%s: workspace %zu < %zu", what, ws_bytes, thr_head_bytes(nsel) + p.total_bytes); return SSS_EWORKSPACE; }
     char* w = reinterpret_cast<char*>(ws);
     ThrArgs t = thr_args(q, c_exact, exact_dtype, scan_dtype, corpus_shift, corpus_resid, corpus_max_norm, qsel, nsel, n, d, k, p.cap,
                          id_offset);
@@ -192,7 +199,15 @@ int ip_topk_threshold(const void* q, const int* qsel, long nsel, const void* c_e
     t.cnt = reinterpret_cast<unsigned*>(w + (size_t)nsel * 4);
     t.cand = reinterpret_cast<unsigned long long*>(w + thr_head_bytes(nsel));
     t.D_out = D_out; t.I_out = I_out; t.status = status;
-    return run_threshold_form(t, c_scan, p, [&] { return launch_thr_prepare(t, st); }, [&] { return launch_select_all(t, st); }, st);
+    t.metric = bias != nullptr ? 1 : 0;
+    return run_threshold_form(t, c_scan, p, [&] { return launch_thr_prepare(t, st); }, [&] { return launch_select_all(t, st); }, st, bias);
+}
+
+int ip_topk_threshold(const void* q, const int* qsel, long nsel, const void* c_exact, int exact_dtype, const void* c_scan,
+                      int scan_dtype, int corpus_shift, float corpus_resid, long n, int d, int k, long id_offset,
+                      float corpus_max_norm, float* D_out, long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st) {
+    return topk_threshold_impl("ip_topk_threshold", q, qsel, nsel, c_exact, exact_dtype, c_scan, scan_dtype, corpus_shift, corpus_resid, n, d,
+                               k, id_offset, corpus_max_norm, D_out, I_out, status, ws, ws_bytes, st);
 }
 
 // RANGE SEARCH, fused route (select_thr.hip: RANGE SEARCH): the threshold rung's scan with thresholds from per-query radii.
@@ -259,6 +274,53 @@ int ip_topk_f16(const float* q, long nq, const float* c, const void* c_f16, int 
                 void* state, size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st) {
     return ip_topk_impl("ip_topk_f16", q, nq, c_f16, DT_F16, corpus_shift, corpus_resid, c, DT_F32, n, d, k, id_offset, corpus_max_norm,
                         D_out, I_out, status, unproven_count, state, state_bytes, ws, ws_bytes, st);
+}
+
+// ------------------------------------------------------------------------------------------
+// L2 top-k on the same scans (include/sss_l2.h): float32 rows, the scan's keys biased by bias[row] = -|c_row|^2 / 2
+// (rowops.hip: l2_row_bias), scores the negated canonical squared distances (select_dev.h: err_bound_l2, DT_F32_L2).
+static int check_l2(const char* what, int scan_dtype, const float* q, const float* c, const float* bias, const float* D_out,
+                    const long* I_out, const int* status) {
+    if (scan_dtype != DT_F32 && scan_dtype != DT_SPLIT && scan_dtype != DT_F16) {
+        set_error("%s: scan_dtype %d is not a scan of float32 rows (0 the rows, 2 the split image, 3 the f16 image)", what, scan_dtype);
+        return SSS_EINVAL;
+    }
+    if (!bias || (reinterpret_cast<uintptr_t>(bias) & 15)) { set_error("%s: row bias missing or not 16-byte aligned", what); return SSS_EINVAL; }
+    if (!q || !c || !D_out || !I_out || !status) { set_error("%s: q, corpus, D_out, I_out and status are required", what); return SSS_EINVAL; }
+    return SSS_OK;
+}
+
+size_t l2_topk_workspace_bytes(long nq, long n, int d, int k, int scan_dtype) {
+    if (scan_dtype != DT_F32 && scan_dtype != DT_SPLIT && scan_dtype != DT_F16) return 0;
+    return ip_topk_scan_workspace_bytes(nq, n, d, k, scan_dtype);
+}
+
+int l2_topk(const float* q, long nq, const float* c, const void* c_scan, int scan_dtype, int corpus_shift, float corpus_resid,
+            const float* bias, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out, int* status,
+            int* unproven_count, void* state, size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (nq <= 0 || n <= 0 || k <= 0) { set_error("l2_topk: nq, n, k must be positive"); return SSS_EINVAL; }
+    int rc = check_scan_source("l2_topk", DT_F32, scan_dtype, d, false, c_scan, corpus_shift, corpus_resid, n, nq);
+    if (!rc) rc = check_l2("l2_topk", scan_dtype, q, c, bias, D_out, I_out, status);
+    if (rc) return rc;
+    return ip_topk_impl("l2_topk", q, nq, c_scan, scan_dtype, corpus_shift, corpus_resid, c, DT_F32, n, d, k, id_offset, corpus_max_norm,
+                        D_out, I_out, status, unproven_count, state, state_bytes, ws, ws_bytes, st, bias);
+}
+
+size_t l2_topk_threshold_workspace_bytes(long nsel, long n, int d, int scan_dtype) {
+    if (scan_dtype != DT_F32 && scan_dtype != DT_SPLIT && scan_dtype != DT_F16) return 0;
+    return ip_topk_threshold_workspace_bytes(nsel, n, d, scan_dtype);
+}
+
+int l2_topk_threshold(const float* q, const int* qsel, long nsel, const float* c, const void* c_scan, int scan_dtype, int corpus_shift,
+                      float corpus_resid, const float* bias, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out,
+                      long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (nsel <= 0 || n <= 0 || k <= 0 || !qsel) { set_error("l2_topk_threshold: nsel, n, k must be positive"); return SSS_EINVAL; }
+    int rc = check_scan_source("l2_topk_threshold", DT_F32, scan_dtype, d, false, c_scan, corpus_shift, corpus_resid, n, nsel);
+    if (!rc) rc = check_l2("l2_topk_threshold", scan_dtype, q, c, bias, D_out, I_out, status);
+    if (rc) return rc;
+    if (!ws) { set_error("l2_topk_threshold: workspace 0 < %zu", l2_topk_threshold_workspace_bytes(nsel, n, d, scan_dtype)); return SSS_EWORKSPACE; }
+    return topk_threshold_impl("l2_topk_threshold", q, qsel, nsel, c, DT_F32, c_scan, scan_dtype, corpus_shift, corpus_resid, n, d, k,
+                               id_offset, corpus_max_norm, D_out, I_out, status, ws, ws_bytes, st, bias);
 }
 
 }  // namespace sss

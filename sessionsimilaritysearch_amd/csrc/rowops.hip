@@ -175,6 +175,22 @@ __global__ __launch_bounds__(256) void k_f16_resid_max(const float* __restrict__
     if (lane == 0 && m > 0.f) atomicMax(reinterpret_cast<unsigned*>(out), __float_as_uint(m));
 }
 
+// bias[i] = -|c_i|^2 / 2 of float32 rows: what every score of row i starts from in the L2 scans (scan_kernel.h: k_scan<..., MET = 1>;
+// |q - c|^2 = |q|^2 - 2 (q.c - |c|^2 / 2)).  The squares of float32 values are exact in float64; their sum (four lanes a
+// row, then the four partial sums) is rounded ONCE to float32 -- the 2^-25 |c|^2 of select_dev.h: err_bound_l2, which also
+// covers the float64 additions in whatever order.  One array per index, unscaled, for all three scans.
+__global__ __launch_bounds__(256) void k_row_bias(const float* __restrict__ c, long n, int d, float* __restrict__ bias) {
+    const int sub = threadIdx.x & 3;
+    const int nv = d / 4;
+    for (long row = (long)blockIdx.x * 64 + (threadIdx.x >> 2); row < n; row += (long)gridDim.x * 64) {
+        const u32x4* p = reinterpret_cast<const u32x4*>(c + row * (long)d);
+        double ss = 0.0;
+        for (int i = sub; i < nv; i += 4) ss = Elem<DT_F32>::chunk_sumsq(ss, p[i]);
+        ss = group_sum<4>(ss);
+        if (sub == 0) bias[row] = (float)(-0.5 * ss);
+    }
+}
+
 template <int LPR>
 __global__ __launch_bounds__(256) void k_gather_rows(const float* __restrict__ table,
                                                      const long* __restrict__ ids, long n, int d,
@@ -315,6 +331,13 @@ int f16_resid_max(const float* x, const unsigned short* y, long n, int d, int sh
     hipLaunchKernelGGL(k_f16_resid_max, dim3((unsigned)blocks), dim3(256), 0, st, x, reinterpret_cast<const _Float16*>(y), n,
                        d, shift, out);
     return check_launch("k_f16_resid_max");
+}
+
+int l2_row_bias(const float* c, long n, int d, float* bias, hipStream_t st) {
+    if (n < 0 || d <= 0 || d % 4 || (n > 0 && (!c || !bias))) { set_error("l2_row_bias: need n >= 0, d %% 4 == 0, rows and bias"); return SSS_EINVAL; }
+    if (n == 0) return SSS_OK;
+    hipLaunchKernelGGL(k_row_bias, dim3(grid_for(n, 4)), dim3(256), 0, st, c, n, d, bias);
+    return check_launch("k_row_bias");
 }
 
 int gather_rows(const float* table, const long* ids, long n, int d, float* out, long ld_out, hipStream_t st) {

@@ -34,6 +34,13 @@ static inline bool long_shape_ok(int d, int exact_dtype, int scan_dtype) {
     return d > 0 && d % 64 == 0 && d * elem_bytes(exact_dtype) <= 16384 && scan_pair_ok(exact_dtype, scan_dtype, true);
 }
 
+// One step of the canonical L2 chain (oracle/search_ref.canonical_l2; exhaustive.hip at metric 1 and the L2 re-score of
+// select_dev.h): acc + (q - c)^2 in float64, one rounding per subtraction, multiplication and addition -- never fused.
+__device__ __forceinline__ double l2_chain_step(double acc, double q, double c) {
+    const double dl = __dsub_rn(q, c);
+    return __dadd_rn(acc, __dmul_rn(dl, dl));
+}
+
 // STATE words (caller-owned, zero before the first call; every call leaves them zero: the select
 // kernel, their last reader, clears what the call used -- no per-call memset launch).  Because the
 // whole buffer is zero between calls, each call may lay it out as it likes:
@@ -66,10 +73,16 @@ struct ScanArgs {
     // threshold form only (k_scan<..., THR = true>): the compact query list and its per-query thresholds
     const int* qsel = nullptr;
     const float* thr = nullptr;
+    // L2 scans only (k_scan<..., MET = 1>; appended, so the inner-product kernels read what they always read): the per-row
+    // bias -|c|^2 / 2 every score starts from, and the DT_F16 image's corpus shift (a lane scales the bias by
+    // 2^(corpus_shift + its query's shift))
+    const float* bias = nullptr;
+    int corpus_shift = 0;
 };
 
 ScanPlan make_thr_plan(long nsel, long n, int d, int scan_dtype, int cap);
 int launch_scan(int dtype, int d, int tile_rows, const ScanArgs& a, hipStream_t st);
+int launch_scan_l2(int dtype, int d, int tile_rows, const ScanArgs& a, hipStream_t st);     // (scan_l2.hip; launch_scan calls it when a.bias is set)
 int scan_boot_expired(int reset);
 
 struct SelectArgs {
@@ -90,6 +103,7 @@ struct SelectArgs {
     long* I_out;
     int* status;
     int* unproven_count;        // optional device counter: += 1 per query left unproven
+    int metric = 0;             // 1: L2 -- scan keys are q.c - |c|^2 / 2, scores are NEGATED squared distances (select_dev.h: query_bound)
 };
 
 int launch_select(const SelectArgs& a, hipStream_t st);
@@ -114,6 +128,7 @@ struct ThrArgs {
     int qb_ready = 0;               //   that computes them (qb_ready == 0), read by the later ones (sss_ip_topk_long: five kernels a search)
     int keep = 0;                   // k_thr_prepare: 1 = keep the rows already kept that pass the NEW threshold (compacted in place)
                                     //                instead of starting from an empty array (sss_ip_topk_long: disjoint levels)
+    int metric = 0;                 // 1: L2 (as SelectArgs::metric; D_out holds distances: its column k-1 is an UPPER bound, negated on the way in)
 };
 int launch_thr_prepare(const ThrArgs& a, hipStream_t st);
 int launch_select_all(const ThrArgs& a, hipStream_t st);
@@ -181,6 +196,16 @@ int range_exhaustive_count(const void* q, const int* qsel, long nsel, const void
                            const float* radius, long* counts, void* ws, size_t ws_bytes, hipStream_t st);
 int range_exhaustive_fill(const int* qsel, long nsel, long n, int metric, const float* radius, const long* lims, long id_offset,
                           float* D_out, long* I_out, const void* ws, size_t ws_bytes, hipStream_t st);
+// L2 top-k on the fused scans (ip_topk.hip; include/sss_l2.h): float32 rows, scan keys q.c + bias[row]
+int l2_row_bias(const float* c, long n, int d, float* bias, hipStream_t st);
+size_t l2_topk_workspace_bytes(long nq, long n, int d, int k, int scan_dtype);
+int l2_topk(const float* q, long nq, const float* c, const void* c_scan, int scan_dtype, int corpus_shift, float corpus_resid,
+            const float* bias, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out, int* status,
+            int* unproven_count, void* state, size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st);
+size_t l2_topk_threshold_workspace_bytes(long nsel, long n, int d, int scan_dtype);
+int l2_topk_threshold(const float* q, const int* qsel, long nsel, const float* c, const void* c_scan, int scan_dtype, int corpus_shift,
+                      float corpus_resid, const float* bias, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out,
+                      long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st);
 int profile_enable(int on);
 int profile_read(double* total_ms, int* launches);
 

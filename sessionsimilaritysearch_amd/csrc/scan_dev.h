@@ -93,10 +93,10 @@ __device__ __forceinline__ void load8_sc1(const unsigned* p, unsigned (&v)[8]) {
 
 // Resident queries of one 32-query MFMA B operand: lane (r, h) ends up with the 16-byte chunks of query row
 // q_ld it meets in the k-groups (qc[u]: k = 16u + 8h .. + 7 for the 16-bit types, k = 32u + 16h .. + 15 for int8, chunk
-// 2u + h for f32).  DT_SPLIT / DT_F16 take float32 queries and split / scale + round them here (scan.h); the others
+// 2u + h for f32; q_shift: where a DT_F16 scan leaves the query's shift).  DT_SPLIT / DT_F16 take float32 queries and split / scale + round them here (scan.h); the others
 // (DT_H16: float16 queries against float16 rows, DT_I8: int8 against int8) load the row as it is stored.
 template <int RB, int DT>
-__device__ __forceinline__ void load_queries(const char* __restrict__ Qb, int q_ld, int h, f32x4 (&qc)[RB / 32]) {
+__device__ __forceinline__ void load_queries(const char* __restrict__ Qb, int q_ld, int h, f32x4 (&qc)[RB / 32], int* q_shift = nullptr) {
     constexpr int NU = RB / 32;
     if constexpr (DT == DT_SPLIT) {
         // f32 queries, split here: qc[u] = hi and qc[u + NU/2] = lo of k-slice u (k = 16u + 8h .. + 7),
@@ -131,6 +131,7 @@ __device__ __forceinline__ void load_queries(const char* __restrict__ Qb, int q_
             amax = fmaxf(fmaxf(amax, fmaxf(fabsf(raw[u].x), fabsf(raw[u].y))), fmaxf(fabsf(raw[u].z), fabsf(raw[u].w)));
         amax = fmaxf(amax, __shfl_xor(amax, 32));            // the other half of the row
         const int sh = f16_shift(amax);
+        if (q_shift) *q_shift = sh;                          // (the L2 scan scales its row bias by it)
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
             const f32x4 a = raw[2 * u], b = raw[2 * u + 1];

@@ -62,7 +62,7 @@ __device__ __forceinline__ unsigned final_tau_ord(const unsigned* slots, int J, 
 template <int NT>
 __device__ __forceinline__ void rank_and_write(const unsigned long long* sel, const double* resc, int K2, int k,
                                                long id_offset, float* Dq, long* Iq, int t, int* s_nvalid,
-                                               double* s_kth) {
+                                               double* s_kth, int metric) {
     for (int c = t; c < K2; c += NT) {
         const unsigned long long key = sel[c];
         const int id = key_id(key);
@@ -76,7 +76,7 @@ __device__ __forceinline__ void rank_and_write(const unsigned long long* sel, co
             if (sj > sc || (sj == sc && idj < id)) ++rank;
         }
         atomicAdd(s_nvalid, 1);
-        if (rank < k) { Dq[rank] = sc; Iq[rank] = (long)id + id_offset; }
+        if (rank < k) { Dq[rank] = out_score(sc, metric); Iq[rank] = (long)id + id_offset; }
         if (rank == k - 1) *s_kth = resc[c];
     }
 }
@@ -85,7 +85,7 @@ __device__ __forceinline__ void rank_and_write(const unsigned long long* sel, co
 // neither enter the top k nor tie with the k-th result AFTER the rounding to float32 if that stays
 // below kth by more than one float32 ulp of kth (select_dev.h: window_top).
 __device__ __forceinline__ int decide_status(unsigned long long edge, unsigned long long maxlast, unsigned tau_o,
-                                             int J, int nvalid, int k, double kth, double B, double unscale) {
+                                             int J, int nvalid, int k, double kth, double B, double unscale, double off) {
     int st = 0;
     const bool edge_real = edge != 0 && key_id(edge) >= 0;
     if (maxlast > edge) st |= 1;                                  // a full list may hide a contender
@@ -93,7 +93,7 @@ __device__ __forceinline__ int decide_status(unsigned long long edge, unsigned l
         if (!(edge_real && f2ord(key_score(edge)) >= tau_o)) st |= 2;
     }
     if (edge_real && nvalid >= k) {
-        if (!(window_top(key_score(edge), unscale, B, kth) < kth)) st |= 4;                              // the error window reaches the k-th result
+        if (!(window_top(key_score(edge), unscale, off, B, kth) < kth)) st |= 4;                              // the error window reaches the k-th result
     }
     return st;
 }
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void k_select_fast(const SelectArgs A) {
     long* Iq = A.I_out + (size_t)q * k;
     const int M = (int)min(A.cnt[q], (unsigned)A.cap);            // (the append form of k_scan counts what it could not store, too)
     if (M > FS_CAP) {                                             // adversarial input: let the exhaustive path decide
-        pad_results(Dq, Iq, 0, k, lane, 64);                      // (no k-th score known)
+        pad_results(Dq, Iq, 0, k, lane, 64, A.metric);            // (no k-th score known)
         if (lane == 0) { A.status[q] = 1; if (A.unproven_count) atomicAdd(A.unproven_count, 1); }
         clear_state(A, q, lane, 64);
         return;
@@ -186,19 +186,20 @@ __global__ __launch_bounds__(256) void k_select_fast(const SelectArgs A) {
     wave_sync();
     // ---- float64 re-score: one lane per candidate walks its corpus row (16-byte loads straight from
     // L2 / HBM, several in flight) sequentially in k -- the canonical order
-    for (int c0 = 0; c0 < K2; c0 += 16) rescore16(sel, resc, c0, K2, A.C, rb, qrow, A.dtype, lane);
-    double B, unscale;
-    query_bound(A, qrow, lane, B, unscale);
+    const int rtype = rescore_type(A.dtype, A.metric);
+    for (int c0 = 0; c0 < K2; c0 += 16) rescore16(sel, resc, c0, K2, A.C, rb, qrow, rtype, lane);
+    double B, unscale, off;
+    query_bound(A, qrow, lane, B, unscale, off);
     wave_sync();
-    rank_and_write<64>(sel, resc, K2, k, A.id_offset, Dq, Iq, lane, s_nvalid, s_kth);
+    rank_and_write<64>(sel, resc, K2, k, A.id_offset, Dq, Iq, lane, s_nvalid, s_kth, A.metric);
     wave_sync();
     const int nvalid = *s_nvalid;
-    pad_results(Dq, Iq, nvalid, k, lane, 64);
+    pad_results(Dq, Iq, nvalid, k, lane, 64, A.metric);
     const unsigned tau_o = A.J > 0 ? final_tau_ord(A.slots + (size_t)q * SLOT_STRIDE, A.J, lane, A.tau_skip) : 0u;
     const unsigned long long maxlast = A.maxlast[q];
     wave_sync();                                                  // every lane has read the state words
     clear_state(A, q, lane, 64);
-    int st = decide_status(sel[K2 - 1], maxlast, tau_o, A.J, nvalid, k, *s_kth, B, unscale);
+    int st = decide_status(sel[K2 - 1], maxlast, tau_o, A.J, nvalid, k, *s_kth, B, unscale, off);
     // ---- second chance for a query whose ONLY problem is the near-tie window (status 4): the pool
     // usually holds more candidates than the K2 the threshold certifies, and it is complete down to
     // max(threshold, largest tail of a full list).  Take candidates from that region -- until the next one
@@ -213,7 +214,7 @@ __global__ __launch_bounds__(256) void k_select_fast(const SelectArgs A) {
         const double kth0 = *s_kth;                               // lower bound of the final k-th result
         for (; K2x < FS_K2; ++K2x) {
             const unsigned long long w = wave_max_u64(best);
-            if (w != 0 && key_id(w) >= 0 && window_top(key_score(w), unscale, B, kth0) < kth0) {
+            if (w != 0 && key_id(w) >= 0 && window_top(key_score(w), unscale, off, B, kth0) < kth0) {
                 edge_score = key_score(w);                        // far enough below: nothing from here on can matter
                 break;
             }
@@ -228,10 +229,10 @@ __global__ __launch_bounds__(256) void k_select_fast(const SelectArgs A) {
         if (K2x == FS_K2) open_end = true;
         wave_sync();
         if (K2x > K2) {
-            for (int c0 = K2; c0 < K2x; c0 += 16) rescore16(sel, resc, c0, K2x, A.C, rb, qrow, A.dtype, lane);
+            for (int c0 = K2; c0 < K2x; c0 += 16) rescore16(sel, resc, c0, K2x, A.C, rb, qrow, rtype, lane);
             if (lane == 0) { *s_nvalid = 0; *s_kth = 0.0; }
             wave_sync();
-            rank_and_write<64>(sel, resc, K2x, k, A.id_offset, Dq, Iq, lane, s_nvalid, s_kth);
+            rank_and_write<64>(sel, resc, K2x, k, A.id_offset, Dq, Iq, lane, s_nvalid, s_kth, A.metric);
             wave_sync();
         }
         // (K2x == K2: the very next candidate already lies far below -- phase 1 only failed because it
@@ -243,8 +244,9 @@ __global__ __launch_bounds__(256) void k_select_fast(const SelectArgs A) {
             if (maxlast != 0 && key_id(maxlast) >= 0) edge_score = fmaxf(edge_score, key_score(maxlast));
         }
         const double kth = *s_kth;
-        st = (*s_nvalid >= k && window_top(edge_score, unscale, B, kth) < kth) ? 0 : 4;
+        st = (*s_nvalid >= k && window_top(edge_score, unscale, off, B, kth) < kth) ? 0 : 4;
     }
+    if (A.metric && !(B < INFINITY)) st |= 4;                     // no finite L2 bound (select_dev.h: err_bound_l2): nothing is proven
     if (lane == 0) {
         A.status[q] = st;
         if (st && A.unproven_count) atomicAdd(A.unproven_count, 1);
@@ -304,23 +306,24 @@ __global__ __launch_bounds__(SORT_THREADS) void k_select_sort(const SelectArgs A
         const unsigned long long key = keys[c];
         const int id = key_id(key);
         double acc = 0.0;
-        if (key != 0 && id >= 0) acc = rescore_row(qrow, reinterpret_cast<const char*>(A.C) + (size_t)id * rb, rb / 16, A.dtype);
+        if (key != 0 && id >= 0) acc = rescore_row(qrow, reinterpret_cast<const char*>(A.C) + (size_t)id * rb, rb / 16, rescore_type(A.dtype, A.metric));
         resc[c] = acc;
     }
     __syncthreads();
-    rank_and_write<SORT_THREADS>(keys, resc, K2, k, A.id_offset, Dq, Iq, tid, &s_nvalid, &s_kth);
+    rank_and_write<SORT_THREADS>(keys, resc, K2, k, A.id_offset, Dq, Iq, tid, &s_nvalid, &s_kth, A.metric);
     __syncthreads();
     const int nvalid = s_nvalid;
-    pad_results(Dq, Iq, nvalid, k, tid, SORT_THREADS);
+    pad_results(Dq, Iq, nvalid, k, tid, SORT_THREADS, A.metric);
     if (tid < 64) {                                               // wave 0 alone touches the state from here on
         const unsigned tau_o = A.J > 0 ? final_tau_ord(A.slots + (size_t)q * SLOT_STRIDE, A.J, lane, A.tau_skip) : 0u;
         const unsigned long long maxlast = A.maxlast[q];
         wave_sync();
         clear_state(A, q, lane, 64);
-        double B, unscale;
-        query_bound(A, qrow, lane, B, unscale);
+        double B, unscale, off;
+        query_bound(A, qrow, lane, B, unscale, off);
         if (tid == 0) {
-            const int st = decide_status(keys[K2 - 1], maxlast, tau_o, A.J, nvalid, k, s_kth, B, unscale);
+            int st = decide_status(keys[K2 - 1], maxlast, tau_o, A.J, nvalid, k, s_kth, B, unscale, off);
+            if (A.metric && !(B < INFINITY)) st |= 4;             // (as k_select_fast)
             A.status[q] = st;
             if (st && A.unproven_count) atomicAdd(A.unproven_count, 1);
         }

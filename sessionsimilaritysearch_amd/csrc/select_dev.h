@@ -8,6 +8,13 @@ namespace sss {
 
 constexpr int SORT_THREADS = 256;
 constexpr int SA_BYTES = 128;      // rescore_kept: bytes of every row staged through LDS per step
+// Re-score "element type" of the L2 metric: float32 rows and queries, the canonical chain of squared differences
+// (scan.h: l2_chain_step), the score its NEGATION -- float negation is exact and commutes with the rounding to float32,
+// so "(score desc, id asc)", the u64 keys and the padding serve "(distance asc, id asc)" as they are; D is negated on
+// the way out (out_score).  Never a storage format: rescore_type() makes it from (dtype, metric).
+constexpr int DT_F32_L2 = 100;
+__device__ __forceinline__ int rescore_type(int dtype, int metric) { return metric ? DT_F32_L2 : dtype; }
+__device__ __forceinline__ float out_score(float s, int metric) { return metric ? -s : s; }
 
 // Wave-wide maximum of a u32 on the DPP network (no LDS round trips): row_shr 1/2/4/8 leave each
 // 16-lane row's maximum in its last lane, row_bcast15 / row_bcast31 carry it across rows, lane 63
@@ -76,11 +83,12 @@ __device__ __forceinline__ void rescore16_t(const unsigned long long* sel, doubl
             if (p == s + 1) acc = up;
         }
     }
-    if (c < c1 && p == 3) resc[c] = live ? acc : 0.0;
+    if (c < c1 && p == 3) resc[c] = live ? (DT == DT_F32_L2 ? -acc : acc) : 0.0;
 }
 __device__ __forceinline__ void rescore16(const unsigned long long* sel, double* resc, int c0, int c1, const void* C, int rb,
                                           const char* qrow, int dtype, int lane) {
     if (dtype == DT_F32) rescore16_t<DT_F32>(sel, resc, c0, c1, C, rb, qrow, lane);
+    else if (dtype == DT_F32_L2) rescore16_t<DT_F32_L2>(sel, resc, c0, c1, C, rb, qrow, lane);
     else if (dtype == DT_H16) rescore16_t<DT_H16>(sel, resc, c0, c1, C, rb, qrow, lane);
     else if (dtype == DT_I8) rescore16_t<DT_I8>(sel, resc, c0, c1, C, rb, qrow, lane);
     else rescore16_t<DT_BF16>(sel, resc, c0, c1, C, rb, qrow, lane);
@@ -106,6 +114,14 @@ __device__ __forceinline__ double dot_chunk(double acc, const char* qrow, int v,
         acc += (double)qv.y * (double)c.y;
         acc += (double)qv.z * (double)c.z;
         acc += (double)qv.w * (double)c.w;
+        return acc;
+    }
+    if (dtype == DT_F32_L2) {
+        const f32x4 qv = *reinterpret_cast<const f32x4*>(qrow + v * 16);
+        acc = l2_chain_step(acc, (double)qv.x, (double)c.x);
+        acc = l2_chain_step(acc, (double)qv.y, (double)c.y);
+        acc = l2_chain_step(acc, (double)qv.z, (double)c.z);
+        acc = l2_chain_step(acc, (double)qv.w, (double)c.w);
         return acc;
     }
     const u32x4 cu = __builtin_bit_cast(u32x4, c);
@@ -155,11 +171,11 @@ __device__ __forceinline__ double rescore_row(const char* qrow, const char* row,
         for (int i = 0; i < 16; ++i)
             if (v0 + i < nchunks) acc = dot_chunk(acc, qrow, v0 + i, c[i], dtype);
     }
-    return acc;
+    return dtype == DT_F32_L2 ? -acc : acc;
 }
 
 __device__ __forceinline__ float elem_to_f32(const void* row, int kk, int dtype) {
-    if (dtype == DT_F32) return reinterpret_cast<const float*>(row)[kk];
+    if (dtype == DT_F32 || dtype == DT_F32_L2) return reinterpret_cast<const float*>(row)[kk];
     if (dtype == DT_I8) return (float)reinterpret_cast<const signed char*>(row)[kk];
     const unsigned short b = reinterpret_cast<const unsigned short*>(row)[kk];
     if (dtype == DT_H16) return (float)__builtin_bit_cast(_Float16, b);   // f16 -> f32 is exact
@@ -227,18 +243,55 @@ __device__ __forceinline__ double err_bound(int d, int scan_dtype, double qnorm,
     return b * 1.02;
 }
 
-// THE PROOF WINDOW.  A row whose scan score is `scan_score` has an exact score of at most scan_score * unscale + B
-// (unscale: what a scan score must be multiplied by to be a score, 1 except for DT_F16; B: err_bound).  window_top is the
+// THE L2 BOUND.  The score of the L2 metric is s = -dist, dist the canonical chain of squared differences; in real
+// arithmetic s = 2 (q.c - |c|^2 / 2) - |q|^2, and the L2 scan's key of a row is kappa~ ~ sigma (q.c + b^), b^ the stored
+// float32 bias and sigma = 2^(corpus shift + query shift) for the DT_F16 scan, else 1.  The score bound of a key is
+//     kappa~ * (2 / sigma) - qn2  (qn2: |q|^2 summed in float64),   and  |bound - s| <= B_l2 =
+//   2 x [ the inner-product bound of the scan that ran, for a chain of d + 1 terms (err_bound(d + 1, ...): its terms grow with d)
+//       + A(d + 1) * cmax^2 / 2     the accumulators start from the bias, so every partial sum of the chain is bounded by
+//                                   |q| cmax + cmax^2 / 2 instead of |q| cmax; A is the scan's accumulation coefficient
+//                                   per unit of that magnitude: d 2^-24 (DT_F32), 3 d 2^-23 (DT_SPLIT: the bias rides through
+//                                   all three passes), d 2^-23 (DT_F16).  (The input roundings -- split residue, f16 residuals --
+//                                   concern q.c alone: the bias is float32 in every scan, and its product with sigma is exact.)
+//       + 2^-126 / sigma ]          DT_F16: a scaled bias below FLT_MIN may lose up to that much
+//   + 2^-24 cmax^2                  the stored bias: -|c|^2 / 2 from a float64 sum of exact squares, rounded ONCE to float32
+//                                   (2^-25 |c|^2, doubled by the factor 2 above; the float64 sum's own d 2^-53 disappears in
+//                                   the headroom), and 2^-149 where it is subnormal
+//   + (d + 2) 2^-53 qn2             the float64 sum of the query's exact squares, in any order
+//   + (d + 3) 2^-52 (|q| + cmax)^2  the canonical chain itself against the real sum: q_k - c_k, its square and the running sum
+//                                   round once each, every term and partial sum at most (|q| + cmax)^2
+// with the 2 % headroom.  The subnormal floors are those of err_bound (the seed counts as one more element of the chain).
+// Where B_l2 is not finite and normal -- sigma outside 2^+-120, a scaled bias that may overflow, norms beyond float32 -- it
+// is +inf: the query is UNPROVEN whatever its keys are (the select kernels force the status), the rung's threshold is -inf,
+// and the exhaustive kernels resolve it.  inf - inf cannot occur in a key: the bias is finite (FlatIndex routes to the
+// scan only where cmax^2 / 2 is a normal float32), so a key is finite, or q.c overflowed and it is +-inf -- ordered, never
+// NaN -- and such a query's keys say nothing the proof accepts: +inf as the edge makes the window infinite.
+__device__ __forceinline__ double err_bound_l2(int d, int scan_dtype, double qnorm, double cmax, double c_resid, double q_resid, double qn2,
+                                               double sigma) {
+    constexpr double U126 = 1.1754943508222875e-38, U149 = 1.4012984643248171e-45;
+    const double d1 = (double)(d + 1), half = 0.5 * cmax * cmax;
+    const double A = scan_dtype == DT_F32 ? d1 * 5.9604644775390625e-08 : scan_dtype == DT_SPLIT ? 3.0 * d1 * 1.1920928955078125e-07 : d1 * 1.1920928955078125e-07;
+    const double scan = err_bound(d + 1, scan_dtype, qnorm, cmax, c_resid, q_resid) + 1.02 * (A * half + (scan_dtype == DT_F16 ? U126 / sigma : 0.0));
+    const double sum = qnorm + cmax;
+    const double b = 2.0 * scan + 1.02 * (5.9604644775390625e-08 * cmax * cmax + U149 + (double)(d + 2) * 1.1102230246251565e-16 * qn2 +
+                                          (double)(d + 3) * 2.220446049250313e-16 * sum * sum);
+    const bool ok = b == b && b < 1.0e300 && sigma > 7.5e-37 && sigma < 1.4e36 && half * sigma < 1.0e36;     // (2^-120 .. 2^120)
+    return ok ? b : INFINITY;
+}
+
+// THE PROOF WINDOW.  A row whose scan score is `scan_score` has an exact score of at most scan_score * unscale + off + B
+// (unscale: what a scan score must be multiplied by to be a score -- 1, 2^-(shifts) for DT_F16, twice that for L2 keys;
+// off: 0, or -|q|^2 for L2 keys; B: err_bound / err_bound_l2).  window_top is the
 // highest score such a row can still show against a reference score `ref` once both are rounded to float32: the row can
 // neither pass `ref` nor tie with it if window_top < ref (ULP32_REL, ULP32_MIN: scan.h).
-__device__ __forceinline__ double window_top(float scan_score, double unscale, double B, double ref) {
-    return (double)scan_score * unscale + B + ULP32_REL * fabs(ref) + ULP32_MIN;
+__device__ __forceinline__ double window_top(float scan_score, double unscale, double off, double B, double ref) {
+    return (double)scan_score * unscale + off + B + ULP32_REL * fabs(ref) + ULP32_MIN;
 }
 
 // Its inverse: the scan threshold that a known lower bound `lb` of the query's k-th score allows: rows the scan does NOT keep have
-// scan score <= thr, hence exact score <= thr * unscale + B < lb - ulp32(lb).  -inf when no bound is known (-FLT_MAX).
-__device__ __forceinline__ float thr_from_bound(double lb, double B, double unscale) {
-    const double t = (lb - B - ULP32_REL * fabs(lb) - ULP32_MIN) / unscale;
+// scan score <= thr, hence exact score <= thr * unscale + off + B < lb - ulp32(lb).  -inf when no bound is known (-FLT_MAX).
+__device__ __forceinline__ float thr_from_bound(double lb, double B, double unscale, double off) {
+    const double t = (lb - off - B - ULP32_REL * fabs(lb) - ULP32_MIN) / unscale;
     float thr = (float)t;                                                   // round to nearest, then step below
     if ((double)thr >= t) thr = nextafterf(thr, -INFINITY);
     if (!(lb > -3.0e38)) thr = -INFINITY;
@@ -256,9 +309,9 @@ __device__ __forceinline__ double f16_resid2(float v, int sh) {
 // 2^-(corpus shift + query shift) of a DT_F16 scan, scan.h; else 1) of the query row at `qrow` (LDS or global, `dtype`
 // elements).  A: SelectArgs or ThrArgs (d, dtype, scan_dtype, corpus_shift, corpus_max_norm, corpus_resid; as the kernel
 // argument itself -- passed field by field the threshold kernels' schedules moved).  Called by ONE whole wave; every
-// lane returns the same values.
+// lane returns the same values.  A.metric == 1 (L2 keys): B = err_bound_l2, unscale doubled, off = -|q|^2; else off = 0.
 template <typename Args>
-__device__ __forceinline__ void query_bound(const Args& A, const char* qrow, int lane, double& B, double& unscale) {
+__device__ __forceinline__ void query_bound(const Args& A, const char* qrow, int lane, double& B, double& unscale, double& off) {
     const int d = A.d, dtype = A.dtype, scan_dtype = A.scan_dtype;
     double qn2 = 0.0;
     float q_amax = 0.f;
@@ -281,6 +334,12 @@ __device__ __forceinline__ void query_bound(const Args& A, const char* qrow, int
     }
     B = err_bound(d, scan_dtype, sqrt(qn2), (double)A.corpus_max_norm, (double)A.corpus_resid, sqrt(rq2));
     unscale = scan_dtype == DT_F16 ? ldexp(1.0, -(A.corpus_shift + f16_shift(q_amax))) : 1.0;
+    off = 0.0;
+    if (A.metric) {
+        B = err_bound_l2(d, scan_dtype, sqrt(qn2), (double)A.corpus_max_norm, (double)A.corpus_resid, sqrt(rq2), qn2, 1.0 / unscale);
+        unscale *= 2.0;
+        off = -qn2;
+    }
 }
 
 // The k-th largest score ordinal (high word of the keys) among keys[0 .. M), k <= M, by the whole workgroup of
@@ -421,7 +480,7 @@ __device__ __forceinline__ void rescore_kept(const unsigned long long* surv, int
         }
         __syncthreads();                                                // (surv is read by every fetch; what emit writes aliases nothing)
         if (tid < SA_ROWS && c0 + tid < K2) {
-            if (c0 + tid < keep) emit(c0 + tid, true, acc, key_id(surv[c0 + tid]));
+            if (c0 + tid < keep) emit(c0 + tid, true, dtype == DT_F32_L2 ? -acc : acc, key_id(surv[c0 + tid]));
             else emit(c0 + tid, false, 0.0, -1);
         }
     }
@@ -439,9 +498,10 @@ __device__ __forceinline__ void load_query_row(char* qrow, const void* Q, int q,
 }
 
 // faiss pads missing results: (-FLT_MAX, -1) in the entries [from, k) of a query's result row
-__device__ __forceinline__ void pad_result(float* Dq, long* Iq, int j) { Dq[j] = -3.4028234663852886e38f; Iq[j] = -1; }
-__device__ __forceinline__ void pad_results(float* Dq, long* Iq, int from, int k, int t, int nthreads) {
-    for (int j = from + t; j < k; j += nthreads) pad_result(Dq, Iq, j);
+// (metric 1: distances, padded with +FLT_MAX)
+__device__ __forceinline__ void pad_result(float* Dq, long* Iq, int j, int metric = 0) { Dq[j] = out_score(-3.4028234663852886e38f, metric); Iq[j] = -1; }
+__device__ __forceinline__ void pad_results(float* Dq, long* Iq, int from, int k, int t, int nthreads, int metric = 0) {
+    for (int j = from + t; j < k; j += nthreads) pad_result(Dq, Iq, j, metric);
 }
 
 }  // namespace sss

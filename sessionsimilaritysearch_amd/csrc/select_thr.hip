@@ -22,9 +22,10 @@ constexpr int SA_ROWS_FULL = 128;                  //   ... the full-capacity la
 //
 // k_thr_prepare: one wave per selected query: its threshold in the scan's domain, counter zeroed.
 // B and unscale of selected query i = row q (select_dev.h: query_bound; ONE wave), through the `qb` cache when there is one.
-__device__ __forceinline__ void query_bound(const ThrArgs& A, int i, int q, int lane, double& B, double& unscale) {
-    if (A.qb != nullptr && A.qb_ready) { B = A.qb[2 * (size_t)i]; unscale = A.qb[2 * (size_t)i + 1]; return; }   // (selected query i = row q)
-    query_bound(A, reinterpret_cast<const char*>(A.Q) + (size_t)q * row_bytes(A.d, A.dtype), lane, B, unscale);
+// (the cache holds inner-product bounds only -- sss_ip_topk_long's: off = 0)
+__device__ __forceinline__ void query_bound(const ThrArgs& A, int i, int q, int lane, double& B, double& unscale, double& off) {
+    if (A.qb != nullptr && A.qb_ready) { B = A.qb[2 * (size_t)i]; unscale = A.qb[2 * (size_t)i + 1]; off = 0.0; return; }   // (selected query i = row q)
+    query_bound(A, reinterpret_cast<const char*>(A.Q) + (size_t)q * row_bytes(A.d, A.dtype), lane, B, unscale, off);
     if (A.qb != nullptr && lane == 0) { A.qb[2 * (size_t)i] = B; A.qb[2 * (size_t)i + 1] = unscale; }
 }
 
@@ -53,9 +54,10 @@ __global__ __launch_bounds__(256) void k_thr_prepare(const ThrArgs A) {
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= A.nsel) return;
     const int q = A.qsel[i];
-    double B, unscale;
-    query_bound(A, i, q, lane, B, unscale);                                 // (every lane ends up with the same B / unscale)
-    const float thr = thr_from_bound((double)A.D_out[(size_t)q * A.k + A.k - 1], B, unscale);    // -FLT_MAX when no k-th score is known
+    double B, unscale, off;
+    query_bound(A, i, q, lane, B, unscale, off);                            // (every lane ends up with the same B / unscale)
+    // (L2: the k-th distance already known is an UPPER bound of the true one: negated, a lower bound of the k-th score)
+    const float thr = thr_from_bound((double)out_score(A.D_out[(size_t)q * A.k + A.k - 1], A.metric), B, unscale, off);    // -FLT_MAX when no k-th score is known
     if (lane == 0) A.thr[i] = thr;
     if (!A.keep) {
         if (lane == 0) A.cnt[i] = 0u;
@@ -79,8 +81,8 @@ __global__ __launch_bounds__(256) void k_long_setup(const ThrArgs A, int* __rest
         for (int kk = lane; kk < A.d; kk += 64) qimg[(size_t)i * A.d + kk] = (_Float16)ldexpf(row[kk], sh);
     }
     for (int j = lane; j < A.k; j += 64) A.D_out[(size_t)i * A.k + j] = -3.4028234663852886e38f;   // "no bound known"
-    double B, unscale;
-    query_bound(A, i, i, lane, B, unscale);         // fills the cache (A.qb_ready == 0 here)
+    double B, unscale, off;
+    query_bound(A, i, i, lane, B, unscale, off);    // fills the cache (A.qb_ready == 0 here)
     if (lane == 0) { qsel[i] = i; A.thr[i] = -INFINITY; A.cnt[i] = 0u; A.status[i] = 1; }
 }
 
@@ -109,16 +111,16 @@ __global__ __launch_bounds__(SORT_THREADS) void k_bound_prepare(const ThrArgs A)
         sk = kth_largest_of([&](int x) { return ords[x]; }, (int)M, k, tid, s_hist);
     }
     if (tid >= 64) return;
-    double B, unscale;
-    query_bound(A, i, q, tid, B, unscale);
+    double B, unscale, off;
+    query_bound(A, i, q, tid, B, unscale, off);
     float lbf = A.D_out[(size_t)q * k + k - 1];
     if (have) {
-        const double lb = (double)ord2f(sk) * unscale - B;
+        const double lb = (double)ord2f(sk) * unscale + off - B;
         float f = (float)lb;
         if ((double)f > lb) f = nextafterf(f, -INFINITY);               // round DOWN: stays a lower bound
         if (f == f && f > lbf) { lbf = f; if (tid == 0) A.D_out[(size_t)q * k + k - 1] = f; }
     }
-    const float thr = thr_from_bound((double)lbf, B, unscale);
+    const float thr = thr_from_bound((double)lbf, B, unscale, off);
     if (tid == 0) A.thr[i] = thr;
     if (!A.keep) {
         if (tid == 0) A.cnt[i] = 0u;
@@ -161,11 +163,11 @@ __global__ __launch_bounds__(SORT_THREADS) void k_select_all(const ThrArgs A, in
     if ((int)M > 2 * k + 64) {                                          // (worth a selection only when there is much to prune)
         const unsigned sk_o = kth_largest_ord(keys, (int)M, k, tid, s_hist);
         if (tid < 64) {
-            double B, unscale;
-            query_bound(A, i, q, tid, B, unscale);
+            double B, unscale, off;
+            query_bound(A, i, q, tid, B, unscale, off);
             if (tid == 0) {
                 const double sk = (double)ord2f(sk_o);
-                const double c = sk - (2.0 * B + ULP32_REL * fabs(sk * unscale) + ULP32_MIN) / unscale;
+                const double c = sk - (2.0 * B + ULP32_REL * fabs(sk * unscale + off) + ULP32_MIN) / unscale;
                 float f = (float)c;
                 if ((double)f > c) f = nextafterf(f, -INFINITY);
                 s_cut = f == f ? f : -INFINITY;                         // (NaN bound: keep everything)
@@ -184,7 +186,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_select_all(const ThrArgs A, in
     while (K2 < keep) K2 <<= 1;
     // canonical re-score of the survivors (rescore_kept: SA_ROWS rows at a time through the staging tile for long rows)
     char* stage = qrow + ((rb + 15) & ~15);                             // [SA_ROWS][SA_BYTES + 16]
-    rescore_kept<SA_ROWS>(surv, keep, K2, A.C, rb, A.dtype, qrow, stage, tid,
+    rescore_kept<SA_ROWS>(surv, keep, K2, A.C, rb, rescore_type(A.dtype, A.metric), qrow, stage, tid,
                           [&](int c, bool valid, double acc, int id) __attribute__((always_inline)) {
                               keys[c] = valid ? make_key((float)acc, id) : 0ull;     // (the scan keys are no longer needed)
                           });
@@ -217,8 +219,8 @@ __global__ __launch_bounds__(SORT_THREADS) void k_select_all(const ThrArgs A, in
     float* Dq = A.D_out + (size_t)q * k;
     long* Iq = A.I_out + (size_t)q * k;
     for (int j = tid; j < k; j += SORT_THREADS) {
-        if (j < keep) { Dq[j] = key_score(outk[j]); Iq[j] = (long)key_id(outk[j]) + A.id_offset; }
-        else pad_result(Dq, Iq, j);
+        if (j < keep) { Dq[j] = out_score(key_score(outk[j]), A.metric); Iq[j] = (long)key_id(outk[j]) + A.id_offset; }
+        else pad_result(Dq, Iq, j, A.metric);
     }
     if (tid == 0) A.status[q] = 0;
 }
@@ -234,9 +236,9 @@ __global__ __launch_bounds__(256) void k_range_prepare(const ThrArgs A, const fl
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= A.nsel) return;
-    double B, unscale;
-    query_bound(A, i, i, lane, B, unscale);                                 // (every lane ends up with the same B / unscale)
-    const float thr = thr_from_bound((double)radius[i], B, unscale);        // -inf for r <= -3e38 (and NaN): keep every row
+    double B, unscale, off;
+    query_bound(A, i, i, lane, B, unscale, off);                            // (every lane ends up with the same B / unscale)
+    const float thr = thr_from_bound((double)radius[i], B, unscale, off);        // -inf for r <= -3e38 (and NaN): keep every row
     if (lane == 0) { qsel[i] = i; A.thr[i] = thr; A.cnt[i] = 0u; }
 }
 

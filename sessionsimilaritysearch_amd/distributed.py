@@ -82,11 +82,11 @@ class HipEngine:
         self.unproven = torch.zeros(1, dtype=torch.int32, device=index.device)
 
     def local_search(self, q, k, D, I, status):
-        """This shard's top-k into D / I, no host sync.  With a fused scan: ``status`` marks the queries it left
-        unproven.  Without one (L2, a d or k no fused scan serves, an empty shard): the exhaustive kernels, which
-        are exact for every query, so ``status`` is all zero."""
+        """This shard's top-k into D / I, no host sync.  With a fused scan (inner product or L2): ``status`` marks the
+        queries it left unproven.  Without one (a dtype, d or k no fused scan serves, an empty shard): the exhaustive
+        kernels, which are exact for every query, so ``status`` is all zero."""
         index = self.index
-        if index.fused_ok(k):
+        if index._route(k):
             index.search_fused(q, k, (D, I, status), self.unproven)
             return
         status.zero_()
@@ -100,7 +100,7 @@ class HipEngine:
             index.search_exhaustive(q, k, D, I)
 
     def fix_unproven(self, q, k, D, I, status):
-        if not self.index.fused_ok(k):
+        if not self.index._route(k):
             return 0                                # the exhaustive route left nothing unproven
         return self.index.fix_unproven(q, k, D, I, status)
 

@@ -75,6 +75,10 @@ SEARCH_CHUNK = 65536             # queries per fused call of search_device (work
 SEARCH_CHUNK_LONG = 16384        # ... on the long-row path (64 KB per query)
 RANGE_CHUNK = 4096               # queries per fused range_search count / fill (workspace 64 KB per query)
 _SCAN_CODE = {"split": 2, "f16": 3}                              # include/sss.h: scan image codes (else the dtype's own)
+# The L2 scans start every score from the row bias -|c|^2 / 2, a float32: the scan route is taken only where the largest
+# row norm keeps cmax^2 / 2 finite and normal with room to spare (2^-121 .. 2^119); beyond, the exhaustive kernels.
+L2_SCAN_MIN_NORM = 2.0 ** -60
+L2_SCAN_MAX_NORM = 2.0 ** 60
 
 
 def _dev(device=None):
@@ -215,6 +219,14 @@ class FlatIndex:
     and a class steps back down after 64 CONSECUTIVE clean searches.  Images are built on first use
     (``prepare(k)`` does it ahead of time) and extended as rows are added.
 
+    ``metric="l2"`` (faiss ``IndexFlatL2``): squared distances, the float64 chain of ``(q_k - c_k)**2`` rounded to
+    float32, ordered by (distance asc, id asc), missing results (+FLT_MAX, -1).  A float32 index runs it on the same
+    scans, same ``scan`` argument and ladder (``l2_scan_for``): the rows nearest to q are those with the largest
+    ``q.c - |c|**2 / 2``, which is the inner-product scan with every score started from a per-row bias (one float32
+    per row, kept beside the images).  ``scan_for`` / ``fused_ok`` describe the inner-product path and stay "" /
+    False for an L2 index.  Other dtypes, d without a scan, k > 500 and corpora whose largest row norm lies outside
+    [2^-60, 2^60] run on the exhaustive kernels.
+
     Queries a scan leaves unproven are resolved in two further stages, both exact: the THRESHOLD RUNG
     (``search_threshold``: one more matrix-core scan for just those queries that keeps every row able to
     reach the k-th score already known, near ties and duplicate rows alike) and, for what exceeds its
@@ -252,6 +264,8 @@ class FlatIndex:
         self._amax_t = torch.zeros(1, dtype=torch.float32, device=self.device)    # largest |element| in the f16 image
         self._resid_t = torch.zeros(1, dtype=torch.float32, device=self.device)   # largest row residual norm of it
         self._resid = None
+        self._bias = None               # [cap] float32 -|row|^2 / 2: what the L2 scans start every score from
+        self._bias_done = 0
         self._xb = torch.empty((0, self.d), dtype=self._tdtype, device=self.device)
         self._store = self._xb          # backing storage of _xb (grown geometrically by add())
         self._cmax_t = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -295,6 +309,11 @@ class FlatIndex:
             return ""
         if self.dtype != "f32":
             return "native"
+        return self._ladder_scan(k)
+
+    def _ladder_scan(self, k: int) -> str:
+        """The scan of a float32 index for k results by its ``scan`` argument and, for "auto", what the searches
+        so far have taught it ("" = this d has none)."""
         want = self.scan
         if want == "auto":
             level = max(self._k_class(k), self._auto_level.get(self._k_class(k), 0))
@@ -306,6 +325,22 @@ class FlatIndex:
         if want == "f16" and not self._scan_served("f16"):
             want = "split"
         return want if self._scan_served(want) else ""
+
+    def l2_scan_for(self, k: int) -> str:
+        """Which candidate scan an L2 search for k results uses ("" = none: exhaustive path): the ladder, ``scan``
+        argument and "auto" escalation state of ``scan_for``, for a float32 index whose d has a fused kernel, k <= 500
+        and a largest row norm in [2^-60, 2^60]."""
+        if self.metric != "l2" or self.dtype != "f32" or k <= 0 or k > FUSED_MAX_K or self.ntotal == 0:
+            return ""
+        if not any(self._scan_served(s) for s in _LADDER):
+            return ""
+        if not L2_SCAN_MIN_NORM <= self.corpus_max_norm() <= L2_SCAN_MAX_NORM:
+            return ""
+        return self._ladder_scan(k)
+
+    def _route(self, k: int) -> str:
+        """The scan a search for k results runs on under this index's metric ("" = the exhaustive kernels)."""
+        return self.l2_scan_for(k) if self.metric == "l2" else self.scan_for(k)
 
     def _long_or_none(self, k: int) -> str:
         """"long": the K-tiled scan for rows beyond the register-resident kernels (``sss_ip_topk_long``)."""
@@ -411,12 +446,29 @@ class FlatIndex:
         _lib.check(rc, "sss_split_bf16")
         self._split_done = n
 
+    def _ensure_bias(self):
+        """Bring the L2 row bias up to date (rows added since the last call)."""
+        n, lo = self.ntotal, self._bias_done
+        if lo == n and self._bias is not None:
+            return
+        if self._bias is None or self._bias.numel() < n:
+            new = torch.empty(max(self._store.shape[0], n), dtype=torch.float32, device=self.device)
+            if self._bias is not None and lo:
+                new[:lo] = self._bias[:lo]
+            self._bias = new
+        rc = _lib.lib().sss_l2_row_bias(self._xb[lo:].data_ptr(), n - lo, self.d, self._bias[lo:].data_ptr(),
+                                        _lib.stream_ptr(self.device))
+        _lib.check(rc, "sss_l2_row_bias")
+        self._bias_done = n
+
     def prepare(self, k: int = 10):
-        """Build whatever a fused search for k results needs (images, norms) now rather than on
+        """Build whatever a fused search for k results needs (images, norms, the L2 row bias) now rather than on
         the first search; returns the scan that will be used."""
-        mode = self.scan_for(k)
+        mode = self._route(k)
         self._scan_image(mode)
         self.corpus_max_norm()
+        if mode and self.metric == "l2":
+            self._ensure_bias()
         return mode
 
     def _scan_image(self, mode: str):
@@ -492,6 +544,7 @@ class FlatIndex:
         self.id_offset = int(id_offset)
         self._split, self._split_done = None, 0
         self._f16, self._f16_done = None, 0
+        self._bias, self._bias_done = None, 0
         self._amax_t.zero_()
         self._resid_t.zero_()
         self._auto_level.clear()
@@ -510,7 +563,8 @@ class FlatIndex:
     def search_fused(self, q: torch.Tensor, k: int, out=None, unproven_count=None):
         """Enqueue the fused MFMA scoring + top-k on the current stream; no host sync.
         Returns (D [nq,k] f32, I [nq,k] i64, status [nq] i32) CUDA tensors; rows with
-        status != 0 must be re-run with ``search_exhaustive`` (``search`` does that).
+        status != 0 must be re-run with ``search_exhaustive`` (``search`` does that).  An L2 index takes the
+        L2 scan ``l2_scan_for(k)`` names.
         ``unproven_count``: optional CUDA int32 [1] tensor, incremented once per unproven query."""
         L = _lib.lib()
         _lib.require_cuda(q, "q", self._tdtype)
@@ -524,7 +578,7 @@ class FlatIndex:
         mode = self.last_scan = self.prepare(k)
         if mode == "":
             raise _lib.SssError("search_fused: this index / k has no fused path (use search)")
-        image, _, shift, resid = self._scan_image(mode)
+        image, code, shift, resid = self._scan_image(mode)
         if mode == "long":
             ws = self._ws.get(L.sss_ip_topk_long_workspace_bytes(nq, n, self.d, self._fmt.code))
             rc = L.sss_ip_topk_long(q.data_ptr(), nq, self._xb.data_ptr(), self._fmt.code, image.data_ptr(), shift, resid,
@@ -534,7 +588,9 @@ class FlatIndex:
             if unproven_count is not None:
                 unproven_count += (status != 0).sum().to(torch.int32)
             return D, I, status
-        if mode == "f16":
+        if self.metric == "l2":
+            nbytes = L.sss_l2_topk_workspace_bytes(nq, n, self.d, k, code)
+        elif mode == "f16":
             nbytes = L.sss_ip_topk_f16_workspace_bytes(nq, n, self.d, k)
         else:
             nbytes = L.sss_ip_topk_workspace_bytes(nq, n, self.d, k, self._fmt.code)
@@ -545,7 +601,10 @@ class FlatIndex:
         tail = (self.corpus_max_norm(), D.data_ptr(), I.data_ptr(), status.data_ptr(),
                 0 if unproven_count is None else unproven_count.data_ptr(),
                 self._state.data_ptr(), self._state.numel(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
-        if mode == "f16":
+        if self.metric == "l2":
+            rc = L.sss_l2_topk(q.data_ptr(), nq, self._xb.data_ptr(), image.data_ptr(), code, shift, resid,
+                               self._bias.data_ptr(), n, self.d, k, self.id_offset, *tail)
+        elif mode == "f16":
             rc = L.sss_ip_topk_f16(q.data_ptr(), nq, self._xb.data_ptr(), image.data_ptr(), shift, resid, n, self.d, k,
                                    self.id_offset, *tail)
         elif mode == "split":
@@ -556,8 +615,15 @@ class FlatIndex:
                                self.id_offset, *tail)
         if rc != 0:
             self._state = None          # re-made (zeroed) on the next call
-        _lib.check(rc, "sss_ip_topk")
+        _lib.check(rc, "sss_l2_topk" if self.metric == "l2" else "sss_ip_topk")
         return D, I, status
+
+    def l2_rung_scan(self) -> str:
+        """The scan the threshold rung of an L2 search uses ("" = none): the choice of ``rung_scan`` among the scans
+        this d has, for an index the L2 scans serve at all."""
+        if self.l2_scan_for(1) == "":
+            return ""
+        return self._rung_pick()
 
     def rung_scan(self) -> str:
         """The scan the threshold rung uses: the one-pass f16 image where the shape has one (cheapest pass
@@ -569,6 +635,10 @@ class FlatIndex:
             return "native" if self.d in self._fmt.fused_dims else ""
         if not any(self._scan_served(s) for s in _LADDER):
             return ""                            # long rows: their scan IS a threshold scan; what it leaves is mass ties
+        return self._rung_pick()
+
+    def _rung_pick(self) -> str:
+        """The rung's scan of a float32 index with a fused shape."""
         if self.scan == "auto":
             # an image that is already complete beats building another one (n * d * 2 bytes) for a handful of queries
             f16_ready = self._f16 is not None and self._f16_done == self.ntotal
@@ -588,13 +658,23 @@ class FlatIndex:
         unproven: one more scan for just those queries keeps every corpus row that could still reach the
         k-th score already known (column k-1 of their rows of D) and re-scores them all.  Resolved rows of
         D / I are rewritten and their status set to 0; returns the rows still unproven."""
-        mode = self.rung_scan()
+        l2 = self.metric == "l2"
+        mode = self.l2_rung_scan() if l2 else self.rung_scan()
         if mode == "" or rows.numel() == 0 or k > 8192:
             return rows
         L = _lib.lib()
         image, code, shift, resid = self._scan_image(mode)
         sel = rows.to(device=self.device, dtype=torch.int32).contiguous()
         n = self.ntotal
+        if l2:
+            self._ensure_bias()
+            ws = self._ws.get(L.sss_l2_topk_threshold_workspace_bytes(sel.numel(), n, self.d, code))
+            rc = L.sss_l2_topk_threshold(q.data_ptr(), sel.data_ptr(), sel.numel(), self._xb.data_ptr(), image.data_ptr(), code,
+                                         shift, resid, self._bias.data_ptr(), n, self.d, k, self.id_offset,
+                                         self.corpus_max_norm(), D.data_ptr(), I.data_ptr(), status.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
+            _lib.check(rc, "sss_l2_topk_threshold")
+            return sel[status[sel.long()] != 0]
         ws = self._ws.get(L.sss_ip_topk_threshold_workspace_bytes(sel.numel(), n, self.d, code))
         rc = L.sss_ip_topk_threshold(q.data_ptr(), sel.data_ptr(), sel.numel(), self._xb.data_ptr(), self._fmt.code,
                                      image.data_ptr(), code, shift, resid, n, self.d, k, self.id_offset,
@@ -658,10 +738,10 @@ class FlatIndex:
             I.fill_(-1)
             return D, I
         self._require_d_aligned()
-        if self.fused_ok(k):
+        if self._route(k):
             # the per-query workspace is 16 KB (fused scans) to 64 KB (long rows, threshold rung): the reference hands
             # `index.search` its whole test set at once (test_amazon_filterd.py:578), so large batches go in chunks
-            step = SEARCH_CHUNK_LONG if self.scan_for(k) == "long" else SEARCH_CHUNK
+            step = SEARCH_CHUNK_LONG if self._route(k) == "long" else SEARCH_CHUNK
             status = torch.empty((nq,), dtype=torch.int32, device=self.device)
             rescans = fallbacks = 0
             for lo in range(0, nq, step):
