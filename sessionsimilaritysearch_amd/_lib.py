@@ -1,4 +1,4 @@
-"""ctypes binding of libsss.so (the C ABI declared in include/sss.h, include/sss_sparse.h and include/sss_l2.h).
+"""ctypes binding of libsss.so (the C ABI declared in include/sss.h, include/sss_sparse.h, include/sss_l2.h and include/sss_pad.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails, this
 module raises.  ``build()`` compiles the library in-tree with hipcc for gfx950.
@@ -130,6 +130,22 @@ _L2_SIGNATURES = {
                                       c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
+# include/sss_pad.h one to one (scans at the next supported width for float32 rows of any width d % 4 == 0)
+_PAD_SIGNATURES = {
+    "sss_pad_rows_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "sss_pad_scale_f16": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sss_pad_split_bf16": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "sss_pad_f16_resid_max": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sss_pad_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int, c_int, c_int]),
+    "sss_pad_topk": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_int, c_int, c_int,
+                             c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                             c_void_p]),
+    "sss_pad_topk_threshold_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int, c_int]),
+    "sss_pad_topk_threshold": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_int64,
+                                       c_int, c_int, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                       c_void_p]),
+}
+
 
 class LinearProblem(ctypes.Structure):
     """``sss_linear_problem`` of include/sss.h."""
@@ -170,6 +186,11 @@ def l2_symbols():
     return sorted(_L2_SIGNATURES)
 
 
+def pad_symbols():
+    """The entry points of include/sss_pad.h."""
+    return sorted(_PAD_SIGNATURES)
+
+
 def build(verbose: bool = False) -> str:
     """Compile libsss.so for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-C", CSRC, "-j4"]
@@ -191,7 +212,8 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C "
                 "sessionsimilaritysearch_amd/csrc`). There is no CPU fallback.")
         h = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in (*_SIGNATURES.items(), *_SPARSE_SIGNATURES.items(), *_L2_SIGNATURES.items()):
+        for name, (res, args) in (*_SIGNATURES.items(), *_SPARSE_SIGNATURES.items(), *_L2_SIGNATURES.items(),
+                                   *_PAD_SIGNATURES.items()):
             fn = getattr(h, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = h

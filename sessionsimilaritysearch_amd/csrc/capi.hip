@@ -1,4 +1,4 @@
-// extern "C" surface of libsss (declared in include/sss.h, include/sss_sparse.h and include/sss_l2.h) + error plumbing.
+// extern "C" surface of libsss (declared in include/sss.h, include/sss_sparse.h, include/sss_l2.h and include/sss_pad.h) + error plumbing.
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -9,6 +9,7 @@
 #include "../../include/sss.h"
 #include "../../include/sss_sparse.h"
 #include "../../include/sss_l2.h"
+#include "../../include/sss_pad.h"
 #include "sss_common.h"
 #include "scan.h"
 #include "kargs.h"
@@ -426,6 +427,38 @@ int sss_l2_topk_threshold(const float* q, const int32_t* qsel, int64_t nsel, con
     return sss::l2_topk_threshold(q, qsel, nsel, corpus, scan_image, scan_dtype, corpus_shift, corpus_resid_norm, bias, n, d, k,
                                   id_offset, corpus_max_norm, D_out, reinterpret_cast<long*>(I_out), status, workspace,
                                   workspace_bytes, ST(stream));
+}
+
+// ---- include/sss_pad.h
+int sss_pad_rows_f32(const float* x, int64_t n, int d, int ds, float* y, void* stream) { return sss::pad_rows_f32(x, n, d, ds, y, ST(stream)); }
+int sss_pad_scale_f16(const float* x, int64_t n, int d, int ds, int shift, uint16_t* y, void* stream) {
+    return sss::pad_scale_f16(x, n, d, ds, shift, y, ST(stream));
+}
+int sss_pad_split_bf16(const float* x, int64_t n, int d, int ds, uint16_t* y, void* stream) { return sss::pad_split_bf16(x, n, d, ds, y, ST(stream)); }
+int sss_pad_f16_resid_max(const float* x, const uint16_t* y, int64_t n, int d, int ds, int shift, float* out, void* stream) {
+    return sss::pad_f16_resid_max(x, y, n, d, ds, shift, out, ST(stream));
+}
+size_t sss_pad_topk_workspace_bytes(int64_t nq, int64_t n, int d_row, int d_scan, int k, int scan_dtype) {
+    return sss::pad_topk_workspace_bytes(nq, n, d_row, d_scan, k, scan_dtype);
+}
+int sss_pad_topk(const float* q, int64_t nq, const float* corpus, const void* scan_image, int scan_dtype, int corpus_shift,
+                 float corpus_resid_norm, const float* bias, int64_t n, int d_row, int d_scan, int k, int64_t id_offset,
+                 float corpus_max_norm, float* D_out, int64_t* I_out, int32_t* status, int32_t* unproven_count, void* state,
+                 size_t state_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    return sss::pad_topk(q, nq, corpus, scan_image, scan_dtype, corpus_shift, corpus_resid_norm, bias, n, d_row, d_scan, k, id_offset,
+                         corpus_max_norm, D_out, reinterpret_cast<long*>(I_out), status, unproven_count, state, state_bytes, workspace,
+                         workspace_bytes, ST(stream));
+}
+size_t sss_pad_topk_threshold_workspace_bytes(int64_t nsel, int64_t n, int d_row, int d_scan, int scan_dtype) {
+    return sss::pad_topk_threshold_workspace_bytes(nsel, n, d_row, d_scan, scan_dtype);
+}
+int sss_pad_topk_threshold(const float* q, const int32_t* qsel, int64_t nsel, const float* corpus, const void* scan_image,
+                           int scan_dtype, int corpus_shift, float corpus_resid_norm, const float* bias, int64_t n, int d_row,
+                           int d_scan, int k, int64_t id_offset, float corpus_max_norm, float* D_out, int64_t* I_out,
+                           int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    return sss::pad_topk_threshold(q, qsel, nsel, corpus, scan_image, scan_dtype, corpus_shift, corpus_resid_norm, bias, n, d_row, d_scan,
+                                   k, id_offset, corpus_max_norm, D_out, reinterpret_cast<long*>(I_out), status, workspace,
+                                   workspace_bytes, ST(stream));
 }
 
 }  // extern "C"

@@ -104,8 +104,9 @@ static int ip_topk_impl(const char* what, const void* q, long nq, const void* c_
                         float corpus_resid, const void* c_exact,
                         int exact_dtype, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out,
                         int* status, int* unproven_count, void* state, size_t state_bytes, void* ws, size_t ws_bytes,
-                        hipStream_t st, const float* bias = nullptr) {
+                        hipStream_t st, const float* bias = nullptr, int d_row = 0) {
     // bias: the L2 search (l2_topk below) -- the scan's keys are q.c + bias[row], the select's scores negated distances
+    // d_row: elements of a stored row of c_exact where it is narrower than d, the width of q and c_scan (pad_topk below); 0: d
     const bool l2 = bias != nullptr;
     if (nq <= 0 || n <= 0 || k <= 0) { set_error("%s: nq, n, k must be positive", what); return SSS_EINVAL; }
     int rc = check_scan_source(what, exact_dtype, scan_dtype, d, false, c_scan, corpus_shift, corpus_resid, n, nq);
@@ -145,6 +146,7 @@ static int ip_topk_impl(const char* what, const void* q, long nq, const void* c_
     s.id_offset = id_offset; s.corpus_max_norm = corpus_max_norm;
     s.D_out = D_out; s.I_out = I_out; s.status = status; s.unproven_count = unproven_count;
     s.metric = l2 ? 1 : 0;
+    s.d_row = d_row;
     rc = launch_select(s, st);
     if (rc) (void)hipMemsetAsync(state, 0, ip_topk_state_bytes(nq), st);   // the scan dirtied it and nobody will clear it
     return rc;
@@ -184,7 +186,7 @@ size_t ip_topk_threshold_workspace_bytes(long nsel, long n, int d, int scan_dtyp
 static int topk_threshold_impl(const char* what, const void* q, const int* qsel, long nsel, const void* c_exact, int exact_dtype,
                                const void* c_scan, int scan_dtype, int corpus_shift, float corpus_resid, long n, int d, int k,
                                long id_offset, float corpus_max_norm, float* D_out, long* I_out, int* status, void* ws, size_t ws_bytes,
-                               hipStream_t st, const float* bias = nullptr) {
+                               hipStream_t st, const float* bias = nullptr, int d_row = 0) {
     if (nsel <= 0 || n <= 0 || k <= 0 || !qsel) { set_error("%s: nsel, n, k must be positive", what); return SSS_EINVAL; }
     const int rc = check_scan_source(what, exact_dtype, scan_dtype, d, false, c_scan, corpus_shift, corpus_resid, n, nsel);
     if (rc) return rc;
@@ -200,6 +202,7 @@ static int topk_threshold_impl(const char* what, const void* q, const int* qsel,
     t.cand = reinterpret_cast<unsigned long long*>(w + thr_head_bytes(nsel));
     t.D_out = D_out; t.I_out = I_out; t.status = status;
     t.metric = bias != nullptr ? 1 : 0;
+    t.d_row = d_row;                    // (pad_topk_threshold; 0: the stored rows are d wide)
     return run_threshold_form(t, c_scan, p, [&] { return launch_thr_prepare(t, st); }, [&] { return launch_select_all(t, st); }, st, bias);
 }
 
@@ -321,6 +324,70 @@ int l2_topk_threshold(const float* q, const int* qsel, long nsel, const float* c
     if (!ws) { set_error("l2_topk_threshold: workspace 0 < %zu", l2_topk_threshold_workspace_bytes(nsel, n, d, scan_dtype)); return SSS_EWORKSPACE; }
     return topk_threshold_impl("l2_topk_threshold", q, qsel, nsel, c, DT_F32, c_scan, scan_dtype, corpus_shift, corpus_resid, n, d, k,
                                id_offset, corpus_max_norm, D_out, I_out, status, ws, ws_bytes, st, bias);
+}
+
+// ------------------------------------------------------------------------------------------
+// Scans at a width the row does not have (include/sss_pad.h): float32 rows of d_row elements, q and c_scan zero-extended to
+// d_scan -- a width of scan_dtype's fused kernels -- by the builders of rowops.hip.  Zero columns add nothing to a dot
+// product or to |c|^2, so the scan, its keys and its bound (for a chain of d_scan terms: what the scan really summed) are
+// those of a d_scan-wide corpus; the select kernels re-score from the d_row-wide rows (SelectArgs::d_row).
+static int check_pad(const char* what, int scan_dtype, int d_row, int d_scan) {
+    if (d_row <= 0 || d_row % 4 || d_row > d_scan) {
+        set_error("%s: need 0 < d_row <= d_scan and d_row %% 4 == 0 (d_row %d, d_scan %d)", what, d_row, d_scan);
+        return SSS_EINVAL;
+    }
+    if (scan_dtype != DT_F32 && scan_dtype != DT_SPLIT && scan_dtype != DT_F16) {
+        set_error("%s: scan_dtype %d is not a scan of float32 rows (0 the padded rows, 2 the split image, 3 the f16 image)", what, scan_dtype);
+        return SSS_EINVAL;
+    }
+    return SSS_OK;
+}
+static bool pad_shape_ok(int d_row, int d_scan, int scan_dtype) {
+    return d_row > 0 && d_row % 4 == 0 && d_row <= d_scan && (scan_dtype == DT_F32 || scan_dtype == DT_SPLIT || scan_dtype == DT_F16) &&
+           fused_shape_ok(d_scan, scan_dtype);
+}
+static int check_pad_buffers(const char* what, const float* q, const float* c, const float* bias, const float* D_out, const long* I_out,
+                             const int* status) {
+    if (bias && (reinterpret_cast<uintptr_t>(bias) & 15)) { set_error("%s: row bias not 16-byte aligned", what); return SSS_EINVAL; }
+    if (!q || !c || !D_out || !I_out || !status) { set_error("%s: q, corpus, D_out, I_out and status are required", what); return SSS_EINVAL; }
+    if ((reinterpret_cast<uintptr_t>(q) & 15) || (reinterpret_cast<uintptr_t>(c) & 15)) { set_error("%s: q and corpus must be 16-byte aligned", what); return SSS_EINVAL; }
+    return SSS_OK;
+}
+
+size_t pad_topk_workspace_bytes(long nq, long n, int d_row, int d_scan, int k, int scan_dtype) {
+    if (!pad_shape_ok(d_row, d_scan, scan_dtype)) return 0;
+    return ip_topk_scan_workspace_bytes(nq, n, d_scan, k, scan_dtype);
+}
+
+int pad_topk(const float* q, long nq, const float* c, const void* c_scan, int scan_dtype, int corpus_shift, float corpus_resid,
+             const float* bias, long n, int d_row, int d_scan, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out,
+             int* status, int* unproven_count, void* state, size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (nq <= 0 || n <= 0 || k <= 0) { set_error("pad_topk: nq, n, k must be positive"); return SSS_EINVAL; }
+    int rc = check_pad("pad_topk", scan_dtype, d_row, d_scan);
+    if (!rc) rc = check_scan_source("pad_topk", DT_F32, scan_dtype, d_scan, false, c_scan, corpus_shift, corpus_resid, n, nq);
+    if (!rc) rc = check_pad_buffers("pad_topk", q, c, bias, D_out, I_out, status);
+    if (rc) return rc;
+    if (!ws) { set_error("pad_topk: workspace 0 < %zu", pad_topk_workspace_bytes(nq, n, d_row, d_scan, k, scan_dtype)); return SSS_EWORKSPACE; }
+    return ip_topk_impl("pad_topk", q, nq, c_scan, scan_dtype, corpus_shift, corpus_resid, c, DT_F32, n, d_scan, k, id_offset, corpus_max_norm,
+                        D_out, I_out, status, unproven_count, state, state_bytes, ws, ws_bytes, st, bias, d_row);
+}
+
+size_t pad_topk_threshold_workspace_bytes(long nsel, long n, int d_row, int d_scan, int scan_dtype) {
+    if (!pad_shape_ok(d_row, d_scan, scan_dtype)) return 0;
+    return ip_topk_threshold_workspace_bytes(nsel, n, d_scan, scan_dtype);
+}
+
+int pad_topk_threshold(const float* q, const int* qsel, long nsel, const float* c, const void* c_scan, int scan_dtype, int corpus_shift,
+                       float corpus_resid, const float* bias, long n, int d_row, int d_scan, int k, long id_offset, float corpus_max_norm,
+                       float* D_out, long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (nsel <= 0 || n <= 0 || k <= 0 || !qsel) { set_error("pad_topk_threshold: nsel, n, k must be positive"); return SSS_EINVAL; }
+    int rc = check_pad("pad_topk_threshold", scan_dtype, d_row, d_scan);
+    if (!rc) rc = check_scan_source("pad_topk_threshold", DT_F32, scan_dtype, d_scan, false, c_scan, corpus_shift, corpus_resid, n, nsel);
+    if (!rc) rc = check_pad_buffers("pad_topk_threshold", q, c, bias, D_out, I_out, status);
+    if (rc) return rc;
+    if (!ws) { set_error("pad_topk_threshold: workspace 0 < %zu", pad_topk_threshold_workspace_bytes(nsel, n, d_row, d_scan, scan_dtype)); return SSS_EWORKSPACE; }
+    return topk_threshold_impl("pad_topk_threshold", q, qsel, nsel, c, DT_F32, c_scan, scan_dtype, corpus_shift, corpus_resid, n, d_scan, k,
+                               id_offset, corpus_max_norm, D_out, I_out, status, ws, ws_bytes, st, bias, d_row);
 }
 
 }  // namespace sss

@@ -175,6 +175,94 @@ __global__ __launch_bounds__(256) void k_f16_resid_max(const float* __restrict__
     if (lane == 0 && m > 0.f) atomicMax(reinterpret_cast<unsigned*>(out), __float_as_uint(m));
 }
 
+// ---- row-widening builders (include/sss_pad.h): float32 rows of d elements -> rows of ds >= d elements whose columns
+// d .. ds-1 are exact +0, for the scans of a width the row does not have.  One thread per 16-byte chunk of the OUTPUT,
+// consecutive threads along the row (coalesced stores; the loads of a row are as contiguous), grid-stride over n * chunks:
+// any n.  d % 4 == 0: a 16-byte chunk of the input lies wholly inside the row or wholly in the padding.
+__global__ __launch_bounds__(256) void k_pad_rows_f32(const float* __restrict__ x, long n, int d4, int ds4, float* __restrict__ y) {
+    const long total = n * ds4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long row = i / ds4;
+        const int j = (int)(i - row * ds4);
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (j < d4) v = reinterpret_cast<const f32x4*>(x)[row * d4 + j];
+        reinterpret_cast<f32x4*>(y)[i] = v;
+    }
+}
+
+// the eight float32 elements 8 j .. 8 j + 7 of a d-wide row (d4 = d / 4 chunks), zeros from column d on
+__device__ __forceinline__ void load8_padded(const float* __restrict__ x, long row, int d4, int j, float v[8]) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4* p = reinterpret_cast<const f32x4*>(x) + row * d4;
+    const f32x4 a = 2 * j < d4 ? p[2 * j] : zero, b = 2 * j + 1 < d4 ? p[2 * j + 1] : zero;
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+
+// k_scale_f16 into ds-wide rows: the same x * 2^shift, rounded to nearest even; ldexpf(+0, shift) = +0
+__global__ __launch_bounds__(256) void k_pad_scale_f16(const float* __restrict__ x, long n, int d4, int ds8, int shift,
+                                                       unsigned short* __restrict__ y) {
+    const long total = n * ds8;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long row = i / ds8;
+        float v[8];
+        load8_padded(x, row, d4, (int)(i - row * ds8), v);
+        f16x8_t o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (_Float16)ldexpf(v[e], shift);
+        reinterpret_cast<f16x8_t*>(y)[i] = o;
+    }
+}
+
+// k_split_bf16 into [hi(ds) | lo(ds)] rows: the same two roundings per element; +0 splits into (+0, +0)
+__global__ __launch_bounds__(256) void k_pad_split_bf16(const float* __restrict__ x, long n, int d4, int ds8,
+                                                        unsigned short* __restrict__ y) {
+    const long total = n * ds8;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long row = i / ds8;
+        const int j = (int)(i - row * ds8);
+        float v[8];
+        load8_padded(x, row, d4, j, v);
+        bf16x8_t hi, lo;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            hi[e] = (__bf16)v[e];
+            const float rem = v[e] - (float)hi[e];
+            lo[e] = (__bf16)(__builtin_isfinite(rem) ? rem : 0.f);
+        }
+        bf16x8_t* out = reinterpret_cast<bf16x8_t*>(y) + row * 2 * ds8;
+        out[j] = hi;
+        out[ds8 + j] = lo;
+    }
+}
+
+// k_f16_resid_max of d-wide rows x against their ds-wide image y: sixteen lanes a row, a lane taking eight elements per
+// step (16 bytes of the image, 32 of the row); the image's columns from d on are +0 against nothing: no residual.
+__global__ __launch_bounds__(256) void k_pad_f16_resid_max(const float* __restrict__ x, const _Float16* __restrict__ y, long n, int d4,
+                                                           int ds8, int shift, float* __restrict__ out) {
+    const int sub = threadIdx.x & 15;
+    const int nj = (d4 + 1) / 2;                                   // 8-element groups that hold a column below d
+    float m = 0.f;
+    for (long row = (long)blockIdx.x * 16 + (threadIdx.x >> 4); row < n; row += (long)gridDim.x * 16) {
+        double s = 0.0;
+        for (int j = sub; j < nj; j += 16) {
+            float v[8];
+            load8_padded(x, row, d4, j, v);
+            const f16x8_t h = reinterpret_cast<const f16x8_t*>(y)[row * ds8 + j];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const double r = ldexp((double)(float)h[e], -shift) - (double)v[e];
+                s += r * r;
+            }
+        }
+        s = group_sum<16>(s);
+        const float f = norm_up(s);                                 // rounded up
+        if (f == f) m = fmaxf(m, f);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(reinterpret_cast<unsigned*>(out), __float_as_uint(m));
+}
+
 // bias[i] = -|c_i|^2 / 2 of float32 rows: what every score of row i starts from in the L2 scans (scan_kernel.h: k_scan<..., MET = 1>;
 // |q - c|^2 = |q|^2 - 2 (q.c - |c|^2 / 2)).  The squares of float32 values are exact in float64; their sum (four lanes a
 // row, then the four partial sums) is rounded ONCE to float32 -- the 2^-25 |c|^2 of select_dev.h: err_bound_l2, which also
@@ -331,6 +419,59 @@ int f16_resid_max(const float* x, const unsigned short* y, long n, int d, int sh
     hipLaunchKernelGGL(k_f16_resid_max, dim3((unsigned)blocks), dim3(256), 0, st, x, reinterpret_cast<const _Float16*>(y), n,
                        d, shift, out);
     return check_launch("k_f16_resid_max");
+}
+
+// the row-widening builders: d % 4 == 0, ds % 8 == 0, 0 < d <= ds <= 2^16; n == 0 is a no-op
+static int check_pad_rows(const char* what, const void* x, const void* y, long n, int d, int ds) {
+    if (n < 0 || d <= 0 || d % 4 || ds % 8 || d > ds || ds > 65536) {
+        set_error("%s: need n >= 0, 0 < d <= ds, d %% 4 == 0, ds %% 8 == 0 (d %d, ds %d)", what, d, ds);
+        return SSS_EINVAL;
+    }
+    if (n > 0 && (!x || !y || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y) & 15))) {
+        set_error("%s: rows and output are required, 16-byte aligned", what);
+        return SSS_EINVAL;
+    }
+    return SSS_OK;
+}
+static unsigned pad_grid(long chunks) {
+    long blocks = (chunks + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    return (unsigned)blocks;
+}
+
+int pad_rows_f32(const float* x, long n, int d, int ds, float* y, hipStream_t st) {
+    const int rc = check_pad_rows("pad_rows_f32", x, y, n, d, ds);
+    if (rc || n == 0) return rc;
+    hipLaunchKernelGGL(k_pad_rows_f32, dim3(pad_grid(n * (ds / 4))), dim3(256), 0, st, x, n, d / 4, ds / 4, y);
+    return check_launch("k_pad_rows_f32");
+}
+
+int pad_scale_f16(const float* x, long n, int d, int ds, int shift, unsigned short* y, hipStream_t st) {
+    const int rc = check_pad_rows("pad_scale_f16", x, y, n, d, ds);
+    if (rc) return rc;
+    if (shift < -160 || shift > 160) { set_error("pad_scale_f16: shift out of range"); return SSS_EINVAL; }
+    if (n == 0) return SSS_OK;
+    hipLaunchKernelGGL(k_pad_scale_f16, dim3(pad_grid(n * (ds / 8))), dim3(256), 0, st, x, n, d / 4, ds / 8, shift, y);
+    return check_launch("k_pad_scale_f16");
+}
+
+int pad_split_bf16(const float* x, long n, int d, int ds, unsigned short* y, hipStream_t st) {
+    const int rc = check_pad_rows("pad_split_bf16", x, y, n, d, ds);
+    if (rc || n == 0) return rc;
+    hipLaunchKernelGGL(k_pad_split_bf16, dim3(pad_grid(n * (ds / 8))), dim3(256), 0, st, x, n, d / 4, ds / 8, y);
+    return check_launch("k_pad_split_bf16");
+}
+
+int pad_f16_resid_max(const float* x, const unsigned short* y, long n, int d, int ds, int shift, float* out, hipStream_t st) {
+    const int rc = check_pad_rows("pad_f16_resid_max", x, y, n, d, ds);
+    if (rc) return rc;
+    if (shift < -160 || shift > 160 || (n > 0 && !out)) { set_error("pad_f16_resid_max: shift out of range or no output"); return SSS_EINVAL; }
+    if (n == 0) return SSS_OK;
+    long blocks = (n + 15) / 16;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(k_pad_f16_resid_max, dim3((unsigned)blocks), dim3(256), 0, st, x, reinterpret_cast<const _Float16*>(y), n, d / 4,
+                       ds / 8, shift, out);
+    return check_launch("k_pad_f16_resid_max");
 }
 
 int l2_row_bias(const float* c, long n, int d, float* bias, hipStream_t st) {

@@ -104,6 +104,7 @@ struct SelectArgs {
     int* status;
     int* unproven_count;        // optional device counter: += 1 per query left unproven
     int metric = 0;             // 1: L2 -- scan keys are q.c - |c|^2 / 2, scores are NEGATED squared distances (select_dev.h: query_bound)
+    int d_row = 0;              // elements of a STORED row of C when it is narrower than the scan (include/sss_pad.h); 0: d.  Q stays [nq, d]
 };
 
 int launch_select(const SelectArgs& a, hipStream_t st);
@@ -129,6 +130,7 @@ struct ThrArgs {
     int keep = 0;                   // k_thr_prepare: 1 = keep the rows already kept that pass the NEW threshold (compacted in place)
                                     //                instead of starting from an empty array (sss_ip_topk_long: disjoint levels)
     int metric = 0;                 // 1: L2 (as SelectArgs::metric; D_out holds distances: its column k-1 is an UPPER bound, negated on the way in)
+    int d_row = 0;                  // as SelectArgs::d_row (k_select_all's re-score; the range kernels never see it set)
 };
 int launch_thr_prepare(const ThrArgs& a, hipStream_t st);
 int launch_select_all(const ThrArgs& a, hipStream_t st);
@@ -206,6 +208,20 @@ size_t l2_topk_threshold_workspace_bytes(long nsel, long n, int d, int scan_dtyp
 int l2_topk_threshold(const float* q, const int* qsel, long nsel, const float* c, const void* c_scan, int scan_dtype, int corpus_shift,
                       float corpus_resid, const float* bias, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out,
                       long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st);
+// Scans at a width d_scan >= d_row of float32 rows stored d_row wide (ip_topk.hip, rowops.hip; include/sss_pad.h): images and
+// queries zero-extended to d_scan, the re-score from the d_row-wide rows.  bias: the L2 row bias, nullptr for inner product.
+int pad_rows_f32(const float* x, long n, int d, int ds, float* y, hipStream_t st);
+int pad_scale_f16(const float* x, long n, int d, int ds, int shift, unsigned short* y, hipStream_t st);
+int pad_split_bf16(const float* x, long n, int d, int ds, unsigned short* y, hipStream_t st);
+int pad_f16_resid_max(const float* x, const unsigned short* y, long n, int d, int ds, int shift, float* out, hipStream_t st);
+size_t pad_topk_workspace_bytes(long nq, long n, int d_row, int d_scan, int k, int scan_dtype);
+int pad_topk(const float* q, long nq, const float* c, const void* c_scan, int scan_dtype, int corpus_shift, float corpus_resid,
+             const float* bias, long n, int d_row, int d_scan, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out,
+             int* status, int* unproven_count, void* state, size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st);
+size_t pad_topk_threshold_workspace_bytes(long nsel, long n, int d_row, int d_scan, int scan_dtype);
+int pad_topk_threshold(const float* q, const int* qsel, long nsel, const float* c, const void* c_scan, int scan_dtype, int corpus_shift,
+                       float corpus_resid, const float* bias, long n, int d_row, int d_scan, int k, long id_offset, float corpus_max_norm,
+                       float* D_out, long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st);
 int profile_enable(int on);
 int profile_read(double* total_ms, int* launches);
 

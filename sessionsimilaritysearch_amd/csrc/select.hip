@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void k_select_fast(const SelectArgs A) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int q = blockIdx.x * 4 + wv;
     if (q >= A.nq) return;                                        // whole wave; no block-level sync below
-    const int rb = row_bytes(A.d, A.dtype);
+    const int rb = row_bytes(A.d, A.dtype), rbc = stored_row_bytes(A);      // a query row, a stored row
     const size_t per_wave = (size_t)FS_CAP * 8 + FS_K2 * 16 + 16 + rb;
     char* base = smem + wv * ((per_wave + 15) & ~(size_t)15);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(base);
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void k_select_fast(const SelectArgs A) {
     // ---- float64 re-score: one lane per candidate walks its corpus row (16-byte loads straight from
     // L2 / HBM, several in flight) sequentially in k -- the canonical order
     const int rtype = rescore_type(A.dtype, A.metric);
-    for (int c0 = 0; c0 < K2; c0 += 16) rescore16(sel, resc, c0, K2, A.C, rb, qrow, rtype, lane);
+    for (int c0 = 0; c0 < K2; c0 += 16) rescore16(sel, resc, c0, K2, A.C, rbc, qrow, rtype, lane);
     double B, unscale, off;
     query_bound(A, qrow, lane, B, unscale, off);
     wave_sync();
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256) void k_select_fast(const SelectArgs A) {
         if (K2x == FS_K2) open_end = true;
         wave_sync();
         if (K2x > K2) {
-            for (int c0 = K2; c0 < K2x; c0 += 16) rescore16(sel, resc, c0, K2x, A.C, rb, qrow, rtype, lane);
+            for (int c0 = K2; c0 < K2x; c0 += 16) rescore16(sel, resc, c0, K2x, A.C, rbc, qrow, rtype, lane);
             if (lane == 0) { *s_nvalid = 0; *s_kth = 0.0; }
             wave_sync();
             rank_and_write<64>(sel, resc, K2x, k, A.id_offset, Dq, Iq, lane, s_nvalid, s_kth, A.metric);
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_select_sort(const SelectArgs A
     __shared__ unsigned s_hist[260];
     __shared__ unsigned s_cnt;
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const int rb = row_bytes(A.d, A.dtype);
+    const int rb = row_bytes(A.d, A.dtype), rbc = stored_row_bytes(A);      // a query row, a stored row
     const int K2 = A.K2, k = A.k;
     float* Dq = A.D_out + (size_t)q * k;
     long* Iq = A.I_out + (size_t)q * k;
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_select_sort(const SelectArgs A
         const unsigned long long key = keys[c];
         const int id = key_id(key);
         double acc = 0.0;
-        if (key != 0 && id >= 0) acc = rescore_row(qrow, reinterpret_cast<const char*>(A.C) + (size_t)id * rb, rb / 16, rescore_type(A.dtype, A.metric));
+        if (key != 0 && id >= 0) acc = rescore_row(qrow, reinterpret_cast<const char*>(A.C) + (size_t)id * rbc, rbc / 16, rescore_type(A.dtype, A.metric));
         resc[c] = acc;
     }
     __syncthreads();

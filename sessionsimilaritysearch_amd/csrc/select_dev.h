@@ -56,27 +56,37 @@ __device__ __forceinline__ void wave_sync() {
 __device__ __forceinline__ double dot_chunk(double acc, const char* qrow, int v, f32x4 c, int dtype);
 // (DT: the element type as a compile-time constant -- with the three-way choice inside the unrolled chain the 32 chunk
 //  registers of a part went to scratch)
-template <int DT>
+// UNEVEN: rows whose chunk count is no multiple of four (rb % 64 != 0: float32 rows narrower than their scan, include/sss_pad.h) --
+// ceil(nchunks / 4) chunks a part, the last part short or empty (5/5/5/2 at d = 68, 1/0/0/0 at d = 4), still at most 32 a
+// part.  Every lane still loads a full window of `per` chunks at constant offsets from one address -- no load is guarded by
+// where the row ends (rescore_row says why) -- the window of a short or empty part CLAMPED back into the row, [nchunks - per,
+// nchunks); the chain then skips the window's first chunks, which belong to the parts before.  The even form is what it
+// always was: a compile-time choice, not a branch in it.
+template <int DT, bool UNEVEN = false>
 __device__ __forceinline__ void rescore16_t(const unsigned long long* sel, double* resc, int c0, int c1, const void* C, int rb,
                                             const char* qrow, int lane) {
     constexpr int dtype = DT;
     const int c = c0 + (lane >> 2), p = lane & 3;
-    const int per = rb / 64;                                       // chunks per part: 4 / 8 / 16 / 32 (rows of 256 .. 2048 bytes)
+    const int nch = rb / 16;
+    const int per = UNEVEN ? (nch + 3) / 4 : rb / 64;              // chunks per part: 4 / 8 / 16 / 32 (rows of 256 .. 2048 bytes)
     const unsigned long long key = c < c1 ? sel[c] : 0ull;
     const bool live = key != 0 && key_id(key) >= 0;
     constexpr int MAXP = 32;
     f32x4 ch[MAXP];
-    const char* row = reinterpret_cast<const char*>(C) + (size_t)(live ? key_id(key) : 0) * rb + (size_t)p * per * 16;
+    const int first = UNEVEN ? min(p * per, nch - per) : p * per;  // the lane's window: chunks [first, first + per)  (per <= nch)
+    const char* row = reinterpret_cast<const char*>(C) + (size_t)(live ? key_id(key) : 0) * rb + (size_t)first * 16;
 #pragma unroll
     for (int i = 0; i < MAXP; ++i)
         if (live && i < per) ch[i] = *reinterpret_cast<const f32x4*>(row + i * 16);
     double acc = 0.0;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
+        const int from = UNEVEN ? min(s * per, nch - per) : s * per;   // part s's window, and how much of it the parts before own
+        const int skip = s * per - from;
         if (live && p == s) {
 #pragma unroll
             for (int i = 0; i < MAXP; ++i)
-                if (i < per) acc = dot_chunk(acc, qrow, s * per + i, ch[i], dtype);
+                if (i < per && (!UNEVEN || i >= skip)) acc = dot_chunk(acc, qrow, from + i, ch[i], dtype);
         }
         if (s < 3) {                                               // hand the chain to the next part's lane
             const double up = __shfl_up(acc, 1);
@@ -85,9 +95,14 @@ __device__ __forceinline__ void rescore16_t(const unsigned long long* sel, doubl
     }
     if (c < c1 && p == 3) resc[c] = live ? (DT == DT_F32_L2 ? -acc : acc) : 0.0;
 }
+// rb: bytes of a STORED row (stored_row_bytes); qrow holds at least as many
 __device__ __forceinline__ void rescore16(const unsigned long long* sel, double* resc, int c0, int c1, const void* C, int rb,
                                           const char* qrow, int dtype, int lane) {
-    if (dtype == DT_F32) rescore16_t<DT_F32>(sel, resc, c0, c1, C, rb, qrow, lane);
+    if (rb & 63) {                                                 // float32 rows only (the other formats' scans take whole 256 bytes)
+        if (dtype == DT_F32_L2) rescore16_t<DT_F32_L2, true>(sel, resc, c0, c1, C, rb, qrow, lane);
+        else rescore16_t<DT_F32, true>(sel, resc, c0, c1, C, rb, qrow, lane);
+    }
+    else if (dtype == DT_F32) rescore16_t<DT_F32>(sel, resc, c0, c1, C, rb, qrow, lane);
     else if (dtype == DT_F32_L2) rescore16_t<DT_F32_L2>(sel, resc, c0, c1, C, rb, qrow, lane);
     else if (dtype == DT_H16) rescore16_t<DT_H16>(sel, resc, c0, c1, C, rb, qrow, lane);
     else if (dtype == DT_I8) rescore16_t<DT_I8>(sel, resc, c0, c1, C, rb, qrow, lane);
@@ -489,6 +504,10 @@ __device__ __forceinline__ void rescore_kept(const unsigned long long* surv, int
 // bytes of a STORED row of d elements (the exact element types: DT_F32, DT_I8, else DT_BF16 / DT_H16; the host's
 // elem_bytes, elem.h, also knows the scan-only images)
 __device__ __forceinline__ int row_bytes(int d, int dtype) { return d * (dtype == DT_F32 ? 4 : dtype == DT_I8 ? 1 : 2); }
+// bytes of a stored row of C (A: SelectArgs or ThrArgs): d_row elements where the rows are narrower than the scan's d
+// (include/sss_pad.h), else d.  The query rows of Q are always d wide.
+template <typename Args>
+__device__ __forceinline__ int stored_row_bytes(const Args& A) { return row_bytes(A.d_row ? A.d_row : A.d, A.dtype); }
 
 // the query row q of Q (rb bytes) into LDS, by the NT threads t of its wave or workgroup
 template <int NT>

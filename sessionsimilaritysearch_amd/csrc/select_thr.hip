@@ -186,7 +186,9 @@ __global__ __launch_bounds__(SORT_THREADS) void k_select_all(const ThrArgs A, in
     while (K2 < keep) K2 <<= 1;
     // canonical re-score of the survivors (rescore_kept: SA_ROWS rows at a time through the staging tile for long rows)
     char* stage = qrow + ((rb + 15) & ~15);                             // [SA_ROWS][SA_BYTES + 16]
-    rescore_kept<SA_ROWS>(surv, keep, K2, A.C, rb, rescore_type(A.dtype, A.metric), qrow, stage, tid,
+    // (stored rows narrower than the scan, ThrArgs::d_row: a stored row of 1024 bytes or more implies a query row -- the
+    //  host sizes the tile by it -- at least as long)
+    rescore_kept<SA_ROWS>(surv, keep, K2, A.C, stored_row_bytes(A), rescore_type(A.dtype, A.metric), qrow, stage, tid,
                           [&](int c, bool valid, double acc, int id) __attribute__((always_inline)) {
                               keys[c] = valid ? make_key((float)acc, id) : 0ull;     // (the scan keys are no longer needed)
                           });

@@ -51,6 +51,7 @@ _FORMATS = {f.name: f for f in (
 )}
 FUSED_DIMS = {f.name: f.fused_dims for f in _FORMATS.values()}
 F16_SCAN_DIMS = (128, 256, 512)                                  # scaled-f16 image: 2 bytes per element
+PAD_SCAN_MAX_D = 512             # pad_scan=True: float32 rows of 4 <= d <= 512, d % 4 == 0, scanned at the next width a scan has
 # scan="auto": the fastest scan whose error bound is still small against the spacing of the scores
 # around rank k (the spacing shrinks as k grows): one-pass f16 up to k = 128, bf16 split up to k = 500
 # (every k the fused path serves); the f32 MFMA scan is reached by escalation only.  Measured on random unit
@@ -230,9 +231,22 @@ class FlatIndex:
     Queries a scan leaves unproven are resolved in two further stages, both exact: the THRESHOLD RUNG
     (``search_threshold``: one more matrix-core scan for just those queries that keeps every row able to
     reach the k-th score already known, near ties and duplicate rows alike) and, for what exceeds its
-    capacity, the exhaustive kernels (``search_exhaustive``)."""
+    capacity, the exhaustive kernels (``search_exhaustive``).
 
-    def __init__(self, d: int, metric: str = "ip", device=None, dtype: str = "f32", scan: str | None = None):
+    ``pad_scan=True`` (off by default) gives a float32 index of ANY width ``4 <= d <= 512`` with ``d % 4 == 0`` the same
+    scans -- d = 200, the reference's default embedding width, among them; without it such an index runs on the exhaustive
+    kernels.  The scan images and the query batch are built at ``scan_width(scan)``, the next width the scan has (f16:
+    128 / 256 / 512; split and f32: 64 / 128 / 256; ``256 < d <= 512`` has the f16 scan only, whatever ``scan`` says), with
+    exact zero columns behind column d: they add nothing to a dot product or to ``|c|**2``, so scan, bound (taken at the
+    scan width) and proof are those of the wider corpus, and candidates are re-scored from the d-wide rows.  Results are
+    the same as without the switch.  It has no effect where d already has a scan (64 / 128 / 256 / 512, ``d % 64 == 0``
+    long rows) and on other dtypes.  An image costs ``scan_width`` elements a row: d = 200 on the f16 scan keeps 512 bytes
+    a row beside the 800-byte row."""
+
+    _pad = False                        # (class default: pad_scan off)
+
+    def __init__(self, d: int, metric: str = "ip", device=None, dtype: str = "f32", scan: str | None = None, *,
+                 pad_scan: bool = False):
         if metric not in ("ip", "l2"):
             raise ValueError("metric must be 'ip' or 'l2'")
         if dtype not in _FORMATS:
@@ -266,6 +280,11 @@ class FlatIndex:
         self._resid = None
         self._bias = None               # [cap] float32 -|row|^2 / 2: what the L2 scans start every score from
         self._bias_done = 0
+        # pad_scan: the scans run at scan_width(scan) >= d; where d has a scan of its own the switch changes nothing
+        self._pad = (bool(pad_scan) and dtype == "f32" and 4 <= self.d <= PAD_SCAN_MAX_D and self.d % 4 == 0
+                     and self.d % 64 != 0)
+        self._p32 = None                # [cap, scan_width("f32")] float32 rows, zero-extended       ("f32" scan of a padded index)
+        self._p32_done = 0
         self._xb = torch.empty((0, self.d), dtype=self._tdtype, device=self.device)
         self._store = self._xb          # backing storage of _xb (grown geometrically by add())
         self._cmax_t = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -302,7 +321,7 @@ class FlatIndex:
         """Which candidate scan a fused search for k results uses ("" = none: exhaustive path)."""
         if self.metric != "ip" or k <= 0 or self.ntotal == 0:
             return ""
-        fused_shape = self.d in self._fmt.fused_dims or (self.dtype == "f32" and self.d in F16_SCAN_DIMS)
+        fused_shape = self.d in self._fmt.fused_dims or (self.dtype == "f32" and self.d in F16_SCAN_DIMS) or self._pad
         if not fused_shape:
             return self._long_or_none(k)         # rows longer than the register-resident scans take (D = 1600 ...)
         if k > FUSED_MAX_K:
@@ -324,6 +343,8 @@ class FlatIndex:
             return served[0] if served else ""
         if want == "f16" and not self._scan_served("f16"):
             want = "split"
+        if self._pad and not self._scan_served(want):
+            want = "f16"                         # pad_scan, 256 < d <= 512: the f16 image is the only scan that wide
         return want if self._scan_served(want) else ""
 
     def l2_scan_for(self, k: int) -> str:
@@ -350,8 +371,16 @@ class FlatIndex:
         return "long" if (self.d % 64 == 0 and row_bytes <= LONG_MAX_ROW_BYTES and k <= LONG_MAX_K) else ""
 
     def _scan_served(self, scan: str) -> bool:
-        """Does a fused kernel exist for this scan at this d?"""
-        return self.d in (F16_SCAN_DIMS if scan == "f16" else FUSED_DIMS["f32"])
+        """Does a fused kernel exist for this scan at this d (``pad_scan``: at a width this d is padded to)?"""
+        return self.scan_width(scan) != 0
+
+    def scan_width(self, scan: str) -> int:
+        """The row width scan "f16" / "split" / "f32" runs at on this float32 index: d where d is one of the scan's
+        widths; on a ``pad_scan`` index the smallest of them that is at least d; 0 where the scan does not serve it."""
+        widths = F16_SCAN_DIMS if scan == "f16" else FUSED_DIMS["f32"]
+        if self._pad:
+            return next((w for w in widths if w >= self.d), 0)
+        return self.d if self.d in widths else 0
 
     def next_scan(self, scan: str) -> str:
         """The next scan up the precision ladder that this d can run ("" = none)."""
@@ -418,15 +447,22 @@ class FlatIndex:
         L, st = _lib.lib(), _lib.stream_ptr(self.device)
         _lib.check(L.sss_abs_max(self._xb[lo:].data_ptr(), (n - lo) * self.d, self._amax_t.data_ptr(), st), "sss_abs_max")
         amax = float(self._amax_t.item())
-        self._f16 = self._grow_image(self._f16, lo, self.d, torch.float16)
+        ds = self.scan_width("f16") if self._pad else self.d
+        self._f16 = self._grow_image(self._f16, lo, ds, torch.float16)
         if lo == 0 or not (amax * 2.0 ** self._c_shift < 32768.0):
             self._c_shift = int(L.sss_f16_shift(amax))
             self._resid_t.zero_()
             lo = 0
-        _lib.check(L.sss_scale_f16(self._xb[lo:].data_ptr(), (n - lo) * self.d, self._c_shift,
-                                   self._f16[lo:].data_ptr(), st), "sss_scale_f16")
-        _lib.check(L.sss_f16_resid_max(self._xb[lo:].data_ptr(), self._f16[lo:].data_ptr(), n - lo, self.d,
-                                       self._c_shift, self._resid_t.data_ptr(), st), "sss_f16_resid_max")
+        if self._pad:                   # the same image, ds wide with zero columns behind column d (include/sss_pad.h)
+            _lib.check(L.sss_pad_scale_f16(self._xb[lo:].data_ptr(), n - lo, self.d, ds, self._c_shift,
+                                           self._f16[lo:].data_ptr(), st), "sss_pad_scale_f16")
+            _lib.check(L.sss_pad_f16_resid_max(self._xb[lo:].data_ptr(), self._f16[lo:].data_ptr(), n - lo, self.d, ds,
+                                               self._c_shift, self._resid_t.data_ptr(), st), "sss_pad_f16_resid_max")
+        else:
+            _lib.check(L.sss_scale_f16(self._xb[lo:].data_ptr(), (n - lo) * self.d, self._c_shift,
+                                       self._f16[lo:].data_ptr(), st), "sss_scale_f16")
+            _lib.check(L.sss_f16_resid_max(self._xb[lo:].data_ptr(), self._f16[lo:].data_ptr(), n - lo, self.d,
+                                           self._c_shift, self._resid_t.data_ptr(), st), "sss_f16_resid_max")
         self._resid = None
         self._f16_done = n
 
@@ -440,11 +476,37 @@ class FlatIndex:
         n, lo = self.ntotal, self._split_done
         if lo == n and self._split is not None:
             return
-        self._split = self._grow_image(self._split, lo, 2 * self.d, torch.bfloat16)
-        rc = _lib.lib().sss_split_bf16(self._xb[lo:].data_ptr(), n - lo, self.d, self._split[lo:].data_ptr(),
-                                       _lib.stream_ptr(self.device))
-        _lib.check(rc, "sss_split_bf16")
+        if self._pad:
+            ds = self.scan_width("split")
+            self._split = self._grow_image(self._split, lo, 2 * ds, torch.bfloat16)
+            rc = _lib.lib().sss_pad_split_bf16(self._xb[lo:].data_ptr(), n - lo, self.d, ds, self._split[lo:].data_ptr(),
+                                               _lib.stream_ptr(self.device))
+            _lib.check(rc, "sss_pad_split_bf16")
+        else:
+            self._split = self._grow_image(self._split, lo, 2 * self.d, torch.bfloat16)
+            rc = _lib.lib().sss_split_bf16(self._xb[lo:].data_ptr(), n - lo, self.d, self._split[lo:].data_ptr(),
+                                           _lib.stream_ptr(self.device))
+            _lib.check(rc, "sss_split_bf16")
         self._split_done = n
+
+    def _ensure_p32(self):
+        """Bring the zero-extended float32 rows up to date: what the "f32" scan of a ``pad_scan`` index reads."""
+        n, lo = self.ntotal, self._p32_done
+        if lo == n and self._p32 is not None:
+            return
+        ds = self.scan_width("f32")
+        self._p32 = self._grow_image(self._p32, lo, ds, torch.float32)
+        rc = _lib.lib().sss_pad_rows_f32(self._xb[lo:].data_ptr(), n - lo, self.d, ds, self._p32[lo:].data_ptr(),
+                                         _lib.stream_ptr(self.device))
+        _lib.check(rc, "sss_pad_rows_f32")
+        self._p32_done = n
+
+    def _padded_queries(self, q: torch.Tensor, ds: int) -> torch.Tensor:
+        """The query batch zero-extended to ds columns: one launch (``sss_pad_rows_f32``)."""
+        qp = torch.empty((q.shape[0], ds), dtype=torch.float32, device=self.device)
+        rc = _lib.lib().sss_pad_rows_f32(q.data_ptr(), q.shape[0], self.d, ds, qp.data_ptr(), _lib.stream_ptr(self.device))
+        _lib.check(rc, "sss_pad_rows_f32")
+        return qp
 
     def _ensure_bias(self):
         """Bring the L2 row bias up to date (rows added since the last call)."""
@@ -481,6 +543,9 @@ class FlatIndex:
         if mode == "split":
             self._ensure_split()
             return self._split, _SCAN_CODE["split"], 0, 0.0
+        if self._pad and mode == "f32":
+            self._ensure_p32()
+            return self._p32, self._fmt.code, 0, 0.0
         return self._xb, self._fmt.code, 0, 0.0
 
     def _require_d_aligned(self):
@@ -545,6 +610,7 @@ class FlatIndex:
         self._split, self._split_done = None, 0
         self._f16, self._f16_done = None, 0
         self._bias, self._bias_done = None, 0
+        self._p32, self._p32_done = None, 0
         self._amax_t.zero_()
         self._resid_t.zero_()
         self._auto_level.clear()
@@ -588,7 +654,10 @@ class FlatIndex:
             if unproven_count is not None:
                 unproven_count += (status != 0).sum().to(torch.int32)
             return D, I, status
-        if self.metric == "l2":
+        if self._pad:
+            ds = self.scan_width(mode)
+            nbytes = L.sss_pad_topk_workspace_bytes(nq, n, self.d, ds, k, code)
+        elif self.metric == "l2":
             nbytes = L.sss_l2_topk_workspace_bytes(nq, n, self.d, k, code)
         elif mode == "f16":
             nbytes = L.sss_ip_topk_f16_workspace_bytes(nq, n, self.d, k)
@@ -601,7 +670,12 @@ class FlatIndex:
         tail = (self.corpus_max_norm(), D.data_ptr(), I.data_ptr(), status.data_ptr(),
                 0 if unproven_count is None else unproven_count.data_ptr(),
                 self._state.data_ptr(), self._state.numel(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
-        if self.metric == "l2":
+        if self._pad:
+            # the scan reads the padded batch and the ds-wide image, the re-score the d-wide rows (include/sss_pad.h)
+            qp = self._padded_queries(q, ds)
+            rc = L.sss_pad_topk(qp.data_ptr(), nq, self._xb.data_ptr(), image.data_ptr(), code, shift, resid,
+                                self._bias.data_ptr() if self.metric == "l2" else None, n, self.d, ds, k, self.id_offset, *tail)
+        elif self.metric == "l2":
             rc = L.sss_l2_topk(q.data_ptr(), nq, self._xb.data_ptr(), image.data_ptr(), code, shift, resid,
                                self._bias.data_ptr(), n, self.d, k, self.id_offset, *tail)
         elif mode == "f16":
@@ -615,7 +689,7 @@ class FlatIndex:
                                self.id_offset, *tail)
         if rc != 0:
             self._state = None          # re-made (zeroed) on the next call
-        _lib.check(rc, "sss_l2_topk" if self.metric == "l2" else "sss_ip_topk")
+        _lib.check(rc, "sss_pad_topk" if self._pad else "sss_l2_topk" if self.metric == "l2" else "sss_ip_topk")
         return D, I, status
 
     def l2_rung_scan(self) -> str:
@@ -666,6 +740,18 @@ class FlatIndex:
         image, code, shift, resid = self._scan_image(mode)
         sel = rows.to(device=self.device, dtype=torch.int32).contiguous()
         n = self.ntotal
+        if self._pad:
+            ds = self.scan_width(mode)
+            if l2:
+                self._ensure_bias()
+            qp = self._padded_queries(q, ds)
+            ws = self._ws.get(L.sss_pad_topk_threshold_workspace_bytes(sel.numel(), n, self.d, ds, code))
+            rc = L.sss_pad_topk_threshold(qp.data_ptr(), sel.data_ptr(), sel.numel(), self._xb.data_ptr(), image.data_ptr(), code,
+                                          shift, resid, self._bias.data_ptr() if l2 else None, n, self.d, ds, k, self.id_offset,
+                                          self.corpus_max_norm(), D.data_ptr(), I.data_ptr(), status.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
+            _lib.check(rc, "sss_pad_topk_threshold")
+            return sel[status[sel.long()] != 0]
         if l2:
             self._ensure_bias()
             ws = self._ws.get(L.sss_l2_topk_threshold_workspace_bytes(sel.numel(), n, self.d, code))
@@ -785,7 +871,8 @@ class FlatIndex:
         """Exact range search, CUDA tensors in and out: (lims int64 [nq + 1], D float32 [lims[nq]], I int64 [lims[nq]]).
         Query i's results are D[lims[i]:lims[i+1]] / I[...], in ascending id order: every row with canonical score
         > radius (inner product) or squared distance < radius (L2), radius converted to float32.  Syncs once per chunk
-        of queries (to size the output)."""
+        of queries (to size the output).  A ``pad_scan`` index answers on the exhaustive route (``last_range_scan == ""``):
+        the fused range route at padded widths is not built."""
         if q.dtype != self._tdtype:
             q = self._rows(q, "range_search")
         nq, n = q.shape[0], self.ntotal
@@ -797,7 +884,7 @@ class FlatIndex:
         self._require_d_aligned()
         L, st = _lib.lib(), _lib.stream_ptr(self.device)
         pieces = []                     # (query rows [host int64], their counts [host int64], D, I) in the order they were produced
-        mode = self.last_range_scan = self.rung_scan()
+        mode = self.last_range_scan = "" if self._pad else self.rung_scan()      # (pad_scan: the exhaustive route)
         left = []                       # query rows for the exhaustive route
         if mode:
             image, code, shift, resid = self._scan_image(mode)
@@ -886,16 +973,17 @@ class FlatIndex:
         return lims, D, I
 
 
-def build_index(emb, metric: str, device=None) -> FlatIndex:
-    """Reference ``build_index(emb, metric)`` (test_amazon_filterd.py:207-223)."""
+def build_index(emb, metric: str, device=None, *, pad_scan: bool = False) -> FlatIndex:
+    """Reference ``build_index(emb, metric)`` (test_amazon_filterd.py:207-223).  ``pad_scan``: as ``FlatIndex`` (the
+    matrix-core scans for widths without one of their own, the reference's emb_len = 200 among them)."""
     if metric == "cos":
-        index = FlatIndex(emb.shape[1], "ip", device)
+        index = FlatIndex(emb.shape[1], "ip", device, pad_scan=pad_scan)
         index.add(normalize(emb))
     elif metric == "l2":
-        index = FlatIndex(emb.shape[1], "l2", device)
+        index = FlatIndex(emb.shape[1], "l2", device, pad_scan=pad_scan)
         index.add(emb)
     elif metric == "ip":
-        index = FlatIndex(emb.shape[1], "ip", device)
+        index = FlatIndex(emb.shape[1], "ip", device, pad_scan=pad_scan)
         index.add(emb)
     else:
         raise RuntimeError("Unregnozed metric", metric)
