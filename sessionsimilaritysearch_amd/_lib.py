@@ -1,4 +1,5 @@
-"""ctypes binding of libsss.so (the C ABI declared in include/sss.h, include/sss_sparse.h, include/sss_l2.h and include/sss_pad.h).
+"""ctypes binding of libsss.so (the C ABI declared in include/sss.h, include/sss_sparse.h, include/sss_l2.h, include/sss_pad.h
+and include/sss_graph.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails, this
 module raises.  ``build()`` compiles the library in-tree with hipcc for gfx950.
@@ -146,6 +147,14 @@ _PAD_SIGNATURES = {
                                        c_void_p]),
 }
 
+# include/sss_graph.h one to one (the graph builder with ignore_query and the last-click outputs)
+GRAPH_IGNORE_QUERY = 1      # SSS_GRAPH_IGNORE_QUERY
+_GRAPH_SIGNATURES = {
+    "sss_graph_counts_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sss_graph_fill_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
+}
+
 
 class LinearProblem(ctypes.Structure):
     """``sss_linear_problem`` of include/sss.h."""
@@ -191,6 +200,11 @@ def pad_symbols():
     return sorted(_PAD_SIGNATURES)
 
 
+def graph_symbols():
+    """The entry points of include/sss_graph.h."""
+    return sorted(_GRAPH_SIGNATURES)
+
+
 def build(verbose: bool = False) -> str:
     """Compile libsss.so for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-C", CSRC, "-j4"]
@@ -213,7 +227,7 @@ def lib():
                 "sessionsimilaritysearch_amd/csrc`). There is no CPU fallback.")
         h = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (*_SIGNATURES.items(), *_SPARSE_SIGNATURES.items(), *_L2_SIGNATURES.items(),
-                                   *_PAD_SIGNATURES.items()):
+                                   *_PAD_SIGNATURES.items(), *_GRAPH_SIGNATURES.items()):
             fn = getattr(h, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = h

@@ -1,4 +1,5 @@
-// extern "C" surface of libsss (declared in include/sss.h, include/sss_sparse.h, include/sss_l2.h and include/sss_pad.h) + error plumbing.
+// extern "C" surface of libsss (declared in include/sss.h, include/sss_sparse.h, include/sss_l2.h, include/sss_pad.h and
+// include/sss_graph.h) + error plumbing.
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -10,6 +11,7 @@
 #include "../../include/sss_sparse.h"
 #include "../../include/sss_l2.h"
 #include "../../include/sss_pad.h"
+#include "../../include/sss_graph.h"
 #include "sss_common.h"
 #include "scan.h"
 #include "kargs.h"
@@ -93,8 +95,9 @@ int hamming_topk_exhaustive(const unsigned char*, const int*, long, const unsign
                             size_t, hipStream_t);
 int pack_sign_bits(const float*, long, int, long, unsigned char*, int, hipStream_t);
 size_t graph_scratch_ints(long S);
-int graph_counts(const long*, const unsigned char*, const long*, long, int*, int*, int*, hipStream_t);
-int graph_fill(const long*, const unsigned char*, const long*, const long*, long, const int*, const GraphOut&, hipStream_t);
+int graph_counts(const long*, const unsigned char*, const long*, long, bool, int*, int*, int*, hipStream_t);
+int graph_fill(const long*, const unsigned char*, const long*, const long*, long, bool, const int*, const GraphOut&, float*, int*,
+               hipStream_t);
 int session_vectors_count(const long*, const unsigned char*, const long*, long, long, int*, int*, hipStream_t);
 int session_vectors_fill(const long*, const unsigned char*, const long*, long, long, int, double, const long*, int*, float*, int*,
                          hipStream_t);
@@ -358,19 +361,23 @@ size_t sss_graph_scratch_ints(int64_t n_sessions) { return sss::graph_scratch_in
 int sss_graph_counts(const int64_t* sess_ptr, const uint8_t* is_search, const int64_t* item_id, int64_t n_sessions,
                      int32_t* bases, int32_t* scratch, int32_t* err, void* stream) {
     return sss::graph_counts(reinterpret_cast<const long*>(sess_ptr), is_search, reinterpret_cast<const long*>(item_id),
-                             n_sessions, bases, scratch, err, ST(stream));
+                             n_sessions, false, bases, scratch, err, ST(stream));
 }
-int sss_graph_fill(const int64_t* sess_ptr, const uint8_t* is_search, const int64_t* item_id, const int64_t* query_tok,
-                   int64_t n_sessions, const int32_t* bases, const sss_graph_out* o, void* stream) {
-    if (!o) { sss::set_error("graph_fill: null outputs"); return SSS_EINVAL; }
+static sss::GraphOut graph_out(const sss_graph_out* o) {
     sss::GraphOut g;
     g.q_x = reinterpret_cast<long*>(o->q_x); g.q_batch = reinterpret_cast<long*>(o->q_batch); g.q_pos = o->q_pos;
     g.p_x = reinterpret_cast<long*>(o->p_x); g.p_batch = reinterpret_cast<long*>(o->p_batch);
     g.p_cnt = reinterpret_cast<long*>(o->p_cnt);
     g.rowptr_qp = o->rowptr_qp; g.col_qp = o->col_qp; g.rowptr_pq = o->rowptr_pq; g.col_pq = o->col_pq;
     g.rowptr_pp = o->rowptr_pp; g.col_pp = o->col_pp; g.w_pp = o->w_pp; g.src_row = o->src_row; g.pos_id = o->pos_id;
+    return g;
+}
+int sss_graph_fill(const int64_t* sess_ptr, const uint8_t* is_search, const int64_t* item_id, const int64_t* query_tok,
+                   int64_t n_sessions, const int32_t* bases, const sss_graph_out* o, void* stream) {
+    if (!o) { sss::set_error("graph_fill: null outputs"); return SSS_EINVAL; }
     return sss::graph_fill(reinterpret_cast<const long*>(sess_ptr), is_search, reinterpret_cast<const long*>(item_id),
-                           reinterpret_cast<const long*>(query_tok), n_sessions, bases, g, ST(stream));
+                           reinterpret_cast<const long*>(query_tok), n_sessions, false, bases, graph_out(o), nullptr, nullptr,
+                           ST(stream));
 }
 int sss_knn_item_vote(const float* D, const int64_t* I, int64_t nq, int s, const int64_t* items_ptr, const int32_t* items,
                       int64_t id_offset, int64_t n_sessions, int k, int64_t* out_items, double* out_weights,
@@ -459,6 +466,27 @@ int sss_pad_topk_threshold(const float* q, const int32_t* qsel, int64_t nsel, co
     return sss::pad_topk_threshold(q, qsel, nsel, corpus, scan_image, scan_dtype, corpus_shift, corpus_resid_norm, bias, n, d_row, d_scan,
                                    k, id_offset, corpus_max_norm, D_out, reinterpret_cast<long*>(I_out), status, workspace,
                                    workspace_bytes, ST(stream));
+}
+
+// ---- include/sss_graph.h
+// (the action arrays of a table without a single action are legitimately NULL: only what every build dereferences is checked)
+int sss_graph_counts_ex(const int64_t* sess_ptr, const uint8_t* is_search, const int64_t* item_id, int64_t n_sessions, int flags,
+                        int32_t* bases, int32_t* scratch, int32_t* err, void* stream) {
+    if (flags & ~SSS_GRAPH_IGNORE_QUERY) { sss::set_error("graph_counts_ex: unknown flags 0x%x", flags); return SSS_EINVAL; }
+    if (n_sessions <= 0) { sss::set_error("graph_counts_ex: need at least one session"); return SSS_EINVAL; }
+    if (!sess_ptr || !bases || !scratch || !err) { sss::set_error("graph_counts_ex: null sess_ptr / bases / scratch / err"); return SSS_EINVAL; }
+    return sss::graph_counts(reinterpret_cast<const long*>(sess_ptr), is_search, reinterpret_cast<const long*>(item_id),
+                             n_sessions, (flags & SSS_GRAPH_IGNORE_QUERY) != 0, bases, scratch, err, ST(stream));
+}
+int sss_graph_fill_ex(const int64_t* sess_ptr, const uint8_t* is_search, const int64_t* item_id, const int64_t* query_tok,
+                      int64_t n_sessions, int flags, const int32_t* bases, const sss_graph_out* o, float* last_click_mask,
+                      int32_t* last_node, void* stream) {
+    if (flags & ~SSS_GRAPH_IGNORE_QUERY) { sss::set_error("graph_fill_ex: unknown flags 0x%x", flags); return SSS_EINVAL; }
+    if (n_sessions <= 0) { sss::set_error("graph_fill_ex: need at least one session"); return SSS_EINVAL; }
+    if (!sess_ptr || !bases || !o) { sss::set_error("graph_fill_ex: null sess_ptr / bases / outputs"); return SSS_EINVAL; }
+    return sss::graph_fill(reinterpret_cast<const long*>(sess_ptr), is_search, reinterpret_cast<const long*>(item_id),
+                           reinterpret_cast<const long*>(query_tok), n_sessions, (flags & SSS_GRAPH_IGNORE_QUERY) != 0, bases,
+                           graph_out(o), last_click_mask, last_node, ST(stream));
 }
 
 }  // extern "C"

@@ -14,6 +14,18 @@
 // -> k_session_fill (recomputes the lane state and writes every array at its final offset).
 // Distinct items keep first-occurrence order (the reference's `list(set(...))` is hash order;
 // documented deviation, sessions.py).
+//
+// IQ (template parameter of both sweeps) = the reference's ignore_query=True (:101-103, CFG.ignore_query, config.py:8):
+// the graph of the session's clicks alone.  The lanes stay the RAW actions -- a search lane just takes no part -- so
+// the limit is 64 raw actions per session in BOTH modes, however few of them are clicks.  What changes is the clock:
+// a click's position is its rank among the clicks popcount(cm & lt), the session length is the click count, the root
+// is the only query node (q_pos = nclk, counts[0] = 1, Nq = S) and every click edge starts there.  First occurrences,
+// transitions and weights never looked at searches.  IQ = false compiles to the code without the parameter.
+//
+// Two optional outputs of k_session_fill (either may be NULL), include/sss_graph.h: last_click_mask float32 [Np], 1.0
+// at the product node of the session's last click (the highest bit of the click ballot; the "unknown item" node of a
+// session without clicks), 0.0 elsewhere -- data['product'].last_click_mask of :203-216 -- and last_node int32 [S],
+// that node's batch-global id.
 #include "sss_common.h"
 #include "kargs.h"
 
@@ -73,6 +85,7 @@ __device__ __forceinline__ LaneState lane_state(const long* __restrict__ sess_pt
     return L;
 }
 
+template <bool IQ>
 __global__ __launch_bounds__(256) void k_session_counts(const long* __restrict__ sess_ptr,
                                                         const unsigned char* __restrict__ is_search,
                                                         const long* __restrict__ item_id, long S,
@@ -88,7 +101,7 @@ __global__ __launch_bounds__(256) void k_session_counts(const long* __restrict__
     const LaneState L = lane_state(sess_ptr, is_search, item_id, s, t);
     if (t == 0) {
         const int nclk = __builtin_popcountll(L.cm), nd = __builtin_popcountll(L.fm);
-        counts[0 * (S + 1) + s] = 1 + __builtin_popcountll(L.sm);
+        counts[0 * (S + 1) + s] = IQ ? 1 : 1 + __builtin_popcountll(L.sm);   // IQ: the root alone
         counts[1 * (S + 1) + s] = nd > 0 ? nd : 1;                // a session without clicks gets the "unknown item" node
         counts[2 * (S + 1) + s] = nclk > 0 ? nclk : 1;            // ... with one expanded row (pos id 0)
         counts[3 * (S + 1) + s] = nclk;
@@ -143,10 +156,12 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_add(int* __restrict__ data,
 }
 
 
+template <bool IQ>
 __global__ __launch_bounds__(256) void k_session_fill(const long* __restrict__ sess_ptr,
                                                       const unsigned char* __restrict__ is_search,
                                                       const long* __restrict__ item_id, const long* __restrict__ query_tok,
-                                                      long S, const int* __restrict__ bases, const GraphOut O) {
+                                                      long S, const int* __restrict__ bases, const GraphOut O,
+                                                      float* __restrict__ last_click_mask, int* __restrict__ last_node) {
     const long s = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int t = threadIdx.x & 63;
     if (s >= S) return;
@@ -156,20 +171,24 @@ __global__ __launch_bounds__(256) void k_session_fill(const long* __restrict__ s
     const int qb = bases[0 * (S + 1) + s], pb = bases[1 * (S + 1) + s], xb = bases[2 * (S + 1) + s];
     const int eb = bases[3 * (S + 1) + s], ppb = bases[4 * (S + 1) + s];
     const int Xp = bases[2 * (S + 1) + S], Nq = bases[0 * (S + 1) + S];   // expanded product rows, query nodes in the batch
-    const int n = L.n;
-    const long a0 = sess_ptr[s];
-    // ---- query nodes: the root, then one per search (util_amazon_filtered.py:7-22)
-    const int lq = __builtin_popcountll(L.sm & L.lt);            // searches before this action
+    const int n = L.n;                                           // raw actions: the bound of every lane loop
+    const int rank = __builtin_popcountll(L.cm & L.lt);          // clicks before this action
+    const int len = IQ ? __builtin_popcountll(L.cm) : n;         // len(seq) of the reference: IQ counts the clicks only
+    const int j = IQ ? rank : t;                                 // this action's index in that sequence
+    // ---- query nodes: the root, then one per search (util_amazon_filtered.py:7-22); IQ: the root alone
+    const int lq = IQ ? 0 : __builtin_popcountll(L.sm & L.lt);   // searches before this action
     if (t == 0) {
-        O.q_x[qb] = 0; O.q_pos[qb] = n; O.q_batch[qb] = s;
+        O.q_x[qb] = 0; O.q_pos[qb] = len; O.q_batch[qb] = s;
         O.rowptr_pq[qb] = eb;
-        O.src_row[Xp + qb] = qb; O.pos_id[Xp + qb] = n;
+        O.src_row[Xp + qb] = qb; O.pos_id[Xp + qb] = len;
     }
-    if (L.srch) {
-        const int k = qb + lq + 1;
-        O.q_x[k] = query_tok[a0 + t]; O.q_pos[k] = n - (t + 1); O.q_batch[k] = s;
-        O.rowptr_pq[k] = eb + __builtin_popcountll(L.cm & L.lt);
-        O.src_row[Xp + k] = k; O.pos_id[Xp + k] = n - (t + 1);
+    if constexpr (!IQ) {
+        if (L.srch) {
+            const int k = qb + lq + 1;
+            O.q_x[k] = query_tok[sess_ptr[s] + t]; O.q_pos[k] = n - (t + 1); O.q_batch[k] = s;
+            O.rowptr_pq[k] = eb + rank;
+            O.src_row[Xp + k] = k; O.pos_id[Xp + k] = n - (t + 1);
+        }
     }
     // ---- product nodes (first occurrences), their edge / row offsets
     int node_off = 0, pp_before = 0;
@@ -182,24 +201,29 @@ __global__ __launch_bounds__(256) void k_session_fill(const long* __restrict__ s
         if (uu && L.clk && bu < L.pidx) ++pp_before;             // unique transitions into earlier nodes
     }
     const int nd = __builtin_popcountll(L.fm);
+    // the session's last click = the highest bit of the click ballot; its product node carries the mask (:203-216)
+    const int lastp = __shfl(L.pidx, L.cm ? 63 - __builtin_clzll(L.cm) : 0);
     if (L.isfirst) {
         const int node = pb + L.pidx;
         O.p_x[node] = L.item; O.p_cnt[node] = L.cnt_same; O.p_batch[node] = s;
         O.rowptr_qp[node] = eb + node_off;
         O.rowptr_pp[node] = ppb + pp_before;
+        if (last_click_mask) last_click_mask[node] = L.pidx == lastp ? 1.0f : 0.0f;
     }
     if (nd == 0 && t == 0) {                                     // no click at all: the "unknown item" node (:132-135)
         O.p_x[pb] = 0; O.p_cnt[pb] = 1; O.p_batch[pb] = s;
         O.rowptr_qp[pb] = eb; O.rowptr_pp[pb] = ppb;
         O.src_row[xb] = pb; O.pos_id[xb] = 0;
+        if (last_click_mask) last_click_mask[pb] = 1.0f;
     }
+    if (t == 0 && last_node) last_node[s] = nd == 0 ? pb : pb + lastp;
     // ---- clicks: grouped by product node in time order (expanded rows, CSR qp), in action order (CSR pq)
     if (L.clk) {
         const int g = node_off + L.earlier_same;
         O.src_row[xb + g] = pb + L.pidx;
-        O.pos_id[xb + g] = n - t;                                // len(seq) - j  (:82)
+        O.pos_id[xb + g] = len - j;                              // len(seq) - j  (:82)
         O.col_qp[eb + g] = qb + lq;                              // most recent query node (:183-191)
-        O.col_pq[eb + __builtin_popcountll(L.cm & L.lt)] = pb + L.pidx;
+        O.col_pq[eb + rank] = pb + L.pidx;
     }
     // ---- unique transitions a -> b, grouped by target b in first-occurrence order (:199-218)
     int pos = 0;
@@ -222,12 +246,14 @@ __global__ __launch_bounds__(256) void k_session_fill(const long* __restrict__ s
 size_t graph_scratch_ints(long S) { return (size_t)NC * ((S + SCAN_BLOCK - 1) / SCAN_BLOCK + 1); }
 
 // bases: int32 [NC][S+1] (out: exclusive scans, totals at [S]); scratch: graph_scratch_ints(S) ints; err: int32 [1]
-int graph_counts(const long* sess_ptr, const unsigned char* is_search, const long* item_id, long S, int* bases, int* scratch,
-                 int* err, hipStream_t st) {
+// ignore_query selects the IQ instantiation of both sweeps
+int graph_counts(const long* sess_ptr, const unsigned char* is_search, const long* item_id, long S, bool ignore_query, int* bases,
+                 int* scratch, int* err, hipStream_t st) {
     if (S <= 0) { set_error("graph_counts: need at least one session"); return SSS_EINVAL; }
     if (hipMemsetAsync(err, 0, sizeof(int), st) != hipSuccess) { set_error("graph_counts: memset failed"); return SSS_EHIP; }
     const unsigned nb = (unsigned)((S * 64 + 255) / 256);
-    hipLaunchKernelGGL(k_session_counts, dim3(nb), dim3(256), 0, st, sess_ptr, is_search, item_id, S, bases, err);
+    if (ignore_query) hipLaunchKernelGGL(k_session_counts<true>, dim3(nb), dim3(256), 0, st, sess_ptr, is_search, item_id, S, bases, err);
+    else hipLaunchKernelGGL(k_session_counts<false>, dim3(nb), dim3(256), 0, st, sess_ptr, is_search, item_id, S, bases, err);
     int rc = check_launch("k_session_counts");
     if (rc) return rc;
     const int nblk = (int)((S + SCAN_BLOCK - 1) / SCAN_BLOCK);
@@ -237,11 +263,17 @@ int graph_counts(const long* sess_ptr, const unsigned char* is_search, const lon
     return check_launch("k_scan");
 }
 
+// last_click_mask [Np] / last_node [S]: optional (NULL = not written); query_tok is not read under ignore_query
 int graph_fill(const long* sess_ptr, const unsigned char* is_search, const long* item_id, const long* query_tok, long S,
-               const int* bases, const GraphOut& out, hipStream_t st) {
+               bool ignore_query, const int* bases, const GraphOut& out, float* last_click_mask, int* last_node, hipStream_t st) {
     if (S <= 0) { set_error("graph_fill: need at least one session"); return SSS_EINVAL; }
     const unsigned nb = (unsigned)((S * 64 + 255) / 256);
-    hipLaunchKernelGGL(k_session_fill, dim3(nb), dim3(256), 0, st, sess_ptr, is_search, item_id, query_tok, S, bases, out);
+    if (ignore_query)
+        hipLaunchKernelGGL(k_session_fill<true>, dim3(nb), dim3(256), 0, st, sess_ptr, is_search, item_id, query_tok, S, bases, out,
+                           last_click_mask, last_node);
+    else
+        hipLaunchKernelGGL(k_session_fill<false>, dim3(nb), dim3(256), 0, st, sess_ptr, is_search, item_id, query_tok, S, bases, out,
+                           last_click_mask, last_node);
     return check_launch("k_session_fill");
 }
 

@@ -350,6 +350,9 @@ class SessionEncoder:
         if int(pb.pos_id.shape[0]) != pb.n_clicks + pb.Nq:
             raise _lib.SssError("product pos_emb_id must have sum(cnt) entries")
         self._check_ids(pb, check_min_pos=True)
+        mask = getattr(p, "last_click_mask", None)                 # SRGNN_Pooling's mask rides along when the batch has one
+        if mask is not None:
+            pb.last_click_mask = mask.to(dev, torch.float32).contiguous()
         click_batch = pb.p_batch[src_p].contiguous()
         pb.pptr = torch.empty(pb.B + 1, dtype=torch.int32, device=dev)
         pb.qptr = torch.empty(pb.B + 1, dtype=torch.int32, device=dev)
@@ -358,7 +361,7 @@ class SessionEncoder:
         return pb
 
     @torch.no_grad()
-    def prepare_actions(self, actions):
+    def prepare_actions(self, actions, ignore_query=False):
         """Native graph construction (``csrc/graphbuild.hip``): a flat action table -- sessions
         stored contiguously: ``sess_ptr``, per action ``is_search`` / ``item_id`` / ``query_tok``
         (the CSV schema of the reference's decompose_data.py:13,30,42) -- becomes the prepared
@@ -366,7 +369,13 @@ class SessionEncoder:
         the host in the reference (util_amazon_filtered.py:98-230, test_amazon_filterd.py:485-488),
         followed by the CSR-by-target conversion.  Two kernel sweeps + one 5-integer read-back
         (the totals that size the outputs).  ``actions`` is an ``ActionTable`` (numpy) or an
-        object with the same four attributes as device tensors."""
+        object with the same four attributes as device tensors.
+
+        ``ignore_query`` is the reference's flag (util_amazon_filtered.py:101-103; True for every graph its
+        pre-training builds): the graphs of ``actions.clicks_only()``, built from the unfiltered table -- no
+        search action's ``item_id`` / ``query_tok`` is read.  The limit stays 64 raw actions per session.
+        The batch always carries ``last_click_mask`` (float32 [Np], the reference's
+        ``data['product'].last_click_mask``) and ``last_node`` (int32 [B], the batch-global id of that node)."""
         cfg, L, dev = self.cfg, _lib.lib(), self.device
         st = self._st()
 
@@ -376,20 +385,22 @@ class SessionEncoder:
         sess_ptr = up(actions.sess_ptr, torch.int64)
         is_search = up(actions.is_search, torch.uint8)
         item_id = up(actions.item_id, torch.int64)
-        query_tok = up(actions.query_tok, torch.int64)
+        query_tok = None if ignore_query else up(actions.query_tok, torch.int64)
+        flags = _lib.GRAPH_IGNORE_QUERY if ignore_query else 0
         S_ = int(sess_ptr.shape[0] - 1)
         if S_ <= 0:
             raise _lib.SssError("prepare_actions: empty action table")
         bases = torch.empty((5, S_ + 1), dtype=torch.int32, device=dev)
         scratch = torch.empty(int(L.sss_graph_scratch_ints(S_)), dtype=torch.int32, device=dev)
         err = torch.empty(1, dtype=torch.int32, device=dev)
-        _lib.check(L.sss_graph_counts(sess_ptr.data_ptr(), is_search.data_ptr(), item_id.data_ptr(), S_, bases.data_ptr(),
-                                      scratch.data_ptr(), err.data_ptr(), st), "sss_graph_counts")
+        _lib.check(L.sss_graph_counts_ex(sess_ptr.data_ptr(), is_search.data_ptr(), item_id.data_ptr(), S_, flags,
+                                         bases.data_ptr(), scratch.data_ptr(), err.data_ptr(), st), "sss_graph_counts_ex")
         # id bounds ride along in the read-back AS INT64: the kernels keep an item id in a 32-bit lane, so an id
         # that does not fit (2**32 + 7) would come out as another, valid one (7) and pass _check_ids below
+        # (ignore_query: a search action's ids are never read, so they bound nothing -- the valid id 0 stands in)
         if item_id.numel():
-            item_lo, item_hi = torch.aminmax(item_id)
-            ends = torch.stack([item_lo, query_tok.min(), item_hi])
+            item_lo, item_hi = torch.aminmax(item_id.masked_fill(is_search.bool(), 0) if ignore_query else item_id)
+            ends = torch.stack([item_lo, torch.zeros_like(item_lo) if ignore_query else query_tok.min(), item_hi])
         else:
             ends = torch.zeros(3, dtype=torch.int64, device=dev)
         tot = torch.cat([bases[:, S_], err, ends.view(torch.int32)]).tolist()   # the one host read-back of the build
@@ -412,13 +423,15 @@ class SessionEncoder:
         rp_pp, c_pp = i32(Np + 1), i32(Epp)
         w_pp = torch.empty(Epp, dtype=torch.float32, device=dev)
         pb.src_row, pb.pos_id = i32(Xp + Nq), i32(Xp + Nq)
+        pb.last_click_mask, pb.last_node = torch.empty(Np, dtype=torch.float32, device=dev), i32(S_)
         out = _lib.GraphOut(q_x=pb.q_ids.data_ptr(), q_batch=pb.q_batch.data_ptr(), q_pos=pb.q_pos.data_ptr(),
                             p_x=pb.p_ids.data_ptr(), p_batch=pb.p_batch.data_ptr(), p_cnt=pb.p_cnt.data_ptr(),
                             rowptr_qp=rp_qp.data_ptr(), col_qp=c_qp.data_ptr(), rowptr_pq=rp_pq.data_ptr(),
                             col_pq=c_pq.data_ptr(), rowptr_pp=rp_pp.data_ptr(), col_pp=c_pp.data_ptr(),
                             w_pp=w_pp.data_ptr(), src_row=pb.src_row.data_ptr(), pos_id=pb.pos_id.data_ptr())
-        _lib.check(L.sss_graph_fill(sess_ptr.data_ptr(), is_search.data_ptr(), item_id.data_ptr(), query_tok.data_ptr(), S_,
-                                    bases.data_ptr(), ctypes.byref(out), st), "sss_graph_fill")
+        _lib.check(L.sss_graph_fill_ex(sess_ptr.data_ptr(), is_search.data_ptr(), item_id.data_ptr(),
+                                       0 if ignore_query else query_tok.data_ptr(), S_, flags, bases.data_ptr(), ctypes.byref(out),
+                                       pb.last_click_mask.data_ptr(), pb.last_node.data_ptr(), st), "sss_graph_fill_ex")
         pb.csr_qp = (rp_qp, c_qp, None)
         pb.csr_pq = (rp_pq, c_pq, None)
         pb.csr_pp = (rp_pp, c_pp, w_pp if self.use_edge_weight else None)

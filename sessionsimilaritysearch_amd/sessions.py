@@ -14,6 +14,7 @@ offset form the encoder reads:
 * ``data['product'].batch``      int64 [Np]   graph id of every product node
 * ``data['product'].cnt``        int64 [Np]   clicks per distinct item
 * ``data['product'].pos_emb_id`` int64 [sum(cnt)]  ``len(seq) - j`` per click, grouped by item
+* ``data['product'].last_click_mask`` float32 [Np]  1.0 at the node of the session's last click
 * ``data['query'].x``            int64 [Nq]   query-feature row (0 = the empty root query)
 * ``data['query'].pos_emb_id``   int64 [Nq]   ``len(seq) - query_pos``
 * ``data['query'].batch``        int64 [Nq]
@@ -80,6 +81,14 @@ class ActionTable:
         ptr = np.zeros(self.num_sessions + 1, np.int64)
         np.cumsum(keep, out=ptr[1:])
         return ActionTable(ptr, self.is_search[m], self.item_id[m], self.query_tok[m])
+
+    def clicks_only(self) -> "ActionTable":
+        """The table without its search actions: what the reference's ``ignore_query=True`` does to a
+        session before anything else is computed (``util_amazon_filtered.py:101-103``).  Sessions keep
+        their place; a search-only session becomes a zero-action session."""
+        keep = ~np.asarray(self.is_search, bool)
+        ptr = np.r_[0, np.cumsum(keep, dtype=np.int64)][self.sess_ptr]
+        return ActionTable(ptr, self.is_search[keep], self.item_id[keep], self.query_tok[keep])
 
 
 def synthetic_actions(n_sessions: int, seed: int, n_items: int = ASIN_NUM,
@@ -166,9 +175,13 @@ def _group_rank(sorted_group: np.ndarray) -> np.ndarray:
     return np.arange(n, dtype=np.int64) - np.repeat(first, np.diff(np.r_[first, n]))
 
 
-def build_batch(actions: ActionTable) -> SessionBatch:
+def build_batch(actions: ActionTable, ignore_query: bool = False) -> SessionBatch:
     """All sessions of ``actions`` as one batch (structure of ``sequence_to_graph`` +
-    ``Batch.from_data_list``; see the module docstring for the field list)."""
+    ``Batch.from_data_list``; see the module docstring for the field list).  ``ignore_query``
+    (the reference's flag, ``util_amazon_filtered.py:101-103``; True in its pre-training) builds
+    the graphs of ``actions.clicks_only()``."""
+    if ignore_query:
+        actions = actions.clicks_only()
     S = actions.num_sessions
     ptr = actions.sess_ptr
     ln = np.diff(ptr)                                   # len(seq) per session
@@ -253,6 +266,11 @@ def build_batch(actions: ActionTable) -> SessionBatch:
     e_to = node_of_click
     ei_qp = np.stack([e_from, e_to]).astype(np.int64)
     ei_pq = np.stack([e_to, e_from]).astype(np.int64)
+    # last_click_mask (util_..:203-216): the node of the session's last click, the unknown-item node without one
+    last_click_mask = np.zeros(Np, np.float32)
+    last_click_mask[e_nodes] = 1.0
+    if c_idx.size:
+        last_click_mask[node_of_click[np.r_[c_sess[1:] != c_sess[:-1], True]]] = 1.0
 
     # ---- item->item transitions, de-duplicated with counts (util_..:199-218)
     if c_idx.size > 1:
@@ -269,7 +287,8 @@ def build_batch(actions: ActionTable) -> SessionBatch:
         w_pp = np.zeros(0, np.float32)
 
     nodes = {
-        "product": NodeStore(x=p_x, batch=p_batch, cnt=p_cnt, pos_emb_id=p_pos.astype(np.int64)),
+        "product": NodeStore(x=p_x, batch=p_batch, cnt=p_cnt, pos_emb_id=p_pos.astype(np.int64),
+                             last_click_mask=last_click_mask),
         "query": NodeStore(x=q_x, batch=q_batch, pos_emb_id=q_pos),
     }
     ei = {EDGE_QP: ei_qp, EDGE_PQ: ei_pq, EDGE_PP: ei_pp}

@@ -155,7 +155,8 @@ class AttentionPooling:
 
 class SRGNNPooling:
     """local = sum(x * last_click_mask); att = lin3(sigmoid(lin1(local)[batch] + lin2(x)));
-    out = lin4([local ; sum(x * att)])."""
+    out = lin4([local ; sum(x * att)]).  The mask is the reference's ``data['product'].last_click_mask``: pass it, or
+    pass the ``PreparedBatch`` that carries it as ``batch=`` (``SessionEncoder.prepare_actions`` always builds one)."""
 
     def __init__(self, weights, device):
         g = lambda n: _d(weights[n], device)
@@ -164,7 +165,11 @@ class SRGNNPooling:
         self.w4, self.b4 = g("lin4.w"), g("lin4.b")
 
     @torch.no_grad()
-    def forward(self, x, ptr, last_click_mask):
+    def forward(self, x, ptr, last_click_mask=None, *, batch=None):
+        if last_click_mask is None:
+            last_click_mask = getattr(batch, "last_click_mask", None)
+        if last_click_mask is None:
+            raise TypeError("SRGNNPooling.forward() needs last_click_mask, or batch= a prepared batch that carries one")
         L, dev = _lib.lib(), x.device
         B, d = ptr.shape[0] - 1, x.shape[1]
         rep = torch.empty((B, 2 * d), dtype=torch.float32, device=dev)
