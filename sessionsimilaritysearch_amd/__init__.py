@@ -10,6 +10,9 @@ Drop-in surface of the reference's path:
   HeteroSAGE, GraphPooling, AttentionPooling, ... (variants.py  <- model/gnn.py, model/model.py variants)
   SparseSessionIndex, session_vectors, find_K_sparse_dense
                                                   (sparse.py    <- test_amazon_filterd.py SKNN / STAN item-vector baselines)
+  evaluate, query_parts, item_overlap, get_*_jaccard, get_*_recall, get_*_map, get_ave_score, get_recall
+                                                  (evaluation.py <- test_amazon_filterd.py:226-382, 443-450 and
+                                                                  fine_tune_ours.py:42-97, the item-set metrics of a result)
   ShardedFlatIndex, ShardedBinaryIndex, ShardedSparseIndex
                                                   (distributed.py: corpus row-sharded over RCCL)
   SessionBatch, build_batch, synthetic_actions    (sessions.py  <- sequence_to_graph + Batch.from_data_list, host side)
@@ -17,7 +20,10 @@ Drop-in surface of the reference's path:
 from ._lib import SssError, build, exported_symbols, lib  # noqa: F401
 
 __all__ = ["SssError", "build", "exported_symbols", "lib", "SessionVectors", "SparseSessionIndex", "session_vectors",
-           "find_K_sparse_dense"]
+           "find_K_sparse_dense", "QueryParts", "query_parts", "item_overlap", "evaluate", "get_cur_jaccard", "get_future_jaccard",
+           "get_all_jaccard", "get_cur_recall", "get_all_recall", "get_future_recall", "get_future_map", "get_cur_map", "get_all_map",
+           "get_ave_score", "get_recall"]
+_EVALUATION = frozenset(__all__[8:])
 
 
 def __getattr__(name):
@@ -25,4 +31,7 @@ def __getattr__(name):
     if name in ("SessionVectors", "SparseSessionIndex", "session_vectors", "find_K_sparse_dense"):
         from . import sparse
         return getattr(sparse, name)
+    if name in _EVALUATION:                              # scoring a result: lazily, for the same reason
+        from . import evaluation
+        return getattr(evaluation, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

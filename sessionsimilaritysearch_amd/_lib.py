@@ -1,5 +1,5 @@
-"""ctypes binding of libsss.so (the C ABI declared in include/sss.h, include/sss_sparse.h, include/sss_l2.h, include/sss_pad.h
-and include/sss_graph.h).
+"""ctypes binding of libsss.so (the C ABI declared in include/sss.h, include/sss_sparse.h, include/sss_l2.h, include/sss_pad.h,
+include/sss_graph.h and include/sss_eval.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails, this
 module raises.  ``build()`` compiles the library in-tree with hipcc for gfx950.
@@ -155,6 +155,13 @@ _GRAPH_SIGNATURES = {
                                   c_void_p]),
 }
 
+# include/sss_eval.h one to one (scoring a search result: pair overlaps of item sets and their per-query sums)
+_EVAL_SIGNATURES = {
+    "sss_item_overlap": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p,
+                                 c_void_p, c_void_p]),
+    "sss_overlap_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+}
+
 
 class LinearProblem(ctypes.Structure):
     """``sss_linear_problem`` of include/sss.h."""
@@ -205,6 +212,11 @@ def graph_symbols():
     return sorted(_GRAPH_SIGNATURES)
 
 
+def eval_symbols():
+    """The entry points of include/sss_eval.h."""
+    return sorted(_EVAL_SIGNATURES)
+
+
 def build(verbose: bool = False) -> str:
     """Compile libsss.so for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-C", CSRC, "-j4"]
@@ -227,7 +239,7 @@ def lib():
                 "sessionsimilaritysearch_amd/csrc`). There is no CPU fallback.")
         h = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (*_SIGNATURES.items(), *_SPARSE_SIGNATURES.items(), *_L2_SIGNATURES.items(),
-                                   *_PAD_SIGNATURES.items(), *_GRAPH_SIGNATURES.items()):
+                                   *_PAD_SIGNATURES.items(), *_GRAPH_SIGNATURES.items(), *_EVAL_SIGNATURES.items()):
             fn = getattr(h, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = h

@@ -1,5 +1,5 @@
-// extern "C" surface of libsss (declared in include/sss.h, include/sss_sparse.h, include/sss_l2.h, include/sss_pad.h and
-// include/sss_graph.h) + error plumbing.
+// extern "C" surface of libsss (declared in include/sss.h, include/sss_sparse.h, include/sss_l2.h, include/sss_pad.h,
+// include/sss_graph.h and include/sss_eval.h) + error plumbing.
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -12,6 +12,7 @@
 #include "../../include/sss_l2.h"
 #include "../../include/sss_pad.h"
 #include "../../include/sss_graph.h"
+#include "../../include/sss_eval.h"
 #include "sss_common.h"
 #include "scan.h"
 #include "kargs.h"
@@ -104,6 +105,8 @@ int session_vectors_fill(const long*, const unsigned char*, const long*, long, l
 size_t sparse_topk_workspace_bytes(long nq, long n);
 int sparse_topk(const long*, const int*, const float*, long, const long*, const int*, const float*, long, int, long, float*, long*, void*,
                 size_t, hipStream_t);
+int item_overlap(const long*, const int*, long, const long*, const int*, long, const long*, int, long, int*, int*, int*, hipStream_t);
+int overlap_metrics(const int*, const int*, const int*, long, int, float, double*, int*, hipStream_t);
 
 }  // namespace sss
 
@@ -487,6 +490,18 @@ int sss_graph_fill_ex(const int64_t* sess_ptr, const uint8_t* is_search, const i
     return sss::graph_fill(reinterpret_cast<const long*>(sess_ptr), is_search, reinterpret_cast<const long*>(item_id),
                            reinterpret_cast<const long*>(query_tok), n_sessions, (flags & SSS_GRAPH_IGNORE_QUERY) != 0, bases,
                            graph_out(o), last_click_mask, last_node, ST(stream));
+}
+
+// ---- include/sss_eval.h
+int sss_item_overlap(const int64_t* q_ptr, const int32_t* q_items, int64_t nq, const int64_t* c_ptr, const int32_t* c_items,
+                     int64_t n, const int64_t* I, int K, int64_t id_offset, int32_t* inter, int32_t* csize, int32_t* err,
+                     void* stream) {
+    return sss::item_overlap(reinterpret_cast<const long*>(q_ptr), q_items, nq, reinterpret_cast<const long*>(c_ptr), c_items, n,
+                             reinterpret_cast<const long*>(I), K, id_offset, inter, csize, err, ST(stream));
+}
+int sss_overlap_metrics(const int32_t* inter, const int32_t* csize, const int32_t* qsize, int64_t nq, int K, float thr,
+                        double* out, int32_t* flags, void* stream) {
+    return sss::overlap_metrics(inter, csize, qsize, nq, K, thr, out, flags, ST(stream));
 }
 
 }  // extern "C"

@@ -82,6 +82,41 @@ class ActionTable:
         np.cumsum(keep, out=ptr[1:])
         return ActionTable(ptr, self.is_search[m], self.item_id[m], self.query_tok[m])
 
+    def split(self, frac_num: int, frac_den: int) -> Tuple["ActionTable", "ActionTable"]:
+        """The ``(seq, tar)`` cut of every session (``test_amazon_filterd.py:546``): ``seq`` is
+        ``prefix(frac_num, frac_den)``, ``tar`` the actions behind it (none when the prefix is the whole
+        session).  Sessions keep their place in both tables."""
+        seq = self.prefix(frac_num, frac_den)
+        keep = np.diff(seq.sess_ptr)
+        ln = np.diff(self.sess_ptr)
+        t_sess = np.repeat(np.arange(self.num_sessions), ln)
+        j = np.arange(self.is_search.shape[0]) - self.sess_ptr[:-1][t_sess]
+        m = j >= keep[t_sess]
+        ptr = np.zeros(self.num_sessions + 1, np.int64)
+        np.cumsum(ln - keep, out=ptr[1:])
+        return seq, ActionTable(ptr, self.is_search[m], self.item_id[m], self.query_tok[m])
+
+    @staticmethod
+    def concat(a: "ActionTable", b: "ActionTable") -> "ActionTable":
+        """Session-wise concatenation: session ``i`` of the result is ``a[i] + b[i]`` (the reference's
+        ``test_data[0][i] + test_data[1][i]``); ``concat(*t.split(num, den))`` is ``t``."""
+        if a.num_sessions != b.num_sessions:
+            raise ValueError(f"concat: {a.num_sessions} sessions against {b.num_sessions}")
+        la, lb = np.diff(a.sess_ptr), np.diff(b.sess_ptr)
+        ptr = np.zeros(a.num_sessions + 1, np.int64)
+        np.cumsum(la + lb, out=ptr[1:])
+        sess_a, sess_b = np.repeat(np.arange(a.num_sessions), la), np.repeat(np.arange(b.num_sessions), lb)
+        # where every action of a / b lands: its session's start, plus its index inside the session (behind a's for b)
+        at_a = ptr[:-1][sess_a] + np.arange(int(la.sum())) - (a.sess_ptr[:-1] - a.sess_ptr[0])[sess_a]
+        at_b = ptr[:-1][sess_b] + la[sess_b] + np.arange(int(lb.sum())) - (b.sess_ptr[:-1] - b.sess_ptr[0])[sess_b]
+        lo_a, hi_a, lo_b, hi_b = int(a.sess_ptr[0]), int(a.sess_ptr[-1]), int(b.sess_ptr[0]), int(b.sess_ptr[-1])
+
+        def join(x, y):
+            out = np.empty(int(ptr[-1]), np.result_type(x.dtype, y.dtype))
+            out[at_a], out[at_b] = x[lo_a:hi_a], y[lo_b:hi_b]
+            return out
+        return ActionTable(ptr, join(a.is_search, b.is_search), join(a.item_id, b.item_id), join(a.query_tok, b.query_tok))
+
     def clicks_only(self) -> "ActionTable":
         """The table without its search actions: what the reference's ``ignore_query=True`` does to a
         session before anything else is computed (``util_amazon_filtered.py:101-103``).  Sessions keep
