@@ -1,5 +1,5 @@
-"""ctypes binding of libsss.so (the C ABI declared in include/sss.h, include/sss_sparse.h, include/sss_l2.h, include/sss_pad.h,
-include/sss_graph.h and include/sss_eval.h).
+"""ctypes binding of libsss.so (the C ABI declared in include/sss.h, include/sss_sparse.h, include/sss_l2.h, include/sss_l2_long.h,
+include/sss_pad.h, include/sss_graph.h and include/sss_eval.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails, this
 module raises.  ``build()`` compiles the library in-tree with hipcc for gfx950.
@@ -131,6 +131,13 @@ _L2_SIGNATURES = {
                                       c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
+# include/sss_l2_long.h one to one (L2 top-k of long float32 rows on the K-tiled scan)
+_L2_LONG_SIGNATURES = {
+    "sss_l2_topk_long_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
+    "sss_l2_topk_long": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_float, c_void_p, c_int64, c_int, c_int, c_int64,
+                                 c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 # include/sss_pad.h one to one (scans at the next supported width for float32 rows of any width d % 4 == 0)
 _PAD_SIGNATURES = {
     "sss_pad_rows_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
@@ -202,6 +209,11 @@ def l2_symbols():
     return sorted(_L2_SIGNATURES)
 
 
+def l2_long_symbols():
+    """The entry points of include/sss_l2_long.h."""
+    return sorted(_L2_LONG_SIGNATURES)
+
+
 def pad_symbols():
     """The entry points of include/sss_pad.h."""
     return sorted(_PAD_SIGNATURES)
@@ -239,7 +251,7 @@ def lib():
                 "sessionsimilaritysearch_amd/csrc`). There is no CPU fallback.")
         h = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (*_SIGNATURES.items(), *_SPARSE_SIGNATURES.items(), *_L2_SIGNATURES.items(),
-                                   *_PAD_SIGNATURES.items(), *_GRAPH_SIGNATURES.items(), *_EVAL_SIGNATURES.items()):
+                                   *_L2_LONG_SIGNATURES.items(), *_PAD_SIGNATURES.items(), *_GRAPH_SIGNATURES.items(), *_EVAL_SIGNATURES.items()):
             fn = getattr(h, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = h

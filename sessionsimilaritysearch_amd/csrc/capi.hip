@@ -1,5 +1,5 @@
-// extern "C" surface of libsss (declared in include/sss.h, include/sss_sparse.h, include/sss_l2.h, include/sss_pad.h,
-// include/sss_graph.h and include/sss_eval.h) + error plumbing.
+// extern "C" surface of libsss (declared in include/sss.h, include/sss_sparse.h, include/sss_l2.h, include/sss_l2_long.h,
+// include/sss_pad.h, include/sss_graph.h and include/sss_eval.h) + error plumbing.
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -10,6 +10,7 @@
 #include "../../include/sss.h"
 #include "../../include/sss_sparse.h"
 #include "../../include/sss_l2.h"
+#include "../../include/sss_l2_long.h"
 #include "../../include/sss_pad.h"
 #include "../../include/sss_graph.h"
 #include "../../include/sss_eval.h"
@@ -437,6 +438,15 @@ int sss_l2_topk_threshold(const float* q, const int32_t* qsel, int64_t nsel, con
     return sss::l2_topk_threshold(q, qsel, nsel, corpus, scan_image, scan_dtype, corpus_shift, corpus_resid_norm, bias, n, d, k,
                                   id_offset, corpus_max_norm, D_out, reinterpret_cast<long*>(I_out), status, workspace,
                                   workspace_bytes, ST(stream));
+}
+
+// ---- include/sss_l2_long.h
+size_t sss_l2_topk_long_workspace_bytes(int64_t nq, int64_t n, int d) { return sss::l2_topk_long_workspace_bytes(nq, n, d); }
+int sss_l2_topk_long(const float* q, int64_t nq, const float* corpus, const void* f16_image, int corpus_shift,
+                     float corpus_resid_norm, const float* bias, int64_t n, int d, int k, int64_t id_offset, float corpus_max_norm,
+                     float* D_out, int64_t* I_out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    return sss::l2_topk_long(q, nq, corpus, f16_image, corpus_shift, corpus_resid_norm, bias, n, d, k, id_offset, corpus_max_norm,
+                             D_out, reinterpret_cast<long*>(I_out), status, workspace, workspace_bytes, ST(stream));
 }
 
 // ---- include/sss_pad.h

@@ -126,7 +126,9 @@ struct ThrArgs {
     long* I_out;
     int* status;                    // [nq]: set to 0 for resolved queries
     double* qb = nullptr;           // optional [nsel][2] cache of the queries' (error bound, unscale): written by the first kernel
-    int qb_ready = 0;               //   that computes them (qb_ready == 0), read by the later ones (sss_ip_topk_long: five kernels a search)
+    int qb_ready = 0;               //   that computes them (qb_ready == 0), read by the later ones (sss_ip_topk_long: five kernels a search);
+                                    //   metric 1: 2 [nsel] more doubles behind the pairs: the queries' off = -|q|^2, then
+                                    //   the bound k_select_all prunes with (select_thr.hip: THE PER-ROW BOUND)
     int keep = 0;                   // k_thr_prepare: 1 = keep the rows already kept that pass the NEW threshold (compacted in place)
                                     //                instead of starting from an empty array (sss_ip_topk_long: disjoint levels)
     int metric = 0;                 // 1: L2 (as SelectArgs::metric; D_out holds distances: its column k-1 is an UPPER bound, negated on the way in)
@@ -138,7 +140,9 @@ int launch_select_all(const ThrArgs& a, hipStream_t st);
 // `qimg` is given, identity selection, D_out rows at -FLT_MAX, thresholds -inf, counters 0, status 1, the per-query
 // (error bound, unscale) cache), and the step between two levels in one launch (bound from the level just scanned ->
 // column k-1 of D_out -> the next level's threshold; counters zeroed, or -- a.keep -- the kept rows pruned in place).
-int launch_long_setup(const ThrArgs& a, int* qsel, void* qimg, hipStream_t st);
+// (seed: L2 only -- [2][2][nsel] floats, the seed coefficients of k_scan_long<DT_F16, 1> for lowered and for raised keys;
+//  nullptr otherwise)
+int launch_long_setup(const ThrArgs& a, int* qsel, void* qimg, float* seed, hipStream_t st);
 int launch_bound_prepare(const ThrArgs& a, hipStream_t st);
 // Range search, fused route (select_thr.hip): scan thresholds from per-query radii (identity selection written to `qsel`,
 // counters zeroed); the canonical re-score + keep (> radius) + sort by id of the kept rows (counts / status per query,
@@ -186,6 +190,11 @@ size_t ip_topk_long_workspace_bytes(long nq, long n, int d, int dtype);
 int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, const void* c_scan, int corpus_shift,
                  float corpus_resid, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out,
                  int* status, void* ws, size_t ws_bytes, hipStream_t st);
+// L2 top-k on the long-row scan (scan_long.hip; include/sss_l2_long.h): float32 rows, their scaled f16 image, keys biased per row
+size_t l2_topk_long_workspace_bytes(long nq, long n, int d);
+int l2_topk_long(const float* q, long nq, const float* c, const void* c_f16, int corpus_shift, float corpus_resid, const float* bias,
+                 long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out, int* status, void* ws,
+                 size_t ws_bytes, hipStream_t st);
 size_t ip_topk_exhaustive_workspace_bytes(long nsel, long n);
 int ip_topk_exhaustive(const void* q, const int* qsel, long nsel, const void* c, long n, int d, int k, int dtype, long id_offset,
                        int metric, const float* lower_bound, float* D_out, long* I_out, void* ws, size_t ws_bytes, hipStream_t st);

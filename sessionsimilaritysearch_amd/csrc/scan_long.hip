@@ -55,6 +55,13 @@ struct LongArgs {
     const float* thr;               // [nq] per-query threshold in the scan's domain
     unsigned* cnt;                  // [nq] rows kept so far
     unsigned long long* cand;       // [nq][cap]
+    // L2 scans only (k_scan_long<DT_F16, MET = 1>; appended, so the inner-product kernels read what they always read): the
+    // per-row bias -|c|^2 / 2 every score starts from, and per query the two coefficients of the seed (k_long_setup;
+    // select_thr.hip: THE PER-ROW BOUND): seed[row] = seed[0][q] * bias[row] + seed[1][q] * |c_row|.  seed[0] is sigma (the
+    // power of two the query's scaled scores live in) times (1 +- Q), seed[1] = -+ sigma P / 2: the key comes out LOWERED
+    // by the row's own error bound on the sample levels and RAISED by it on the last level.
+    const float* bias = nullptr;    // [n]
+    const float* seed = nullptr;    // [2][nq]
 };
 
 // (the f16 image of f32 queries -- scaled by the query's own power of two, scan.h: f16_shift -- is written by
@@ -67,9 +74,15 @@ constexpr int LT_LOADERS = SSS_LT_LOADERS;             // loader waves per workg
 constexpr int LT_NP = 32 / LT_LOADERS;                 // 1 KiB pieces of an operand slab per loader
 constexpr int LT_THREADS = (8 + LT_LOADERS) * 64;
 
-template <int DT>
+// MET = 1 is the L2 form (as k_scan's, scan_kernel.h): the key of (query, row) is sigma (q.c) + seed[row] -- every
+// accumulator of a tile starts from its rows' seeds instead of zero, landed in the accumulator layout by one
+// v_mfma_f32_32x32x2_f32 per accumulator (A = the 32 rows' biases in the k = 0 column and their norms |c| in k = 1;
+// B = the lane's query's two seed coefficients), and everything from the K loop to the appends runs as before.  The
+// inner-product instantiations (MET = 0) compile to what they were: every L2 statement sits under `if constexpr (MET)`.
+template <int DT, int MET = 0>
 __global__ __launch_bounds__(LT_THREADS, (LT_THREADS + 255) / 256) void k_scan_long(const LongArgs A) {
     static_assert(DT == DT_F16 || DT == DT_BF16, "16-bit rows");
+    static_assert(MET == 0 || DT == DT_F16, "an L2 index is float32: its long scan reads the scaled f16 image");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int nq = A.nq, n = A.n, S = A.S, G = A.G;
     const int rb = A.d * 2;                             // bytes per row (queries and corpus alike)
@@ -199,9 +212,39 @@ __global__ __launch_bounds__(LT_THREADS, (LT_THREADS + 255) / 256) void k_scan_l
     f32x16 acc[4][2];
     const int keyq0 = ((wq * 64 + r) >> 1) & 7, keyq1 = ((wq * 64 + 32 + r) >> 1) & 7;
     int step = 0, bufa = 0;                                     // bufa = step % 3
-    for (int j = j_lo; j < j_hi; ++j) {
+    // L2: bias of row (128 wr + 32 b + r) of the current tile in the lanes h = 0 (the k = 0 column of the seeding MFMA's A
+    // operand); the lanes h = 1 hold its k = 1 column: an upper bound of the row's norm, sqrt(-2 bias) (1 + 2^-20) (the
+    // bias is -|c|^2 / 2 rounded once; the factor covers that rounding and the square root's).  Rows at and beyond n read
+    // row n - 1's and are masked by the epilogue's `row < n` like every other score of such a row.  The K loop issues no
+    // vector-memory instruction in these waves, so a tile's four biases are fetched in the epilogue of the tile before
+    // (the first tile's here) and waited for where they are used.  The coefficients are finite (k_long_setup).
+    [[maybe_unused]] float bcur[MET ? 4 : 1];
+    [[maybe_unused]] float sig0 = 1.f, sig1 = 1.f;
+    [[maybe_unused]] auto bias_fetch = [&](int tl) __attribute__((always_inline)) {
 #pragma unroll
-        for (int b = 0; b < 4; ++b) { acc[b][0] = zero; acc[b][1] = zero; }
+        for (int b = 0; b < 4; ++b) {
+            long row = (long)tl * LT_ROWS + wr * 128 + b * 32 + r;
+            if (row > (long)n - 1) row = (long)n - 1;
+            const float bv = A.bias[row];
+            bcur[b] = h == 0 ? bv : sqrtf(-2.f * bv) * 1.000001f;
+        }
+    };
+    if constexpr (MET) {
+        sig0 = q0 < nq ? A.seed[(size_t)h * nq + q0] : 0.f;
+        sig1 = q1 < nq ? A.seed[(size_t)h * nq + q1] : 0.f;
+        bias_fetch(tile);
+    }
+    for (int j = j_lo; j < j_hi; ++j) {
+        if constexpr (MET) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                acc[b][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(bcur[b], sig0, zero, 0, 0, 0);
+                acc[b][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(bcur[b], sig1, zero, 0, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) { acc[b][0] = zero; acc[b][1] = zero; }
+        }
         for (int s = 0; s < nslab; ++s, ++step) {
             const int bufb = step & 1;
             __syncthreads();                                    // the loaders have seen this step's slabs land
@@ -229,6 +272,13 @@ __global__ __launch_bounds__(LT_THREADS, (LT_THREADS + 255) / 256) void k_scan_l
                 }
             }
             bufa = bufa == 2 ? 0 : bufa + 1;
+        }
+        if constexpr (MET) {                                    // the next tile's biases (this tile's are dead: it has been seeded)
+            if (j + 1 < j_hi) {
+                int ntile = tile, nfrac = tile_frac;
+                next_tile(ntile, nfrac);
+                bias_fetch(ntile);
+            }
         }
         // ---- tile epilogue: acc[b][s][jj] is (corpus row tile * 256 + 128 wr + 32 b + (jj & 3) + 8 (jj >> 2) + 4 h,
         // query r (s = 0) / 32 + r (s = 1) of the wave's 64)
@@ -328,26 +378,43 @@ size_t ip_topk_long_workspace_bytes(long nq, long n, int d, int dtype) {
     return al256((size_t)nq * d * 2) + al256((size_t)nq * 4) * 3 + al256((size_t)nq * 16) + (size_t)nq * LONG_CAP * 8;
 }
 
+// L2 (include/sss_l2_long.h): the same arrays, the bound cache two doubles wider (off = -|q|^2 and the select's bound
+// behind the (B, unscale) pairs) and four floats per query more (the seed coefficients of the two kinds of level)
+size_t l2_topk_long_workspace_bytes(long nq, long n, int d) {
+    if (nq <= 0 || n <= 0 || !long_shape_ok(d, DT_F32, DT_F16)) return 0;
+    return al256((size_t)nq * d * 2) + al256((size_t)nq * 4) * 3 + al256((size_t)nq * 16) + al256((size_t)nq * 32) +
+           (size_t)nq * LONG_CAP * 8;
+}
 
-int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, const void* c_scan, int corpus_shift,
-                 float corpus_resid, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out,
-                 int* status, void* ws, size_t ws_bytes, hipStream_t st) {
+// The long-row search of both metrics.  bias == nullptr: inner product (`what` = "ip_topk_long").  bias != nullptr: L2
+// over float32 rows (`what` = "l2_topk_long"; the caller has checked its buffers) -- k_scan_long<DT_F16, 1> seeds every
+// accumulator from its row's bias and norm, the ThrArgs carry metric 1, and everything else -- the level plan,
+// launch_bound_prepare, launch_select_all -- is what the inner product runs.  Two things differ (select_thr.hip: THE
+// PER-ROW BOUND): the sample levels scan keys LOWERED by each row's own error bound and the last level keys RAISED by
+// it, and the levels are never disjoint -- a sample's kept rows carry lowered keys, which the final threshold (made for
+// raised keys) must not prune.
+static int topk_long_impl(const char* what, const float* bias, const void* q, long nq, const void* c_exact, int exact_dtype,
+                          const void* c_scan, int corpus_shift, float corpus_resid, long n, int d, int k, long id_offset,
+                          float corpus_max_norm, float* D_out, long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st) {
+    const bool l2 = bias != nullptr;
     const int scan_dtype = long_scan_dtype(exact_dtype);
     const bool f16_mfma = scan_dtype != DT_BF16;        // the scaled image and stored f16 rows share k_scan_long<DT_F16>
-    if (nq <= 0 || n <= 0 || k <= 0) { set_error("ip_topk_long: nq, n, k must be positive"); return SSS_EINVAL; }
-    int rc = check_scan_source("ip_topk_long", exact_dtype, scan_dtype, d, true, c_scan, corpus_shift, corpus_resid, n, nq);
+    if (nq <= 0 || n <= 0 || k <= 0) { set_error("%s: nq, n, k must be positive", what); return SSS_EINVAL; }
+    int rc = check_scan_source(what, exact_dtype, scan_dtype, d, true, c_scan, corpus_shift, corpus_resid, n, nq);
     if (rc) return rc;
-    if (k > LONG_MAX_K) { set_error("ip_topk_long: k too large (max %d)", LONG_MAX_K); return SSS_EINVAL; }
+    if (k > LONG_MAX_K) { set_error("%s: k too large (max %d)", what, LONG_MAX_K); return SSS_EINVAL; }
     const int cap = long_cap(d, exact_dtype);
-    if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("ip_topk_long: workspace must be 256-byte aligned"); return SSS_EINVAL; }
-    const size_t need = ip_topk_long_workspace_bytes(nq, n, d, exact_dtype);
-    if (ws_bytes < need) { set_error("ip_topk_long: workspace %zu < %zu", ws_bytes, need); return SSS_EWORKSPACE; }
+    if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("%s: workspace must be 256-byte aligned", what); return SSS_EINVAL; }
+    const size_t need = l2 ? l2_topk_long_workspace_bytes(nq, n, d) : ip_topk_long_workspace_bytes(nq, n, d, exact_dtype);
+    if (ws_bytes < need) { set_error("%s: workspace %zu < %zu", what, ws_bytes, need); return SSS_EWORKSPACE; }
     char* w = reinterpret_cast<char*>(ws);
     void* qimg = w;                              w += al256((size_t)nq * d * 2);
     int* qsel = reinterpret_cast<int*>(w);       w += al256((size_t)nq * 4);
     float* thr = reinterpret_cast<float*>(w);    w += al256((size_t)nq * 4);
     unsigned* cnt = reinterpret_cast<unsigned*>(w); w += al256((size_t)nq * 4);
-    double* qb = reinterpret_cast<double*>(w);   w += al256((size_t)nq * 16);       // (error bound, unscale) per query: computed once
+    float* seed = nullptr;                       // L2: [2][2][nq] seed coefficients: lowered keys, then raised keys
+    if (l2) { seed = reinterpret_cast<float*>(w); w += al256((size_t)nq * 16); }
+    double* qb = reinterpret_cast<double*>(w);   w += al256((size_t)nq * (l2 ? 32 : 16));   // (error bound, unscale) per query, computed once; L2: + [nq] off + [nq] select bound
     unsigned long long* cand = reinterpret_cast<unsigned long long*>(w);
 
     // (the f16 query image, the identity selection, D_out at "no bound known", thresholds, counters, status and the
@@ -382,19 +449,22 @@ int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, c
         level_tiles[levels++] = first;
     }
     const size_t lds = LT_LDS_BYTES;
-    rc = f16_mfma ? opt_in_lds(reinterpret_cast<const void*>(&k_scan_long<DT_F16>), "k_scan_long", lds)
-                              : opt_in_lds(reinterpret_cast<const void*>(&k_scan_long<DT_BF16>), "k_scan_long", lds);
+    rc = l2         ? opt_in_lds(reinterpret_cast<const void*>(&k_scan_long<DT_F16, 1>), "k_scan_long", lds)
+         : f16_mfma ? opt_in_lds(reinterpret_cast<const void*>(&k_scan_long<DT_F16>), "k_scan_long", lds)
+                    : opt_in_lds(reinterpret_cast<const void*>(&k_scan_long<DT_BF16>), "k_scan_long", lds);
     if (rc) return rc;
     ThrArgs t = thr_args(q, c_exact, exact_dtype, scan_dtype, corpus_shift, corpus_resid, corpus_max_norm, qsel, nq, n, d, k, cap,
                          id_offset);
     t.thr = thr; t.cnt = cnt; t.cand = cand; t.D_out = D_out; t.I_out = I_out; t.status = status;
     t.qb = qb;
-    rc = launch_long_setup(t, qsel, scan_dtype == DT_F16 ? qimg : nullptr, st);
+    t.metric = l2 ? 1 : 0;
+    rc = launch_long_setup(t, qsel, scan_dtype == DT_F16 ? qimg : nullptr, seed, st);
     if (rc) return rc;
     t.qb_ready = 1;
     LongArgs a;
     a.Qimg = q_scan; a.C = c_scan; a.nq = (int)nq; a.n = (int)n; a.d = d; a.G = (int)((nq + LT_Q - 1) / LT_Q);
     a.total_tiles = total_tiles; a.cap = cap; a.thr = thr; a.cnt = cnt; a.cand = cand;
+    a.bias = bias;
     a.gpx = a.G;                    // groups per XCD (block map of k_scan_long): all of them (fewer measured slower, see the kernel)
     // DISJOINT LEVELS (three levels and more).  The last sample used to be scanned twice: once as a sample, once more as
     // part of the whole corpus -- 9 % of the matrix work at 1M x 1600, K = 100.  Now the last sample takes EVERY R-th
@@ -404,7 +474,7 @@ int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, c
     // them.  Together they are exactly the rows of the whole corpus above the final threshold -- what k_select_all's
     // proof needs -- and there are fewer of them (the sample's rows are filtered by the final threshold now).
     int R = 0;
-    if (levels >= 3) {
+    if (levels >= 3 && !l2) {
         R = (int)((double)total_tiles / (double)level_tiles[1] + 0.5);
         if (R < 2) R = 0;                              // (ratio below 1.5: the planned sample is most of the corpus -- keep the plain form)
     }
@@ -421,6 +491,7 @@ int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, c
             a.skip_R = R;
         }
         a.tile_count = tiles;
+        a.seed = l2 ? seed + (last ? 2 * nq : 0) : nullptr;
         a.dense = last ? 0 : 1;
         int S = (256 / a.G) & ~7;
         if (S < 8) S = 8;
@@ -429,7 +500,8 @@ int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, c
         a.tiles_per_split = (tiles + S - 1) / S;
         // (thresholds and counters of this level: written by launch_long_setup -- first level -- or by the previous level's
         //  launch_bound_prepare)
-        if (f16_mfma) hipLaunchKernelGGL(k_scan_long<DT_F16>, dim3(a.S * a.G), dim3(LT_THREADS), lds, st, a);
+        if (l2) hipLaunchKernelGGL((k_scan_long<DT_F16, 1>), dim3(a.S * a.G), dim3(LT_THREADS), lds, st, a);
+        else if (f16_mfma) hipLaunchKernelGGL(k_scan_long<DT_F16>, dim3(a.S * a.G), dim3(LT_THREADS), lds, st, a);
         else hipLaunchKernelGGL(k_scan_long<DT_BF16>, dim3(a.S * a.G), dim3(LT_THREADS), lds, st, a);
         rc = check_launch("k_scan_long");
         if (rc) return rc;
@@ -443,6 +515,24 @@ int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, c
         if (rc) return rc;
     }
     return SSS_OK;
+}
+
+int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, const void* c_scan, int corpus_shift,
+                 float corpus_resid, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out,
+                 int* status, void* ws, size_t ws_bytes, hipStream_t st) {
+    return topk_long_impl("ip_topk_long", nullptr, q, nq, c_exact, exact_dtype, c_scan, corpus_shift, corpus_resid, n, d, k, id_offset,
+                          corpus_max_norm, D_out, I_out, status, ws, ws_bytes, st);
+}
+
+// L2 top-k of long float32 rows (include/sss_l2_long.h): the buffers an inner-product call does not have are checked
+// here, the shape / image / k / workspace checks are topk_long_impl's own -- all of them before the first launch.
+int l2_topk_long(const float* q, long nq, const float* c, const void* c_f16, int corpus_shift, float corpus_resid, const float* bias,
+                 long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out, int* status, void* ws,
+                 size_t ws_bytes, hipStream_t st) {
+    if (!bias || (reinterpret_cast<uintptr_t>(bias) & 15)) { set_error("l2_topk_long: row bias missing or not 16-byte aligned"); return SSS_EINVAL; }
+    if (!q || !c || !D_out || !I_out || !status) { set_error("l2_topk_long: q, corpus, D_out, I_out and status are required"); return SSS_EINVAL; }
+    return topk_long_impl("l2_topk_long", bias, q, nq, c, DT_F32, c_f16, corpus_shift, corpus_resid, n, d, k, id_offset, corpus_max_norm,
+                          D_out, I_out, status, ws, ws_bytes, st);
 }
 
 }  // namespace sss

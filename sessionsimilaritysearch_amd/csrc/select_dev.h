@@ -277,8 +277,10 @@ __device__ __forceinline__ double err_bound(int d, int scan_dtype, double qnorm,
 //                                   round once each, every term and partial sum at most (|q| + cmax)^2
 // with the 2 % headroom.  The subnormal floors are those of err_bound (the seed counts as one more element of the chain).
 // Where B_l2 is not finite and normal -- sigma outside 2^+-120, a scaled bias that may overflow, norms beyond float32 -- it
-// is +inf: the query is UNPROVEN whatever its keys are (the select kernels force the status), the rung's threshold is -inf,
-// and the exhaustive kernels resolve it.  inf - inf cannot occur in a key: the bias is finite (FlatIndex routes to the
+// is +inf: the query is UNPROVEN whatever its keys are (the fused select forces the status), the rung's threshold is -inf,
+// and the exhaustive kernels resolve it.  (The long-row search, whose k_select_all proves by "every kept row was
+// re-scored" and forces nothing, gives such a query the threshold +inf instead -- it keeps no row: select_thr.hip,
+// long_thr -- and scans with a per-row form of this bound: select_thr.hip, THE PER-ROW BOUND.)  inf - inf cannot occur in a key: the bias is finite (FlatIndex routes to the
 // scan only where cmax^2 / 2 is a normal float32), so a key is finite, or q.c overflowed and it is +-inf -- ordered, never
 // NaN -- and such a query's keys say nothing the proof accepts: +inf as the edge makes the window infinite.
 __device__ __forceinline__ double err_bound_l2(int d, int scan_dtype, double qnorm, double cmax, double c_resid, double q_resid, double qn2,

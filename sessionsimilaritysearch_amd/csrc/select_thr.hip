@@ -22,11 +22,90 @@ constexpr int SA_ROWS_FULL = 128;                  //   ... the full-capacity la
 //
 // k_thr_prepare: one wave per selected query: its threshold in the scan's domain, counter zeroed.
 // B and unscale of selected query i = row q (select_dev.h: query_bound; ONE wave), through the `qb` cache when there is one.
-// (the cache holds inner-product bounds only -- sss_ip_topk_long's: off = 0)
+// (the cache of the long-row searches: [nsel] (B, unscale) pairs -- off = 0 for the inner product -- and, metric 1, the [nsel]
+//  off = -|q|^2 and the [nsel] bounds of k_select_all's pruning behind them; there B is the per-query REST of the per-row bound)
 __device__ __forceinline__ void query_bound(const ThrArgs& A, int i, int q, int lane, double& B, double& unscale, double& off) {
-    if (A.qb != nullptr && A.qb_ready) { B = A.qb[2 * (size_t)i]; unscale = A.qb[2 * (size_t)i + 1]; off = 0.0; return; }   // (selected query i = row q)
+    if (A.qb != nullptr && A.qb_ready) {                                    // (selected query i = row q)
+        B = A.qb[2 * (size_t)i]; unscale = A.qb[2 * (size_t)i + 1];
+        off = A.metric ? A.qb[2 * (size_t)A.nsel + i] : 0.0;
+        return;
+    }
     query_bound(A, reinterpret_cast<const char*>(A.Q) + (size_t)q * row_bytes(A.d, A.dtype), lane, B, unscale, off);
-    if (A.qb != nullptr && lane == 0) { A.qb[2 * (size_t)i] = B; A.qb[2 * (size_t)i + 1] = unscale; }
+    if (A.qb != nullptr && lane == 0) {
+        A.qb[2 * (size_t)i] = B; A.qb[2 * (size_t)i + 1] = unscale;
+        if (A.metric) A.qb[2 * (size_t)A.nsel + i] = off;
+    }
+}
+
+// L2 on long rows: a query whose bound is not finite (sigma or a scaled bias beyond float32's range, select_dev.h:
+// err_bound_l2) has scan keys that prove nothing -- a scaled bias that overflowed is -inf, which no threshold keeps.  Its
+// threshold is +inf at every level: it keeps no row, stays at status 1 and is resolved by the exhaustive kernels.
+__device__ __forceinline__ float long_thr(const ThrArgs& A, float thr, double B) {
+    return A.metric && !(B < (double)INFINITY) ? INFINITY : thr;
+}
+
+// THE PER-ROW BOUND (L2 on long rows).  err_bound_l2 bounds |key -> score - exact score| of EVERY row through the largest
+// corpus norm cmax.  On a corpus whose norms are spread, the rows nearest to a query are the small ones, whose own error
+// is far smaller -- and a proof window 2 B_l2(cmax) wide holds tens of thousands of them at 1M rows.  Every term of
+// err_bound_l2 holds row by row with |c| in place of cmax (cmax only ever stands for "at least |c|"), and the row's f16
+// residual norm is at most 2^-11 |c| + rho0 (an element that lands in the f16 normal range is rounded to 11 significant
+// bits; one below it -- 2^-14 in the scaled domain -- moves by at most 2^-25 there: rho0 = sqrt(d) 2^-25 / 2^corpus_shift).
+// With qn = |q|, rq = the query's residual norm, g = 2^-25 sqrt(d + 1) + (d + 1) 2^-23, A = (d + 4) 2^-23 (three roundings
+// more than err_bound_l2 counts: the seed is a sum of two rounded products now, not an exact one), the bound of a row is
+//     err(c) = P |c| + Q |c|^2 + R,
+//     P = 2.04 (2^-11 qn + (1 + 2^-11) rq + g qn) + 1.02 (d + 3) 2^-52 2 qn
+//     Q = 2.04 A / 2 + 1.02 (2^-24 + (d + 3) 2^-52)
+//     R = 2.04 (rho0 (qn + rq) + 2^-126 / sigma) + 1.02 (2^-149 + (3 d + 8) 2^-53 qn^2) + P 2^-74
+// (the last term: a bias in the float32 subnormal range gives the scan a norm that may be 2^-74 short).  In the scan's
+// domain (score = key 2 / sigma + off) that is sigma / 2 err(c), and -2 bias is |c|^2: the scan LOWERS a key by it with the
+// seed sigma (1 + Q) bias - sigma P / 2 |c| and RAISES it with sigma (1 - Q) bias + sigma P / 2 |c| (P and Q inflated by
+// 1e-3 for the float32 roundings of the coefficients and of the norm the scan derives from the bias).  Then
+//   * a LOWERED key maps to a score at most R above the exact one: the k-th largest lowered key of a sample is a lower
+//     bound of the k-th score with B = R (k_bound_prepare as it is);
+//   * a RAISED key maps to a score at least the exact one minus R: on the last level a row that is not kept (raised key
+//     <= thr_from_bound(lb, R, ...)) cannot reach lb -- the proof k_select_all needs, with a window of the NEAR rows' own
+//     errors.  Sample levels compare lowered keys with that threshold: they keep fewer rows, which a lower bound allows;
+//   * k_select_all prunes the kept rows of the last level by raised keys, which lie within 2 err(cmax) + R of the exact
+//     score: its B is 3 max(B_l2(cmax), err(cmax)), the fourth array of the cache.
+// Writes the four seed coefficients of query i ([2][2][nsel]: lowered (k0, k1), raised (k0, k1)) and the cache entries;
+// ONE wave.  B_glob: err_bound_l2 of the query (infinite: zeros -- the query keeps nothing).
+__device__ __forceinline__ void l2_long_bound(const ThrArgs& A, int i, int lane, double B_glob, double unscale, float* __restrict__ seed) {
+    const float* row = reinterpret_cast<const float*>(A.Q) + (size_t)i * A.d;
+    double qn2 = 0.0;
+    float amax = 0.f;
+    for (int kk = lane; kk < A.d; kk += 64) { const float v = row[kk]; qn2 += (double)v * (double)v; amax = fmaxf(amax, fabsf(v)); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { qn2 += __shfl_xor(qn2, o); amax = fmaxf(amax, __shfl_xor(amax, o)); }
+    const int sh = f16_shift(amax);
+    double rq2 = 0.0;
+    for (int kk = lane; kk < A.d; kk += 64) rq2 += f16_resid2(row[kk], sh);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) rq2 += __shfl_xor(rq2, o);
+    if (lane != 0) return;
+    const double d = (double)A.d, qn = sqrt(qn2), rq = sqrt(rq2), cmax = (double)A.corpus_max_norm;
+    const double sigma = 2.0 / unscale;                                     // (unscale: the L2 one, 2 / sigma)
+    const double rho0 = sqrt(d) * 2.98023223876953125e-08 * ldexp(1.0, -A.corpus_shift);
+    const double g = 2.98023223876953125e-08 * sqrt(d + 1.0) + (d + 1.0) * 1.1920928955078125e-07;
+    const double Aq = (d + 4.0) * 1.1920928955078125e-07;
+    const double P = 2.04 * (4.8828125e-04 * qn + (1.0 + 4.8828125e-04) * rq + g * qn) + 1.02 * (d + 3.0) * 2.220446049250313e-16 * 2.0 * qn;
+    const double Q = 2.04 * Aq * 0.5 + 1.02 * (5.9604644775390625e-08 + (d + 3.0) * 2.220446049250313e-16);
+    const double R = 2.04 * (rho0 * (qn + rq) + 1.1754943508222875e-38 / sigma) +
+                     1.02 * (1.4012984643248171e-45 + (3.0 * d + 8.0) * 1.1102230246251565e-16 * qn2) + P * 5.293955920339377e-23;
+    const double errmax = P * cmax + Q * cmax * cmax + R;
+    const bool ok = B_glob < (double)INFINITY && errmax == errmax && errmax < 1.0e300;
+    const double Pi = P * 1.001, Qi = Q * 1.001;
+    const size_t ns = (size_t)A.nsel;
+    seed[i] = ok ? (float)(sigma * (1.0 + Qi)) : 0.f;
+    seed[ns + i] = ok ? (float)(-0.5 * sigma * Pi) : 0.f;
+    seed[2 * ns + i] = ok ? (float)(sigma * (1.0 - Qi)) : 0.f;
+    seed[3 * ns + i] = ok ? (float)(0.5 * sigma * Pi) : 0.f;
+    A.qb[2 * (size_t)i] = ok ? R : (double)INFINITY;
+    A.qb[3 * ns + i] = ok ? 3.0 * fmax(B_glob, errmax) : (double)INFINITY;
+}
+
+// the bound k_select_all prunes with: the query's B, or -- long-row L2, whose cached B is the rest R -- the cache's fourth array
+__device__ __forceinline__ double select_bound(const ThrArgs& A, int i, double B) {
+    return A.metric && A.qb != nullptr && A.qb_ready ? A.qb[3 * (size_t)A.nsel + i] : B;
 }
 
 // keep mode (one wave): the rows kept so far were kept under an OLDER, lower threshold over tiles the next scan will not
@@ -66,8 +145,14 @@ __global__ __launch_bounds__(256) void k_thr_prepare(const ThrArgs A) {
     prune_kept(A, i, thr, lane);
 }
 
-// sss_ip_topk_long, before the first scan: one wave per query (scan.h: launch_long_setup).
-__global__ __launch_bounds__(256) void k_long_setup(const ThrArgs A, int* __restrict__ qsel, _Float16* __restrict__ qimg) {
+// sss_ip_topk_long / sss_l2_topk_long, before the first scan: one wave per query (scan.h: launch_long_setup).
+// D_out's rows start at "no bound known" in the domain the caller reads -- -FLT_MAX scores, +FLT_MAX distances (metric 1) --
+// and column k-1 stays in that domain while the levels run: k_bound_prepare converts on the way in and out (out_score).
+// seed (L2): the scan's seed coefficients per query (THE PER-ROW BOUND above), from sigma = 2^(corpus_shift + the query's
+// shift) -- the shift query_bound re-derives; zeros where the query's bound is infinite (it keeps nothing: no inf or NaN
+// enters the seeding MFMA).
+__global__ __launch_bounds__(256) void k_long_setup(const ThrArgs A, int* __restrict__ qsel, _Float16* __restrict__ qimg,
+                                                    float* __restrict__ seed) {
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= A.nsel) return;
@@ -80,10 +165,11 @@ __global__ __launch_bounds__(256) void k_long_setup(const ThrArgs A, int* __rest
         const int sh = f16_shift(amax);
         for (int kk = lane; kk < A.d; kk += 64) qimg[(size_t)i * A.d + kk] = (_Float16)ldexpf(row[kk], sh);
     }
-    for (int j = lane; j < A.k; j += 64) A.D_out[(size_t)i * A.k + j] = -3.4028234663852886e38f;   // "no bound known"
+    for (int j = lane; j < A.k; j += 64) A.D_out[(size_t)i * A.k + j] = out_score(-3.4028234663852886e38f, A.metric);   // "no bound known"
     double B, unscale, off;
     query_bound(A, i, i, lane, B, unscale, off);    // fills the cache (A.qb_ready == 0 here)
-    if (lane == 0) { qsel[i] = i; A.thr[i] = -INFINITY; A.cnt[i] = 0u; A.status[i] = 1; }
+    if (seed != nullptr) l2_long_bound(A, i, lane, B, unscale, seed);       // (B stays the global bound: infinite or not is all the threshold asks)
+    if (lane == 0) { qsel[i] = i; A.thr[i] = long_thr(A, -INFINITY, B); A.cnt[i] = 0u; A.status[i] = 1; }
 }
 
 // k_bound_prepare (sss_ip_topk_long, between two levels; scan.h: launch_bound_prepare): no row is read.  At least k of
@@ -113,14 +199,14 @@ __global__ __launch_bounds__(SORT_THREADS) void k_bound_prepare(const ThrArgs A)
     if (tid >= 64) return;
     double B, unscale, off;
     query_bound(A, i, q, tid, B, unscale, off);
-    float lbf = A.D_out[(size_t)q * k + k - 1];
+    float lbf = out_score(A.D_out[(size_t)q * k + k - 1], A.metric);    // (L2: the column holds an UPPER bound of the k-th distance)
     if (have) {
         const double lb = (double)ord2f(sk) * unscale + off - B;
         float f = (float)lb;
         if ((double)f > lb) f = nextafterf(f, -INFINITY);               // round DOWN: stays a lower bound
-        if (f == f && f > lbf) { lbf = f; if (tid == 0) A.D_out[(size_t)q * k + k - 1] = f; }
+        if (f == f && f > lbf) { lbf = f; if (tid == 0) A.D_out[(size_t)q * k + k - 1] = out_score(f, A.metric); }
     }
-    const float thr = thr_from_bound((double)lbf, B, unscale, off);
+    const float thr = long_thr(A, thr_from_bound((double)lbf, B, unscale, off), B);
     if (tid == 0) A.thr[i] = thr;
     if (!A.keep) {
         if (tid == 0) A.cnt[i] = 0u;
@@ -165,6 +251,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_select_all(const ThrArgs A, in
         if (tid < 64) {
             double B, unscale, off;
             query_bound(A, i, q, tid, B, unscale, off);
+            B = select_bound(A, i, B);
             if (tid == 0) {
                 const double sk = (double)ord2f(sk_o);
                 const double c = sk - (2.0 * B + ULP32_REL * fabs(sk * unscale + off) + ULP32_MIN) / unscale;
@@ -328,8 +415,8 @@ int launch_thr_prepare(const ThrArgs& a, hipStream_t st) {
     return check_launch("k_thr_prepare");
 }
 
-int launch_long_setup(const ThrArgs& a, int* qsel, void* qimg, hipStream_t st) {
-    hipLaunchKernelGGL(k_long_setup, dim3((unsigned)((a.nsel + 3) / 4)), dim3(256), 0, st, a, qsel, reinterpret_cast<_Float16*>(qimg));
+int launch_long_setup(const ThrArgs& a, int* qsel, void* qimg, float* seed, hipStream_t st) {
+    hipLaunchKernelGGL(k_long_setup, dim3((unsigned)((a.nsel + 3) / 4)), dim3(256), 0, st, a, qsel, reinterpret_cast<_Float16*>(qimg), seed);
     return check_launch("k_long_setup");
 }
 

@@ -359,9 +359,22 @@ class FlatIndex:
             return ""
         return self._ladder_scan(k)
 
+    def l2_long_for(self, k: int) -> str:
+        """"long" where an L2 search for k results runs on the K-tiled long-row scan (``sss_l2_topk_long``), else "": a
+        float32 index whose rows are beyond the fused scans (d % 64 == 0, no fused kernel at this d, a row of at most
+        ``LONG_MAX_ROW_BYTES``), k <= ``LONG_MAX_K`` and a largest row norm in [2^-60, 2^60].  A ``pad_scan`` index has a
+        fused scan at every width it accepts and never comes here."""
+        if self.metric != "l2" or self.dtype != "f32" or k <= 0 or k > LONG_MAX_K or self.ntotal == 0:
+            return ""
+        if self.d % 64 or self.d * 4 > LONG_MAX_ROW_BYTES or any(self._scan_served(s) for s in _LADDER):
+            return ""
+        if not L2_SCAN_MIN_NORM <= self.corpus_max_norm() <= L2_SCAN_MAX_NORM:
+            return ""
+        return "long"
+
     def _route(self, k: int) -> str:
         """The scan a search for k results runs on under this index's metric ("" = the exhaustive kernels)."""
-        return self.l2_scan_for(k) if self.metric == "l2" else self.scan_for(k)
+        return (self.l2_scan_for(k) or self.l2_long_for(k)) if self.metric == "l2" else self.scan_for(k)
 
     def _long_or_none(self, k: int) -> str:
         """"long": the K-tiled scan for rows beyond the register-resident kernels (``sss_ip_topk_long``)."""
@@ -630,7 +643,7 @@ class FlatIndex:
         """Enqueue the fused MFMA scoring + top-k on the current stream; no host sync.
         Returns (D [nq,k] f32, I [nq,k] i64, status [nq] i32) CUDA tensors; rows with
         status != 0 must be re-run with ``search_exhaustive`` (``search`` does that).  An L2 index takes the
-        L2 scan ``l2_scan_for(k)`` names.
+        L2 scan ``l2_scan_for(k)`` names, or the long-row scan where ``l2_long_for(k)`` says so.
         ``unproven_count``: optional CUDA int32 [1] tensor, incremented once per unproven query."""
         L = _lib.lib()
         _lib.require_cuda(q, "q", self._tdtype)
@@ -645,12 +658,20 @@ class FlatIndex:
         if mode == "":
             raise _lib.SssError("search_fused: this index / k has no fused path (use search)")
         image, code, shift, resid = self._scan_image(mode)
-        if mode == "long":
+        if mode == "long" and self.metric == "l2":
+            self._ensure_bias()
+            ws = self._ws.get(L.sss_l2_topk_long_workspace_bytes(nq, n, self.d))
+            rc = L.sss_l2_topk_long(q.data_ptr(), nq, self._xb.data_ptr(), image.data_ptr(), shift, resid, self._bias.data_ptr(),
+                                    n, self.d, k, self.id_offset, self.corpus_max_norm(), D.data_ptr(), I.data_ptr(),
+                                    status.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
+            _lib.check(rc, "sss_l2_topk_long")
+        elif mode == "long":
             ws = self._ws.get(L.sss_ip_topk_long_workspace_bytes(nq, n, self.d, self._fmt.code))
             rc = L.sss_ip_topk_long(q.data_ptr(), nq, self._xb.data_ptr(), self._fmt.code, image.data_ptr(), shift, resid,
                                     n, self.d, k, self.id_offset, self.corpus_max_norm(), D.data_ptr(), I.data_ptr(),
                                     status.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
             _lib.check(rc, "sss_ip_topk_long")
+        if mode == "long":
             if unproven_count is not None:
                 unproven_count += (status != 0).sum().to(torch.int32)
             return D, I, status
