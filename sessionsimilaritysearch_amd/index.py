@@ -21,6 +21,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from .routing import (AUTO_DECAY_SEARCHES, AUTO_ESCALATE, AUTO_F16_MAX_K, AUTO_SPLIT_MAX_K, F16_SCAN_DIMS, F32_SCAN_DIMS,  # noqa: F401
+                      FUSED_MAX_K, L2_SCAN_MAX_NORM, L2_SCAN_MIN_NORM, LONG_MAX_K, LONG_MAX_ROW_BYTES, PAD_SCAN_MAX_D, _LADDER,
+                      ScanRouting)
 from ._device import EXHAUSTIVE_WS_BYTES as _EXHAUSTIVE_WS_BYTES, Workspace, exhaustive_chunk, grow_rows
 
 
@@ -44,30 +47,12 @@ class _Format:
 
 
 _FORMATS = {f.name: f for f in (
-    _Format("f32", 0, torch.float32, np.float32, 4, (64, 128, 256), True, lambda x, what: x),
+    _Format("f32", 0, torch.float32, np.float32, 4, F32_SCAN_DIMS, True, lambda x, what: x),
     _Format("bf16", 1, torch.bfloat16, None, 2, (128, 256, 512), True, lambda x, what: to_bf16(x)),
     _Format("f16", 4, torch.float16, np.float16, 2, (128, 256, 512), True, lambda x, what: to_f16(x), checks_finite=True),
     _Format("i8", 6, torch.int8, np.int8, 1, (256, 512, 1024), False, lambda x, what: _i8_from_f32(x, what)),
 )}
 FUSED_DIMS = {f.name: f.fused_dims for f in _FORMATS.values()}
-F16_SCAN_DIMS = (128, 256, 512)                                  # scaled-f16 image: 2 bytes per element
-PAD_SCAN_MAX_D = 512             # pad_scan=True: float32 rows of 4 <= d <= 512, d % 4 == 0, scanned at the next width a scan has
-# scan="auto": the fastest scan whose error bound is still small against the spacing of the scores
-# around rank k (the spacing shrinks as k grows): one-pass f16 up to k = 128, bf16 split up to k = 500
-# (every k the fused path serves); the f32 MFMA scan is reached by escalation only.  Measured on random unit
-# rows, d = 128, 1024 queries (round 3): f16 leaves 0 of 6144 queries unproven at k <= 64 on 10M rows, 8 at k = 128,
-# 60 at k = 200 (the k classes are cut there); split leaves 0-1 up to k = 500, at 0.4x the f32 scan's time.  A
-# search whose fallback share exceeds AUTO_ESCALATE moves that k class one scan up for the following searches
-# (near-duplicate-heavy or unusually dense corpora); an unproven query costs a share of one more scan of the
-# corpus for the unproven ones only (the threshold rung), so a few per batch are cheaper than the slower scan.
-AUTO_F16_MAX_K = 128
-AUTO_SPLIT_MAX_K = 500
-AUTO_ESCALATE = 0.005
-AUTO_DECAY_SEARCHES = 64        # clean searches at an escalated level before the class steps back down one scan
-_LADDER = ("f16", "split", "f32")
-FUSED_MAX_K = 500
-LONG_MAX_K = 1024                                                # sss_ip_topk_long: what its exhaustive fallback resolves
-LONG_MAX_ROW_BYTES = 16384
 _CODE = {f.name: f.code for f in _FORMATS.values()}              # include/sss.h: dtype (2, 3 are scan images, below; 5 is unassigned)
 _TORCH_DTYPE = {f.name: f.torch_dtype for f in _FORMATS.values()}
 DTYPE_CODE = {n: c for n, c in _CODE.items() if _TORCH_DTYPE[n].is_floating_point}    # the public views: float formats ...
@@ -76,10 +61,30 @@ SEARCH_CHUNK = 65536             # queries per fused call of search_device (work
 SEARCH_CHUNK_LONG = 16384        # ... on the long-row path (64 KB per query)
 RANGE_CHUNK = 4096               # queries per fused range_search count / fill (workspace 64 KB per query)
 _SCAN_CODE = {"split": 2, "f16": 3}                              # include/sss.h: scan image codes (else the dtype's own)
-# The L2 scans start every score from the row bias -|c|^2 / 2, a float32: the scan route is taken only where the largest
-# row norm keeps cmax^2 / 2 finite and normal with room to spare (2^-121 .. 2^119); beyond, the exhaustive kernels.
-L2_SCAN_MIN_NORM = 2.0 ** -60
-L2_SCAN_MAX_NORM = 2.0 ** 60
+
+
+class _Entry:
+    """The libsss entry point of one scan family: its name, the fields its argument list opens with (the rest -- bound,
+    outputs, workspace, stream -- is the same in every family) and the fields its workspace-size function takes."""
+    def __init__(self, name: str, lead: str, ws_lead: str, ws_name: str | None = None):
+        self.name, self.lead, self.ws_lead, self.ws_name = name, lead.split(), ws_lead.split(), ws_name or name + "_workspace_bytes"
+
+
+# Field names are those of FlatIndex._fields: "dtype" is the stored rows' code, "code" the scan image's, "id" the id offset.
+_TOPK = {                                # search_fused, by FlatIndex._family ("ip": by scan, else the index's own rows)
+    "pad": _Entry("sss_pad_topk", "q nq xb image code shift resid bias n d ds k id", "nq n d ds k code"),
+    "l2": _Entry("sss_l2_topk", "q nq xb image code shift resid bias n d k id", "nq n d k code"),
+    "ip_f16": _Entry("sss_ip_topk_f16", "q nq xb image shift resid n d k id", "nq n d k"),
+    "ip_split": _Entry("sss_ip_topk_split", "q nq xb image n d k id", "nq n d k dtype", "sss_ip_topk_workspace_bytes"),
+    "ip": _Entry("sss_ip_topk", "q nq xb n d k dtype id", "nq n d k dtype"),
+    "long_ip": _Entry("sss_ip_topk_long", "q nq xb dtype image shift resid n d k id", "nq n d dtype"),
+    "long_l2": _Entry("sss_l2_topk_long", "q nq xb image shift resid bias n d k id", "nq n d"),
+}
+_THRESHOLD = {                           # search_threshold (nq: the selected queries); long rows have no rung
+    "pad": _Entry("sss_pad_topk_threshold", "q sel nq xb image code shift resid bias n d ds k id", "nq n d ds code"),
+    "l2": _Entry("sss_l2_topk_threshold", "q sel nq xb image code shift resid bias n d k id", "nq n d code"),
+    "ip": _Entry("sss_ip_topk_threshold", "q sel nq xb dtype image code shift resid n d k id", "nq n d code"),
+}
 
 
 def _dev(device=None):
@@ -182,7 +187,7 @@ def normalize(vec, eps: float = 1e-6, rule: int = 0):
     return x.cpu().numpy() if is_np else x
 
 
-class FlatIndex:
+class FlatIndex(ScanRouting):
     """Exact flat index (faiss ``IndexFlatIP`` / ``IndexFlatL2`` semantics) with
     the canonical result contract of DESIGN.md: scores are float64-accumulated dot products
     rounded to float32, ordered by (score desc, id asc); missing results are (-FLT_MAX, -1).
@@ -213,20 +218,16 @@ class FlatIndex:
     ``"split"`` keeps each element as a bfloat16 hi/lo pair (same bytes as the f32 row) and scans
     with three bf16 MFMA passes -- error <= ~2^-14 |q||c|;
     ``"f32"`` scans the float32 rows on the f32 MFMA (error ~ d 2^-24) and needs no second image;
-    ``"auto"`` (default) takes "f16" for k <= 128 where the shape allows and "split" up to k = 500 (every k
-    the fused path serves; the scores around rank k lie closer together as k grows); "f32" is reached by
-    escalation only: a k class moves one scan up when a search left more than 0.5 % of its queries (at least
-    4) unproven, the step is taken back (and the class pinned) when the slower scan proves no more of them,
-    and a class steps back down after 64 CONSECUTIVE clean searches.  Images are built on first use
-    (``prepare(k)`` does it ahead of time) and extended as rows are added.
+    ``"auto"`` (default) takes "f16" for k <= 128 where the shape allows and "split" up to k = 500; "f32" is reached
+    by escalation only, after searches that left too many queries unproven (``ScanRouting._note_fallbacks``).
+    Images are built on first use (``prepare(k)`` does it ahead of time) and extended as rows are added.
 
     ``metric="l2"`` (faiss ``IndexFlatL2``): squared distances, the float64 chain of ``(q_k - c_k)**2`` rounded to
     float32, ordered by (distance asc, id asc), missing results (+FLT_MAX, -1).  A float32 index runs it on the same
     scans, same ``scan`` argument and ladder (``l2_scan_for``): the rows nearest to q are those with the largest
     ``q.c - |c|**2 / 2``, which is the inner-product scan with every score started from a per-row bias (one float32
-    per row, kept beside the images).  ``scan_for`` / ``fused_ok`` describe the inner-product path and stay "" /
-    False for an L2 index.  Other dtypes, d without a scan, k > 500 and corpora whose largest row norm lies outside
-    [2^-60, 2^60] run on the exhaustive kernels.
+    per row, kept beside the images).  Other dtypes, d without a scan, k > 500 and corpora whose largest row norm lies
+    outside [2^-60, 2^60] run on the exhaustive kernels.
 
     Queries a scan leaves unproven are resolved in two further stages, both exact: the THRESHOLD RUNG
     (``search_threshold``: one more matrix-core scan for just those queries that keeps every row able to
@@ -235,56 +236,27 @@ class FlatIndex:
 
     ``pad_scan=True`` (off by default) gives a float32 index of ANY width ``4 <= d <= 512`` with ``d % 4 == 0`` the same
     scans -- d = 200, the reference's default embedding width, among them; without it such an index runs on the exhaustive
-    kernels.  The scan images and the query batch are built at ``scan_width(scan)``, the next width the scan has (f16:
-    128 / 256 / 512; split and f32: 64 / 128 / 256; ``256 < d <= 512`` has the f16 scan only, whatever ``scan`` says), with
+    kernels.  The scan images and the query batch are built at ``scan_width(scan)``, the next width the scan has, with
     exact zero columns behind column d: they add nothing to a dot product or to ``|c|**2``, so scan, bound (taken at the
     scan width) and proof are those of the wider corpus, and candidates are re-scored from the d-wide rows.  Results are
     the same as without the switch.  It has no effect where d already has a scan (64 / 128 / 256 / 512, ``d % 64 == 0``
     long rows) and on other dtypes.  An image costs ``scan_width`` elements a row: d = 200 on the f16 scan keeps 512 bytes
     a row beside the 800-byte row."""
 
-    _pad = False                        # (class default: pad_scan off)
-
     def __init__(self, d: int, metric: str = "ip", device=None, dtype: str = "f32", scan: str | None = None, *,
                  pad_scan: bool = False):
-        if metric not in ("ip", "l2"):
-            raise ValueError("metric must be 'ip' or 'l2'")
         if dtype not in _FORMATS:
             names = [repr(n) for n in _FORMATS]
             raise ValueError(f"dtype must be {', '.join(names[:-1])} or {names[-1]}")
         fmt = _FORMATS[dtype]
         if dtype != "f32" and d % fmt.align:
             raise ValueError(f"{dtype} index needs d % {fmt.align} == 0")
-        if scan is None:
-            scan = "auto" if dtype == "f32" else "native"
-        if scan not in (("auto", "f16", "split", "f32") if dtype == "f32" else ("native",)):
-            raise ValueError("scan must be 'auto', 'f16', 'split' or 'f32' for a float32 index")
-        self.scan = scan
-        self.last_scan = None           # the scan the last fused search used
-        self._auto_level = {}           # scan="auto": k class -> lowest ladder level still allowed
-        self._auto_clean = {}           # scan="auto": k class -> consecutive clean searches at the escalated level
-        self._auto_rows = 0             # scan="auto": corpus size when a class last escalated
-        self.d = int(d)
-        self.metric = metric
-        self.dtype = dtype
+        ScanRouting.__init__(self, d, metric, dtype, scan, pad_scan, fmt=fmt)
         self._tdtype = fmt.torch_dtype
         self.device = _dev(device)
-        # derived corpus images, built on first use and extended as rows are added
-        self._split = None              # [cap, 2d] bf16 hi|lo image of the rows        ("split" scan)
-        self._split_done = 0            # rows of it that are valid
-        self._f16 = None                # [cap, d] float16 image of rows * 2^_c_shift  ("f16" scan)
-        self._f16_done = 0
-        self._c_shift = 0
-        self._amax_t = torch.zeros(1, dtype=torch.float32, device=self.device)    # largest |element| in the f16 image
-        self._resid_t = torch.zeros(1, dtype=torch.float32, device=self.device)   # largest row residual norm of it
+        self._c_shift = 0               # the float16 image holds rows * 2^_c_shift
         self._resid = None
-        self._bias = None               # [cap] float32 -|row|^2 / 2: what the L2 scans start every score from
-        self._bias_done = 0
-        # pad_scan: the scans run at scan_width(scan) >= d; where d has a scan of its own the switch changes nothing
-        self._pad = (bool(pad_scan) and dtype == "f32" and 4 <= self.d <= PAD_SCAN_MAX_D and self.d % 4 == 0
-                     and self.d % 64 != 0)
-        self._p32 = None                # [cap, scan_width("f32")] float32 rows, zero-extended       ("f32" scan of a padded index)
-        self._p32_done = 0
+        self._reset_images()
         self._xb = torch.empty((0, self.d), dtype=self._tdtype, device=self.device)
         self._store = self._xb          # backing storage of _xb (grown geometrically by add())
         self._cmax_t = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -297,10 +269,16 @@ class FlatIndex:
         self.last_range_scan = None     # the scan the last range_search used ("" = exhaustive route only)
         self.last_range_overflow_queries = 0    # queries of the last range_search the fused route sent to the exhaustive one
 
-    @property
-    def _fmt(self) -> _Format:
-        """The record of this index's storage format (``dtype`` names it)."""
-        return _FORMATS[self.dtype]
+    def _reset_images(self):
+        """No derived corpus image yet: each is built on first use and extended as rows are added."""
+        self._split, self._split_done = None, 0         # [cap, 2 w] bf16 hi|lo image of the rows ("split" scan; w = scan_width)
+        self._f16, self._f16_done = None, 0             # [cap, w] float16 image of rows * 2^_c_shift ("f16" scan)
+        self._p32, self._p32_done = None, 0             # [cap, w] float32 rows, zero-extended ("f32" scan of a padded index)
+        self._bias, self._bias_done = None, 0           # [cap] float32 -|row|^2 / 2: what the L2 scans start every score from
+        self._amax_t = torch.zeros(1, dtype=torch.float32, device=self.device)    # largest |element| in the f16 image
+        self._resid_t = torch.zeros(1, dtype=torch.float32, device=self.device)   # largest row residual norm of it
+
+    _fmt = property(lambda self: _FORMATS[self.dtype], doc="The record of this index's storage format (``dtype`` names it).")
 
     @property
     def ntotal(self) -> int:
@@ -317,134 +295,16 @@ class FlatIndex:
             self._auto_level.clear()
             self._auto_clean.clear()
 
-    def scan_for(self, k: int) -> str:
-        """Which candidate scan a fused search for k results uses ("" = none: exhaustive path)."""
-        if self.metric != "ip" or k <= 0 or self.ntotal == 0:
-            return ""
-        fused_shape = self.d in self._fmt.fused_dims or (self.dtype == "f32" and self.d in F16_SCAN_DIMS) or self._pad
-        if not fused_shape:
-            return self._long_or_none(k)         # rows longer than the register-resident scans take (D = 1600 ...)
-        if k > FUSED_MAX_K:
-            return ""
-        if self.dtype != "f32":
-            return "native"
-        return self._ladder_scan(k)
+    def _image_complete(self, scan: str) -> bool:
+        image, done = (self._f16, self._f16_done) if scan == "f16" else (self._split, self._split_done)
+        return image is not None and done == self.ntotal
 
-    def _ladder_scan(self, k: int) -> str:
-        """The scan of a float32 index for k results by its ``scan`` argument and, for "auto", what the searches
-        so far have taught it ("" = this d has none)."""
-        want = self.scan
-        if want == "auto":
-            level = max(self._k_class(k), self._auto_level.get(self._k_class(k), 0))
-            served = [s for s in _LADDER[level:] if self._scan_served(s)]
-            # nothing at or above the wanted level fits this d (e.g. d = 512: only the f16 image does):
-            # stay on the fastest scan that does rather than fall off the ladder
-            served = served or [s for s in _LADDER if self._scan_served(s)]
-            return served[0] if served else ""
-        if want == "f16" and not self._scan_served("f16"):
-            want = "split"
-        if self._pad and not self._scan_served(want):
-            want = "f16"                         # pad_scan, 256 < d <= 512: the f16 image is the only scan that wide
-        return want if self._scan_served(want) else ""
-
-    def l2_scan_for(self, k: int) -> str:
-        """Which candidate scan an L2 search for k results uses ("" = none: exhaustive path): the ladder, ``scan``
-        argument and "auto" escalation state of ``scan_for``, for a float32 index whose d has a fused kernel, k <= 500
-        and a largest row norm in [2^-60, 2^60]."""
-        if self.metric != "l2" or self.dtype != "f32" or k <= 0 or k > FUSED_MAX_K or self.ntotal == 0:
-            return ""
-        if not any(self._scan_served(s) for s in _LADDER):
-            return ""
-        if not L2_SCAN_MIN_NORM <= self.corpus_max_norm() <= L2_SCAN_MAX_NORM:
-            return ""
-        return self._ladder_scan(k)
-
-    def l2_long_for(self, k: int) -> str:
-        """"long" where an L2 search for k results runs on the K-tiled long-row scan (``sss_l2_topk_long``), else "": a
-        float32 index whose rows are beyond the fused scans (d % 64 == 0, no fused kernel at this d, a row of at most
-        ``LONG_MAX_ROW_BYTES``), k <= ``LONG_MAX_K`` and a largest row norm in [2^-60, 2^60].  A ``pad_scan`` index has a
-        fused scan at every width it accepts and never comes here."""
-        if self.metric != "l2" or self.dtype != "f32" or k <= 0 or k > LONG_MAX_K or self.ntotal == 0:
-            return ""
-        if self.d % 64 or self.d * 4 > LONG_MAX_ROW_BYTES or any(self._scan_served(s) for s in _LADDER):
-            return ""
-        if not L2_SCAN_MIN_NORM <= self.corpus_max_norm() <= L2_SCAN_MAX_NORM:
-            return ""
-        return "long"
-
-    def _route(self, k: int) -> str:
-        """The scan a search for k results runs on under this index's metric ("" = the exhaustive kernels)."""
-        return (self.l2_scan_for(k) or self.l2_long_for(k)) if self.metric == "l2" else self.scan_for(k)
-
-    def _long_or_none(self, k: int) -> str:
-        """"long": the K-tiled scan for rows beyond the register-resident kernels (``sss_ip_topk_long``)."""
-        if not self._fmt.long_rows:
-            return ""                            # (int8 rows: the exhaustive kernels)
-        row_bytes = self.d * self._fmt.elem_bytes
-        return "long" if (self.d % 64 == 0 and row_bytes <= LONG_MAX_ROW_BYTES and k <= LONG_MAX_K) else ""
-
-    def _scan_served(self, scan: str) -> bool:
-        """Does a fused kernel exist for this scan at this d (``pad_scan``: at a width this d is padded to)?"""
-        return self.scan_width(scan) != 0
-
-    def scan_width(self, scan: str) -> int:
-        """The row width scan "f16" / "split" / "f32" runs at on this float32 index: d where d is one of the scan's
-        widths; on a ``pad_scan`` index the smallest of them that is at least d; 0 where the scan does not serve it."""
-        widths = F16_SCAN_DIMS if scan == "f16" else FUSED_DIMS["f32"]
-        if self._pad:
-            return next((w for w in widths if w >= self.d), 0)
-        return self.d if self.d in widths else 0
-
-    def next_scan(self, scan: str) -> str:
-        """The next scan up the precision ladder that this d can run ("" = none)."""
-        if self.dtype != "f32" or scan not in _LADDER:
-            return ""
-        return next((s for s in _LADDER[_LADDER.index(scan) + 1:] if self._scan_served(s)), "")
-
-    @staticmethod
-    def _k_class(k: int) -> int:
-        return 0 if k <= AUTO_F16_MAX_K else 1 if k <= AUTO_SPLIT_MAX_K else 2
-
-    def _note_fallbacks(self, k: int, nq: int, bad: int):
-        """scan="auto": move this k class one scan up when too many queries of a search were left
-        unproven by it -- only to a scan this d can run -- and back down one scan after
-        AUTO_DECAY_SEARCHES consecutive clean searches (one near-duplicate-heavy batch does not demote
-        the index for good); an escalation that proves no more queries than the faster scan did is undone."""
-        if self.scan != "auto" or self.last_scan not in _LADDER:
-            return
-        kc = self._k_class(k)
-        share = bad / max(nq, 1)
-        # The first search after an escalation tells whether it helped: exact ties (duplicate rows at the k-th place)
-        # stay unproven under EVERY scan -- the threshold rung resolves them, at a cost that hardly depends on how
-        # many there are -- so a slower scan that still leaves more than AUTO_ESCALATE of the batch unproven only
-        # costs time.  Such a step is taken back and the class pinned for AUTO_DECAY_SEARCHES searches.
-        probe = self._auto_clean.pop(("probe", kc), None)
-        if probe is not None and nq >= 32 and bad >= 4 and share > AUTO_ESCALATE:
-            self._auto_level[kc] = probe[0]
-            self._auto_clean[("pin", kc)] = AUTO_DECAY_SEARCHES
-            self._auto_clean[kc] = 0
-            return
-        pin = self._auto_clean.get(("pin", kc), 0)
-        if pin > 0:
-            self._auto_clean[("pin", kc)] = pin - 1
-            return
-        if nq >= 32 and bad >= 4 and bad > AUTO_ESCALATE * nq:
-            up = self.next_scan(self.last_scan)
-            if up:
-                self._auto_clean[("probe", kc)] = (_LADDER.index(self.last_scan), share)
-                self._auto_level[kc] = _LADDER.index(up)
-                self._auto_rows = self.ntotal
-            self._auto_clean[kc] = 0
-        elif self._auto_level.get(kc, 0) > kc and nq >= 32:
-            self._auto_clean[kc] = self._auto_clean.get(kc, 0) + 1 if bad == 0 else 0      # consecutive: any unproven query restarts the count
-            if self._auto_clean[kc] >= AUTO_DECAY_SEARCHES:
-                self._auto_level[kc] -= 1
-                self._auto_clean[kc] = 0
-
-    def _grow_image(self, img, done, width, tdtype):
-        """The image tensor with room for every row of the store, its first `done` rows kept."""
-        if img is None or img.shape[0] < self._store.shape[0] or img.shape[0] < self.ntotal:
-            new = torch.empty((max(self._store.shape[0], self.ntotal), width), dtype=tdtype, device=self.device)
+    def _grow_image(self, img, done, tdtype, width=None):
+        """A derived per-row array -- [cap, width], or [cap] without a width -- with room for every row of the store, its
+        first `done` rows kept."""
+        cap = max(self._store.shape[0], self.ntotal)
+        if img is None or img.shape[0] < cap:
+            new = torch.empty((cap,) if width is None else (cap, width), dtype=tdtype, device=self.device)
             if img is not None and done:
                 new[:done] = img[:done]
             img = new
@@ -461,7 +321,7 @@ class FlatIndex:
         _lib.check(L.sss_abs_max(self._xb[lo:].data_ptr(), (n - lo) * self.d, self._amax_t.data_ptr(), st), "sss_abs_max")
         amax = float(self._amax_t.item())
         ds = self.scan_width("f16") if self._pad else self.d
-        self._f16 = self._grow_image(self._f16, lo, ds, torch.float16)
+        self._f16 = self._grow_image(self._f16, lo, torch.float16, ds)
         if lo == 0 or not (amax * 2.0 ** self._c_shift < 32768.0):
             self._c_shift = int(L.sss_f16_shift(amax))
             self._resid_t.zero_()
@@ -489,17 +349,14 @@ class FlatIndex:
         n, lo = self.ntotal, self._split_done
         if lo == n and self._split is not None:
             return
+        L, st = _lib.lib(), _lib.stream_ptr(self.device)
+        ds = self.scan_width("split")
+        self._split = self._grow_image(self._split, lo, torch.bfloat16, 2 * ds)
         if self._pad:
-            ds = self.scan_width("split")
-            self._split = self._grow_image(self._split, lo, 2 * ds, torch.bfloat16)
-            rc = _lib.lib().sss_pad_split_bf16(self._xb[lo:].data_ptr(), n - lo, self.d, ds, self._split[lo:].data_ptr(),
-                                               _lib.stream_ptr(self.device))
-            _lib.check(rc, "sss_pad_split_bf16")
+            _lib.check(L.sss_pad_split_bf16(self._xb[lo:].data_ptr(), n - lo, self.d, ds, self._split[lo:].data_ptr(), st),
+                       "sss_pad_split_bf16")
         else:
-            self._split = self._grow_image(self._split, lo, 2 * self.d, torch.bfloat16)
-            rc = _lib.lib().sss_split_bf16(self._xb[lo:].data_ptr(), n - lo, self.d, self._split[lo:].data_ptr(),
-                                           _lib.stream_ptr(self.device))
-            _lib.check(rc, "sss_split_bf16")
+            _lib.check(L.sss_split_bf16(self._xb[lo:].data_ptr(), n - lo, self.d, self._split[lo:].data_ptr(), st), "sss_split_bf16")
         self._split_done = n
 
     def _ensure_p32(self):
@@ -508,7 +365,7 @@ class FlatIndex:
         if lo == n and self._p32 is not None:
             return
         ds = self.scan_width("f32")
-        self._p32 = self._grow_image(self._p32, lo, ds, torch.float32)
+        self._p32 = self._grow_image(self._p32, lo, torch.float32, ds)
         rc = _lib.lib().sss_pad_rows_f32(self._xb[lo:].data_ptr(), n - lo, self.d, ds, self._p32[lo:].data_ptr(),
                                          _lib.stream_ptr(self.device))
         _lib.check(rc, "sss_pad_rows_f32")
@@ -526,11 +383,7 @@ class FlatIndex:
         n, lo = self.ntotal, self._bias_done
         if lo == n and self._bias is not None:
             return
-        if self._bias is None or self._bias.numel() < n:
-            new = torch.empty(max(self._store.shape[0], n), dtype=torch.float32, device=self.device)
-            if self._bias is not None and lo:
-                new[:lo] = self._bias[:lo]
-            self._bias = new
+        self._bias = self._grow_image(self._bias, lo, torch.float32)
         rc = _lib.lib().sss_l2_row_bias(self._xb[lo:].data_ptr(), n - lo, self.d, self._bias[lo:].data_ptr(),
                                         _lib.stream_ptr(self.device))
         _lib.check(rc, "sss_l2_row_bias")
@@ -540,11 +393,16 @@ class FlatIndex:
         """Build whatever a fused search for k results needs (images, norms, the L2 row bias) now rather than on
         the first search; returns the scan that will be used."""
         mode = self._route(k)
-        self._scan_image(mode)
+        self._source(mode)
+        return mode
+
+    def _source(self, mode: str):
+        """``_scan_image(mode)``, with the largest row norm and an L2 index's row bias brought up to date as well."""
+        source = self._scan_image(mode)
         self.corpus_max_norm()
         if mode and self.metric == "l2":
             self._ensure_bias()
-        return mode
+        return source
 
     def _scan_image(self, mode: str):
         """(image, scan code, corpus_shift, corpus_resid_norm) of what scan `mode` reads, the image brought up to date:
@@ -620,12 +478,7 @@ class FlatIndex:
         self._take_norm_max(xb, reset=True)
         self._xb = self._store = xb
         self.id_offset = int(id_offset)
-        self._split, self._split_done = None, 0
-        self._f16, self._f16_done = None, 0
-        self._bias, self._bias_done = None, 0
-        self._p32, self._p32_done = None, 0
-        self._amax_t.zero_()
-        self._resid_t.zero_()
+        self._reset_images()
         self._auto_level.clear()
         self._auto_clean.clear()
         return self
@@ -636,9 +489,6 @@ class FlatIndex:
         return self._cmax
 
     # ------------------------------------------------------------------ device-level search
-    def fused_ok(self, k: int) -> bool:
-        return self.scan_for(k) != ""
-
     def search_fused(self, q: torch.Tensor, k: int, out=None, unproven_count=None):
         """Enqueue the fused MFMA scoring + top-k on the current stream; no host sync.
         Returns (D [nq,k] f32, I [nq,k] i64, status [nq] i32) CUDA tensors; rows with
@@ -654,140 +504,73 @@ class FlatIndex:
             status = torch.empty((nq,), dtype=torch.int32, device=self.device)
         else:
             D, I, status = out
-        mode = self.last_scan = self.prepare(k)
+        mode = self.last_scan = self._route(k)
+        source = self._source(mode)
         if mode == "":
             raise _lib.SssError("search_fused: this index / k has no fused path (use search)")
-        image, code, shift, resid = self._scan_image(mode)
-        if mode == "long" and self.metric == "l2":
-            self._ensure_bias()
-            ws = self._ws.get(L.sss_l2_topk_long_workspace_bytes(nq, n, self.d))
-            rc = L.sss_l2_topk_long(q.data_ptr(), nq, self._xb.data_ptr(), image.data_ptr(), shift, resid, self._bias.data_ptr(),
-                                    n, self.d, k, self.id_offset, self.corpus_max_norm(), D.data_ptr(), I.data_ptr(),
-                                    status.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
-            _lib.check(rc, "sss_l2_topk_long")
-        elif mode == "long":
-            ws = self._ws.get(L.sss_ip_topk_long_workspace_bytes(nq, n, self.d, self._fmt.code))
-            rc = L.sss_ip_topk_long(q.data_ptr(), nq, self._xb.data_ptr(), self._fmt.code, image.data_ptr(), shift, resid,
-                                    n, self.d, k, self.id_offset, self.corpus_max_norm(), D.data_ptr(), I.data_ptr(),
-                                    status.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
-            _lib.check(rc, "sss_ip_topk_long")
+        family = self._family(mode)
+        entry = _TOPK.get(f"{family}_{mode}") or _TOPK[family]
+        v = self._fields(q, nq, source, k, mode)
+        ws = self._workspace(entry, v)
+        res = (self.corpus_max_norm(), D.data_ptr(), I.data_ptr(), status.data_ptr())
+        space = (ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
         if mode == "long":
+            _lib.check(getattr(L, entry.name)(*[v[f] for f in entry.lead], *res, *space), entry.name)
             if unproven_count is not None:
                 unproven_count += (status != 0).sum().to(torch.int32)
             return D, I, status
-        if self._pad:
-            ds = self.scan_width(mode)
-            nbytes = L.sss_pad_topk_workspace_bytes(nq, n, self.d, ds, k, code)
-        elif self.metric == "l2":
-            nbytes = L.sss_l2_topk_workspace_bytes(nq, n, self.d, k, code)
-        elif mode == "f16":
-            nbytes = L.sss_ip_topk_f16_workspace_bytes(nq, n, self.d, k)
-        else:
-            nbytes = L.sss_ip_topk_workspace_bytes(nq, n, self.d, k, self._fmt.code)
-        ws = self._ws.get(nbytes)
         sbytes = L.sss_ip_topk_state_bytes(nq)
         if self._state is None or self._state.numel() < sbytes:
             self._state = torch.zeros(sbytes, dtype=torch.uint8, device=self.device)
-        tail = (self.corpus_max_norm(), D.data_ptr(), I.data_ptr(), status.data_ptr(),
-                0 if unproven_count is None else unproven_count.data_ptr(),
-                self._state.data_ptr(), self._state.numel(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
         if self._pad:
             # the scan reads the padded batch and the ds-wide image, the re-score the d-wide rows (include/sss_pad.h)
-            qp = self._padded_queries(q, ds)
-            rc = L.sss_pad_topk(qp.data_ptr(), nq, self._xb.data_ptr(), image.data_ptr(), code, shift, resid,
-                                self._bias.data_ptr() if self.metric == "l2" else None, n, self.d, ds, k, self.id_offset, *tail)
-        elif self.metric == "l2":
-            rc = L.sss_l2_topk(q.data_ptr(), nq, self._xb.data_ptr(), image.data_ptr(), code, shift, resid,
-                               self._bias.data_ptr(), n, self.d, k, self.id_offset, *tail)
-        elif mode == "f16":
-            rc = L.sss_ip_topk_f16(q.data_ptr(), nq, self._xb.data_ptr(), image.data_ptr(), shift, resid, n, self.d, k,
-                                   self.id_offset, *tail)
-        elif mode == "split":
-            rc = L.sss_ip_topk_split(q.data_ptr(), nq, self._xb.data_ptr(), image.data_ptr(), n, self.d, k, self.id_offset,
-                                     *tail)
-        else:
-            rc = L.sss_ip_topk(q.data_ptr(), nq, self._xb.data_ptr(), n, self.d, k, self._fmt.code,
-                               self.id_offset, *tail)
+            qp = self._padded_queries(q, v["ds"])
+            v["q"] = qp.data_ptr()
+        rc = getattr(L, entry.name)(*[v[f] for f in entry.lead], *res, 0 if unproven_count is None else unproven_count.data_ptr(),
+                                    self._state.data_ptr(), self._state.numel(), *space)
         if rc != 0:
             self._state = None          # re-made (zeroed) on the next call
-        _lib.check(rc, "sss_pad_topk" if self._pad else "sss_l2_topk" if self.metric == "l2" else "sss_ip_topk")
+        _lib.check(rc, entry.name)
         return D, I, status
 
-    def l2_rung_scan(self) -> str:
-        """The scan the threshold rung of an L2 search uses ("" = none): the choice of ``rung_scan`` among the scans
-        this d has, for an index the L2 scans serve at all."""
-        if self.l2_scan_for(1) == "":
-            return ""
-        return self._rung_pick()
+    def _family(self, mode: str) -> str:
+        """The scan family of a fused call on scan `mode`: which entry of ``_TOPK`` / ``_THRESHOLD`` serves it."""
+        if mode == "long":
+            return "long_" + self.metric
+        return "pad" if self._pad else self.metric
 
-    def rung_scan(self) -> str:
-        """The scan the threshold rung uses: the one-pass f16 image where the shape has one (cheapest pass
-        over the corpus; its wider error window only means a few more rows to re-score), else the index's
-        own rows."""
-        if self.metric != "ip" or self.ntotal == 0:
-            return ""
-        if self.dtype != "f32":
-            return "native" if self.d in self._fmt.fused_dims else ""
-        if not any(self._scan_served(s) for s in _LADDER):
-            return ""                            # long rows: their scan IS a threshold scan; what it leaves is mass ties
-        return self._rung_pick()
+    def _fields(self, q: torch.Tensor, nq: int, source, k: int, mode: str) -> dict:
+        """The values ``_Entry.lead`` names; ``source`` is ``_scan_image(mode)``'s, an L2 index's row bias up to date."""
+        image, code, shift, resid = source
+        return {"q": q.data_ptr(), "nq": nq, "xb": self._xb.data_ptr(), "dtype": self._fmt.code, "image": image.data_ptr(),
+                "code": code, "shift": shift, "resid": resid, "bias": self._bias.data_ptr() if self.metric == "l2" else None,
+                "n": self.ntotal, "d": self.d, "ds": self.scan_width(mode) if self._pad else 0, "k": k, "id": self.id_offset}
 
-    def _rung_pick(self) -> str:
-        """The rung's scan of a float32 index with a fused shape."""
-        if self.scan == "auto":
-            # an image that is already complete beats building another one (n * d * 2 bytes) for a handful of queries
-            f16_ready = self._f16 is not None and self._f16_done == self.ntotal
-            split_ready = self._split is not None and self._split_done == self.ntotal
-            if self._scan_served("f16") and (f16_ready or not split_ready):
-                return "f16"
-            if split_ready and self._scan_served("split"):
-                return "split"
-        if self.scan == "f16" and self._scan_served("f16"):
-            return "f16"
-        if self.scan == "split" and self._scan_served("split"):
-            return "split"
-        return "f32" if self._scan_served("f32") else ("f16" if self._scan_served("f16") else "")
+    def _workspace(self, entry: _Entry, v: dict) -> torch.Tensor:
+        return self._ws.get(getattr(_lib.lib(), entry.ws_name)(*[v[f] for f in entry.ws_lead]))
 
     def search_threshold(self, q: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor, status: torch.Tensor, rows):
         """Threshold rung (``sss_ip_topk_threshold``) for the query rows ``rows`` a fused search left
         unproven: one more scan for just those queries keeps every corpus row that could still reach the
         k-th score already known (column k-1 of their rows of D) and re-scores them all.  Resolved rows of
         D / I are rewritten and their status set to 0; returns the rows still unproven."""
-        l2 = self.metric == "l2"
-        mode = self.l2_rung_scan() if l2 else self.rung_scan()
+        mode = self._rung_route()
         if mode == "" or rows.numel() == 0 or k > 8192:
             return rows
-        L = _lib.lib()
-        image, code, shift, resid = self._scan_image(mode)
+        source = self._scan_image(mode)
         sel = rows.to(device=self.device, dtype=torch.int32).contiguous()
-        n = self.ntotal
-        if self._pad:
-            ds = self.scan_width(mode)
-            if l2:
-                self._ensure_bias()
-            qp = self._padded_queries(q, ds)
-            ws = self._ws.get(L.sss_pad_topk_threshold_workspace_bytes(sel.numel(), n, self.d, ds, code))
-            rc = L.sss_pad_topk_threshold(qp.data_ptr(), sel.data_ptr(), sel.numel(), self._xb.data_ptr(), image.data_ptr(), code,
-                                          shift, resid, self._bias.data_ptr() if l2 else None, n, self.d, ds, k, self.id_offset,
-                                          self.corpus_max_norm(), D.data_ptr(), I.data_ptr(), status.data_ptr(),
-                                          ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
-            _lib.check(rc, "sss_pad_topk_threshold")
-            return sel[status[sel.long()] != 0]
-        if l2:
+        if self.metric == "l2":
             self._ensure_bias()
-            ws = self._ws.get(L.sss_l2_topk_threshold_workspace_bytes(sel.numel(), n, self.d, code))
-            rc = L.sss_l2_topk_threshold(q.data_ptr(), sel.data_ptr(), sel.numel(), self._xb.data_ptr(), image.data_ptr(), code,
-                                         shift, resid, self._bias.data_ptr(), n, self.d, k, self.id_offset,
-                                         self.corpus_max_norm(), D.data_ptr(), I.data_ptr(), status.data_ptr(),
-                                         ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
-            _lib.check(rc, "sss_l2_topk_threshold")
-            return sel[status[sel.long()] != 0]
-        ws = self._ws.get(L.sss_ip_topk_threshold_workspace_bytes(sel.numel(), n, self.d, code))
-        rc = L.sss_ip_topk_threshold(q.data_ptr(), sel.data_ptr(), sel.numel(), self._xb.data_ptr(), self._fmt.code,
-                                     image.data_ptr(), code, shift, resid, n, self.d, k, self.id_offset,
-                                     self.corpus_max_norm(), D.data_ptr(), I.data_ptr(), status.data_ptr(),
-                                     ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
-        _lib.check(rc, "sss_ip_topk_threshold")
+        entry = _THRESHOLD[self._family(mode)]
+        v = self._fields(q, sel.numel(), source, k, mode)
+        v["sel"] = sel.data_ptr()
+        if self._pad:
+            qp = self._padded_queries(q, v["ds"])
+            v["q"] = qp.data_ptr()
+        ws = self._workspace(entry, v)
+        rc = getattr(_lib.lib(), entry.name)(*[v[f] for f in entry.lead], self.corpus_max_norm(), D.data_ptr(), I.data_ptr(),
+                                             status.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
+        _lib.check(rc, entry.name)
         return sel[status[sel.long()] != 0]
 
     def fix_unproven(self, q: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor, status: torch.Tensor) -> int:
@@ -845,10 +628,11 @@ class FlatIndex:
             I.fill_(-1)
             return D, I
         self._require_d_aligned()
-        if self._route(k):
+        mode = self._route(k)
+        if mode:
             # the per-query workspace is 16 KB (fused scans) to 64 KB (long rows, threshold rung): the reference hands
             # `index.search` its whole test set at once (test_amazon_filterd.py:578), so large batches go in chunks
-            step = SEARCH_CHUNK_LONG if self._route(k) == "long" else SEARCH_CHUNK
+            step = SEARCH_CHUNK_LONG if mode == "long" else SEARCH_CHUNK
             status = torch.empty((nq,), dtype=torch.int32, device=self.device)
             rescans = fallbacks = 0
             for lo in range(0, nq, step):

@@ -1,7 +1,13 @@
 """The float16 corpus dtype (``FlatIndex(d, dtype="f16")``, C ABI ``dtype = 4``) without a device: the dtype is accepted,
 its scan policy is the bf16 index's, and every C entry point that takes ``dtype`` lets 4 through its host-side argument
 checks exactly where it lets 1 through -- while 2 and 3 (scan images of a float32 corpus) and 5 stay rejected."""
+import functools
+import os
+import sys
+
 import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 
 P = 1 << 20                     # a 256-byte aligned stand-in for device pointers: never dereferenced
 
@@ -41,14 +47,8 @@ def test_f16_dtype_is_accepted_as_far_as_the_others():
 
 def test_f16_scan_policy_is_host_logic():
     """scan_for / rung_scan of an f16 index: the bf16 index's policy (stored rows are the only scan source)."""
-    from sessionsimilaritysearch_amd import index as ix
-
-    class Stub(ix.FlatIndex):
-        def __init__(self, d, metric="ip", dtype="f16", scan="native", n=1000):     # no device: only the policy fields
-            self.d, self.metric, self.dtype, self.scan, self._n, self._auto_level, self._auto_clean = d, metric, dtype, scan, n, {}, {}
-            self._auto_rows, self._f16, self._f16_done, self._split, self._split_done = 0, None, 0, None, 0
-
-        ntotal = property(lambda self: self._n)
+    from routing_stub import make_routing
+    Stub = functools.partial(make_routing, dtype="f16")     # no device: only the policy
 
     for d in (128, 256, 512):
         assert [Stub(d).scan_for(k) for k in (1, 10, 100, 500, 501, 600)] == ["native"] * 4 + ["", ""]

@@ -4,8 +4,10 @@ argument checks of every C entry point that takes ``dtype``, and the canonical s
 
 The code is 6, not 5: tests/test_f16_index_cpu.py passes 5 to every entry point as a value that must stay invalid (and
 pins ``index.DTYPE_CODE`` to the three float formats, so the int8 code lives in ``index.INT_DTYPE_CODE``)."""
+import functools
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
@@ -13,6 +15,7 @@ import pytest
 P = 1 << 20                     # a 256-byte aligned stand-in for device pointers: never dereferenced
 I8 = 6
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 
 
 @pytest.fixture(scope="module")
@@ -100,14 +103,8 @@ def test_integer_valued_check_on_host_tensors():
 def test_scan_policy_is_host_logic():
     """scan_for / rung_scan of an i8 index: the fused scan at d = 256 / 512 / 1024 up to k = 500, nothing else -- no
     long-row scan (d = 1600 and every other d go to the exhaustive kernels), no L2."""
-    from sessionsimilaritysearch_amd import index as ix
-
-    class Stub(ix.FlatIndex):
-        def __init__(self, d, metric="ip", dtype="i8", scan="native", n=1000):     # no device: only the policy fields
-            self.d, self.metric, self.dtype, self.scan, self._n, self._auto_level, self._auto_clean = d, metric, dtype, scan, n, {}, {}
-            self._auto_rows, self._f16, self._f16_done, self._split, self._split_done = 0, None, 0, None, 0
-
-        ntotal = property(lambda self: self._n)
+    from routing_stub import make_routing
+    Stub = functools.partial(make_routing, dtype="i8")      # no device: only the policy
 
     for d in (256, 512, 1024):
         assert [Stub(d).scan_for(k) for k in (1, 10, 100, 500, 501, 600)] == ["native"] * 4 + ["", ""]

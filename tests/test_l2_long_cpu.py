@@ -2,10 +2,13 @@
 headers' lists, the workspace size is host arithmetic, and the routing policy of ``FlatIndex.l2_long_for`` is host logic."""
 import os
 import re
+import sys
 
 from sessionsimilaritysearch_amd import _lib, index as ix
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from routing_stub import make_routing  # noqa: E402
 NAMES = ["sss_l2_topk_long", "sss_l2_topk_long_workspace_bytes"]
 
 
@@ -42,15 +45,9 @@ def test_l2_long_workspace_bytes_is_host_arithmetic():
     assert L.sss_l2_topk_long_workspace_bytes(8, 20000, 4160) == 0          # a row over 16 KB
 
 
-class Stub(ix.FlatIndex):
-    """No device: only the policy fields."""
-
-    def __init__(self, d, metric="l2", dtype="f32", scan="auto", n=1000, cmax=1.0):
-        self.d, self.metric, self.dtype, self.scan, self._n, self._cmax = d, metric, dtype, scan, n, cmax
-        self._auto_level, self._auto_clean, self._auto_rows = {}, {}, 0
-        self._f16, self._f16_done, self._split, self._split_done = None, 0, None, 0
-
-    ntotal = property(lambda self: self._n)
+def Stub(d, metric="l2", **kw):
+    """No device: only the policy."""
+    return make_routing(d, metric, **kw)
 
 
 def test_l2_long_policy():

@@ -4,25 +4,15 @@ same entry points; and every argument rule of the new entry points is checked be
 null or never-dereferenced pointers, as tests/test_abi_contract_cpu.py makes them)."""
 import os
 import re
+import sys
 
 import pytest
 
 from sessionsimilaritysearch_amd import _lib, index as ix
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-class Stub(ix.FlatIndex):
-    """No device: only the policy fields."""
-
-    def __init__(self, d, metric="ip", dtype="f32", scan="auto", n=1000, cmax=1.0, pad_scan=None):
-        self.d, self.metric, self.dtype, self.scan, self._n, self._cmax = d, metric, dtype, scan, n, cmax
-        self._auto_level, self._auto_clean, self._auto_rows = {}, {}, 0
-        self._f16, self._f16_done, self._split, self._split_done = None, 0, None, 0
-        if pad_scan is not None:        # (None: the attribute is left to the class, as in the stubs of the older test files)
-            self._pad = bool(pad_scan) and dtype == "f32" and 4 <= d <= ix.PAD_SCAN_MAX_D and d % 4 == 0 and d % 64 != 0
-
-    ntotal = property(lambda self: self._n)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from routing_stub import make_routing as Stub  # noqa: E402    (no device: only the policy)
 
 
 def _route(d, k, **kw):
@@ -109,7 +99,7 @@ def test_padded_views_report_the_scan_truthfully():
     assert l2.l2_rung_scan() == "f16" and l2.rung_scan() == "" and l2.scan_for(10) == "" and l2.fused_ok(10) is False
     assert Stub(200, "l2", cmax=2.0 ** 61, pad_scan=True).l2_scan_for(10) == ""          # the magnitude guard holds
     r = Stub(200, pad_scan=True)                           # scan="auto": a complete split image beats building an f16 one
-    r._split, r._split_done = object(), 1000
+    r._complete.add("split")
     assert r.rung_scan() == "split"
 
 
