@@ -10,7 +10,7 @@ in seconds instead of a minute at 450 001 rows.
 Rows are "varnorm": Gaussian directions with norms log-uniform in [1/4, 4].  On unit rows the L2 order is the
 inner-product order and a missing or mis-indexed bias would go unnoticed."""
 import os
-from concurrent.futures import ThreadPoolExecutor
+import sys
 
 import numpy as np
 import pytest
@@ -18,43 +18,11 @@ import torch
 
 from oracle import search_ref as sr
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from l2_long_ref import ORACLE_BLOCK, _equal, _oracle, _varnorm  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 FLT_MAX = np.float32(3.4028234663852886e38)
-ORACLE_BLOCK = 8192
-
-
-def _oracle(q, c, k):
-    q, c = np.ascontiguousarray(q, np.float32), np.ascontiguousarray(c, np.float32)
-    if c.shape[0] <= 2 * ORACLE_BLOCK:
-        return sr.build_index(c, "l2").search(q, k)
-
-    def block(lo):
-        D, I = sr.build_index(c[lo:lo + ORACLE_BLOCK], "l2").search(q, k)
-        return D, np.where(I >= 0, I + lo, -1)
-
-    with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as ex:
-        parts = list(ex.map(block, range(0, c.shape[0], ORACLE_BLOCK)))
-    D, I = np.concatenate([p[0] for p in parts], 1), np.concatenate([p[1] for p in parts], 1)
-    order = np.lexsort((np.where(I < 0, np.iinfo(np.int64).max, I), D), axis=1)[:, :k]
-    return np.take_along_axis(D, order, 1), np.take_along_axis(I, order, 1)
-
-
-def _varnorm(n, d, nq, seed):
-    rng = np.random.default_rng(seed)
-
-    def rows(m):
-        x = rng.standard_normal((m, d), dtype=np.float32)
-        s = np.exp(rng.uniform(np.log(.25), np.log(4), m))
-        return (x / np.linalg.norm(x, axis=1, keepdims=True) * s[:, None]).astype(np.float32)
-
-    return rows(n), rows(nq)
-
-
-def _equal(got, want):
-    D, I = got
-    Dr, Ir = want
-    assert np.array_equal(I, Ir), int((I != Ir).sum())
-    assert np.array_equal(D, Dr), int((D != Dr).sum())
 
 
 def _l2_index(cuda, c):
