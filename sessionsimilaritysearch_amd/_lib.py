@@ -1,5 +1,5 @@
-"""ctypes binding of libsss.so (the C ABI declared in include/sss.h, include/sss_sparse.h, include/sss_l2.h, include/sss_l2_long.h,
-include/sss_pad.h, include/sss_graph.h and include/sss_eval.h).
+"""ctypes binding of libsss.so: the C ABI declared in the headers of include/, one signature table per header
+(``HEADERS`` below names them all).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails, this
 module raises.  ``build()`` compiles the library in-tree with hipcc for gfx950.
@@ -170,6 +170,18 @@ _EVAL_SIGNATURES = {
 }
 
 
+# header of include/ -> its signature table: what lib() binds, and every *_symbols() view below
+HEADERS = {
+    "sss.h": _SIGNATURES,
+    "sss_sparse.h": _SPARSE_SIGNATURES,
+    "sss_l2.h": _L2_SIGNATURES,
+    "sss_l2_long.h": _L2_LONG_SIGNATURES,
+    "sss_pad.h": _PAD_SIGNATURES,
+    "sss_graph.h": _GRAPH_SIGNATURES,
+    "sss_eval.h": _EVAL_SIGNATURES,
+}
+
+
 class LinearProblem(ctypes.Structure):
     """``sss_linear_problem`` of include/sss.h."""
     _fields_ = [("x", c_void_p), ("ldx", c_int64), ("ids", c_void_p), ("table", c_void_p), ("xcopy", c_void_p),
@@ -196,37 +208,37 @@ class LayerArgs(ctypes.Structure):
 
 
 def exported_symbols():
-    return sorted(_SIGNATURES)
+    return sorted(HEADERS["sss.h"])
 
 
 def sparse_symbols():
     """The entry points of include/sss_sparse.h."""
-    return sorted(_SPARSE_SIGNATURES)
+    return sorted(HEADERS["sss_sparse.h"])
 
 
 def l2_symbols():
     """The entry points of include/sss_l2.h."""
-    return sorted(_L2_SIGNATURES)
+    return sorted(HEADERS["sss_l2.h"])
 
 
 def l2_long_symbols():
     """The entry points of include/sss_l2_long.h."""
-    return sorted(_L2_LONG_SIGNATURES)
+    return sorted(HEADERS["sss_l2_long.h"])
 
 
 def pad_symbols():
     """The entry points of include/sss_pad.h."""
-    return sorted(_PAD_SIGNATURES)
+    return sorted(HEADERS["sss_pad.h"])
 
 
 def graph_symbols():
     """The entry points of include/sss_graph.h."""
-    return sorted(_GRAPH_SIGNATURES)
+    return sorted(HEADERS["sss_graph.h"])
 
 
 def eval_symbols():
     """The entry points of include/sss_eval.h."""
-    return sorted(_EVAL_SIGNATURES)
+    return sorted(HEADERS["sss_eval.h"])
 
 
 def build(verbose: bool = False) -> str:
@@ -250,10 +262,10 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C "
                 "sessionsimilaritysearch_amd/csrc`). There is no CPU fallback.")
         h = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in (*_SIGNATURES.items(), *_SPARSE_SIGNATURES.items(), *_L2_SIGNATURES.items(),
-                                   *_L2_LONG_SIGNATURES.items(), *_PAD_SIGNATURES.items(), *_GRAPH_SIGNATURES.items(), *_EVAL_SIGNATURES.items()):
-            fn = getattr(h, name)          # AttributeError if the .so lacks a declared symbol
-            fn.restype, fn.argtypes = res, args
+        for table in HEADERS.values():
+            for name, (res, args) in table.items():
+                fn = getattr(h, name)      # AttributeError if the .so lacks a declared symbol
+                fn.restype, fn.argtypes = res, args
         _lib = h
     return _lib
 

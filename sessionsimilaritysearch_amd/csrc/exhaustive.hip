@@ -535,20 +535,21 @@ static int launch_exact_scores(const void* q, const int* qsel, long nsel, const 
     return check_launch("k_exact_scores");
 }
 
-size_t ip_topk_exhaustive_workspace_bytes(long nsel, long n) {
+extern "C" size_t sss_ip_topk_exhaustive_workspace_bytes(int64_t nsel, int64_t n) {
     return (((size_t)nsel * n * 4 + 255) & ~(size_t)255) + 256 + compact_bytes(nsel, n);
 }
 
-int ip_topk_exhaustive(const void* q, const int* qsel, long nsel, const void* c, long n, int d,
-                       int k, int dtype, long id_offset, int metric, const float* lower_bound, float* D_out, long* I_out,
-                       void* ws, size_t ws_bytes, hipStream_t st) {
+// sss_ip_topk_exhaustive and sss_ip_topk_exhaustive_lb below are the two views of this one
+static int ip_topk_exhaustive(const void* q, const int* qsel, long nsel, const void* c, long n, int d,
+                              int k, int dtype, long id_offset, int metric, const float* lower_bound, float* D_out, long* I_out,
+                              void* ws, size_t ws_bytes, hipStream_t st) {
     if (nsel <= 0 || n <= 0 || k <= 0 || d <= 0 || !corpus_dtype_ok(dtype) ||
         d % elems_per_chunk(dtype) || (metric != 0 && metric != 1)) {
         set_error("ip_topk_exhaustive: need nsel, n, k > 0, %s, metric in {0,1}", row_align_text());
         return SSS_EINVAL;
     }
     if (n >= (1L << 31) || nsel > 65535 || k > RS_MAX_K) { set_error("ip_topk_exhaustive: n < 2^31, nsel <= 65535, k <= 1024"); return SSS_EINVAL; }
-    if (ws_bytes < ip_topk_exhaustive_workspace_bytes(nsel, n)) {
+    if (ws_bytes < sss_ip_topk_exhaustive_workspace_bytes(nsel, n)) {
         set_error("ip_topk_exhaustive: workspace too small");
         return SSS_EWORKSPACE;
     }
@@ -557,6 +558,20 @@ int ip_topk_exhaustive(const void* q, const int* qsel, long nsel, const void* c,
     if (rc) return rc;
     return topk_of_scores(scores, qsel, nsel, n, k, id_offset, metric, D_out, I_out,
                           reinterpret_cast<char*>(ws) + (((size_t)nsel * n * 4 + 255) & ~(size_t)255), st);
+}
+
+extern "C" int sss_ip_topk_exhaustive(const void* q, const int32_t* qsel, int64_t nsel, const void* corpus, int64_t n, int d, int k, int dtype,
+                                      int64_t id_offset, int metric, float* D_out, int64_t* I_out, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    return ip_topk_exhaustive(q, qsel, nsel, corpus, n, d, k, dtype, id_offset, metric, nullptr, D_out, I_out, workspace, workspace_bytes,
+                              static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sss_ip_topk_exhaustive_lb(const void* q, const int32_t* qsel, int64_t nsel, const void* corpus, int64_t n, int d, int k,
+                                         int dtype, int64_t id_offset, const float* lower_bound, float* D_out, int64_t* I_out,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+    return ip_topk_exhaustive(q, qsel, nsel, corpus, n, d, k, dtype, id_offset, 0, lower_bound, D_out, I_out, workspace, workspace_bytes,
+                              static_cast<hipStream_t>(stream));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -650,7 +665,7 @@ __global__ __launch_bounds__(RG_THREADS) void k_range_compact(const float* __res
     }
 }
 
-size_t range_exhaustive_workspace_bytes(long nsel, long n) {
+extern "C" size_t sss_range_search_exhaustive_workspace_bytes(int64_t nsel, int64_t n) {
     if (nsel <= 0 || n <= 0) return 0;
     return rg_scores_bytes(nsel, n) + (((size_t)nsel * rg_slabs(n) * 4 + 255) & ~(size_t)255);
 }
@@ -663,27 +678,29 @@ static int range_exhaustive_check(const char* what, const int* qsel, long nsel, 
     }
     if (n >= (1L << 31) || nsel > 65535) { set_error("%s: n < 2^31, nsel <= 65535", what); return SSS_EINVAL; }
     if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("%s: workspace must be 256-byte aligned", what); return SSS_EINVAL; }
-    if (!ws || ws_bytes < range_exhaustive_workspace_bytes(nsel, n)) {
-        set_error("%s: workspace %zu < %zu", what, ws_bytes, range_exhaustive_workspace_bytes(nsel, n));
+    if (!ws || ws_bytes < sss_range_search_exhaustive_workspace_bytes(nsel, n)) {
+        set_error("%s: workspace %zu < %zu", what, ws_bytes, sss_range_search_exhaustive_workspace_bytes(nsel, n));
         return SSS_EWORKSPACE;
     }
     return SSS_OK;
 }
 
-int range_exhaustive_count(const void* q, const int* qsel, long nsel, const void* c, long n, int d, int dtype, int metric, const float* radius,
-                           long* counts, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (d <= 0 || !corpus_dtype_ok(dtype) || d % elems_per_chunk(dtype) || !q || !c || !counts) {
+extern "C" int sss_range_search_exhaustive_count(const void* q, const int32_t* qsel, int64_t nsel, const void* corpus, int64_t n, int d,
+                                                 int dtype, int metric, const float* radius, int64_t* counts, void* workspace,
+                                                 size_t workspace_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (d <= 0 || !corpus_dtype_ok(dtype) || d % elems_per_chunk(dtype) || !q || !corpus || !counts) {
         set_error("range_exhaustive_count: need %s, q, corpus and counts", row_align_text());
         return SSS_EINVAL;
     }
-    int rc = range_exhaustive_check("range_exhaustive_count", qsel, nsel, n, metric, radius, ws, ws_bytes);
+    int rc = range_exhaustive_check("range_exhaustive_count", qsel, nsel, n, metric, radius, workspace, workspace_bytes);
     if (rc) return rc;
-    float* scores = reinterpret_cast<float*>(ws);
-    unsigned* cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + rg_scores_bytes(nsel, n));
+    float* scores = reinterpret_cast<float*>(workspace);
+    unsigned* cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) + rg_scores_bytes(nsel, n));
     const int nslabs = (int)rg_slabs(n);
     // inner product: the radius is a valid pre-test bound -- a row k_exact_scores_rows skips (score -FLT_MAX) provably
     // rounds to at most the radius, so it fails "> radius" either way
-    rc = launch_exact_scores(q, qsel, nsel, c, n, d, dtype, metric, scores, metric == 0 ? radius : nullptr, 1, st);
+    rc = launch_exact_scores(q, qsel, nsel, corpus, n, d, dtype, metric, scores, metric == 0 ? radius : nullptr, 1, st);
     if (rc) return rc;
     hipLaunchKernelGGL(k_range_count, dim3((unsigned)nslabs, (unsigned)nsel), dim3(RG_THREADS), 0, st, scores, n, metric, radius, qsel,
                        nslabs, cnt);
@@ -693,13 +710,15 @@ int range_exhaustive_count(const void* q, const int* qsel, long nsel, const void
     return check_launch("k_range_scan");
 }
 
-int range_exhaustive_fill(const int* qsel, long nsel, long n, int metric, const float* radius, const long* lims, long id_offset, float* D_out,
-                          long* I_out, const void* ws, size_t ws_bytes, hipStream_t st) {
-    int rc = range_exhaustive_check("range_exhaustive_fill", qsel, nsel, n, metric, radius, ws, ws_bytes);
+extern "C" int sss_range_search_exhaustive_fill(const int32_t* qsel, int64_t nsel, int64_t n, int metric, const float* radius,
+                                                const int64_t* lims, int64_t id_offset, float* D_out, int64_t* I_out,
+                                                const void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc = range_exhaustive_check("range_exhaustive_fill", qsel, nsel, n, metric, radius, workspace, workspace_bytes);
     if (rc) return rc;
     if (!lims) { set_error("range_exhaustive_fill: lims is required"); return SSS_EINVAL; }
-    const float* scores = reinterpret_cast<const float*>(ws);
-    const unsigned* off = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(ws) + rg_scores_bytes(nsel, n));
+    const float* scores = reinterpret_cast<const float*>(workspace);
+    const unsigned* off = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(workspace) + rg_scores_bytes(nsel, n));
     const int nslabs = (int)rg_slabs(n);
     hipLaunchKernelGGL(k_range_compact, dim3((unsigned)nslabs, (unsigned)nsel), dim3(RG_THREADS), 0, st, scores, n, metric, radius, qsel,
                        nslabs, off, (int)nsel, lims, id_offset, D_out, I_out);

@@ -17,11 +17,9 @@
 
 namespace sss {
 
-int normalize_rows(float* x, long n, int d, long ld, float eps, int rule, hipStream_t st);    // rowops.hip
-
 constexpr int LT = 64;      // GEMM tile rows (X) and columns (W rows): see k_linear_grouped below
 
-int linear_grouped(LinBatch& b, hipStream_t st);
+static int linear_grouped(LinBatch& b, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------
 // Per target node i (CSR by target): e_ij = leaky_relu(as[j] + ad[i], 0.2);
@@ -305,24 +303,26 @@ static unsigned grid_rows(long n, int lpr) {
 
 // Y[N, M] = X[N, K] * W[M, K]^T (+ bias[M]): one problem of the grouped kernel (round 3: the separate 64 x 64
 // kernel this entry point used to launch computed the identical fma chains 8-20 % slower on every shape).
-int linear_f32(const float* X, long ldx, const float* W, long ldw, const float* bias, float* Y, long ldy,
-               long N, int M, int K, hipStream_t st) {
-    if (N < 0 || M <= 0 || K <= 0 || K % 32 || ldx % 4 || ldw % 4 || ldx < K || ldw < K || ldy < M) {
-        set_error("linear: need K %% 32 == 0, ldx/ldw %% 4 == 0 and >= K, ldy >= M (N=%ld M=%d K=%d)", N, M, K);
+extern "C" int sss_linear(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, float* y, int64_t ldy, int64_t n,
+                          int m, int k, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n < 0 || m <= 0 || k <= 0 || k % 32 || ldx % 4 || ldw % 4 || ldx < k || ldw < k || ldy < m) {
+        set_error("linear: need K %% 32 == 0, ldx/ldw %% 4 == 0 and >= K, ldy >= M (N=%ld M=%d K=%d)", n, m, k);
         return SSS_EINVAL;
     }
-    if (N == 0) return SSS_OK;
+    if (n == 0) return SSS_OK;
     LinBatch b = {};
-    b.nprob = 1; b.K = K;
+    b.nprob = 1; b.K = k;
     LinProb& p = b.p[0];
-    p.x = X; p.ldx = ldx; p.ids = nullptr; p.table = nullptr; p.xcopy = nullptr; p.ld_xcopy = 0;
-    p.w = W; p.ldw = ldw; p.bias = bias; p.y = Y; p.ldy = ldy; p.n = N; p.m = M; p.act = 0;
+    p.x = x; p.ldx = ldx; p.ids = nullptr; p.table = nullptr; p.xcopy = nullptr; p.ld_xcopy = 0;
+    p.w = w; p.ldw = ldw; p.bias = bias; p.y = y; p.ldy = ldy; p.n = n; p.m = m; p.act = 0;
     return linear_grouped(b, st);
 }
 
-int gat_aggregate(const float* xs, long ld_xs, const float* a_src, long ld_as, const float* a_dst, long ld_ad,
-                  const int* rowptr, const int* col, long n_dst, int h, const float* bias, int relu, long n_self_loop,
-                  float* out, long ld_out, hipStream_t st) {
+extern "C" int sss_gat_aggregate(const float* xs, int64_t ld_xs, const float* a_src, int64_t ld_as, const float* a_dst, int64_t ld_ad,
+                                 const int32_t* rowptr, const int32_t* col, int64_t n_dst, int h, const float* bias, int relu,
+                                 int64_t n_self_loop, float* out, int64_t ld_out, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_dst < 0 || h <= 0 || h % 4 || ld_xs % 4 || ld_out % 4 || ld_out < h) {
         set_error("gat_aggregate: need h %% 4 == 0 and 16-byte aligned row strides");
         return SSS_EINVAL;
@@ -335,8 +335,9 @@ int gat_aggregate(const float* xs, long ld_xs, const float* a_src, long ld_as, c
     return check_launch("k_gat_aggregate");
 }
 
-int csr_weighted_sum(const float* m, long ld_m, const int* rowptr, const int* col, const float* w, long n_dst,
-                     int h, float* out, long ld_out, hipStream_t st) {
+extern "C" int sss_csr_weighted_sum(const float* m, int64_t ld_m, const int32_t* rowptr, const int32_t* col, const float* w,
+                                    int64_t n_dst, int h, float* out, int64_t ld_out, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_dst < 0 || h <= 0 || h % 4 || ld_m % 4 || ld_out % 4 || ld_out < h) {
         set_error("csr_weighted_sum: need h %% 4 == 0 and 16-byte aligned row strides");
         return SSS_EINVAL;
@@ -348,8 +349,9 @@ int csr_weighted_sum(const float* m, long ld_m, const int* rowptr, const int* co
     return check_launch("k_csr_weighted_sum");
 }
 
-int gru_combine(const float* gi, long ld_gi, const float* gh, long ld_gh, const float* x, long ld_x, int d_x,
-                const float* add, long ld_add, long n, int h, float* out, long ld_out, hipStream_t st) {
+extern "C" int sss_gru_combine(const float* gi, int64_t ld_gi, const float* gh, int64_t ld_gh, const float* x, int64_t ld_x, int d_x,
+                               const float* add, int64_t ld_add, int64_t n, int h, float* out, int64_t ld_out, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (n < 0 || h <= 0 || h % 4 || d_x > h || ld_gi % 4 || ld_gh % 4 || ld_out % 4 || (add && ld_add % 4) ||
         (d_x >= 4 && ld_x % 4)) {
         set_error("gru_combine: need h %% 4 == 0, d_x <= h and 16-byte aligned row strides");
@@ -363,38 +365,41 @@ int gru_combine(const float* gi, long ld_gi, const float* gh, long ld_gh, const 
     return check_launch("k_gru_combine");
 }
 
-int pool_expand(const float* lin_p, const float* lin_q, long ld_lin, const int* src_row, const int* pos_id,
-                long n_clicks, long n_exp, int Dl, int P, const float* pos_emb, float* node, long ld_node,
-                hipStream_t st) {
-    if (n_exp < 0 || n_clicks < 0 || n_clicks > n_exp || Dl <= 0 || P < 0 || ld_node < Dl + P) {
+extern "C" int sss_pool_expand(const float* lin_p, const float* lin_q, int64_t ld_lin, const int32_t* src_row, const int32_t* pos_id,
+                               int64_t n_clicks, int64_t n_exp, int d_lin, int p, const float* pos_emb, float* node, int64_t ld_node,
+                               void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n_exp < 0 || n_clicks < 0 || n_clicks > n_exp || d_lin <= 0 || p < 0 || ld_node < d_lin + p) {
         set_error("pool_expand: bad arguments");
         return SSS_EINVAL;
     }
     if (n_exp == 0) return SSS_OK;
-    long blocks = (n_exp * (Dl + P) + 255) / 256;
+    long blocks = (n_exp * (d_lin + p) + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_pool_expand, dim3((unsigned)blocks), dim3(256), 0, st, lin_p, lin_q, ld_lin, src_row, pos_id,
-                       n_clicks, n_exp, Dl, P, pos_emb, node, ld_node);
+                       n_clicks, n_exp, d_lin, p, pos_emb, node, ld_node);
     return check_launch("k_pool_expand");
 }
 
-int segment_pool(const float* node, long ld_node, const int* pptr, const int* qptr, long n_clicks, long n_graphs,
-                 int D, const float* A, long ld_a, const float* bcoarse, long ld_b, const float* watt, float* out,
-                 long ld_out, hipStream_t st) {
-    if (n_graphs < 0 || D <= 0 || D % 4 || ld_node % 4 || ld_out % 4 ||
-        (watt && (!A || !bcoarse || ld_a % 4 || ld_b % 4))) {
+extern "C" int sss_segment_pool(const float* node, int64_t ld_node, const int32_t* pptr, const int32_t* qptr, int64_t n_clicks,
+                                int64_t n_graphs, int d, const float* a, int64_t ld_a, const float* bcoarse, int64_t ld_b,
+                                const float* watt, float* out, int64_t ld_out, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n_graphs < 0 || d <= 0 || d % 4 || ld_node % 4 || ld_out % 4 ||
+        (watt && (!a || !bcoarse || ld_a % 4 || ld_b % 4))) {
         set_error("segment_pool: need D %% 4 == 0 and 16-byte aligned row strides");
         return SSS_EINVAL;
     }
     if (n_graphs == 0) return SSS_OK;
-    const int lpr = lanes_for(D);
+    const int lpr = lanes_for(d);
     SSS_LPR_SWITCH(lpr, hipLaunchKernelGGL(k_segment_pool<L>, dim3(grid_rows(n_graphs, L)), dim3(256), 0, st, node,
-                                           ld_node, pptr, qptr, n_clicks, n_graphs, D, A, ld_a, bcoarse, ld_b, watt,
+                                           ld_node, pptr, qptr, n_clicks, n_graphs, d, a, ld_a, bcoarse, ld_b, watt,
                                            out, ld_out));
     return check_launch("k_segment_pool");
 }
 
-int segment_ptr(const long* batch, long n, long n_graphs, int* ptr, hipStream_t st) {
+extern "C" int sss_segment_ptr(const int64_t* batch, int64_t n, int64_t n_graphs, int32_t* ptr, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (n < 0 || n_graphs < 0) { set_error("segment_ptr: bad arguments"); return SSS_EINVAL; }
     hipLaunchKernelGGL(k_segment_ptr, dim3((unsigned)((n_graphs + 1 + 255) / 256)), dim3(256), 0, st, batch, n, n_graphs, ptr);
     return check_launch("k_segment_ptr");
@@ -864,7 +869,7 @@ __global__ __launch_bounds__(256) void k_pool_attention_tab(const float* __restr
 }
 
 // ------------------------------------------------------------------------------ host launchers
-int linear_grouped(LinBatch& b, hipStream_t st) {
+static int linear_grouped(LinBatch& b, hipStream_t st) {
     if (b.nprob < 1 || b.nprob > 4 || b.K <= 0 || b.K % 32) { set_error("linear_grouped: 1..4 problems, K %% 32 == 0"); return SSS_EINVAL; }
     int total = 0;
     for (int i = 0; i < b.nprob; ++i) {
@@ -889,7 +894,25 @@ int linear_grouped(LinBatch& b, hipStream_t st) {
     return check_launch("k_linear_grouped");
 }
 
-int layer_update(const LayerArgs& a, hipStream_t st) {
+extern "C" int sss_linear_grouped(const sss_linear_problem* problems, int n_problems, int k, void* stream) {
+    if (!problems || n_problems < 1 || n_problems > 4) { set_error("linear_grouped: 1..4 problems"); return SSS_EINVAL; }
+    LinBatch b;
+    b.nprob = n_problems; b.K = k;
+    for (int i = 0; i < n_problems; ++i) {
+        const sss_linear_problem& s = problems[i];
+        LinProb& p = b.p[i];
+        p.x = s.x; p.ldx = s.ldx; p.ids = s.ids; p.table = s.table; p.xcopy = s.xcopy;
+        p.ld_xcopy = s.ld_xcopy; p.w = s.w; p.ldw = s.ldw; p.bias = s.bias; p.y = s.y; p.ldy = s.ldy; p.n = s.n; p.m = s.m;
+        p.act = s.act; p.post_scale = s.post_scale; p.post_shift = s.post_shift; p.tiles_m = 0; p.tile_begin = 0;
+        if (s.act < 0 || s.act > 4 || (s.post_scale == nullptr) != (s.post_shift == nullptr)) {
+            set_error("linear_grouped: problem %d: act must be 0..4, post_scale / post_shift come together", i);
+            return SSS_EINVAL;
+        }
+    }
+    return linear_grouped(b, static_cast<hipStream_t>(stream));
+}
+
+static int layer_update(const LayerArgs& a, hipStream_t st) {
     if (a.h <= 0 || a.h % 4 || a.h > 256 || a.Np < 0 || a.Nq < 0 || a.d_x > a.h || a.ldyp % 4 || a.ldyq % 4 || a.ld_outp % 4 ||
         a.ld_outq % 4 || (a.d_x >= 4 && a.ld_xin % 4) || a.ldyp < 7 * a.h + 2 || a.ldyq < a.h + 2) {
         set_error("layer_update: need h %% 4 == 0, h <= 256, d_x <= h, 16-byte aligned row strides, ldyp >= 7h+2, ldyq >= h+2");
@@ -907,11 +930,26 @@ int layer_update(const LayerArgs& a, hipStream_t st) {
     return check_launch("k_layer_update");
 }
 
-int pool_expand_mean(const float* lin_p, const float* lin_q, long ld_lin, const int* src_row, const int* pos_id,
-                     const int* pptr, const int* qptr, long n_clicks, long n_graphs, int Dl, int P, const float* pos_emb,
-                     float* node, long ld_node, float* coarse, long ld_coarse, hipStream_t st) {
-    const int D = Dl + P;
-    if (n_graphs < 0 || Dl <= 0 || P < 0 || D % 4 || D > 256 || ld_node % 4 || ld_node < D || ld_coarse % 4 || ld_coarse < D) {
+extern "C" int sss_hetero_layer_update(const sss_layer_args* args, void* stream) {
+    if (!args) { set_error("hetero_layer_update: null args"); return SSS_EINVAL; }
+    LayerArgs l;
+    l.Yp = args->yp; l.ldyp = args->ld_yp; l.Yq = args->yq; l.ldyq = args->ld_yq; l.h = args->h; l.d_x = args->d_x;
+    l.rowptr_qp = args->rowptr_qp; l.col_qp = args->col_qp; l.rowptr_pp = args->rowptr_pp; l.col_pp = args->col_pp; l.w_pp = args->w_pp;
+    l.bias_qp = args->bias_qp; l.b_ih = args->b_ih; l.xin_p = args->xin_p; l.ld_xin = args->ld_xin; l.out_p = args->out_p;
+    l.ld_outp = args->ld_out_p; l.Np = args->np; l.rowptr_pq = args->rowptr_pq; l.col_pq = args->col_pq; l.bias_pq = args->bias_pq;
+    l.out_q = args->out_q; l.ld_outq = args->ld_out_q; l.Nq = args->nq; l.n_self_loop = args->n_self_loop;
+    l.row_p = args->row_p; l.row_q = args->row_q;
+    l.x0_p = args->x0_p; l.ld_x0p = args->ld_x0_p; l.xq_table = args->xq_table; l.ld_xq = args->ld_xq; l.x0_q = args->x0_q; l.ld_x0q = args->ld_x0_q;
+    return layer_update(l, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sss_pool_expand_mean(const float* lin_p, const float* lin_q, int64_t ld_lin, const int32_t* src_row,
+                                    const int32_t* pos_id, const int32_t* pptr, const int32_t* qptr, int64_t n_clicks, int64_t n_graphs,
+                                    int d_lin, int p, const float* pos_emb, float* node, int64_t ld_node, float* coarse,
+                                    int64_t ld_coarse, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int D = d_lin + p;
+    if (n_graphs < 0 || d_lin <= 0 || p < 0 || D % 4 || D > 256 || ld_node % 4 || ld_node < D || ld_coarse % 4 || ld_coarse < D) {
         set_error("pool_expand_mean: need (Dl + P) %% 4 == 0, <= 256, 16-byte aligned row strides");
         return SSS_EINVAL;
     }
@@ -919,51 +957,54 @@ int pool_expand_mean(const float* lin_p, const float* lin_q, long ld_lin, const 
     const int lpr = lanes_for(D);
     const long per = 256 / lpr;
     SSS_LPR_SWITCH(lpr, hipLaunchKernelGGL(k_pool_expand_mean<L>, dim3((unsigned)((n_graphs + per - 1) / per)), dim3(256), 0, st,
-                                           lin_p, lin_q, ld_lin, src_row, pos_id, pptr, qptr, n_clicks, n_graphs, Dl, P, pos_emb,
+                                           lin_p, lin_q, ld_lin, src_row, pos_id, pptr, qptr, n_clicks, n_graphs, d_lin, p, pos_emb,
                                            node, ld_node, coarse, ld_coarse));
     return check_launch("k_pool_expand_mean");
 }
 
-int pool_attention(const float* node, long ld_node, const float* Aa, long ld_a, const float* Bc, long ld_b, const float* watt,
-                   const int* pptr, const int* qptr, long n_clicks, long n_graphs, int D, int normalize, float eps, int reduce_sum,
-                   float* out, long ld_out, hipStream_t st) {
-    if (n_graphs < 0 || D <= 0 || D % 4 || ld_node % 4 || ld_a % 4 || ld_b % 4 || ld_out % 4 || ld_out < D) {
+extern "C" int sss_pool_attention(const float* node, int64_t ld_node, const float* a, int64_t ld_a, const float* b, int64_t ld_b,
+                                  const float* watt, const int32_t* pptr, const int32_t* qptr, int64_t n_clicks, int64_t n_graphs,
+                                  int d, int normalize, float eps, int reduce_sum, float* out, int64_t ld_out, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n_graphs < 0 || d <= 0 || d % 4 || ld_node % 4 || ld_a % 4 || ld_b % 4 || ld_out % 4 || ld_out < d) {
         set_error("pool_attention: need D %% 4 == 0, 16-byte aligned row strides");
         return SSS_EINVAL;
     }
     if (n_graphs == 0) return SSS_OK;
-    const int lpr = lanes_for(D);
-    if (D > 256) {
+    const int lpr = lanes_for(d);
+    if (d > 256) {
         // rows wider than one float4 column per lane (the reference's gnn_nout = 800, config.py:16): the column-chunked
         // sweep of k_segment_pool, which computes a node's attention weight once for all of a lane's columns
         SSS_LPR_SWITCH(lpr, hipLaunchKernelGGL(k_segment_pool<L>, dim3(grid_rows(n_graphs, L)), dim3(256), 0, st, node, ld_node,
-                                               pptr, qptr, n_clicks, n_graphs, D, Aa, ld_a, Bc, ld_b, watt, out, ld_out, reduce_sum));
+                                               pptr, qptr, n_clicks, n_graphs, d, a, ld_a, b, ld_b, watt, out, ld_out, reduce_sum));
         const int rc = check_launch("k_segment_pool");
         if (rc || !normalize) return rc;
-        return normalize_rows(out, n_graphs, D, ld_out, eps, 0, st);
+        return sss_normalize_rows(out, n_graphs, d, ld_out, eps, 0, st);
     }
     const long per = 256 / lpr;
     SSS_LPR_SWITCH(lpr, hipLaunchKernelGGL(k_pool_attention<L>, dim3((unsigned)((n_graphs + per - 1) / per)), dim3(256), 0, st, node,
-                                           ld_node, Aa, ld_a, Bc, ld_b, watt, pptr, qptr, n_clicks, n_graphs, D, normalize, eps,
+                                           ld_node, a, ld_a, b, ld_b, watt, pptr, qptr, n_clicks, n_graphs, d, normalize, eps,
                                            reduce_sum, out, ld_out));
     return check_launch("k_pool_attention");
 }
 
-int pool_attention_tab(const float* T, long ld_t, const float* AC, long ld_ac, const float* tanhpos, const float* A2tab,
-                       const float* C2tab, const float* watt, const int* src_row, const int* pos_id, const int* pptr,
-                       const int* qptr, long n_clicks, long Np, long n_graphs, int Dl, int P, int normalize, float eps, float* out,
-                       long ld_out, hipStream_t st) {
-    const int D = Dl + P;
-    if (n_graphs < 0 || Dl <= 0 || P < 0 || D % 4 || D > 256 || ld_t < Dl || ld_ac % 4 || ld_ac < 2 * D || ld_out % 4 || ld_out < D) {
+extern "C" int sss_pool_attention_tab(const float* t, int64_t ld_t, const float* ac, int64_t ld_ac, const float* tanhpos,
+                                      const float* a2tab, const float* c2tab, const float* watt, const int32_t* src_row,
+                                      const int32_t* pos_id, const int32_t* pptr, const int32_t* qptr, int64_t n_clicks, int64_t np,
+                                      int64_t n_graphs, int d_lin, int p, int normalize, float eps, float* out, int64_t ld_out,
+                                      void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int D = d_lin + p;
+    if (n_graphs < 0 || d_lin <= 0 || p < 0 || D % 4 || D > 256 || ld_t < d_lin || ld_ac % 4 || ld_ac < 2 * D || ld_out % 4 || ld_out < D) {
         set_error("pool_attention_tab: need (Dl + P) %% 4 == 0, <= 256, ld_ac >= 2 (Dl + P), 16-byte aligned row strides");
         return SSS_EINVAL;
     }
     if (n_graphs == 0) return SSS_OK;
     const int lpr = lanes_for(D);
     const long per = 4;                                          // one wave per graph
-    SSS_LPR_SWITCH(lpr, hipLaunchKernelGGL(k_pool_attention_tab<L>, dim3((unsigned)((n_graphs + per - 1) / per)), dim3(256), 0, st, T,
-                                           ld_t, AC, ld_ac, tanhpos, A2tab, C2tab, watt, src_row, pos_id, pptr, qptr, n_clicks, Np,
-                                           n_graphs, Dl, P, normalize, eps, out, ld_out));
+    SSS_LPR_SWITCH(lpr, hipLaunchKernelGGL(k_pool_attention_tab<L>, dim3((unsigned)((n_graphs + per - 1) / per)), dim3(256), 0, st, t,
+                                           ld_t, ac, ld_ac, tanhpos, a2tab, c2tab, watt, src_row, pos_id, pptr, qptr, n_clicks, np,
+                                           n_graphs, d_lin, p, normalize, eps, out, ld_out));
     return check_launch("k_pool_attention_tab");
 }
 

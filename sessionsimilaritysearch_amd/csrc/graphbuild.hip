@@ -243,12 +243,12 @@ __global__ __launch_bounds__(256) void k_session_fill(const long* __restrict__ s
 }
 
 // ------------------------------------------------------------------------------ host launchers
-size_t graph_scratch_ints(long S) { return (size_t)NC * ((S + SCAN_BLOCK - 1) / SCAN_BLOCK + 1); }
+extern "C" size_t sss_graph_scratch_ints(int64_t n_sessions) { return (size_t)NC * ((n_sessions + SCAN_BLOCK - 1) / SCAN_BLOCK + 1); }
 
-// bases: int32 [NC][S+1] (out: exclusive scans, totals at [S]); scratch: graph_scratch_ints(S) ints; err: int32 [1]
+// bases: int32 [NC][S+1] (out: exclusive scans, totals at [S]); scratch: sss_graph_scratch_ints(S) ints; err: int32 [1]
 // ignore_query selects the IQ instantiation of both sweeps
-int graph_counts(const long* sess_ptr, const unsigned char* is_search, const long* item_id, long S, bool ignore_query, int* bases,
-                 int* scratch, int* err, hipStream_t st) {
+static int graph_counts(const long* sess_ptr, const unsigned char* is_search, const long* item_id, long S, bool ignore_query, int* bases,
+                        int* scratch, int* err, hipStream_t st) {
     if (S <= 0) { set_error("graph_counts: need at least one session"); return SSS_EINVAL; }
     if (hipMemsetAsync(err, 0, sizeof(int), st) != hipSuccess) { set_error("graph_counts: memset failed"); return SSS_EHIP; }
     const unsigned nb = (unsigned)((S * 64 + 255) / 256);
@@ -264,8 +264,8 @@ int graph_counts(const long* sess_ptr, const unsigned char* is_search, const lon
 }
 
 // last_click_mask [Np] / last_node [S]: optional (NULL = not written); query_tok is not read under ignore_query
-int graph_fill(const long* sess_ptr, const unsigned char* is_search, const long* item_id, const long* query_tok, long S,
-               bool ignore_query, const int* bases, const GraphOut& out, float* last_click_mask, int* last_node, hipStream_t st) {
+static int graph_fill(const long* sess_ptr, const unsigned char* is_search, const long* item_id, const long* query_tok, long S,
+                      bool ignore_query, const int* bases, const GraphOut& out, float* last_click_mask, int* last_node, hipStream_t st) {
     if (S <= 0) { set_error("graph_fill: need at least one session"); return SSS_EINVAL; }
     const unsigned nb = (unsigned)((S * 64 + 255) / 256);
     if (ignore_query)
@@ -275,6 +275,48 @@ int graph_fill(const long* sess_ptr, const unsigned char* is_search, const long*
         hipLaunchKernelGGL(k_session_fill<false>, dim3(nb), dim3(256), 0, st, sess_ptr, is_search, item_id, query_tok, S, bases, out,
                            last_click_mask, last_node);
     return check_launch("k_session_fill");
+}
+
+static GraphOut graph_out(const sss_graph_out* o) {
+    GraphOut g;
+    g.q_x = o->q_x; g.q_batch = o->q_batch; g.q_pos = o->q_pos;
+    g.p_x = o->p_x; g.p_batch = o->p_batch; g.p_cnt = o->p_cnt;
+    g.rowptr_qp = o->rowptr_qp; g.col_qp = o->col_qp; g.rowptr_pq = o->rowptr_pq; g.col_pq = o->col_pq;
+    g.rowptr_pp = o->rowptr_pp; g.col_pp = o->col_pp; g.w_pp = o->w_pp; g.src_row = o->src_row; g.pos_id = o->pos_id;
+    return g;
+}
+
+extern "C" int sss_graph_counts(const int64_t* sess_ptr, const uint8_t* is_search, const int64_t* item_id, int64_t n_sessions, int32_t* bases,
+                                int32_t* scratch, int32_t* err, void* stream) {
+    return graph_counts(sess_ptr, is_search, item_id, n_sessions, false, bases, scratch, err, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sss_graph_fill(const int64_t* sess_ptr, const uint8_t* is_search, const int64_t* item_id, const int64_t* query_tok,
+                              int64_t n_sessions, const int32_t* bases, const sss_graph_out* out, void* stream) {
+    if (!out) { set_error("graph_fill: null outputs"); return SSS_EINVAL; }
+    return graph_fill(sess_ptr, is_search, item_id, query_tok, n_sessions, false, bases, graph_out(out), nullptr, nullptr,
+                      static_cast<hipStream_t>(stream));
+}
+
+// ---- include/sss_graph.h
+// (the action arrays of a table without a single action are legitimately NULL: only what every build dereferences is checked)
+extern "C" int sss_graph_counts_ex(const int64_t* sess_ptr, const uint8_t* is_search, const int64_t* item_id, int64_t n_sessions, int flags,
+                                   int32_t* bases, int32_t* scratch, int32_t* err, void* stream) {
+    if (flags & ~SSS_GRAPH_IGNORE_QUERY) { set_error("graph_counts_ex: unknown flags 0x%x", flags); return SSS_EINVAL; }
+    if (n_sessions <= 0) { set_error("graph_counts_ex: need at least one session"); return SSS_EINVAL; }
+    if (!sess_ptr || !bases || !scratch || !err) { set_error("graph_counts_ex: null sess_ptr / bases / scratch / err"); return SSS_EINVAL; }
+    return graph_counts(sess_ptr, is_search, item_id, n_sessions, (flags & SSS_GRAPH_IGNORE_QUERY) != 0, bases, scratch, err,
+                        static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sss_graph_fill_ex(const int64_t* sess_ptr, const uint8_t* is_search, const int64_t* item_id, const int64_t* query_tok,
+                                 int64_t n_sessions, int flags, const int32_t* bases, const sss_graph_out* out, float* last_click_mask,
+                                 int32_t* last_node, void* stream) {
+    if (flags & ~SSS_GRAPH_IGNORE_QUERY) { set_error("graph_fill_ex: unknown flags 0x%x", flags); return SSS_EINVAL; }
+    if (n_sessions <= 0) { set_error("graph_fill_ex: need at least one session"); return SSS_EINVAL; }
+    if (!sess_ptr || !bases || !out) { set_error("graph_fill_ex: null sess_ptr / bases / outputs"); return SSS_EINVAL; }
+    return graph_fill(sess_ptr, is_search, item_id, query_tok, n_sessions, (flags & SSS_GRAPH_IGNORE_QUERY) != 0, bases, graph_out(out),
+                      last_click_mask, last_node, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace sss

@@ -25,7 +25,7 @@
 // rows would need 256 partial distances per thread; this needs none, and the inner loop stays the 512-bit
 // kernel's: broadcast ds_read_b128, v_xor + v_bcnt, four rows per trip.
 // THE TILE-TO-SPLIT RULE IS UNCHANGED: what is dealt round-robin is still the 256-row tile, so row id belongs to
-// split (id / 256) % S at every width, S = hamming_capacity / 16; sub-tiles of one tile stay in one list.
+// split (id / 256) % S at every width, S = sss_hamming_topk_capacity / 16; sub-tiles of one tile stay in one list.
 // Registers per thread at NW = 64: query 64 + stage 16 + list 32 + the row words in flight; no scratch (see
 // DESIGN.md for the compiler's figures and the occupancy).
 #include "sss_common.h"
@@ -339,8 +339,8 @@ static int hsplits(long nq, long n) {
     if (S > tiles) S = (int)tiles;
     return S < 1 ? 1 : S;
 }
-size_t hamming_workspace_bytes(long nq, long n) { return (size_t)nq * hsplits(nq, n) * HK * 8 + 256; }
-int hamming_capacity(long nq, long n) { return (nq <= 0 || n <= 0) ? 0 : hsplits(nq, n) * HK; }
+extern "C" size_t sss_hamming_topk_workspace_bytes(int64_t nq, int64_t n) { return (size_t)nq * hsplits(nq, n) * HK * 8 + 256; }
+extern "C" int sss_hamming_topk_capacity(int64_t nq, int64_t n) { return (nq <= 0 || n <= 0) ? 0 : hsplits(nq, n) * HK; }
 
 template <int NW>
 static void launch_hscan(const unsigned* q, int nq, const unsigned* c, int n, int S, unsigned long long* cand, hipStream_t st) {
@@ -354,8 +354,9 @@ static void launch_hscan_wide(const unsigned* q, int nq, const unsigned* c, int 
 }
 static bool hwidth_ok(int nbytes) { return nbytes == 16 || nbytes == 32 || nbytes == 64 || nbytes == 128 || nbytes == 256; }
 
-int hamming_topk(const unsigned char* q, long nq, const unsigned char* codes, long n, int nbytes, int k, long id_offset,
-                 int* D_out, long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int sss_hamming_topk(const uint8_t* q, int64_t nq, const uint8_t* codes, int64_t n, int nbytes, int k, int64_t id_offset,
+                                int32_t* D_out, int64_t* I_out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (nq <= 0 || n <= 0 || k <= 0 || !hwidth_ok(nbytes)) {
         set_error("hamming_topk: need nq, n, k > 0 and 16, 32, 64, 128 or 256 code bytes (got %d)", nbytes);
         return SSS_EINVAL;
@@ -364,8 +365,8 @@ int hamming_topk(const unsigned char* q, long nq, const unsigned char* codes, lo
     const int S = hsplits(nq, n);
     const int M = S * HK;
     if (k > M) { set_error("hamming_topk: k %d exceeds the fused capacity %d for this shape (use the exhaustive path)", k, M); return SSS_EINVAL; }
-    if (ws_bytes < hamming_workspace_bytes(nq, n)) { set_error("hamming_topk: workspace too small"); return SSS_EWORKSPACE; }
-    unsigned long long* cand = reinterpret_cast<unsigned long long*>(ws);
+    if (workspace_bytes < sss_hamming_topk_workspace_bytes(nq, n)) { set_error("hamming_topk: workspace too small"); return SSS_EWORKSPACE; }
+    unsigned long long* cand = reinterpret_cast<unsigned long long*>(workspace);
     const unsigned* qu = reinterpret_cast<const unsigned*>(q);
     const unsigned* cu = reinterpret_cast<const unsigned*>(codes);
     if (nbytes == 16) launch_hscan<4>(qu, (int)nq, cu, (int)n, S, cand, st);
@@ -382,16 +383,18 @@ int hamming_topk(const unsigned char* q, long nq, const unsigned char* codes, lo
     return check_launch("k_hamming_select");
 }
 
-size_t hamming_exhaustive_workspace_bytes(long nsel, long n) { return (size_t)nsel * n * 2 + 256; }
+extern "C" size_t sss_hamming_topk_exhaustive_workspace_bytes(int64_t nsel, int64_t n) { return (size_t)nsel * n * 2 + 256; }
 
-int hamming_topk_exhaustive(const unsigned char* q, const int* qsel, long nsel, const unsigned char* codes, long n, int nbytes,
-                            int k, long id_offset, int* D_out, long* I_out, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int sss_hamming_topk_exhaustive(const uint8_t* q, const int32_t* qsel, int64_t nsel, const uint8_t* codes, int64_t n,
+                                           int nbytes, int k, int64_t id_offset, int32_t* D_out, int64_t* I_out, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (nsel <= 0 || n <= 0 || k <= 0 || nsel > 65535 || !hwidth_ok(nbytes)) {
         set_error("hamming_topk_exhaustive: need 0 < nsel <= 65535, n, k > 0 and 16, 32, 64, 128 or 256 code bytes (got %d)", nbytes);
         return SSS_EINVAL;
     }
-    if (ws_bytes < hamming_exhaustive_workspace_bytes(nsel, n)) { set_error("hamming_topk_exhaustive: workspace too small"); return SSS_EWORKSPACE; }
-    unsigned short* dist = reinterpret_cast<unsigned short*>(ws);
+    if (workspace_bytes < sss_hamming_topk_exhaustive_workspace_bytes(nsel, n)) { set_error("hamming_topk_exhaustive: workspace too small"); return SSS_EWORKSPACE; }
+    unsigned short* dist = reinterpret_cast<unsigned short*>(workspace);
     const unsigned* qu = reinterpret_cast<const unsigned*>(q);
     const unsigned* cu = reinterpret_cast<const unsigned*>(codes);
     long gx = (n + 255) / 256;
@@ -408,7 +411,8 @@ int hamming_topk_exhaustive(const unsigned char* q, const int* qsel, long nsel, 
     return check_launch("k_hamming_topk_full");
 }
 
-int pack_sign_bits(const float* x, long n, int c, long ldx, unsigned char* out, int nbytes, hipStream_t st) {
+extern "C" int sss_pack_sign_bits(const float* x, int64_t n, int c, int64_t ldx, uint8_t* out, int nbytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (n < 0 || c <= 0 || nbytes * 8 < c || ldx < c) { set_error("pack_sign_bits: need nbytes * 8 >= c and ldx >= c"); return SSS_EINVAL; }
     if (n == 0) return SSS_OK;
     long blocks = (n * nbytes + 255) / 256;

@@ -7,7 +7,7 @@
 namespace sss {
 
 // Optional timing of the dominant kernel (bench.py roofline leg): when enabled, every k_scan
-// launch is bracketed by a hipEvent pair on ITS stream; profile_read() drains the ring of the
+// launch is bracketed by a hipEvent pair on ITS stream; sss_profile_read() drains the ring of the
 // calling thread's current device.
 namespace {
 constexpr int PROF_RING = 512;
@@ -20,7 +20,7 @@ struct Prof {
 Prof g_prof[MAX_DEVICES];
 }  // namespace
 
-int profile_enable(int on) {
+extern "C" int sss_profile_enable(int on) {
     Prof& p = g_prof[current_device()];
     if (on && !p.made) {
         for (int i = 0; i < 2 * PROF_RING; ++i)
@@ -32,7 +32,7 @@ int profile_enable(int on) {
     return SSS_OK;
 }
 
-int profile_read(double* total_ms, int* launches) {
+extern "C" int sss_profile_read(double* total_ms, int* launches) {
     Prof& p = g_prof[current_device()];
     double sum = 0.0;
     for (int i = 0; i < p.n; ++i) {
@@ -85,17 +85,23 @@ ThrArgs thr_args(const void* q, const void* c_exact, int exact_dtype, int scan_d
     return t;
 }
 
-size_t ip_topk_state_bytes(long nq) { return nq > 0 ? state_words(nq) * 4 : 0; }
+extern "C" size_t sss_ip_topk_state_bytes(int64_t nq) { return nq > 0 ? state_words(nq) * 4 : 0; }
 
-size_t ip_topk_workspace_bytes(long nq, long n, int d, int k, int dtype) {      // dtype: the C ABI's (0 / 1 / 4 / 6)
+extern "C" size_t sss_ip_topk_workspace_bytes(int64_t nq, int64_t n, int d, int k, int dtype) {      // dtype: the C ABI's (0 / 1 / 4 / 6)
     if (nq <= 0 || n <= 0 || k <= 0 || !corpus_dtype_ok(dtype) || !fused_shape_ok(d, dtype)) return 0;
     return make_plan(nq, n, d, k, dtype).total_bytes;
 }
 
-size_t ip_topk_scan_workspace_bytes(long nq, long n, int d, int k, int scan_dtype) {   // scan.h codes (0..4, 6)
+static size_t ip_topk_scan_workspace_bytes(long nq, long n, int d, int k, int scan_dtype) {   // scan.h codes (0..4, 6)
     if (nq <= 0 || n <= 0 || k <= 0 || !fused_shape_ok(d, scan_dtype)) return 0;
     return make_plan(nq, n, d, k, scan_dtype).total_bytes;
 }
+
+extern "C" size_t sss_ip_topk_f16_workspace_bytes(int64_t nq, int64_t n, int d, int k) {
+    return ip_topk_scan_workspace_bytes(nq, n, d, k, DT_F16);
+}
+
+extern "C" int sss_f16_shift(float amax) { return f16_shift(amax); }
 
 // scan_dtype: what k_scan reads at c_scan (DT_F32 / DT_BF16 / DT_H16 / DT_I8: the corpus itself; DT_SPLIT: the
 // [hi | lo] bf16 image of an f32 corpus; DT_F16: its scaled f16 image, corpus * 2^corpus_shift);
@@ -105,8 +111,8 @@ static int ip_topk_impl(const char* what, const void* q, long nq, const void* c_
                         int exact_dtype, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out,
                         int* status, int* unproven_count, void* state, size_t state_bytes, void* ws, size_t ws_bytes,
                         hipStream_t st, const float* bias = nullptr, int d_row = 0) {
-    // bias: the L2 search (l2_topk below) -- the scan's keys are q.c + bias[row], the select's scores negated distances
-    // d_row: elements of a stored row of c_exact where it is narrower than d, the width of q and c_scan (pad_topk below); 0: d
+    // bias: the L2 search (sss_l2_topk below) -- the scan's keys are q.c + bias[row], the select's scores negated distances
+    // d_row: elements of a stored row of c_exact where it is narrower than d, the width of q and c_scan (sss_pad_topk below); 0: d
     const bool l2 = bias != nullptr;
     if (nq <= 0 || n <= 0 || k <= 0) { set_error("%s: nq, n, k must be positive", what); return SSS_EINVAL; }
     int rc = check_scan_source(what, exact_dtype, scan_dtype, d, false, c_scan, corpus_shift, corpus_resid, n, nq);
@@ -116,7 +122,7 @@ static int ip_topk_impl(const char* what, const void* q, long nq, const void* c_
         set_error("%s: workspace must be 256-byte aligned, state 16-byte aligned", what);
         return SSS_EINVAL;
     }
-    if (!state || state_bytes < ip_topk_state_bytes(nq)) { set_error("%s: state %zu < %zu bytes", what, state_bytes, ip_topk_state_bytes(nq)); return SSS_EWORKSPACE; }
+    if (!state || state_bytes < sss_ip_topk_state_bytes(nq)) { set_error("%s: state %zu < %zu bytes", what, state_bytes, sss_ip_topk_state_bytes(nq)); return SSS_EWORKSPACE; }
     const ScanPlan p = make_plan(nq, n, d, k, scan_dtype);
     if (ws_bytes < p.total_bytes) { set_error("%s: workspace %zu < %zu", what, ws_bytes, p.total_bytes); return SSS_EWORKSPACE; }
     char* w = reinterpret_cast<char*>(ws);
@@ -148,7 +154,7 @@ static int ip_topk_impl(const char* what, const void* q, long nq, const void* c_
     s.metric = l2 ? 1 : 0;
     s.d_row = d_row;
     rc = launch_select(s, st);
-    if (rc) (void)hipMemsetAsync(state, 0, ip_topk_state_bytes(nq), st);   // the scan dirtied it and nobody will clear it
+    if (rc) (void)hipMemsetAsync(state, 0, sss_ip_topk_state_bytes(nq), st);   // the scan dirtied it and nobody will clear it
     return rc;
 }
 
@@ -178,9 +184,9 @@ static int run_threshold_form(const ThrArgs& t, const void* c_scan, const ScanPl
 constexpr int THR_CAP = 8192;       // rows kept per query (64 KB of keys in LDS for the sort)
 static size_t thr_head_bytes(long nsel) { return ((size_t)nsel * 8 + 255) & ~(size_t)255; }
 
-size_t ip_topk_threshold_workspace_bytes(long nsel, long n, int d, int scan_dtype) {
-    if (nsel <= 0 || n <= 0 || !fused_shape_ok(d, scan_dtype)) return 0;
-    return thr_head_bytes(nsel) + make_thr_plan(nsel, n, d, scan_dtype, THR_CAP).total_bytes;
+extern "C" size_t sss_ip_topk_threshold_workspace_bytes(int64_t nsel, int64_t n, int d, int scan) {
+    if (nsel <= 0 || n <= 0 || !fused_shape_ok(d, scan)) return 0;
+    return thr_head_bytes(nsel) + make_thr_plan(nsel, n, d, scan, THR_CAP).total_bytes;
 }
 
 static int topk_threshold_impl(const char* what, const void* q, const int* qsel, long nsel, const void* c_exact, int exact_dtype,
@@ -202,86 +208,96 @@ static int topk_threshold_impl(const char* what, const void* q, const int* qsel,
     t.cand = reinterpret_cast<unsigned long long*>(w + thr_head_bytes(nsel));
     t.D_out = D_out; t.I_out = I_out; t.status = status;
     t.metric = bias != nullptr ? 1 : 0;
-    t.d_row = d_row;                    // (pad_topk_threshold; 0: the stored rows are d wide)
+    t.d_row = d_row;                    // (sss_pad_topk_threshold; 0: the stored rows are d wide)
     return run_threshold_form(t, c_scan, p, [&] { return launch_thr_prepare(t, st); }, [&] { return launch_select_all(t, st); }, st, bias);
 }
 
-int ip_topk_threshold(const void* q, const int* qsel, long nsel, const void* c_exact, int exact_dtype, const void* c_scan,
-                      int scan_dtype, int corpus_shift, float corpus_resid, long n, int d, int k, long id_offset,
-                      float corpus_max_norm, float* D_out, long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st) {
-    return topk_threshold_impl("ip_topk_threshold", q, qsel, nsel, c_exact, exact_dtype, c_scan, scan_dtype, corpus_shift, corpus_resid, n, d,
-                               k, id_offset, corpus_max_norm, D_out, I_out, status, ws, ws_bytes, st);
+extern "C" int sss_ip_topk_threshold(const void* q, const int32_t* qsel, int64_t nsel, const void* corpus, int dtype,
+                                     const void* scan_image, int scan, int corpus_shift, float corpus_resid_norm, int64_t n, int d,
+                                     int k, int64_t id_offset, float corpus_max_norm, float* D_out, int64_t* I_out, int32_t* status,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return topk_threshold_impl("ip_topk_threshold", q, qsel, nsel, corpus, dtype, scan_image, scan, corpus_shift, corpus_resid_norm, n, d,
+                               k, id_offset, corpus_max_norm, D_out, I_out, status, workspace, workspace_bytes, st);
 }
 
 // RANGE SEARCH, fused route (select_thr.hip: RANGE SEARCH): the threshold rung's scan with thresholds from per-query radii.
 // Workspace: thr f32 [nq] | cnt u32 [nq] | (256-byte aligned) qsel i32 [nq] | (256-byte aligned) cand u64 [nq][THR_CAP].
-// range_search_count leaves each resolved query's entries in its candidate row; range_search_fill copies them out.
+// sss_range_search_count leaves each resolved query's entries in its candidate row; sss_range_search_fill copies them out.
 static size_t range_head_bytes(long nq) { return thr_head_bytes(nq) + (((size_t)nq * 4 + 255) & ~(size_t)255); }
 static size_t range_cand_bytes(long nq) { return ((size_t)nq * THR_CAP * 8 + 255) & ~(size_t)255; }
 
-size_t range_search_workspace_bytes(long nq, long n, int d, int scan_dtype) {
-    if (nq <= 0 || n <= 0 || !fused_shape_ok(d, scan_dtype)) return 0;
-    return range_head_bytes(nq) + make_thr_plan(nq, n, d, scan_dtype, THR_CAP).total_bytes;
+extern "C" size_t sss_range_search_workspace_bytes(int64_t nq, int64_t n, int d, int scan) {
+    if (nq <= 0 || n <= 0 || !fused_shape_ok(d, scan)) return 0;
+    return range_head_bytes(nq) + make_thr_plan(nq, n, d, scan, THR_CAP).total_bytes;
 }
 
-int range_search_count(const void* q, long nq, const void* c_exact, int exact_dtype, const void* c_scan, int scan_dtype, int corpus_shift,
-                       float corpus_resid, long n, int d, const float* radius, float corpus_max_norm, long* counts, int* status, void* ws,
-                       size_t ws_bytes, hipStream_t st) {
+extern "C" int sss_range_search_count(const void* q, int64_t nq, const void* corpus, int dtype, const void* scan_image, int scan,
+                                      int corpus_shift, float corpus_resid_norm, int64_t n, int d, const float* radius,
+                                      float corpus_max_norm, int64_t* counts, int32_t* status, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (nq <= 0 || n <= 0) { set_error("range_search_count: nq, n must be positive"); return SSS_EINVAL; }
-    const int rc = check_scan_source("range_search_count", exact_dtype, scan_dtype, d, false, c_scan, corpus_shift, corpus_resid, n, nq);
+    const int rc = check_scan_source("range_search_count", dtype, scan, d, false, scan_image, corpus_shift, corpus_resid_norm, n, nq);
     if (rc) return rc;
-    if (!q || !c_exact || !radius || !counts || !status) { set_error("range_search_count: q, corpus, radius, counts and status are required"); return SSS_EINVAL; }
-    if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("range_search_count: workspace must be 256-byte aligned"); return SSS_EINVAL; }
-    const ScanPlan p = make_thr_plan(nq, n, d, scan_dtype, THR_CAP);
+    if (!q || !corpus || !radius || !counts || !status) { set_error("range_search_count: q, corpus, radius, counts and status are required"); return SSS_EINVAL; }
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) { set_error("range_search_count: workspace must be 256-byte aligned"); return SSS_EINVAL; }
+    const ScanPlan p = make_thr_plan(nq, n, d, scan, THR_CAP);
     const size_t need = range_head_bytes(nq) + p.total_bytes;
-    if (!ws || ws_bytes < need) { set_error("range_search_count: workspace %zu < %zu", ws_bytes, need); return SSS_EWORKSPACE; }
-    char* w = reinterpret_cast<char*>(ws);
+    if (!workspace || workspace_bytes < need) { set_error("range_search_count: workspace %zu < %zu", workspace_bytes, need); return SSS_EWORKSPACE; }
+    char* w = reinterpret_cast<char*>(workspace);
     int* qsel = reinterpret_cast<int*>(w + thr_head_bytes(nq));
-    ThrArgs t = thr_args(q, c_exact, exact_dtype, scan_dtype, corpus_shift, corpus_resid, corpus_max_norm, qsel, nq, n, d, 1, p.cap, 0);
+    ThrArgs t = thr_args(q, corpus, dtype, scan, corpus_shift, corpus_resid_norm, corpus_max_norm, qsel, nq, n, d, 1, p.cap, 0);
     t.thr = reinterpret_cast<float*>(w);
     t.cnt = reinterpret_cast<unsigned*>(w + (size_t)nq * 4);
     t.cand = reinterpret_cast<unsigned long long*>(w + range_head_bytes(nq));
-    return run_threshold_form(t, c_scan, p, [&] { return launch_range_prepare(t, radius, qsel, st); },
+    return run_threshold_form(t, scan_image, p, [&] { return launch_range_prepare(t, radius, qsel, st); },
                               [&] { return launch_range_select(t, radius, counts, status, st); }, st);
 }
 
-int range_search_fill(long nq, const long* lims, long id_offset, float* D_out, long* I_out, const void* ws, size_t ws_bytes,
-                      hipStream_t st) {
+extern "C" int sss_range_search_fill(int64_t nq, const int64_t* lims, int64_t id_offset, float* D_out, int64_t* I_out,
+                                     const void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (nq <= 0 || nq >= (1L << 31)) { set_error("range_search_fill: nq must be in [1, 2^31)"); return SSS_EINVAL; }
     if (!lims) { set_error("range_search_fill: lims is required"); return SSS_EINVAL; }
-    if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("range_search_fill: workspace must be 256-byte aligned"); return SSS_EINVAL; }
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) { set_error("range_search_fill: workspace must be 256-byte aligned"); return SSS_EINVAL; }
     const size_t need = range_head_bytes(nq) + range_cand_bytes(nq);
-    if (!ws || ws_bytes < need) { set_error("range_search_fill: workspace %zu < %zu", ws_bytes, need); return SSS_EWORKSPACE; }
-    const char* w = reinterpret_cast<const char*>(ws);
+    if (!workspace || workspace_bytes < need) { set_error("range_search_fill: workspace %zu < %zu", workspace_bytes, need); return SSS_EWORKSPACE; }
+    const char* w = reinterpret_cast<const char*>(workspace);
     return launch_range_fill(reinterpret_cast<const unsigned*>(w + (size_t)nq * 4),
                              reinterpret_cast<const unsigned long long*>(w + range_head_bytes(nq)), THR_CAP, nq, lims, id_offset, D_out,
                              I_out, st);
 }
 
-int ip_topk(const void* q, long nq, const void* c, long n, int d, int k, int dtype, long id_offset,
-            float corpus_max_norm, float* D_out, long* I_out, int* status, int* unproven_count, void* state,
-            size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st) {
-    return ip_topk_impl("ip_topk", q, nq, c, dtype, 0, 0.f, c, dtype, n, d, k, id_offset, corpus_max_norm, D_out, I_out, status,
-                        unproven_count, state, state_bytes, ws, ws_bytes, st);
+extern "C" int sss_ip_topk(const void* q, int64_t nq, const void* corpus, int64_t n, int d, int k, int dtype, int64_t id_offset,
+                           float corpus_max_norm, float* D_out, int64_t* I_out, int32_t* status, int32_t* unproven_count, void* state,
+                           size_t state_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return ip_topk_impl("ip_topk", q, nq, corpus, dtype, 0, 0.f, corpus, dtype, n, d, k, id_offset, corpus_max_norm, D_out, I_out, status,
+                        unproven_count, state, state_bytes, workspace, workspace_bytes, st);
 }
 
-int ip_topk_split(const float* q, long nq, const float* c, const void* c_split, long n, int d, int k, long id_offset,
-                  float corpus_max_norm, float* D_out, long* I_out, int* status, int* unproven_count, void* state,
-                  size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st) {
-    return ip_topk_impl("ip_topk_split", q, nq, c_split, DT_SPLIT, 0, 0.f, c, DT_F32, n, d, k, id_offset, corpus_max_norm, D_out,
-                        I_out, status, unproven_count, state, state_bytes, ws, ws_bytes, st);
+extern "C" int sss_ip_topk_split(const float* q, int64_t nq, const float* corpus, const uint16_t* corpus_split, int64_t n, int d, int k,
+                                 int64_t id_offset, float corpus_max_norm, float* D_out, int64_t* I_out, int32_t* status,
+                                 int32_t* unproven_count, void* state, size_t state_bytes, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return ip_topk_impl("ip_topk_split", q, nq, corpus_split, DT_SPLIT, 0, 0.f, corpus, DT_F32, n, d, k, id_offset, corpus_max_norm, D_out,
+                        I_out, status, unproven_count, state, state_bytes, workspace, workspace_bytes, st);
 }
 
-int ip_topk_f16(const float* q, long nq, const float* c, const void* c_f16, int corpus_shift, float corpus_resid, long n, int d, int k,
-                long id_offset, float corpus_max_norm, float* D_out, long* I_out, int* status, int* unproven_count,
-                void* state, size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st) {
-    return ip_topk_impl("ip_topk_f16", q, nq, c_f16, DT_F16, corpus_shift, corpus_resid, c, DT_F32, n, d, k, id_offset, corpus_max_norm,
-                        D_out, I_out, status, unproven_count, state, state_bytes, ws, ws_bytes, st);
+extern "C" int sss_ip_topk_f16(const float* q, int64_t nq, const float* corpus, const uint16_t* corpus_f16, int corpus_shift,
+                               float corpus_resid_norm, int64_t n, int d, int k, int64_t id_offset, float corpus_max_norm, float* D_out,
+                               int64_t* I_out, int32_t* status, int32_t* unproven_count, void* state, size_t state_bytes,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return ip_topk_impl("ip_topk_f16", q, nq, corpus_f16, DT_F16, corpus_shift, corpus_resid_norm, corpus, DT_F32, n, d, k, id_offset, corpus_max_norm,
+                        D_out, I_out, status, unproven_count, state, state_bytes, workspace, workspace_bytes, st);
 }
 
 // ------------------------------------------------------------------------------------------
 // L2 top-k on the same scans (include/sss_l2.h): float32 rows, the scan's keys biased by bias[row] = -|c_row|^2 / 2
-// (rowops.hip: l2_row_bias), scores the negated canonical squared distances (select_dev.h: err_bound_l2, DT_F32_L2).
+// (rowops.hip: sss_l2_row_bias), scores the negated canonical squared distances (select_dev.h: err_bound_l2, DT_F32_L2).
 static int check_l2(const char* what, int scan_dtype, const float* q, const float* c, const float* bias, const float* D_out,
                     const long* I_out, const int* status) {
     if (scan_dtype != DT_F32 && scan_dtype != DT_SPLIT && scan_dtype != DT_F16) {
@@ -293,37 +309,41 @@ static int check_l2(const char* what, int scan_dtype, const float* q, const floa
     return SSS_OK;
 }
 
-size_t l2_topk_workspace_bytes(long nq, long n, int d, int k, int scan_dtype) {
+extern "C" size_t sss_l2_topk_workspace_bytes(int64_t nq, int64_t n, int d, int k, int scan_dtype) {
     if (scan_dtype != DT_F32 && scan_dtype != DT_SPLIT && scan_dtype != DT_F16) return 0;
     return ip_topk_scan_workspace_bytes(nq, n, d, k, scan_dtype);
 }
 
-int l2_topk(const float* q, long nq, const float* c, const void* c_scan, int scan_dtype, int corpus_shift, float corpus_resid,
-            const float* bias, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out, int* status,
-            int* unproven_count, void* state, size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int sss_l2_topk(const float* q, int64_t nq, const float* corpus, const void* scan_image, int scan_dtype, int corpus_shift,
+                           float corpus_resid_norm, const float* bias, int64_t n, int d, int k, int64_t id_offset,
+                           float corpus_max_norm, float* D_out, int64_t* I_out, int32_t* status, int32_t* unproven_count, void* state,
+                           size_t state_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (nq <= 0 || n <= 0 || k <= 0) { set_error("l2_topk: nq, n, k must be positive"); return SSS_EINVAL; }
-    int rc = check_scan_source("l2_topk", DT_F32, scan_dtype, d, false, c_scan, corpus_shift, corpus_resid, n, nq);
-    if (!rc) rc = check_l2("l2_topk", scan_dtype, q, c, bias, D_out, I_out, status);
+    int rc = check_scan_source("l2_topk", DT_F32, scan_dtype, d, false, scan_image, corpus_shift, corpus_resid_norm, n, nq);
+    if (!rc) rc = check_l2("l2_topk", scan_dtype, q, corpus, bias, D_out, I_out, status);
     if (rc) return rc;
-    return ip_topk_impl("l2_topk", q, nq, c_scan, scan_dtype, corpus_shift, corpus_resid, c, DT_F32, n, d, k, id_offset, corpus_max_norm,
-                        D_out, I_out, status, unproven_count, state, state_bytes, ws, ws_bytes, st, bias);
+    return ip_topk_impl("l2_topk", q, nq, scan_image, scan_dtype, corpus_shift, corpus_resid_norm, corpus, DT_F32, n, d, k, id_offset, corpus_max_norm,
+                        D_out, I_out, status, unproven_count, state, state_bytes, workspace, workspace_bytes, st, bias);
 }
 
-size_t l2_topk_threshold_workspace_bytes(long nsel, long n, int d, int scan_dtype) {
+extern "C" size_t sss_l2_topk_threshold_workspace_bytes(int64_t nsel, int64_t n, int d, int scan_dtype) {
     if (scan_dtype != DT_F32 && scan_dtype != DT_SPLIT && scan_dtype != DT_F16) return 0;
-    return ip_topk_threshold_workspace_bytes(nsel, n, d, scan_dtype);
+    return sss_ip_topk_threshold_workspace_bytes(nsel, n, d, scan_dtype);
 }
 
-int l2_topk_threshold(const float* q, const int* qsel, long nsel, const float* c, const void* c_scan, int scan_dtype, int corpus_shift,
-                      float corpus_resid, const float* bias, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out,
-                      long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int sss_l2_topk_threshold(const float* q, const int32_t* qsel, int64_t nsel, const float* corpus, const void* scan_image,
+                                     int scan_dtype, int corpus_shift, float corpus_resid_norm, const float* bias, int64_t n, int d,
+                                     int k, int64_t id_offset, float corpus_max_norm, float* D_out, int64_t* I_out, int32_t* status,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (nsel <= 0 || n <= 0 || k <= 0 || !qsel) { set_error("l2_topk_threshold: nsel, n, k must be positive"); return SSS_EINVAL; }
-    int rc = check_scan_source("l2_topk_threshold", DT_F32, scan_dtype, d, false, c_scan, corpus_shift, corpus_resid, n, nsel);
-    if (!rc) rc = check_l2("l2_topk_threshold", scan_dtype, q, c, bias, D_out, I_out, status);
+    int rc = check_scan_source("l2_topk_threshold", DT_F32, scan_dtype, d, false, scan_image, corpus_shift, corpus_resid_norm, n, nsel);
+    if (!rc) rc = check_l2("l2_topk_threshold", scan_dtype, q, corpus, bias, D_out, I_out, status);
     if (rc) return rc;
-    if (!ws) { set_error("l2_topk_threshold: workspace 0 < %zu", l2_topk_threshold_workspace_bytes(nsel, n, d, scan_dtype)); return SSS_EWORKSPACE; }
-    return topk_threshold_impl("l2_topk_threshold", q, qsel, nsel, c, DT_F32, c_scan, scan_dtype, corpus_shift, corpus_resid, n, d, k,
-                               id_offset, corpus_max_norm, D_out, I_out, status, ws, ws_bytes, st, bias);
+    if (!workspace) { set_error("l2_topk_threshold: workspace 0 < %zu", sss_l2_topk_threshold_workspace_bytes(nsel, n, d, scan_dtype)); return SSS_EWORKSPACE; }
+    return topk_threshold_impl("l2_topk_threshold", q, qsel, nsel, corpus, DT_F32, scan_image, scan_dtype, corpus_shift, corpus_resid_norm, n, d, k,
+                               id_offset, corpus_max_norm, D_out, I_out, status, workspace, workspace_bytes, st, bias);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -354,40 +374,44 @@ static int check_pad_buffers(const char* what, const float* q, const float* c, c
     return SSS_OK;
 }
 
-size_t pad_topk_workspace_bytes(long nq, long n, int d_row, int d_scan, int k, int scan_dtype) {
+extern "C" size_t sss_pad_topk_workspace_bytes(int64_t nq, int64_t n, int d_row, int d_scan, int k, int scan_dtype) {
     if (!pad_shape_ok(d_row, d_scan, scan_dtype)) return 0;
     return ip_topk_scan_workspace_bytes(nq, n, d_scan, k, scan_dtype);
 }
 
-int pad_topk(const float* q, long nq, const float* c, const void* c_scan, int scan_dtype, int corpus_shift, float corpus_resid,
-             const float* bias, long n, int d_row, int d_scan, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out,
-             int* status, int* unproven_count, void* state, size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int sss_pad_topk(const float* q, int64_t nq, const float* corpus, const void* scan_image, int scan_dtype, int corpus_shift,
+                            float corpus_resid_norm, const float* bias, int64_t n, int d_row, int d_scan, int k, int64_t id_offset,
+                            float corpus_max_norm, float* D_out, int64_t* I_out, int32_t* status, int32_t* unproven_count, void* state,
+                            size_t state_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (nq <= 0 || n <= 0 || k <= 0) { set_error("pad_topk: nq, n, k must be positive"); return SSS_EINVAL; }
     int rc = check_pad("pad_topk", scan_dtype, d_row, d_scan);
-    if (!rc) rc = check_scan_source("pad_topk", DT_F32, scan_dtype, d_scan, false, c_scan, corpus_shift, corpus_resid, n, nq);
-    if (!rc) rc = check_pad_buffers("pad_topk", q, c, bias, D_out, I_out, status);
+    if (!rc) rc = check_scan_source("pad_topk", DT_F32, scan_dtype, d_scan, false, scan_image, corpus_shift, corpus_resid_norm, n, nq);
+    if (!rc) rc = check_pad_buffers("pad_topk", q, corpus, bias, D_out, I_out, status);
     if (rc) return rc;
-    if (!ws) { set_error("pad_topk: workspace 0 < %zu", pad_topk_workspace_bytes(nq, n, d_row, d_scan, k, scan_dtype)); return SSS_EWORKSPACE; }
-    return ip_topk_impl("pad_topk", q, nq, c_scan, scan_dtype, corpus_shift, corpus_resid, c, DT_F32, n, d_scan, k, id_offset, corpus_max_norm,
-                        D_out, I_out, status, unproven_count, state, state_bytes, ws, ws_bytes, st, bias, d_row);
+    if (!workspace) { set_error("pad_topk: workspace 0 < %zu", sss_pad_topk_workspace_bytes(nq, n, d_row, d_scan, k, scan_dtype)); return SSS_EWORKSPACE; }
+    return ip_topk_impl("pad_topk", q, nq, scan_image, scan_dtype, corpus_shift, corpus_resid_norm, corpus, DT_F32, n, d_scan, k, id_offset, corpus_max_norm,
+                        D_out, I_out, status, unproven_count, state, state_bytes, workspace, workspace_bytes, st, bias, d_row);
 }
 
-size_t pad_topk_threshold_workspace_bytes(long nsel, long n, int d_row, int d_scan, int scan_dtype) {
+extern "C" size_t sss_pad_topk_threshold_workspace_bytes(int64_t nsel, int64_t n, int d_row, int d_scan, int scan_dtype) {
     if (!pad_shape_ok(d_row, d_scan, scan_dtype)) return 0;
-    return ip_topk_threshold_workspace_bytes(nsel, n, d_scan, scan_dtype);
+    return sss_ip_topk_threshold_workspace_bytes(nsel, n, d_scan, scan_dtype);
 }
 
-int pad_topk_threshold(const float* q, const int* qsel, long nsel, const float* c, const void* c_scan, int scan_dtype, int corpus_shift,
-                       float corpus_resid, const float* bias, long n, int d_row, int d_scan, int k, long id_offset, float corpus_max_norm,
-                       float* D_out, long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int sss_pad_topk_threshold(const float* q, const int32_t* qsel, int64_t nsel, const float* corpus, const void* scan_image,
+                                      int scan_dtype, int corpus_shift, float corpus_resid_norm, const float* bias, int64_t n,
+                                      int d_row, int d_scan, int k, int64_t id_offset, float corpus_max_norm, float* D_out,
+                                      int64_t* I_out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (nsel <= 0 || n <= 0 || k <= 0 || !qsel) { set_error("pad_topk_threshold: nsel, n, k must be positive"); return SSS_EINVAL; }
     int rc = check_pad("pad_topk_threshold", scan_dtype, d_row, d_scan);
-    if (!rc) rc = check_scan_source("pad_topk_threshold", DT_F32, scan_dtype, d_scan, false, c_scan, corpus_shift, corpus_resid, n, nsel);
-    if (!rc) rc = check_pad_buffers("pad_topk_threshold", q, c, bias, D_out, I_out, status);
+    if (!rc) rc = check_scan_source("pad_topk_threshold", DT_F32, scan_dtype, d_scan, false, scan_image, corpus_shift, corpus_resid_norm, n, nsel);
+    if (!rc) rc = check_pad_buffers("pad_topk_threshold", q, corpus, bias, D_out, I_out, status);
     if (rc) return rc;
-    if (!ws) { set_error("pad_topk_threshold: workspace 0 < %zu", pad_topk_threshold_workspace_bytes(nsel, n, d_row, d_scan, scan_dtype)); return SSS_EWORKSPACE; }
-    return topk_threshold_impl("pad_topk_threshold", q, qsel, nsel, c, DT_F32, c_scan, scan_dtype, corpus_shift, corpus_resid, n, d_scan, k,
-                               id_offset, corpus_max_norm, D_out, I_out, status, ws, ws_bytes, st, bias, d_row);
+    if (!workspace) { set_error("pad_topk_threshold: workspace 0 < %zu", sss_pad_topk_threshold_workspace_bytes(nsel, n, d_row, d_scan, scan_dtype)); return SSS_EWORKSPACE; }
+    return topk_threshold_impl("pad_topk_threshold", q, qsel, nsel, corpus, DT_F32, scan_image, scan_dtype, corpus_shift, corpus_resid_norm, n, d_scan, k,
+                               id_offset, corpus_max_norm, D_out, I_out, status, workspace, workspace_bytes, st, bias, d_row);
 }
 
 }  // namespace sss

@@ -1,5 +1,5 @@
-// Argument structures shared by the kernel translation units (gnn.hip, graphbuild.hip) and the C-ABI
-// wrappers (capi.hip): ONE definition, so the two sides cannot drift apart.
+// Argument structures of the kernels of gnn.hip and graphbuild.hip, filled by the entry points there from the C ABI's
+// structs (include/sss.h): kernel arguments, so their layouts are the kernels' own.
 #pragma once
 #include "sss_common.h"
 

@@ -157,8 +157,10 @@ __global__ __launch_bounds__(OM_Q) void k_overlap_metrics(const int* __restrict_
 }
 
 // ------------------------------------------------------------------------------ host launchers
-int item_overlap(const long* q_ptr, const int* q_items, long nq, const long* c_ptr, const int* c_items, long n, const long* I, int K,
-                 long id_offset, int* inter, int* csize, int* err, hipStream_t st) {
+extern "C" int sss_item_overlap(const int64_t* q_ptr, const int32_t* q_items, int64_t nq, const int64_t* c_ptr, const int32_t* c_items,
+                                int64_t n, const int64_t* I, int K, int64_t id_offset, int32_t* inter, int32_t* csize, int32_t* err,
+                                void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (nq <= 0 || nq >= (1L << 31) || K <= 0 || K > OV_MAX_K || n <= 0 || n >= (1L << 31)) {
         set_error("item_overlap: need 0 < nq < 2^31, 0 < K <= 1024, 0 < n < 2^31");
         return SSS_EINVAL;
@@ -174,8 +176,9 @@ int item_overlap(const long* q_ptr, const int* q_items, long nq, const long* c_p
     return check_launch("k_item_overlap");
 }
 
-int overlap_metrics(const int* inter, const int* csize, const int* qsize, long nq, int K, float thr, double* out, int* flags,
-                    hipStream_t st) {
+extern "C" int sss_overlap_metrics(const int32_t* inter, const int32_t* csize, const int32_t* qsize, int64_t nq, int K, float thr,
+                                   double* out, int32_t* flags, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (nq <= 0 || nq >= (1L << 31) || K <= 0 || K > OV_MAX_K) {
         set_error("overlap_metrics: need 0 < nq < 2^31, 0 < K <= 1024");
         return SSS_EINVAL;

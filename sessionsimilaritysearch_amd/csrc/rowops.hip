@@ -346,7 +346,8 @@ static unsigned grid_for(long n, int lpr) {
         default: { constexpr int L = 64; CALL; } break; \
     }
 
-int normalize_rows(float* x, long n, int d, long ld, float eps, int rule, hipStream_t st) {
+extern "C" int sss_normalize_rows(float* x, int64_t n, int d, int64_t ld, float eps, int rule, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (n < 0 || d <= 0 || d % 4 || ld < d || ld % 4 || (rule != 0 && rule != 1)) {
         set_error("normalize_rows: need n >= 0, d %% 4 == 0, ld >= d, ld %% 4 == 0, rule in {0,1}");
         return SSS_EINVAL;
@@ -357,7 +358,8 @@ int normalize_rows(float* x, long n, int d, long ld, float eps, int rule, hipStr
     return check_launch("k_normalize_rows");
 }
 
-int row_norm_max(const void* x, long n, int d, int dtype, float* out, hipStream_t st) {
+extern "C" int sss_row_norm_max(const void* x, int64_t n, int d, int dtype, float* out, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (!corpus_dtype_ok(dtype) || n < 0 || d <= 0 || d % elems_per_chunk(dtype)) {
         set_error("row_norm_max: need dtype in {0,1,4,6}, n >= 0, %s", row_align_text());
         return SSS_EINVAL;
@@ -374,7 +376,8 @@ int row_norm_max(const void* x, long n, int d, int dtype, float* out, hipStream_
     return check_launch("k_row_norm_max");
 }
 
-int f32_to_bf16(const float* x, long count, unsigned short* y, hipStream_t st) {
+extern "C" int sss_f32_to_bf16(const float* x, int64_t count, uint16_t* y, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (count < 0 || count % 8) { set_error("f32_to_bf16: element count must be a multiple of 8"); return SSS_EINVAL; }
     if (count == 0) return SSS_OK;
     long blocks = (count / 8 + 255) / 256;
@@ -383,7 +386,8 @@ int f32_to_bf16(const float* x, long count, unsigned short* y, hipStream_t st) {
     return check_launch("k_f32_to_bf16");
 }
 
-int split_bf16(const float* x, long n, int d, unsigned short* y, hipStream_t st) {
+extern "C" int sss_split_bf16(const float* x, int64_t n, int d, uint16_t* y, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (n < 0 || d <= 0 || d % 8) { set_error("split_bf16: need n >= 0, d %% 8 == 0"); return SSS_EINVAL; }
     if (n == 0) return SSS_OK;
     long blocks = (n * (d / 8) + 255) / 256;
@@ -392,7 +396,8 @@ int split_bf16(const float* x, long n, int d, unsigned short* y, hipStream_t st)
     return check_launch("k_split_bf16");
 }
 
-int abs_max(const float* x, long count, float* out, hipStream_t st) {
+extern "C" int sss_abs_max(const float* x, int64_t count, float* out, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (count < 0 || count % 4) { set_error("abs_max: element count must be a multiple of 4"); return SSS_EINVAL; }
     if (count == 0) return SSS_OK;
     long blocks = (count / 4 + 255) / 256;
@@ -401,7 +406,8 @@ int abs_max(const float* x, long count, float* out, hipStream_t st) {
     return check_launch("k_abs_max");
 }
 
-int scale_f16(const float* x, long count, int shift, unsigned short* y, hipStream_t st) {
+extern "C" int sss_scale_f16(const float* x, int64_t count, int shift, uint16_t* y, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (count < 0 || count % 8) { set_error("scale_f16: element count must be a multiple of 8"); return SSS_EINVAL; }
     if (shift < -160 || shift > 160) { set_error("scale_f16: shift out of range"); return SSS_EINVAL; }
     if (count == 0) return SSS_OK;
@@ -411,7 +417,8 @@ int scale_f16(const float* x, long count, int shift, unsigned short* y, hipStrea
     return check_launch("k_scale_f16");
 }
 
-int f16_resid_max(const float* x, const unsigned short* y, long n, int d, int shift, float* out, hipStream_t st) {
+extern "C" int sss_f16_resid_max(const float* x, const uint16_t* y, int64_t n, int d, int shift, float* out, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (n < 0 || d <= 0 || shift < -160 || shift > 160) { set_error("f16_resid_max: bad arguments"); return SSS_EINVAL; }
     if (n == 0) return SSS_OK;
     long blocks = (n + 3) / 4;
@@ -439,14 +446,16 @@ static unsigned pad_grid(long chunks) {
     return (unsigned)blocks;
 }
 
-int pad_rows_f32(const float* x, long n, int d, int ds, float* y, hipStream_t st) {
+extern "C" int sss_pad_rows_f32(const float* x, int64_t n, int d, int ds, float* y, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     const int rc = check_pad_rows("pad_rows_f32", x, y, n, d, ds);
     if (rc || n == 0) return rc;
     hipLaunchKernelGGL(k_pad_rows_f32, dim3(pad_grid(n * (ds / 4))), dim3(256), 0, st, x, n, d / 4, ds / 4, y);
     return check_launch("k_pad_rows_f32");
 }
 
-int pad_scale_f16(const float* x, long n, int d, int ds, int shift, unsigned short* y, hipStream_t st) {
+extern "C" int sss_pad_scale_f16(const float* x, int64_t n, int d, int ds, int shift, uint16_t* y, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     const int rc = check_pad_rows("pad_scale_f16", x, y, n, d, ds);
     if (rc) return rc;
     if (shift < -160 || shift > 160) { set_error("pad_scale_f16: shift out of range"); return SSS_EINVAL; }
@@ -455,14 +464,16 @@ int pad_scale_f16(const float* x, long n, int d, int ds, int shift, unsigned sho
     return check_launch("k_pad_scale_f16");
 }
 
-int pad_split_bf16(const float* x, long n, int d, int ds, unsigned short* y, hipStream_t st) {
+extern "C" int sss_pad_split_bf16(const float* x, int64_t n, int d, int ds, uint16_t* y, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     const int rc = check_pad_rows("pad_split_bf16", x, y, n, d, ds);
     if (rc || n == 0) return rc;
     hipLaunchKernelGGL(k_pad_split_bf16, dim3(pad_grid(n * (ds / 8))), dim3(256), 0, st, x, n, d / 4, ds / 8, y);
     return check_launch("k_pad_split_bf16");
 }
 
-int pad_f16_resid_max(const float* x, const unsigned short* y, long n, int d, int ds, int shift, float* out, hipStream_t st) {
+extern "C" int sss_pad_f16_resid_max(const float* x, const uint16_t* y, int64_t n, int d, int ds, int shift, float* out, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     const int rc = check_pad_rows("pad_f16_resid_max", x, y, n, d, ds);
     if (rc) return rc;
     if (shift < -160 || shift > 160 || (n > 0 && !out)) { set_error("pad_f16_resid_max: shift out of range or no output"); return SSS_EINVAL; }
@@ -474,14 +485,16 @@ int pad_f16_resid_max(const float* x, const unsigned short* y, long n, int d, in
     return check_launch("k_pad_f16_resid_max");
 }
 
-int l2_row_bias(const float* c, long n, int d, float* bias, hipStream_t st) {
-    if (n < 0 || d <= 0 || d % 4 || (n > 0 && (!c || !bias))) { set_error("l2_row_bias: need n >= 0, d %% 4 == 0, rows and bias"); return SSS_EINVAL; }
+extern "C" int sss_l2_row_bias(const float* corpus, int64_t n, int d, float* bias, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n < 0 || d <= 0 || d % 4 || (n > 0 && (!corpus || !bias))) { set_error("l2_row_bias: need n >= 0, d %% 4 == 0, rows and bias"); return SSS_EINVAL; }
     if (n == 0) return SSS_OK;
-    hipLaunchKernelGGL(k_row_bias, dim3(grid_for(n, 4)), dim3(256), 0, st, c, n, d, bias);
+    hipLaunchKernelGGL(k_row_bias, dim3(grid_for(n, 4)), dim3(256), 0, st, corpus, n, d, bias);
     return check_launch("k_row_bias");
 }
 
-int gather_rows(const float* table, const long* ids, long n, int d, float* out, long ld_out, hipStream_t st) {
+extern "C" int sss_gather_rows(const float* table, const int64_t* ids, int64_t n, int d, float* out, int64_t ld_out, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (n < 0 || d <= 0 || d % 4 || ld_out < d || ld_out % 4) {
         set_error("gather_rows: need n >= 0, d %% 4 == 0, ld_out >= d, ld_out %% 4 == 0");
         return SSS_EINVAL;
@@ -492,17 +505,18 @@ int gather_rows(const float* table, const long* ids, long n, int d, float* out, 
     return check_launch("k_gather_rows");
 }
 
-int gather_concat_rows(const float* table, const long* ids, int d_id, const float* feat, long ld_feat, int d_f, int d_pad,
-                       long n, float* out, long ld_out, hipStream_t st) {
-    if (n < 0 || d_id < 0 || d_f < 0 || d_pad < 0 || d_id % 4 || d_f % 4 || d_pad % 4 || d_id + d_f + d_pad <= 0 ||
-        ld_out % 4 || ld_out < d_id + d_f + d_pad || (feat && (ld_feat % 4 || ld_feat < d_f)) || (d_id > 0 && (!table || !ids))) {
+extern "C" int sss_gather_concat_rows(const float* table, const int64_t* ids, int d_id, const float* feat, int64_t ld_feat, int d_feat,
+                                      int d_pad, int64_t n, float* out, int64_t ld_out, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n < 0 || d_id < 0 || d_feat < 0 || d_pad < 0 || d_id % 4 || d_feat % 4 || d_pad % 4 || d_id + d_feat + d_pad <= 0 ||
+        ld_out % 4 || ld_out < d_id + d_feat + d_pad || (feat && (ld_feat % 4 || ld_feat < d_feat)) || (d_id > 0 && (!table || !ids))) {
         set_error("gather_concat_rows: need widths %% 4 == 0, ld_out >= d_id + d_f + d_pad, 16-byte aligned row strides");
         return SSS_EINVAL;
     }
     if (n == 0) return SSS_OK;
-    const int lpr = lanes_per_row(d_id + d_f + d_pad);
+    const int lpr = lanes_per_row(d_id + d_feat + d_pad);
     SSS_DISPATCH_LPR(lpr, hipLaunchKernelGGL(k_gather_concat_rows<L>, dim3(grid_for(n, L)), dim3(256), 0, st, table, ids, d_id, feat,
-                                             ld_feat, d_f, d_pad, n, out, ld_out));
+                                             ld_feat, d_feat, d_pad, n, out, ld_out));
     return check_launch("k_gather_concat_rows");
 }
 

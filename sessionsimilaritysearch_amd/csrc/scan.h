@@ -83,7 +83,6 @@ struct ScanArgs {
 ScanPlan make_thr_plan(long nsel, long n, int d, int scan_dtype, int cap);
 int launch_scan(int dtype, int d, int tile_rows, const ScanArgs& a, hipStream_t st);
 int launch_scan_l2(int dtype, int d, int tile_rows, const ScanArgs& a, hipStream_t st);     // (scan_l2.hip; launch_scan calls it when a.bias is set)
-int scan_boot_expired(int reset);
 
 struct SelectArgs {
     const void* Q;
@@ -163,75 +162,9 @@ int check_scan_source(const char* what, int exact_dtype, int scan_dtype, int d, 
 ThrArgs thr_args(const void* q, const void* c_exact, int exact_dtype, int scan_dtype, int corpus_shift, float corpus_resid,
                  float corpus_max_norm, const int* qsel, long nsel, long n, int d, int k, int cap, long id_offset);
 
-// The search family behind the C ABI (capi.hip): ip_topk.hip, scan_long.hip, exhaustive.hip.
-size_t ip_topk_state_bytes(long nq);
-size_t ip_topk_workspace_bytes(long nq, long n, int d, int k, int dtype);
-size_t ip_topk_scan_workspace_bytes(long nq, long n, int d, int k, int scan_dtype);
-int ip_topk(const void* q, long nq, const void* c, long n, int d, int k, int dtype, long id_offset, float corpus_max_norm,
-            float* D_out, long* I_out, int* status, int* unproven_count, void* state, size_t state_bytes, void* ws, size_t ws_bytes,
-            hipStream_t st);
-int ip_topk_split(const float* q, long nq, const float* c, const void* c_split, long n, int d, int k, long id_offset,
-                  float corpus_max_norm, float* D_out, long* I_out, int* status, int* unproven_count, void* state,
-                  size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st);
-int ip_topk_f16(const float* q, long nq, const float* c, const void* c_f16, int corpus_shift, float corpus_resid, long n, int d, int k,
-                long id_offset, float corpus_max_norm, float* D_out, long* I_out, int* status, int* unproven_count,
-                void* state, size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st);
-size_t ip_topk_threshold_workspace_bytes(long nsel, long n, int d, int scan_dtype);
-int ip_topk_threshold(const void* q, const int* qsel, long nsel, const void* c_exact, int exact_dtype, const void* c_scan,
-                      int scan_dtype, int corpus_shift, float corpus_resid, long n, int d, int k, long id_offset,
-                      float corpus_max_norm, float* D_out, long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st);
-size_t range_search_workspace_bytes(long nq, long n, int d, int scan_dtype);
-int range_search_count(const void* q, long nq, const void* c_exact, int exact_dtype, const void* c_scan, int scan_dtype, int corpus_shift,
-                       float corpus_resid, long n, int d, const float* radius, float corpus_max_norm, long* counts, int* status, void* ws,
-                       size_t ws_bytes, hipStream_t st);
-int range_search_fill(long nq, const long* lims, long id_offset, float* D_out, long* I_out, const void* ws, size_t ws_bytes,
-                      hipStream_t st);
-size_t ip_topk_long_workspace_bytes(long nq, long n, int d, int dtype);
-int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, const void* c_scan, int corpus_shift,
-                 float corpus_resid, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out,
-                 int* status, void* ws, size_t ws_bytes, hipStream_t st);
-// L2 top-k on the long-row scan (scan_long.hip; include/sss_l2_long.h): float32 rows, their scaled f16 image, keys biased per row
-size_t l2_topk_long_workspace_bytes(long nq, long n, int d);
-int l2_topk_long(const float* q, long nq, const float* c, const void* c_f16, int corpus_shift, float corpus_resid, const float* bias,
-                 long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out, int* status, void* ws,
-                 size_t ws_bytes, hipStream_t st);
-size_t ip_topk_exhaustive_workspace_bytes(long nsel, long n);
-int ip_topk_exhaustive(const void* q, const int* qsel, long nsel, const void* c, long n, int d, int k, int dtype, long id_offset,
-                       int metric, const float* lower_bound, float* D_out, long* I_out, void* ws, size_t ws_bytes, hipStream_t st);
-// the exact top-k of a finished [nsel][n] score matrix (exhaustive.hip): the tail of ip_topk_exhaustive, also sparse.hip's
+// the exact top-k of a finished [nsel][n] score matrix (exhaustive.hip): the tail of the exhaustive search, also sparse.hip's
 size_t topk_of_scores_bytes(long nsel, long n);
 int topk_of_scores(const float* scores, const int* qsel, long nsel, long n, int k, long id_offset, int metric, float* D_out,
                    long* I_out, void* tail, hipStream_t st);
-size_t range_exhaustive_workspace_bytes(long nsel, long n);
-int range_exhaustive_count(const void* q, const int* qsel, long nsel, const void* c, long n, int d, int dtype, int metric,
-                           const float* radius, long* counts, void* ws, size_t ws_bytes, hipStream_t st);
-int range_exhaustive_fill(const int* qsel, long nsel, long n, int metric, const float* radius, const long* lims, long id_offset,
-                          float* D_out, long* I_out, const void* ws, size_t ws_bytes, hipStream_t st);
-// L2 top-k on the fused scans (ip_topk.hip; include/sss_l2.h): float32 rows, scan keys q.c + bias[row]
-int l2_row_bias(const float* c, long n, int d, float* bias, hipStream_t st);
-size_t l2_topk_workspace_bytes(long nq, long n, int d, int k, int scan_dtype);
-int l2_topk(const float* q, long nq, const float* c, const void* c_scan, int scan_dtype, int corpus_shift, float corpus_resid,
-            const float* bias, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out, int* status,
-            int* unproven_count, void* state, size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st);
-size_t l2_topk_threshold_workspace_bytes(long nsel, long n, int d, int scan_dtype);
-int l2_topk_threshold(const float* q, const int* qsel, long nsel, const float* c, const void* c_scan, int scan_dtype, int corpus_shift,
-                      float corpus_resid, const float* bias, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out,
-                      long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st);
-// Scans at a width d_scan >= d_row of float32 rows stored d_row wide (ip_topk.hip, rowops.hip; include/sss_pad.h): images and
-// queries zero-extended to d_scan, the re-score from the d_row-wide rows.  bias: the L2 row bias, nullptr for inner product.
-int pad_rows_f32(const float* x, long n, int d, int ds, float* y, hipStream_t st);
-int pad_scale_f16(const float* x, long n, int d, int ds, int shift, unsigned short* y, hipStream_t st);
-int pad_split_bf16(const float* x, long n, int d, int ds, unsigned short* y, hipStream_t st);
-int pad_f16_resid_max(const float* x, const unsigned short* y, long n, int d, int ds, int shift, float* out, hipStream_t st);
-size_t pad_topk_workspace_bytes(long nq, long n, int d_row, int d_scan, int k, int scan_dtype);
-int pad_topk(const float* q, long nq, const float* c, const void* c_scan, int scan_dtype, int corpus_shift, float corpus_resid,
-             const float* bias, long n, int d_row, int d_scan, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out,
-             int* status, int* unproven_count, void* state, size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t st);
-size_t pad_topk_threshold_workspace_bytes(long nsel, long n, int d_row, int d_scan, int scan_dtype);
-int pad_topk_threshold(const float* q, const int* qsel, long nsel, const float* c, const void* c_scan, int scan_dtype, int corpus_shift,
-                       float corpus_resid, const float* bias, long n, int d_row, int d_scan, int k, long id_offset, float corpus_max_norm,
-                       float* D_out, long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st);
-int profile_enable(int on);
-int profile_read(double* total_ms, int* launches);
 
 }  // namespace sss

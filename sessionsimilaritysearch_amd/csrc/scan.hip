@@ -57,7 +57,7 @@ __device__ unsigned g_boot_expired;              // (declared in scan_kernel.h)
 
 // ------------------------------------------------------------------------------ host side
 // Number of waves, since the last reset, whose bootstrap wait ran out (synchronises the device: a debugging / bench aid).
-int scan_boot_expired(int reset) {
+extern "C" int sss_scan_boot_expired(int reset) {
     unsigned v = 0, zero = 0;
     if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_boot_expired), sizeof(v)) != hipSuccess) { set_error("scan_boot_expired: read failed"); return SSS_EHIP; }
     if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_boot_expired), &zero, sizeof(zero)) != hipSuccess) { set_error("scan_boot_expired: reset failed"); return SSS_EHIP; }

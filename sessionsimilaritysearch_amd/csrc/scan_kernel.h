@@ -14,10 +14,10 @@ namespace sss {
 // NW = waves per workgroup: 8 (two per SIMD, 256 VGPRs each) or, for 1024-byte rows whose resident
 // queries alone take 128 VGPRs, 4 (one per SIMD, 512 VGPRs: no spills; NW * 32 queries per workgroup).
 // THR = true is the THRESHOLD form (the rung between the fused search and the exhaustive kernels,
-// ip_topk.hip: ip_topk_threshold): the queries are the compact list A.qsel, every lane compares against
+// ip_topk.hip: sss_ip_topk_threshold): the queries are the compact list A.qsel, every lane compares against
 // its query's FIXED threshold A.thr[] (scan domain) instead of a running list, and every row above it is
 // appended to the query's candidate array -- no lists, no shared threshold, no bootstrap.
-// waves whose bootstrap wait expired before the threshold existed (read + reset through scan_boot_expired)
+// waves whose bootstrap wait expired before the threshold existed (read + reset through sss_scan_boot_expired)
 extern __device__ unsigned g_boot_expired;       // (defined in scan.hip; counted by the inner-product scans only: MET = 0)
 
 // MET = 1 is the L2 form: the scan key of (query, row) is q.c - |c|^2 / 2 -- the rows nearest to q in L2 are the rows with

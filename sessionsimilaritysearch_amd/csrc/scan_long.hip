@@ -373,14 +373,14 @@ constexpr int LONG_MAX_K = 1024;    // what the exhaustive kernels -- the path o
 static int long_cap(int d, int exact_dtype) { return d * elem_bytes(exact_dtype) > 10240 ? LONG_CAP / 2 : LONG_CAP; }
 static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-size_t ip_topk_long_workspace_bytes(long nq, long n, int d, int dtype) {
+extern "C" size_t sss_ip_topk_long_workspace_bytes(int64_t nq, int64_t n, int d, int dtype) {
     if (nq <= 0 || n <= 0 || !long_shape_ok(d, dtype, long_scan_dtype(dtype))) return 0;
     return al256((size_t)nq * d * 2) + al256((size_t)nq * 4) * 3 + al256((size_t)nq * 16) + (size_t)nq * LONG_CAP * 8;
 }
 
 // L2 (include/sss_l2_long.h): the same arrays, the bound cache two doubles wider (off = -|q|^2 and the select's bound
 // behind the (B, unscale) pairs) and four floats per query more (the seed coefficients of the two kinds of level)
-size_t l2_topk_long_workspace_bytes(long nq, long n, int d) {
+extern "C" size_t sss_l2_topk_long_workspace_bytes(int64_t nq, int64_t n, int d) {
     if (nq <= 0 || n <= 0 || !long_shape_ok(d, DT_F32, DT_F16)) return 0;
     return al256((size_t)nq * d * 2) + al256((size_t)nq * 4) * 3 + al256((size_t)nq * 16) + al256((size_t)nq * 32) +
            (size_t)nq * LONG_CAP * 8;
@@ -405,7 +405,7 @@ static int topk_long_impl(const char* what, const float* bias, const void* q, lo
     if (k > LONG_MAX_K) { set_error("%s: k too large (max %d)", what, LONG_MAX_K); return SSS_EINVAL; }
     const int cap = long_cap(d, exact_dtype);
     if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("%s: workspace must be 256-byte aligned", what); return SSS_EINVAL; }
-    const size_t need = l2 ? l2_topk_long_workspace_bytes(nq, n, d) : ip_topk_long_workspace_bytes(nq, n, d, exact_dtype);
+    const size_t need = l2 ? sss_l2_topk_long_workspace_bytes(nq, n, d) : sss_ip_topk_long_workspace_bytes(nq, n, d, exact_dtype);
     if (ws_bytes < need) { set_error("%s: workspace %zu < %zu", what, ws_bytes, need); return SSS_EWORKSPACE; }
     char* w = reinterpret_cast<char*>(ws);
     void* qimg = w;                              w += al256((size_t)nq * d * 2);
@@ -517,22 +517,25 @@ static int topk_long_impl(const char* what, const float* bias, const void* q, lo
     return SSS_OK;
 }
 
-int ip_topk_long(const void* q, long nq, const void* c_exact, int exact_dtype, const void* c_scan, int corpus_shift,
-                 float corpus_resid, long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out,
-                 int* status, void* ws, size_t ws_bytes, hipStream_t st) {
-    return topk_long_impl("ip_topk_long", nullptr, q, nq, c_exact, exact_dtype, c_scan, corpus_shift, corpus_resid, n, d, k, id_offset,
-                          corpus_max_norm, D_out, I_out, status, ws, ws_bytes, st);
+extern "C" int sss_ip_topk_long(const void* q, int64_t nq, const void* corpus, int dtype, const void* scan_image, int corpus_shift,
+                                float corpus_resid_norm, int64_t n, int d, int k, int64_t id_offset, float corpus_max_norm,
+                                float* D_out, int64_t* I_out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return topk_long_impl("ip_topk_long", nullptr, q, nq, corpus, dtype, scan_image, corpus_shift, corpus_resid_norm, n, d, k, id_offset,
+                          corpus_max_norm, D_out, I_out, status, workspace, workspace_bytes, st);
 }
 
 // L2 top-k of long float32 rows (include/sss_l2_long.h): the buffers an inner-product call does not have are checked
 // here, the shape / image / k / workspace checks are topk_long_impl's own -- all of them before the first launch.
-int l2_topk_long(const float* q, long nq, const float* c, const void* c_f16, int corpus_shift, float corpus_resid, const float* bias,
-                 long n, int d, int k, long id_offset, float corpus_max_norm, float* D_out, long* I_out, int* status, void* ws,
-                 size_t ws_bytes, hipStream_t st) {
+extern "C" int sss_l2_topk_long(const float* q, int64_t nq, const float* corpus, const void* f16_image, int corpus_shift,
+                                float corpus_resid_norm, const float* bias, int64_t n, int d, int k, int64_t id_offset,
+                                float corpus_max_norm, float* D_out, int64_t* I_out, int32_t* status, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (!bias || (reinterpret_cast<uintptr_t>(bias) & 15)) { set_error("l2_topk_long: row bias missing or not 16-byte aligned"); return SSS_EINVAL; }
-    if (!q || !c || !D_out || !I_out || !status) { set_error("l2_topk_long: q, corpus, D_out, I_out and status are required"); return SSS_EINVAL; }
-    return topk_long_impl("l2_topk_long", bias, q, nq, c, DT_F32, c_f16, corpus_shift, corpus_resid, n, d, k, id_offset, corpus_max_norm,
-                          D_out, I_out, status, ws, ws_bytes, st);
+    if (!q || !corpus || !D_out || !I_out || !status) { set_error("l2_topk_long: q, corpus, D_out, I_out and status are required"); return SSS_EINVAL; }
+    return topk_long_impl("l2_topk_long", bias, q, nq, corpus, DT_F32, f16_image, corpus_shift, corpus_resid_norm, n, d, k, id_offset, corpus_max_norm,
+                          D_out, I_out, status, workspace, workspace_bytes, st);
 }
 
 }  // namespace sss

@@ -315,7 +315,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_select_all(const ThrArgs A, in
 }
 
 // ------------------------------------------------------------------------------------------
-// RANGE SEARCH, fused route (ip_topk.hip: range_search_count / range_search_fill).  The threshold rung with the caller's
+// RANGE SEARCH, fused route (ip_topk.hip: sss_range_search_count / sss_range_search_fill).  The threshold rung with the caller's
 // radius r in place of a known k-th score: a row the scan does NOT keep has scan score <= thr_from_bound(r), hence an
 // exact score below r - one float32 ulp of r, which rounds to at most r -- never "> r".  So the rows kept are a superset
 // of the answer, and re-scoring all of them canonically decides it exactly (when they fit the capacity).

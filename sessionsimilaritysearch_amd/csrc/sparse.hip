@@ -198,20 +198,23 @@ static int session_args_ok(const char* what, const void* sess_ptr, const void* i
     return SSS_OK;
 }
 
-int session_vectors_count(const long* sess_ptr, const unsigned char* is_search, const long* item_id, long S, long n_items, int* counts,
-                          int* err, hipStream_t st) {
-    int rc = session_args_ok("session_vectors_count", sess_ptr, is_search, item_id, S, n_items, err);
+extern "C" int sss_session_vectors_count(const int64_t* sess_ptr, const uint8_t* is_search, const int64_t* item_id, int64_t n_sessions,
+                                         int64_t n_items, int32_t* counts, int32_t* err, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc = session_args_ok("session_vectors_count", sess_ptr, is_search, item_id, n_sessions, n_items, err);
     if (rc) return rc;
     if (!counts) { set_error("session_vectors_count: counts is required"); return SSS_EINVAL; }
     if (hipMemsetAsync(err, 0, sizeof(int), st) != hipSuccess) { set_error("session_vectors_count: memset failed"); return SSS_EHIP; }
-    const unsigned nb = (unsigned)((S * 64 + 255) / 256);
-    hipLaunchKernelGGL(k_svec_count, dim3(nb), dim3(256), 0, st, sess_ptr, is_search, item_id, S, n_items, counts, err);
+    const unsigned nb = (unsigned)((n_sessions * 64 + 255) / 256);
+    hipLaunchKernelGGL(k_svec_count, dim3(nb), dim3(256), 0, st, sess_ptr, is_search, item_id, n_sessions, n_items, counts, err);
     return check_launch("k_svec_count");
 }
 
-int session_vectors_fill(const long* sess_ptr, const unsigned char* is_search, const long* item_id, long S, long n_items, int mode,
-                         double lammy, const long* ptr, int* items, float* weights, int* err, hipStream_t st) {
-    int rc = session_args_ok("session_vectors_fill", sess_ptr, is_search, item_id, S, n_items, err);
+extern "C" int sss_session_vectors_fill(const int64_t* sess_ptr, const uint8_t* is_search, const int64_t* item_id, int64_t n_sessions,
+                                        int64_t n_items, int mode, double lammy, const int64_t* ptr, int32_t* items, float* weights,
+                                        int32_t* err, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc = session_args_ok("session_vectors_fill", sess_ptr, is_search, item_id, n_sessions, n_items, err);
     if (rc) return rc;
     if ((mode != 0 && mode != 1) || (mode == 1 && !(lammy > 0.0 && lammy <= 1.7976931348623157e308))) {
         set_error("session_vectors_fill: mode is 0 (binary) or 1 (stan, with a finite lammy > 0)");
@@ -221,8 +224,8 @@ int session_vectors_fill(const long* sess_ptr, const unsigned char* is_search, c
     InvSqrtTable tab;
     tab.v[0] = 0.f;
     for (int m = 1; m <= SV_MAX_ITEMS; ++m) tab.v[m] = (float)(1.0 / sqrt((double)m));
-    const unsigned nb = (unsigned)((S * 64 + 255) / 256);
-    hipLaunchKernelGGL(k_svec_fill, dim3(nb), dim3(256), 0, st, sess_ptr, is_search, item_id, S, n_items, mode, lammy, tab, ptr, items,
+    const unsigned nb = (unsigned)((n_sessions * 64 + 255) / 256);
+    hipLaunchKernelGGL(k_svec_fill, dim3(nb), dim3(256), 0, st, sess_ptr, is_search, item_id, n_sessions, n_items, mode, lammy, tab, ptr, items,
                        weights, err);
     return check_launch("k_svec_fill");
 }
@@ -231,29 +234,30 @@ int session_vectors_fill(const long* sess_ptr, const unsigned char* is_search, c
 static size_t sp_scores_bytes(long nq, long n) { return ((size_t)nq * n * 4 + 255) & ~(size_t)255; }
 static size_t sp_qsel_bytes(long nq) { return ((size_t)nq * 4 + 255) & ~(size_t)255; }
 
-size_t sparse_topk_workspace_bytes(long nq, long n) {
+extern "C" size_t sss_sparse_topk_workspace_bytes(int64_t nq, int64_t n) {
     if (nq <= 0 || n <= 0) return 0;
     return sp_scores_bytes(nq, n) + sp_qsel_bytes(nq) + topk_of_scores_bytes(nq, n);
 }
 
-int sparse_topk(const long* q_ptr, const int* q_items, const float* q_weights, long nq, const long* c_ptr, const int* c_items,
-                const float* c_weights, long n, int k, long id_offset, float* D_out, long* I_out, void* ws, size_t ws_bytes,
-                hipStream_t st) {
+extern "C" int sss_sparse_topk(const int64_t* q_ptr, const int32_t* q_items, const float* q_weights, int64_t nq, const int64_t* c_ptr,
+                               const int32_t* c_items, const float* c_weights, int64_t n, int k, int64_t id_offset, float* D_out,
+                               int64_t* I_out, void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (nq <= 0 || n <= 0 || k <= 0 || k > SP_MAX_K || n >= (1L << 31) || nq > 65535) {
         set_error("sparse_topk: need 0 < nq <= 65535, 0 < n < 2^31, 0 < k <= 1024");
         return SSS_EINVAL;
     }
-    if (!q_ptr || !q_items || !q_weights || !c_ptr || !c_items || !c_weights || !D_out || !I_out || !ws) {
+    if (!q_ptr || !q_items || !q_weights || !c_ptr || !c_items || !c_weights || !D_out || !I_out || !workspace) {
         set_error("sparse_topk: a null pointer (both CSR triples, D_out, I_out and the workspace are required)");
         return SSS_EINVAL;
     }
-    if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("sparse_topk: workspace must be 256-byte aligned"); return SSS_EINVAL; }
-    if (ws_bytes < sparse_topk_workspace_bytes(nq, n)) {
-        set_error("sparse_topk: workspace %zu < %zu", ws_bytes, sparse_topk_workspace_bytes(nq, n));
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) { set_error("sparse_topk: workspace must be 256-byte aligned"); return SSS_EINVAL; }
+    if (workspace_bytes < sss_sparse_topk_workspace_bytes(nq, n)) {
+        set_error("sparse_topk: workspace %zu < %zu", workspace_bytes, sss_sparse_topk_workspace_bytes(nq, n));
         return SSS_EWORKSPACE;
     }
-    float* scores = reinterpret_cast<float*>(ws);
-    int* qsel = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + sp_scores_bytes(nq, n));
+    float* scores = reinterpret_cast<float*>(workspace);
+    int* qsel = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + sp_scores_bytes(nq, n));
     void* tail = reinterpret_cast<char*>(qsel) + sp_qsel_bytes(nq);
     const long nbx = (n + SP_ROWS - 1) / SP_ROWS;
     long ny = (1024 + nbx - 1) / nbx;                            // a small corpus: split the queries too, ~1024 workgroups

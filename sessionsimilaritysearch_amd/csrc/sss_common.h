@@ -3,6 +3,20 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+// The whole C ABI: every entry point is DEFINED, extern "C", in the translation unit that implements it, and every
+// translation unit sees every declaration -- a definition that differs from its header does not compile.
+#include "../../include/sss.h"
+#include "../../include/sss_eval.h"
+#include "../../include/sss_graph.h"
+#include "../../include/sss_l2.h"
+#include "../../include/sss_l2_long.h"
+#include "../../include/sss_pad.h"
+#include "../../include/sss_sparse.h"
+
+static_assert(std::is_same<int64_t, long>::value, "the kernels take the ABI's int64_t arrays as long");
+
 #define SSS_OK 0
 #define SSS_EINVAL (-1)
 #define SSS_EWORKSPACE (-2)

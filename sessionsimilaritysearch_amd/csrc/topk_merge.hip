@@ -1,4 +1,4 @@
-// sss_topk_merge of the C ABI (capi.hip; gfx950): k-way merge of per-shard results (after the RCCL all-gather):
+// sss_topk_merge of the C ABI (include/sss.h; gfx950): k-way merge of per-shard results (after the RCCL all-gather):
 // [shards][nq][k] -> [nq][k] by (score desc, id asc); ids < 0 are padding.  One thread per query (k*shards is tiny).
 #include "scan.h"
 
@@ -26,14 +26,15 @@ __global__ void k_topk_merge(const float* __restrict__ D_in, long d_stride, cons
     }
 }
 
-int topk_merge(const float* D_in, long d_stride, const long* I_in, long i_stride, int shards, long nq, int k,
-               float* D_out, long* I_out, hipStream_t st) {
-    if (shards < 1 || shards > 64 || nq <= 0 || k <= 0 || d_stride < nq * k || i_stride < nq * k) {
+extern "C" int sss_topk_merge(const float* D_in, int64_t d_shard_stride, const int64_t* I_in, int64_t i_shard_stride, int shards,
+                              int64_t nq, int k, float* D_out, int64_t* I_out, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (shards < 1 || shards > 64 || nq <= 0 || k <= 0 || d_shard_stride < nq * k || i_shard_stride < nq * k) {
         set_error("topk_merge: bad arguments");
         return SSS_EINVAL;
     }
-    hipLaunchKernelGGL(k_topk_merge, dim3((unsigned)((nq + 127) / 128)), dim3(128), 0, st, D_in, d_stride, I_in,
-                       i_stride, shards, (int)nq, k, D_out, I_out);
+    hipLaunchKernelGGL(k_topk_merge, dim3((unsigned)((nq + 127) / 128)), dim3(128), 0, st, D_in, d_shard_stride, I_in,
+                       i_shard_stride, shards, (int)nq, k, D_out, I_out);
     return check_launch("k_topk_merge");
 }
 

@@ -129,7 +129,9 @@ static int lanes4(int d) {
 constexpr int MAX_WIDTH = 2048;     // 8 column chunks of 64 lanes x 4 floats (k_attention_dot_pool keeps them in registers)
 static bool ok_rows(int d, long a, long b) { return d > 0 && d % 4 == 0 && d <= MAX_WIDTH && a % 4 == 0 && b % 4 == 0 && a >= d && b >= d; }
 
-int csr_mean(const float* x, long ld_x, const int* rowptr, const int* col, long n_dst, int d, float* out, long ld_out, hipStream_t st) {
+extern "C" int sss_csr_mean(const float* x, int64_t ld_x, const int32_t* rowptr, const int32_t* col, int64_t n_dst, int d, float* out,
+                            int64_t ld_out, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_dst < 0 || !ok_rows(d, ld_x, ld_out)) { set_error("csr_mean: need d %% 4 == 0, d <= 2048, 16-byte aligned row strides"); return SSS_EINVAL; }
     if (n_dst == 0) return SSS_OK;
     const int lpr = lanes4(d);
@@ -137,8 +139,9 @@ int csr_mean(const float* x, long ld_x, const int* rowptr, const int* col, long 
     SSS_LPRV(lpr, hipLaunchKernelGGL(k_csr_mean<L>, dim3((unsigned)((n_dst + per - 1) / per)), dim3(256), 0, st, x, ld_x, rowptr, col, n_dst, d, out, ld_out));
     return check_launch("k_csr_mean");
 }
-int segment_reduce(const float* x, long ld_x, const float* w, const int* ptr, long n_graphs, int d, int mode, float* out, long ld_out,
-                   hipStream_t st) {
+extern "C" int sss_segment_reduce(const float* x, int64_t ld_x, const float* w, const int32_t* ptr, int64_t n_graphs, int d, int mode,
+                                  float* out, int64_t ld_out, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_graphs < 0 || mode < 0 || mode > 2 || !ok_rows(d, ld_x, ld_out)) { set_error("segment_reduce: need mode in {0,1,2}, d %% 4 == 0, d <= 2048"); return SSS_EINVAL; }
     if (n_graphs == 0) return SSS_OK;
     const int lpr = lanes4(d);
@@ -146,7 +149,9 @@ int segment_reduce(const float* x, long ld_x, const float* w, const int* ptr, lo
     SSS_LPRV(lpr, hipLaunchKernelGGL(k_segment_reduce<L>, dim3((unsigned)((n_graphs + per - 1) / per)), dim3(256), 0, st, x, ld_x, w, ptr, n_graphs, d, mode, out, ld_out));
     return check_launch("k_segment_reduce");
 }
-int attention_dot_pool(const float* x, long ld_x, const int* ptr, long n_graphs, int d, float* out, long ld_out, hipStream_t st) {
+extern "C" int sss_attention_dot_pool(const float* x, int64_t ld_x, const int32_t* ptr, int64_t n_graphs, int d, float* out,
+                                      int64_t ld_out, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_graphs < 0 || !ok_rows(d, ld_x, ld_out)) { set_error("attention_dot_pool: need d %% 4 == 0, d <= 2048"); return SSS_EINVAL; }
     if (n_graphs == 0) return SSS_OK;
     const int lpr = lanes4(d);

@@ -152,9 +152,11 @@ __global__ __launch_bounds__(VT) void k_item_vote(const float* __restrict__ D, c
 
 size_t item_vote_lds_bytes(int cap) { return (size_t)cap * 8; }
 
-int item_vote(const float* D, const long* I, long nq, int S, const long* items_ptr, const int* items, long id_offset,
-              long n_sessions, int K, long* out_items, double* out_w, int* status, hipStream_t st) {
-    if (nq <= 0 || S <= 0 || S > 32767 || K <= 0 || n_sessions < 0) {
+extern "C" int sss_knn_item_vote(const float* D, const int64_t* I, int64_t nq, int s, const int64_t* items_ptr, const int32_t* items,
+                                 int64_t id_offset, int64_t n_sessions, int k, int64_t* out_items, double* out_weights, int32_t* status,
+                                 void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (nq <= 0 || s <= 0 || s > 32767 || k <= 0 || n_sessions < 0) {
         set_error("item_vote: need nq, K > 0 and 0 < sample_size < 32768");
         return SSS_EINVAL;
     }
@@ -165,10 +167,10 @@ int item_vote(const float* D, const long* I, long nq, int S, const long* items_p
     const int cap = VOTE_MAX_ENTRIES, cap_small = VOTE_SMALL_ENTRIES;
     const int rc = opt_in_lds(reinterpret_cast<const void*>(&k_item_vote), "k_item_vote", item_vote_lds_bytes(cap));
     if (rc) return rc;
-    hipLaunchKernelGGL(k_item_vote, dim3((unsigned)nq), dim3(VT), item_vote_lds_bytes(cap_small), st, D, I, S, items_ptr, items,
-                       id_offset, n_sessions, K, cap_small, out_items, out_w, status, cap, 0);
-    hipLaunchKernelGGL(k_item_vote, dim3((unsigned)nq), dim3(VT), item_vote_lds_bytes(cap), st, D, I, S, items_ptr, items,
-                       id_offset, n_sessions, K, cap, out_items, out_w, status, cap, 1);
+    hipLaunchKernelGGL(k_item_vote, dim3((unsigned)nq), dim3(VT), item_vote_lds_bytes(cap_small), st, D, I, s, items_ptr, items,
+                       id_offset, n_sessions, k, cap_small, out_items, out_weights, status, cap, 0);
+    hipLaunchKernelGGL(k_item_vote, dim3((unsigned)nq), dim3(VT), item_vote_lds_bytes(cap), st, D, I, s, items_ptr, items,
+                       id_offset, n_sessions, k, cap, out_items, out_weights, status, cap, 1);
     return check_launch("k_item_vote");
 }
 
