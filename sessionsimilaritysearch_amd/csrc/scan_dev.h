@@ -32,6 +32,14 @@ __device__ __forceinline__ float vmax3(float a, float b, float c) {
     return r;
 }
 
+// The same right behind the 16-pass MFMA that wrote a, b or c: its 19 wait states first, inside the statement -- hipcc pads
+// the distance from an MFMA to its own instructions, not to the inside of an asm statement.
+__device__ __forceinline__ float vmax3_settled(float a, float b, float c) {
+    float r;
+    asm volatile("s_nop 15\n\ts_nop 2\n\tv_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
 // Two 16-byte agent-scope (sc1: not served from this CU's L1) loads + their wait, as ONE asm
 // statement so the destinations are never touched before the data has landed.
 __device__ __forceinline__ unsigned min8_sc1(const unsigned* p) {

@@ -8,6 +8,13 @@
 #ifndef SSS_STAGGER
 #define SSS_STAGGER 1
 #endif
+// The f32 list form's step order for 512-byte rows (k_scan, "F32S"): 0 = the order every scan shares; bit 0 = its own loop
+// (fragments prefetched across the step boundary, tile hand-over in front of the last k-group, step scalars behind
+// k-group 0), bit 1 = the next tile's DMA one piece per k-group, bit 2 = half the max tree under the other accumulator's
+// last MFMAs.  (A/B builds: DESIGN.md 5.1.)
+#ifndef SSS_F32_SCHED
+#define SSS_F32_SCHED 7
+#endif
 
 namespace sss {
 
@@ -39,6 +46,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
     constexpr int WGQ = NW * 32;                      // queries per workgroup
     constexpr bool PRECOMP = RB <= 512 && !AP;        // keep the DMA lane offsets in VGPRs (register budget; not at 128 VGPRs)
     constexpr int TAU_LDS = 2 * TILE_BYTES;           // [8 waves][32 queries][16 slots] u32 behind the two tile buffers
+    constexpr bool F32S = (SSS_F32_SCHED & 1) && DT == DT_F32 && !AP && !THR && RB == 512;   // (the loop is in front of the split loop, below)
     static_assert(CH <= 64, "row longer than one LDS-DMA instruction");
     static_assert(LOADS_PER_WAVE >= 1, "a tile is at least one DMA piece per wave");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -621,7 +629,169 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
             tile_end(i);
         }
     }
-    while (t < T) {
+    if constexpr (F32S) {
+        // The f32 list form's own step order (512-byte rows).  One k-group of this scan is 8 v_mfma_f32_32x32x2_f32 = 512
+        // matrix-pipe cycles during which the wave's issue port is idle, so everything a step needs besides its MFMAs is
+        // issued BETWEEN the k-groups, in that shadow, instead of between the last MFMA of a step and the first of the
+        // next (where the 16-bit scans, bound by instruction issue, want it):
+        //  * the fragments of k-group 0 of the NEXT step are read during the last k-group of this one (nf0 / nf1 carry them
+        //    over the step boundary and through the rare path): the first MFMA of a step waits for no LDS round trip;
+        //  * the step's scalar values (tile, next tile, DMA source and destination, first row, ragged flag) and the
+        //    threshold refresh of tile_top() follow the MFMAs of k-group 0, which need none of them;
+        //  * the next tile's DMA pieces go out one per k-group, behind the MFMAs of k-groups 1 .. LOADS_PER_WAVE of the
+        //    tile's first step (a ragged next tile -- the last tile of the corpus -- keeps the clamped burst);
+        //  * the last k-group issues acc0's four MFMAs first, so acc0's half of the max tree runs under acc1's (the k order
+        //    of each accumulator's chain is what it was: every score keeps its bits);
+        //  * THE TILE HAND-OVER (tile_end: wait for the own DMA share, barrier) sits in front of the last k-group's MFMAs
+        //    of the tile's last step, not behind the step.  Why that is enough: the fragments of that last k-group were
+        //    read one group earlier and the wait for them (lgkmcnt) precedes the barrier, so a wave that arrives there has
+        //    received every LDS read it will ever make of the current buffer; and its vmcnt(0) retired its share of the
+        //    next tile.  Behind the barrier, therefore, (a) the current buffer is free for the DMA of the tile after the
+        //    next -- which goes out during the NEXT tile's first step, i.e. behind this barrier -- and (b) everybody's share
+        //    of the next tile has landed: exactly what the barrier at the end of the step guaranteed.  The last k-group's
+        //    512 cycles then cover the next tile's first fragment reads and the threshold read-back.
+        //    The bootstrap tile keeps the old order (publish behind its tree, wait, barrier, bounded poll): once a launch.
+        constexpr bool SPREAD = (SSS_F32_SCHED & 2) != 0, EARLY_TREE = (SSS_F32_SCHED & 4) != 0;
+        static_assert(LOADS_PER_WAVE + 1 < NU, "a DMA piece per k-group, behind k-groups 1 .. LOADS_PER_WAVE");
+        const unsigned frag_lane = (unsigned)(r * CH) * 16u;          // (the chunk term is added per k-group: compile-time xor)
+        f32x4 nf0 = {0}, nf1 = {0};
+        auto frag_ptr = [&](unsigned step_off, int u) -> const f32x4* {
+            const int c = (2 * u) ^ x;                          // == (2u + h) ^ (r & 15)
+            return reinterpret_cast<const f32x4*>(smem + step_off + frag_lane + c * 16);
+        };
+        auto read_first = [&](unsigned step_off) { const f32x4* p = frag_ptr(step_off, 0); nf0 = p[0]; nf1 = p[32 * CH]; };
+        float tm0 = -INFINITY;                                    // acc0's half of the tree (EARLY_TREE)
+        // MFMAs of step t (and, inside its last k-group, the hand-over when it ends a tile); returns the lane's maximum
+        auto step = [&](int t) -> float {
+            const int i = (int)((unsigned)t / (unsigned)H), sub = (int)((unsigned)t % (unsigned)H);
+            const unsigned off = (unsigned)((i & 1) * TILE_BYTES + sub * (64 * RB));
+            f32x4 as0[NU], as1[NU];
+            as0[0] = nf0; as1[0] = nf1;
+            const f32x16 zero = {0};
+            if constexpr (MET) {
+                float b0 = bcur[0], b1 = bcur[1];
+#pragma unroll
+                for (int s = 1; s < H; ++s) { b0 = sub == s ? bcur[2 * s] : b0; b1 = sub == s ? bcur[2 * s + 1] : b1; }
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, bscale, zero, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, bscale, zero, 0, 0, 0);
+            } else {
+                acc0 = zero; acc1 = zero;
+            }
+            auto fetch = [&](int u) { const f32x4* p = frag_ptr(off, u); as0[u] = p[0]; as1[u] = p[32 * CH]; };
+            auto mfma8 = [&](int u) {
+                const f32x4 a0 = as0[u], a1 = as1[u];
+                __builtin_amdgcn_sched_barrier(0);   // keep the prefetch ABOVE this group's MFMAs
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, qc[u].x, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, qc[u].x, acc1, 0, 0, 0);
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, qc[u].y, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, qc[u].y, acc1, 0, 0, 0);
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, qc[u].z, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, qc[u].z, acc1, 0, 0, 0);
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, qc[u].w, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, qc[u].w, acc1, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            // ---- k-group 0: its fragments came with the previous step; behind its MFMAs, whatever the step needs besides
+            fetch(1);
+            mfma8(0);
+            if (sub == 0) tile_top(i);
+            const int next_tile = (sub == 0 && i + 1 < niter && !(two_ahead && i == 0)) ? tile_of(i + 1) : -1;
+            const long nrow0 = (long)next_tile * TR;
+            const bool dma_plain = next_tile >= 0 && nrow0 + TR <= (long)n;
+            const char* dma_src = Cb + (size_t)nrow0 * RB;
+            const unsigned dma_dst = __builtin_amdgcn_readfirstlane(lds_base + ((i & 1) ^ 1) * TILE_BYTES + wave * LOADS_PER_WAVE * 1024);
+            row0_of_step = (long)tile_of(i) * TR + sub * 64;
+            const bool ragged_step = row0_of_step + 64 > n;                 // wave-uniform, last tile only
+            const bool ends_tile = sub == H - 1 && !(boot && i == 0);       // (the bootstrap tile's end comes behind its tree)
+            if (next_tile >= 0 && (!dma_plain || !SPREAD)) stage((i & 1) ^ 1, next_tile);
+            // ---- k-groups 1 .. NU - 2, a DMA piece behind each of the first LOADS_PER_WAVE
+#pragma unroll
+            for (int u = 1; u < NU - 1; ++u) {
+                fetch(u + 1);
+                mfma8(u);
+                if constexpr (SPREAD) {
+                    if (u <= LOADS_PER_WAVE && dma_plain)
+                        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2"
+                                     : : "v"(lane_off[u - 1]), "s"(dma_dst + (u - 1) * 1024), "s"(dma_src) : "memory");
+                }
+            }
+            // ---- the last k-group: the hand-over in front of its MFMAs when it ends a tile (see above)
+            constexpr int u = NU - 1;
+            if (ends_tile) {
+                asm volatile("" : "+v"(as0[u]), "+v"(as1[u]));      // every LDS read this wave makes of the buffer has landed
+                tile_end(i);
+            }
+            if (t + 1 < T && (sub < H - 1 || ends_tile))
+                read_first(sub == H - 1 ? (unsigned)(((i + 1) & 1) * TILE_BYTES) : off + 64 * RB);
+            if constexpr (!EARLY_TREE) {
+                mfma8(u);
+            } else {
+                // acc0's chain first (back to back on one accumulator is free: 64-cycle issue = the dependent latency); its
+                // half of the tree goes in behind acc1's SECOND MFMA -- two MFMA times after acc0's last one was issued
+                const f32x4 a0 = as0[u], a1 = as1[u];
+                __builtin_amdgcn_sched_barrier(0);
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, qc[u].x, acc0, 0, 0, 0);
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, qc[u].y, acc0, 0, 0, 0);
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, qc[u].z, acc0, 0, 0, 0);
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, qc[u].w, acc0, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);   // (acc0's last MFMA strictly in front of acc1's two: see the tree below)
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, qc[u].x, acc1, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, qc[u].y, acc1, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                // (the tree is inline asm, which hipcc does not pad against the MFMA that wrote its operands: what keeps
+                //  acc0's readers clear of acc0's last MFMA is the order -- acc1's second MFMA cannot issue before the
+                //  first has had the pipe for its 64 cycles, and that one not before acc0's last has: 128 cycles, against
+                //  the 19 wait states (76 cycles) a 16-pass MFMA's result needs before a VALU reads it)
+                if (ragged_step) {
+#pragma unroll
+                    for (int j = 0; j < 16; ++j)
+                        if ((int)row0_of_step + 4 * h + (j & 3) + 8 * (j >> 2) >= n) acc0[j] = -INFINITY;
+                }
+                tm0 = vmax3(acc0[0], acc0[1], acc0[2]);
+#pragma unroll
+                for (int j = 3; j < 15; j += 2) tm0 = vmax3(tm0, acc0[j], acc0[j + 1]);
+                __builtin_amdgcn_sched_barrier(0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, qc[u].z, acc1, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, qc[u].w, acc1, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (ragged_step) {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    const int rr = (int)row0_of_step + 4 * h + (j & 3) + 8 * (j >> 2);
+                    if (!EARLY_TREE && rr >= n) acc0[j] = -INFINITY;
+                    if (rr + 32 >= n) acc1[j] = -INFINITY;
+                }
+            }
+            if constexpr (!EARLY_TREE) return score_tree();
+            float m1 = vmax3_settled(acc1[0], acc1[1], acc1[2]);      // (acc1's last MFMA is the instruction in front of it)
+#pragma unroll
+            for (int j = 3; j < 15; j += 2) m1 = vmax3(m1, acc1[j], acc1[j + 1]);
+            const float m = vmax3(tm0, m1, acc0[15]);
+            rmax = vmax3(m, acc1[15], rmax);
+            return vmax3(m, acc1[15], acc1[15]);
+        };
+        if (T > 0) read_first(0);
+        while (t < T) {
+            bool rare = false;
+            for (; t < T; ++t) {                // ---- hot loop (never writes the list state, like the one below)
+                const float m = step(t);
+                if (t < t_live) {               // bootstrap tile: lane maximum only; its end in the old order
+                    if (t == t_live - 1) {
+                        tile_end(0);
+                        if (t + 1 < T) read_first((unsigned)TILE_BYTES);
+                    }
+                    continue;
+                }
+                if (__builtin_amdgcn_ballot_w64(m > thr) != 0) { rare = true; break; }
+            }
+            if (!rare) break;
+            insert_block(acc0, (int)row0_of_step + 4 * h);
+            insert_block(acc1, (int)row0_of_step + 32 + 4 * h);
+            ++t;
+        }
+    }
+    while (!F32S && t < T) {
         bool rare = false;
         for (; t < T; ++t) {                    // ---- hot loop
             const bool last = (unsigned)t % (unsigned)H == H - 1;
