@@ -13,7 +13,10 @@ Drop-in surface of the reference's path:
   evaluate, query_parts, item_overlap, get_*_jaccard, get_*_recall, get_*_map, get_ave_score, get_recall
                                                   (evaluation.py <- test_amazon_filterd.py:226-382, 443-450 and
                                                                   fine_tune_ours.py:42-97, the item-set metrics of a result)
-  ShardedFlatIndex, ShardedBinaryIndex, ShardedSparseIndex
+  JaccardIndex, mine_triples, neighbourhood_recall
+                                                  (jaccard.py   <- fine_tune_ours.py get_score :42-55 over the whole corpus,
+                                                                  the triple mining :187-235: the ground truth)
+  ShardedFlatIndex, ShardedBinaryIndex, ShardedSparseIndex, ShardedJaccardIndex
                                                   (distributed.py: corpus row-sharded over RCCL)
   SessionBatch, build_batch, synthetic_actions    (sessions.py  <- sequence_to_graph + Batch.from_data_list, host side)
 """
@@ -24,6 +27,8 @@ __all__ = ["SssError", "build", "exported_symbols", "lib", "SessionVectors", "Sp
            "get_all_jaccard", "get_cur_recall", "get_all_recall", "get_future_recall", "get_future_map", "get_cur_map", "get_all_map",
            "get_ave_score", "get_recall"]
 _EVALUATION = frozenset(__all__[8:])
+_JACCARD = ("JaccardIndex", "mine_triples", "neighbourhood_recall")
+__all__ += list(_JACCARD)
 
 
 def __getattr__(name):
@@ -34,4 +39,7 @@ def __getattr__(name):
     if name in _EVALUATION:                              # scoring a result: lazily, for the same reason
         from . import evaluation
         return getattr(evaluation, name)
+    if name in _JACCARD:                                 # the ground-truth index: lazily, for the same reason
+        from . import jaccard
+        return getattr(jaccard, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -169,6 +169,16 @@ _EVAL_SIGNATURES = {
     "sss_overlap_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p]),
 }
 
+# include/sss_jaccard.h one to one (ground truth: exact item-set Jaccard top-k and band counts over the whole corpus;
+# `edges` of sss_jaccard_bands is the one HOST pointer of the ABI)
+_JACCARD_SIGNATURES = {
+    "sss_jaccard_topk_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "sss_jaccard_topk": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p,
+                                 c_void_p, c_size_t, c_void_p]),
+    "sss_jaccard_bands": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int64, c_void_p,
+                                  c_void_p, c_void_p]),
+}
+
 
 # header of include/ -> its signature table: what lib() binds, and every *_symbols() view below
 HEADERS = {
@@ -179,6 +189,7 @@ HEADERS = {
     "sss_pad.h": _PAD_SIGNATURES,
     "sss_graph.h": _GRAPH_SIGNATURES,
     "sss_eval.h": _EVAL_SIGNATURES,
+    "sss_jaccard.h": _JACCARD_SIGNATURES,
 }
 
 
@@ -239,6 +250,11 @@ def graph_symbols():
 def eval_symbols():
     """The entry points of include/sss_eval.h."""
     return sorted(HEADERS["sss_eval.h"])
+
+
+def jaccard_symbols():
+    """The entry points of include/sss_jaccard.h."""
+    return sorted(HEADERS["sss_jaccard.h"])
 
 
 def build(verbose: bool = False) -> str:

@@ -12,7 +12,8 @@ every rank would be the Amdahl term of strong scaling.
 
 Every index kind shards this way.  ``ShardedFlatIndex`` serves both metrics and every d / k of ``FlatIndex``
 (shapes without a fused scan run the shard's exhaustive kernels) and ``range_search``; ``ShardedBinaryIndex``
-serves ``BinaryFlatIndex``; ``ShardedSparseIndex`` serves ``SparseSessionIndex``.  All of them merge through the one ``sss_topk_merge`` -- (score desc, id asc) --
+serves ``BinaryFlatIndex``; ``ShardedSparseIndex`` serves ``SparseSessionIndex``; ``ShardedJaccardIndex`` serves
+``JaccardIndex`` (its band counts by two all-reduces).  All of them merge through the one ``sss_topk_merge`` -- (score desc, id asc) --
 so a contract that orders ascending (L2, Hamming) crosses the exchange NEGATED: float negation is exact and
 ``(-dist desc, id asc)`` is ``(dist asc, id asc)``.
 
@@ -137,6 +138,24 @@ class SparseEngine:
         """This shard's top-k by (score desc, id asc) with global ids (``index.id_offset`` = first row of the shard),
         padding (-FLT_MAX, -1), into D / I; no host sync."""
         self.index.search_device(vectors, k, D, I)
+
+    def merge(self, pack_all, chunk, shards, nq, k, D_out, I_out):
+        _merge_packs(pack_all, chunk, shards, nq, k, D_out, I_out)
+
+
+class JaccardEngine:
+    """Local search, bands + merge of a ``JaccardIndex`` shard through libsss."""
+
+    def __init__(self, index):
+        self.index = index
+
+    def local_search(self, sets, k, D, I):
+        """This shard's top-k by (score desc, id asc) with global ids, padding (-FLT_MAX, -1), into D / I; no host sync."""
+        self.index.search_device(sets, k, D, I)
+
+    def local_bands(self, sets, edges):
+        """This shard's (counts, first) int64 [nq, len(edges) + 1] with global ids in ``first`` (-1: none)."""
+        return self.index.bands(sets, edges)
 
     def merge(self, pack_all, chunk, shards, nq, k, D_out, I_out):
         _merge_packs(pack_all, chunk, shards, nq, k, D_out, I_out)
@@ -339,3 +358,24 @@ class ShardedSparseIndex(_Sharded):
         dist.all_gather_into_tensor(pack_all, pack, group=self.group)
         self.engine.merge(pack_all, chunk, self.world, nq, k, Do, Io)
         return Do, Io
+
+
+INT64_MAX = 2 ** 63 - 1
+
+
+class ShardedJaccardIndex(ShardedSparseIndex):
+    """``JaccardIndex`` over item sets row-sharded across ``dist`` ranks.  ``search`` is ``ShardedSparseIndex``'s: the local
+    result is already in the order and the padding of ``sss_topk_merge``.  ``bands(sets, edges) -> (counts, first)`` sums the
+    shards' counts (``all_reduce`` SUM) and takes the lowest of their first rows (``all_reduce`` MIN, a band a shard does not
+    hold crossing as INT64_MAX in place of its -1); ``engine.local_bands`` returns this rank's pair with GLOBAL ids.  Every
+    rank returns the full result."""
+
+    def bands(self, sets, edges):
+        counts, first = self.engine.local_bands(sets, edges)
+        if not self.exchange:
+            return counts, first
+        counts = counts.clone()
+        first = torch.where(first < 0, torch.full_like(first, INT64_MAX), first)
+        dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
+        dist.all_reduce(first, op=dist.ReduceOp.MIN, group=self.group)
+        return counts, torch.where(first == INT64_MAX, torch.full_like(first, -1), first)

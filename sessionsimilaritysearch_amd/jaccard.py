@@ -1,0 +1,200 @@
+"""Ground truth on the device: the exact item-set Jaccard of a query session against EVERY corpus session.
+
+Everything else in the package ranks sessions under an embedding.  What the encoder is trained to approximate is the
+reference's ``get_score`` (``fine_tune_ours.py:42-55``): the Jaccard index of two sessions' item sets, over the items of
+``seq + tar`` (``'all_jaccard'``, ``CFG.sim_type``) or of ``seq`` (``'cur_jaccard'``).  ``JaccardIndex`` answers the three
+questions the reference could only put to a Python double loop: the true top-k neighbours (its commented-out loop,
+``fine_tune_ours.py:899-907``), how many corpus sessions lie in each score band, and the first session of each band --
+the fine-tuning triple mining of ``fine_tune_ours.py:187-235`` (``mine_triples``).  ``neighbourhood_recall`` is the ratio
+``get_recall`` (``test_amazon_filterd.py:443-450``) approximates by dividing by K: the neighbours above a threshold that a
+result ``I`` found, over those the whole corpus holds.
+
+Item sets are ``SessionVectors`` (``sparse.session_vectors(actions, "binary")``, the parts of ``evaluation.query_parts``);
+the weights are not read.  The contract -- the score of record, the order, the bands -- is stated once, in
+``include/sss_jaccard.h``.  No CPU fallback.
+
+Deviation from the reference: a pair of two empty sets scores 0, ``get_score('cur_jaccard')``'s rule; for ``'all_jaccard'``
+the reference divides by zero there (``evaluation.get_ave_score`` raises for it; a search over a whole corpus cannot, one
+search-only corpus session would fail every query).
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._device import Workspace, exhaustive_chunk
+from .evaluation import item_overlap
+from .index import _dev
+from .sparse import FLT_MAX, SessionVectors, _ptr_of
+
+MAX_EDGES = 7
+MAX_QUERIES = 65535                  # per call of either entry point (include/sss_jaccard.h)
+
+
+def check_edges(edges) -> np.ndarray:
+    """``edges`` as a float64 array, or ValueError: 1..7 values, finite, strictly ascending."""
+    e = np.atleast_1d(np.asarray(edges, np.float64))
+    if e.ndim != 1 or not 1 <= e.size <= MAX_EDGES or not np.isfinite(e).all() or not (np.diff(e) > 0).all():
+        raise ValueError(f"edges must be 1..{MAX_EDGES} finite, strictly ascending values, got {edges!r}")
+    return np.ascontiguousarray(e)
+
+
+def query_chunks(nq: int, per: int):
+    """The (first query, queries) pieces of a batch of ``nq`` at ``per`` a call, never more than a call takes."""
+    per = max(1, min(int(per), MAX_QUERIES))
+    return [(lo, min(per, nq - lo)) for lo in range(0, nq, per)]
+
+
+class JaccardIndex:
+    """Exact search under the item-set Jaccard: ``add(sets)``; ``search(sets, k) -> (D float32 [nq, k], I int64 [nq, k])``
+    by (score desc, id asc), ids = row + ``id_offset``, padding (-FLT_MAX, -1) when ``ntotal < k``, rows scoring 0 ordinary
+    results, k <= 1024; ``bands(sets, edges) -> (counts, first)``.  Scores, order and bands: ``include/sss_jaccard.h``."""
+
+    def __init__(self, n_items: int, device=None):
+        if not 0 < int(n_items) < 2 ** 31:
+            raise ValueError("n_items must be in (0, 2^31)")
+        self.n_items = int(n_items)
+        self.device = _dev(device)
+        self.id_offset = 0
+        self._ptr = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._items = torch.zeros(1, dtype=torch.int32, device=self.device)[:0]      # never NULL
+        self._ws = Workspace(self.device)
+        self.last_chunks = 0                             # query chunks of the last search / bands
+
+    @property
+    def ntotal(self) -> int:
+        return int(self._ptr.shape[0] - 1)
+
+    @property
+    def sets(self) -> SessionVectors:
+        """The corpus item sets (what ``evaluation.item_overlap`` takes); the weights are zeros, nothing reads them."""
+        return SessionVectors(self._ptr, self._items, torch.zeros(self._items.numel(), dtype=torch.float32, device=self.device))
+
+    def _take(self, v, what) -> SessionVectors:
+        if not isinstance(v, SessionVectors):
+            raise TypeError(f"{what}: expected SessionVectors, got {type(v).__name__}")
+        _lib.require_cuda(v.ptr, "ptr", torch.int64)
+        _lib.require_cuda(v.items, "items", torch.int32)
+        return v.check(self.n_items)
+
+    def add(self, sets):
+        v = self._take(sets, "add")
+        if len(v) == 0:
+            return self
+        lo, hi = int(v.ptr[0].item()), int(v.ptr[-1].item())         # the entries these rows own (v may be a slice of a larger batch)
+        nnz_old, nnz = int(self._items.numel()), hi - lo
+        items = torch.zeros(nnz_old + nnz + 1, dtype=torch.int32, device=self.device)
+        items[:nnz_old] = self._items; items[nnz_old:nnz_old + nnz] = v.items[lo:hi].to(self.device)
+        self._ptr = torch.cat([self._ptr, v.ptr[1:].to(self.device) - lo + nnz_old])
+        self._items = items[:nnz_old + nnz]
+        return self
+
+    def search_device(self, q: SessionVectors, k: int, D: torch.Tensor | None = None, I: torch.Tensor | None = None):
+        """``search`` into ``D`` / ``I`` when given; no host sync.  Queries go in chunks under the exhaustive score budget."""
+        k = int(k)
+        if not 0 < k <= 1024:
+            raise ValueError("k must be in 1..1024")
+        nq, n = len(q.require_contiguous()), self.ntotal
+        if D is None:
+            D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+            I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        elif (I is None or tuple(D.shape) != (nq, k) or tuple(I.shape) != (nq, k) or D.dtype != torch.float32
+              or I.dtype != torch.int64 or not D.is_contiguous() or not I.is_contiguous()):
+            raise ValueError(f"D / I must be contiguous float32 / int64 [{nq}, {k}] tensors")
+        self.last_chunks = 0
+        if n == 0:
+            D.fill_(-FLT_MAX); I.fill_(-1)
+            return D, I
+        L, st = _lib.lib(), _lib.stream_ptr(self.device)
+        for lo, m in query_chunks(nq, exhaustive_chunk(n, 4)):
+            ws = self._ws.get(L.sss_jaccard_topk_workspace_bytes(m, n))
+            rc = L.sss_jaccard_topk(q.ptr.data_ptr() + 8 * lo, _ptr_of(q.items), m, self._ptr.data_ptr(), _ptr_of(self._items), n, k,
+                                    self.id_offset, D.data_ptr() + 4 * lo * k, I.data_ptr() + 8 * lo * k, ws.data_ptr(), ws.numel(), st)
+            _lib.check(rc, "sss_jaccard_topk")
+            self.last_chunks += 1
+        return D, I
+
+    def search(self, sets, k: int):
+        return self.search_device(self._take(sets, "search"), k)
+
+    def bands(self, sets, edges):
+        """``(counts, first)``, device int64 ``[nq, len(edges) + 1]``: per query, the rows of every band and the lowest row
+        + ``id_offset`` in it (-1: none).  The band of a row is the number of edges its float64 ``inter / uni`` reaches
+        (``>=``); ``score > t`` is the edge ``nextafter(t, inf)``.  No host sync."""
+        e = check_edges(edges)
+        q = self._take(sets, "bands")
+        nq, n, nb = len(q), self.ntotal, e.size + 1
+        counts = torch.zeros((nq, nb), dtype=torch.int64, device=self.device)
+        first = torch.full((nq, nb), -1, dtype=torch.int64, device=self.device)
+        self.last_chunks = 0
+        if n == 0:
+            return counts, first
+        L, st = _lib.lib(), _lib.stream_ptr(self.device)
+        host_edges = (ctypes.c_double * e.size)(*e.tolist())
+        for lo, m in query_chunks(nq, MAX_QUERIES):
+            rc = L.sss_jaccard_bands(q.ptr.data_ptr() + 8 * lo, _ptr_of(q.items), m, self._ptr.data_ptr(), _ptr_of(self._items), n,
+                                     ctypes.addressof(host_edges), e.size, self.id_offset, counts.data_ptr() + 8 * lo * nb,
+                                     first.data_ptr() + 8 * lo * nb, st)
+            _lib.check(rc, "sss_jaccard_bands")
+            self.last_chunks += 1
+        return counts, first
+
+
+def pair_scores(I, query_sets: SessionVectors, index: JaccardIndex):
+    """Float64 ``inter / uni`` of every (query i, row ``I[i, j]``) pair, numpy ``[nq, K]``, from ``evaluation.item_overlap``;
+    an empty union scores 0, a missing neighbour (-1) is nan."""
+    inter, csize = item_overlap(I, query_sets, index.sets, index.id_offset)
+    qsize = (query_sets.ptr[1:] - query_sets.ptr[:-1])[:, None]
+    inter, csize = inter.to(torch.int64), csize.to(torch.int64)
+    uni = qsize + csize - inter
+    s = torch.where(uni > 0, inter.double() / uni.clamp(min=1).double(), torch.zeros((), dtype=torch.float64, device=uni.device))
+    return torch.where(csize >= 0, s, torch.full((), float("nan"), dtype=torch.float64, device=uni.device)).cpu().numpy()
+
+
+class Triples(NamedTuple):
+    """``mine_triples``' result, numpy, one entry per query: the ids (-1: no such row) and float64 scores (nan: none) of the
+    three picks, and ``keep``: all three exist."""
+    pos: np.ndarray
+    half: np.ndarray
+    neg: np.ndarray
+    pos_score: np.ndarray
+    half_score: np.ndarray
+    neg_score: np.ndarray
+    keep: np.ndarray
+
+
+def mine_triples(index: JaccardIndex, query_sets: SessionVectors, lo: float = 0.2, hi: float = 0.8) -> Triples:
+    """The fine-tuning triple mining of the reference (``fine_tune_ours.py:187-235``) for a whole query batch: per query the
+    FIRST corpus row scoring ``>= hi`` (``pos``), the first in ``[lo, hi)`` (``half``) and the first ``< lo`` (``neg``), with
+    their scores, and ``keep`` where all three exist (the reference's ``cnt == 3``).  The rows are ``index.bands``' first
+    rows of bands 2 / 1 / 0, the scores float64 ``inter / uni`` as the reference's Python computes them.  "First" is add
+    order: the reference walks ``db_data`` as loaded, so a caller who wants other triples shuffles before ``add``."""
+    _, first = index.bands(query_sets, (lo, hi))
+    picks = first[:, [2, 1, 0]].contiguous()
+    if picks.shape[0] == 0 or index.ntotal == 0:
+        s = np.full(tuple(picks.shape), np.nan)
+    else:
+        s = pair_scores(picks, query_sets, index)
+    p = picks.cpu().numpy()
+    return Triples(p[:, 0], p[:, 1], p[:, 2], s[:, 0], s[:, 1], s[:, 2], (p >= 0).all(axis=1))
+
+
+def neighbourhood_recall(I, index: JaccardIndex, query_sets: SessionVectors, thres: float):
+    """``(mean, skipped)``: per query, the rows of ``I[i]`` scoring ``> thres`` over the corpus rows scoring ``> thres``,
+    averaged over the queries that have such a row; the others are skipped and counted.  This is the ratio the reference's
+    ``get_recall`` approximates by dividing by K (it could not count over the corpus).  Numerator: float64 ``inter / uni``
+    of ``evaluation.item_overlap`` (ids of -1 are missing and never count; ``I`` should not repeat an id); denominator:
+    ``index.bands`` with the edge ``nextafter(thres, inf)``."""
+    thres = float(thres)
+    counts, _ = index.bands(query_sets, (np.nextafter(thres, np.inf),))
+    den = counts[:, 1].cpu().numpy()
+    if den.size == 0 or index.ntotal == 0:
+        return float("nan"), int(den.size)
+    s = pair_scores(I, query_sets, index)
+    num = (s > thres).sum(axis=1)                        # nan > thres is False
+    ok = den > 0
+    return (float(np.mean(num[ok] / den[ok])) if ok.any() else float("nan")), int((~ok).sum())
