@@ -211,14 +211,21 @@ def test_identical_rows_resolved_by_the_exhaustive_kernels_at_every_magnitude(cu
 
 
 @pytest.mark.parametrize("s", [-60, -40, 0, 30, 50])
-def test_l2_exhaustive_at_every_magnitude(cuda, s):
-    """IndexFlatL2 (always the exhaustive kernels), both sides scaled: distances scale by 2^(2 s)."""
+def test_l2_auto_scan_at_every_magnitude(cuda, s):
+    """IndexFlatL2 as ``build_index`` makes it (``scan="auto"``), both sides scaled: distances scale by 2^(2 s).  Every scale
+    keeps the largest row norm (2^3.8 at s = 0) inside the routing guard, so ``search`` takes the scan ``auto`` picks for
+    k = 10 at d = 128 -- the one-pass f16 scan, not the exhaustive kernels that served this search when the test was
+    written -- and the route is asserted.  (tests/test_l2_scan_bound_gpu.py takes every L2 scan through the magnitudes,
+    near ties included, and the exhaustive kernels beyond the guard.)"""
     from sessionsimilaritysearch_amd.index import build_index
     rng = np.random.default_rng(9)
     q = rng.standard_normal((10, 128)).astype(np.float32)
     c = rng.standard_normal((2000, 128)).astype(np.float32)
     c[100:110] = c[5]
     qs, cs = _ldexp(q, s), _ldexp(c, s)
-    D, I = build_index(cs, "l2", cuda).search(qs, K)
+    idx = build_index(cs, "l2", cuda)
+    assert idx.l2_scan_for(K) == "f16"
+    D, I = idx.search(qs, K)
+    assert idx.last_scan == "f16"
     Dr, Ir = sr.build_index(cs, "l2").search(qs, K)
     assert np.array_equal(I, Ir) and np.array_equal(D, Dr)
