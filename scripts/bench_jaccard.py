@@ -12,7 +12,7 @@ Prints one JSON line; per corpus:
   bands_traffic_bound_ms     the corpus ptr and items once per query range, no output matrix, at 8 TB/s
   host_restatement_ms        the reference's algorithm on the host -- get_score's python sets, one pair at a time, single
                              thread -- on --host-queries x --host-rows pairs, SCALED to nq x n
---lib PATH times another build of libsss.so (the JC_SIGNATURE / JC_STAGE switches of csrc/jaccard.hip)."""
+--lib PATH times another build of libsss.so with the same C ABI (another commit's, or an experiment's: DESIGN.md 5.7)."""
 import argparse
 import json
 import os

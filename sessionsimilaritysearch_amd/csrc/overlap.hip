@@ -14,7 +14,7 @@
 //   k_overlap_metrics   one thread per query, float64 sums in ascending j (the canonical order); [64 queries x 32
 //                       neighbours] tiles pass through LDS so that the global reads are whole lines and the walk is
 //                       conflict-free (row stride 33).
-#include "sss_common.h"
+#include "csr_walk.h"
 
 namespace sss {
 
@@ -22,11 +22,6 @@ constexpr int OV_WAVES = 4;           // queries per workgroup
 constexpr int OV_QCAP = 2048;         // query items staged per wave: 8 KiB, 32 KiB a workgroup, five workgroups a CU
 constexpr int OV_LONG = 64;           // neighbour rows longer than this are walked by the whole wave
 constexpr int OV_MAX_K = 1024;
-
-__device__ __forceinline__ int ov_len(long a, long b) {
-    const long l = b - a;
-    return l < 0 ? 0 : l > 0x7fffffffL ? 0x7fffffff : (int)l;
-}
 
 __device__ __forceinline__ long readlane_i64(long x, int lane) {
     const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(unsigned long)x, lane);
@@ -46,7 +41,7 @@ __global__ __launch_bounds__(OV_WAVES * 64) void k_item_overlap(const long* __re
     int ql = 0;
     if (i < nq) {
         q0 = qptr[i];
-        ql = ov_len(q0, qptr[i + 1]);
+        ql = csr_len(q0, qptr[i + 1]);
     }
     const bool staged = ql <= OV_QCAP;                               // wave-uniform
     if (staged)
@@ -75,7 +70,7 @@ __global__ __launch_bounds__(OV_WAVES * 64) void k_item_overlap(const long* __re
                 const unsigned long r = (unsigned long)id - (unsigned long)id_offset;
                 if (id != -1 && r < (unsigned long)n) {
                     c0 = cptr[r];
-                    len = ov_len(c0, cptr[r + 1]);
+                    len = csr_len(c0, cptr[r + 1]);
                 } else if (id != -1) {
                     bad = true;
                 }

@@ -10,11 +10,11 @@
 //
 //   k_svec_count / k_svec_fill         one wave per session: item actions compacted onto the lanes, "seen before" and
 //                                      ranks by readlane broadcasts (as graphbuild.hip), float64 weights
-//   k_sparse_scores                    one thread per corpus row (its list in a conflict-free LDS column), queries walked
-//                                      with wave-uniform loads, stores coalesced across rows
+//   k_sparse_scores                    one thread per corpus row: the walk of csr_walk.h, stores coalesced across rows
 //   topk_of_scores (exhaustive.hip)    the exact top-k of the score matrix, shared with the dense exhaustive search
 #include <math.h>
 
+#include "csr_walk.h"
 #include "scan.h"
 
 namespace sss {
@@ -132,60 +132,31 @@ __global__ __launch_bounds__(256) void k_svec_fill(const long* __restrict__ sess
 }
 
 // ---- scores[f][row] = float32( sum over shared items, ascending, of (double)wq * (double)wc ), accumulated in float64.
-// A thread owns one corpus row; the first SP_RL entries of its list sit in its own LDS column ([entry][thread]: the bank is
-// the thread's, whatever entry each lane is at); a wave holding a longer row reads its rows from global memory instead.  The query entries are the same
-// for the whole wave (uniform loads); each lane advances through its row as the query's items ascend.  grid (row blocks,
-// query ranges); block (0, y) also writes the identity query selection the top-k reads.
-constexpr int SP_ROWS = 256;
+// The walk of csr_walk.h over (item, weight) entries, SP_RL of a row staged.  grid (row blocks, query ranges); block (0, y)
+// also writes the identity query selection the top-k reads.
 constexpr int SP_RL = 16;
 
-__global__ __launch_bounds__(SP_ROWS) void k_sparse_scores(const long* __restrict__ qptr, const int* __restrict__ qitems,
-                                                           const float* __restrict__ qw, int nq, int q_per,
-                                                           const long* __restrict__ cptr, const int* __restrict__ citems,
-                                                           const float* __restrict__ cw, long n, float* __restrict__ scores,
-                                                           int* __restrict__ qsel) {
-    __shared__ int r_it[SP_RL * SP_ROWS];
-    __shared__ float r_w[SP_RL * SP_ROWS];
+__global__ __launch_bounds__(CSR_ROWS) void k_sparse_scores(const long* __restrict__ qptr, const int* __restrict__ qitems,
+                                                            const float* __restrict__ qw, int nq, int q_per,
+                                                            const long* __restrict__ cptr, const int* __restrict__ citems,
+                                                            const float* __restrict__ cw, long n, float* __restrict__ scores,
+                                                            int* __restrict__ qsel) {
+    __shared__ int r_it[SP_RL * CSR_ROWS];
+    __shared__ float r_w[SP_RL * CSR_ROWS];
     const int tid = threadIdx.x;
-    const long row = (long)blockIdx.x * SP_ROWS + tid;
-    long r0 = 0;
-    int lr = 0;
-    if (row < n) {
-        r0 = cptr[row];
-        const long l = cptr[row + 1] - r0;
-        lr = l < 0 ? 0 : l > 0x7fffffffL ? 0x7fffffff : (int)l;
-    }
-    for (int j = 0; j < SP_RL && j < lr; ++j) {
-        r_it[j * SP_ROWS + tid] = citems[r0 + j];
-        r_w[j * SP_ROWS + tid] = cw[r0 + j];
-    }
-    // Two forms of the same walk, chosen per wave: every row of the wave fits its LDS column (the rule: ds_read only), or
-    // some row is longer and the whole wave reads its rows from global memory.  One address space per loop -- a per-lane
-    // choice between an LDS and a global address would turn every step into a flat load.
-    const bool wave_long = __builtin_amdgcn_ballot_w64(lr > SP_RL) != 0ull;
+    const long row = (long)blockIdx.x * CSR_ROWS + tid;
+    CsrRow<SP_RL, true> R{citems, cw, r_it, r_w, tid};
+    R.stage(cptr, row, n);
     const int f_lo = blockIdx.y * q_per, f_hi = f_lo + q_per < nq ? f_lo + q_per : nq;
-    auto walk = [&](auto item_at, auto weight_at) {
-        const int first = lr > 0 ? item_at(0) : 0x7fffffff;
+    R.each_space([&](auto V) {
         for (int f = f_lo; f < f_hi; ++f) {
             if (blockIdx.x == 0 && tid == 0) qsel[f] = f;
-            const long q0 = qptr[f], q1 = qptr[f + 1];
-            int j = 0, cur = first;
+            const long q0 = qptr[f], q1 = q0 + csr_len(q0, qptr[f + 1]);
             double acc = 0.0;
-            for (long p = q0; p < q1; ++p) {
-                const int qi = qitems[p];
-                while (cur < qi) {
-                    ++j;
-                    cur = j < lr ? item_at(j) : 0x7fffffff;
-                }
-                if (cur == qi && j < lr) acc += (double)qw[p] * (double)weight_at(j);
-            }
+            csr_merge(qitems, q0, q1, V, [&](long p, int j) { acc += (double)qw[p] * (double)V.weight(j); });
             if (row < n) scores[(size_t)f * n + row] = (float)acc;
         }
-    };
-    if (!wave_long)
-        walk([&](int j) { return r_it[j * SP_ROWS + tid]; }, [&](int j) { return r_w[j * SP_ROWS + tid]; });
-    else
-        walk([&](int j) { return citems[r0 + j]; }, [&](int j) { return cw[r0 + j]; });
+    });
 }
 
 // ------------------------------------------------------------------------------ host launchers
@@ -230,14 +201,43 @@ extern "C" int sss_session_vectors_fill(const int64_t* sess_ptr, const uint8_t* 
     return check_launch("k_svec_fill");
 }
 
-// Workspace: scores f32 [nq][n] | (256-byte aligned) identity query selection i32 [nq] | (aligned) the top-k's tail.
-static size_t sp_scores_bytes(long nq, long n) { return ((size_t)nq * n * 4 + 255) & ~(size_t)255; }
-static size_t sp_qsel_bytes(long nq) { return ((size_t)nq * 4 + 255) & ~(size_t)255; }
+// ---- the host pieces declared in csr_walk.h (jaccard.hip's entry points use them too)
+static size_t ws_scores_bytes(long nq, long n) { return ((size_t)nq * n * 4 + 255) & ~(size_t)255; }
+static size_t ws_qsel_bytes(long nq) { return ((size_t)nq * 4 + 255) & ~(size_t)255; }
 
-extern "C" size_t sss_sparse_topk_workspace_bytes(int64_t nq, int64_t n) {
+size_t score_ws_bytes(long nq, long n) {
     if (nq <= 0 || n <= 0) return 0;
-    return sp_scores_bytes(nq, n) + sp_qsel_bytes(nq) + topk_of_scores_bytes(nq, n);
+    return ws_scores_bytes(nq, n) + ws_qsel_bytes(nq) + topk_of_scores_bytes(nq, n);
 }
+
+int score_ws_carve(const char* what, void* workspace, size_t workspace_bytes, long nq, long n, ScoreWs* w) {
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) { set_error("%s: workspace must be 256-byte aligned", what); return SSS_EINVAL; }
+    if (workspace_bytes < score_ws_bytes(nq, n)) {
+        set_error("%s: workspace %zu < %zu", what, workspace_bytes, score_ws_bytes(nq, n));
+        return SSS_EWORKSPACE;
+    }
+    w->scores = reinterpret_cast<float*>(workspace);
+    w->qsel = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + ws_scores_bytes(nq, n));
+    w->tail = reinterpret_cast<char*>(w->qsel) + ws_qsel_bytes(nq);
+    return SSS_OK;
+}
+
+dim3 csr_grid(long nq, long n, int* q_per) {
+    const long nbx = (n + CSR_ROWS - 1) / CSR_ROWS;
+    long ny = (1024 + nbx - 1) / nbx;
+    if (ny > nq) ny = nq;
+    *q_per = (int)((nq + ny - 1) / ny);
+    ny = (nq + *q_per - 1) / *q_per;
+    return dim3((unsigned)nbx, (unsigned)ny);
+}
+
+int scores_topk(const char* kernel, const ScoreWs& w, long nq, long n, int k, long id_offset, float* D_out, long* I_out, hipStream_t st) {
+    const int rc = check_launch(kernel);
+    if (rc) return rc;
+    return topk_of_scores(w.scores, w.qsel, nq, n, k, id_offset, 0, D_out, I_out, w.tail, st);
+}
+
+extern "C" size_t sss_sparse_topk_workspace_bytes(int64_t nq, int64_t n) { return score_ws_bytes(nq, n); }
 
 extern "C" int sss_sparse_topk(const int64_t* q_ptr, const int32_t* q_items, const float* q_weights, int64_t nq, const int64_t* c_ptr,
                                const int32_t* c_items, const float* c_weights, int64_t n, int k, int64_t id_offset, float* D_out,
@@ -251,24 +251,14 @@ extern "C" int sss_sparse_topk(const int64_t* q_ptr, const int32_t* q_items, con
         set_error("sparse_topk: a null pointer (both CSR triples, D_out, I_out and the workspace are required)");
         return SSS_EINVAL;
     }
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) { set_error("sparse_topk: workspace must be 256-byte aligned"); return SSS_EINVAL; }
-    if (workspace_bytes < sss_sparse_topk_workspace_bytes(nq, n)) {
-        set_error("sparse_topk: workspace %zu < %zu", workspace_bytes, sss_sparse_topk_workspace_bytes(nq, n));
-        return SSS_EWORKSPACE;
-    }
-    float* scores = reinterpret_cast<float*>(workspace);
-    int* qsel = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + sp_scores_bytes(nq, n));
-    void* tail = reinterpret_cast<char*>(qsel) + sp_qsel_bytes(nq);
-    const long nbx = (n + SP_ROWS - 1) / SP_ROWS;
-    long ny = (1024 + nbx - 1) / nbx;                            // a small corpus: split the queries too, ~1024 workgroups
-    if (ny > nq) ny = nq;
-    const int q_per = (int)((nq + ny - 1) / ny);
-    ny = (nq + q_per - 1) / q_per;
-    hipLaunchKernelGGL(k_sparse_scores, dim3((unsigned)nbx, (unsigned)ny), dim3(SP_ROWS), 0, st, q_ptr, q_items, q_weights, (int)nq, q_per,
-                       c_ptr, c_items, c_weights, n, scores, qsel);
-    int rc = check_launch("k_sparse_scores");
+    ScoreWs w;
+    int rc = score_ws_carve("sparse_topk", workspace, workspace_bytes, nq, n, &w);
     if (rc) return rc;
-    return topk_of_scores(scores, qsel, nq, n, k, id_offset, 0, D_out, I_out, tail, st);
+    int q_per = 0;
+    const dim3 grid = csr_grid(nq, n, &q_per);
+    hipLaunchKernelGGL(k_sparse_scores, grid, dim3(CSR_ROWS), 0, st, q_ptr, q_items, q_weights, (int)nq, q_per, c_ptr, c_items, c_weights,
+                       n, w.scores, w.qsel);
+    return scores_topk("k_sparse_scores", w, nq, n, k, id_offset, D_out, I_out, st);
 }
 
 }  // namespace sss

@@ -73,11 +73,21 @@ def _merge_packs(pack_all, chunk, shards, nq, k, D_out, I_out):
     _lib.check(rc, "sss_topk_merge")
 
 
-class HipEngine:
-    """Local search + merge of a ``FlatIndex`` shard through libsss (the product engine)."""
+class _Engine:
+    """A shard's index and the merge of the ranks' packed results, the same for every index kind."""
 
     def __init__(self, index):
         self.index = index
+
+    def merge(self, pack_all, chunk, shards, nq, k, D_out, I_out):
+        _merge_packs(pack_all, chunk, shards, nq, k, D_out, I_out)
+
+
+class HipEngine(_Engine):
+    """Local search + merge of a ``FlatIndex`` shard through libsss (the product engine)."""
+
+    def __init__(self, index):
+        super().__init__(index)
         self.ascending = index.metric == "l2"       # results ordered (distance asc, id asc), padding (+FLT_MAX, -1)
         # running count of queries the fused path could not prove exact (device side, no sync)
         self.unproven = torch.zeros(1, dtype=torch.int32, device=index.device)
@@ -109,45 +119,27 @@ class HipEngine:
         """This shard's (lims, D, I) with global ids, ids ascending per query."""
         return self.index.range_search_device(q, radius)
 
-    def merge(self, pack_all, chunk, shards, nq, k, D_out, I_out):
-        _merge_packs(pack_all, chunk, shards, nq, k, D_out, I_out)
 
-
-class HammingEngine:
+class HammingEngine(_Engine):
     """Local search + merge of a ``BinaryFlatIndex`` shard through libsss."""
-
-    def __init__(self, index):
-        self.index = index
 
     def local_search(self, codes, k):
         """This shard's (D int32, I int64) by (distance asc, id asc) with global ids, padding (0x7fffffff, -1);
         any k (beyond the fused capacity: the shard's exhaustive route)."""
         return self.index.search(codes, k)
 
-    def merge(self, pack_all, chunk, shards, nq, k, D_out, I_out):
-        _merge_packs(pack_all, chunk, shards, nq, k, D_out, I_out)
 
-
-class SparseEngine:
+class SparseEngine(_Engine):
     """Local search + merge of a ``SparseSessionIndex`` shard through libsss."""
-
-    def __init__(self, index):
-        self.index = index
 
     def local_search(self, vectors, k, D, I):
         """This shard's top-k by (score desc, id asc) with global ids (``index.id_offset`` = first row of the shard),
         padding (-FLT_MAX, -1), into D / I; no host sync."""
         self.index.search_device(vectors, k, D, I)
 
-    def merge(self, pack_all, chunk, shards, nq, k, D_out, I_out):
-        _merge_packs(pack_all, chunk, shards, nq, k, D_out, I_out)
 
-
-class JaccardEngine:
+class JaccardEngine(_Engine):
     """Local search, bands + merge of a ``JaccardIndex`` shard through libsss."""
-
-    def __init__(self, index):
-        self.index = index
 
     def local_search(self, sets, k, D, I):
         """This shard's top-k by (score desc, id asc) with global ids, padding (-FLT_MAX, -1), into D / I; no host sync."""
@@ -156,9 +148,6 @@ class JaccardEngine:
     def local_bands(self, sets, edges):
         """This shard's (counts, first) int64 [nq, len(edges) + 1] with global ids in ``first`` (-1: none)."""
         return self.index.bands(sets, edges)
-
-    def merge(self, pack_all, chunk, shards, nq, k, D_out, I_out):
-        _merge_packs(pack_all, chunk, shards, nq, k, D_out, I_out)
 
 
 def range_chunk_words(m: int) -> int:

@@ -26,10 +26,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._device import Workspace, exhaustive_chunk
+from ._device import exhaustive_chunk
 from .evaluation import item_overlap
-from .index import _dev
-from .sparse import FLT_MAX, SessionVectors, _ptr_of
+from .sparse import CsrIndex, SessionVectors, _ptr_of, query_pieces
 
 MAX_EDGES = 7
 MAX_QUERIES = 65535                  # per call of either entry point (include/sss_jaccard.h)
@@ -45,29 +44,14 @@ def check_edges(edges) -> np.ndarray:
 
 def query_chunks(nq: int, per: int):
     """The (first query, queries) pieces of a batch of ``nq`` at ``per`` a call, never more than a call takes."""
-    per = max(1, min(int(per), MAX_QUERIES))
-    return [(lo, min(per, nq - lo)) for lo in range(0, nq, per)]
+    return query_pieces(nq, max(1, min(int(per), MAX_QUERIES)))
 
 
-class JaccardIndex:
+class JaccardIndex(CsrIndex):
     """Exact search under the item-set Jaccard: ``add(sets)``; ``search(sets, k) -> (D float32 [nq, k], I int64 [nq, k])``
     by (score desc, id asc), ids = row + ``id_offset``, padding (-FLT_MAX, -1) when ``ntotal < k``, rows scoring 0 ordinary
     results, k <= 1024; ``bands(sets, edges) -> (counts, first)``.  Scores, order and bands: ``include/sss_jaccard.h``."""
-
-    def __init__(self, n_items: int, device=None):
-        if not 0 < int(n_items) < 2 ** 31:
-            raise ValueError("n_items must be in (0, 2^31)")
-        self.n_items = int(n_items)
-        self.device = _dev(device)
-        self.id_offset = 0
-        self._ptr = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self._items = torch.zeros(1, dtype=torch.int32, device=self.device)[:0]      # never NULL
-        self._ws = Workspace(self.device)
-        self.last_chunks = 0                             # query chunks of the last search / bands
-
-    @property
-    def ntotal(self) -> int:
-        return int(self._ptr.shape[0] - 1)
+    weighted = False
 
     @property
     def sets(self) -> SessionVectors:
@@ -81,42 +65,14 @@ class JaccardIndex:
         _lib.require_cuda(v.items, "items", torch.int32)
         return v.check(self.n_items)
 
-    def add(self, sets):
-        v = self._take(sets, "add")
-        if len(v) == 0:
-            return self
-        lo, hi = int(v.ptr[0].item()), int(v.ptr[-1].item())         # the entries these rows own (v may be a slice of a larger batch)
-        nnz_old, nnz = int(self._items.numel()), hi - lo
-        items = torch.zeros(nnz_old + nnz + 1, dtype=torch.int32, device=self.device)
-        items[:nnz_old] = self._items; items[nnz_old:nnz_old + nnz] = v.items[lo:hi].to(self.device)
-        self._ptr = torch.cat([self._ptr, v.ptr[1:].to(self.device) - lo + nnz_old])
-        self._items = items[:nnz_old + nnz]
-        return self
+    def _pieces(self, nq, n):
+        return query_chunks(nq, exhaustive_chunk(n, 4))
 
-    def search_device(self, q: SessionVectors, k: int, D: torch.Tensor | None = None, I: torch.Tensor | None = None):
-        """``search`` into ``D`` / ``I`` when given; no host sync.  Queries go in chunks under the exhaustive score budget."""
-        k = int(k)
-        if not 0 < k <= 1024:
-            raise ValueError("k must be in 1..1024")
-        nq, n = len(q.require_contiguous()), self.ntotal
-        if D is None:
-            D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-            I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        elif (I is None or tuple(D.shape) != (nq, k) or tuple(I.shape) != (nq, k) or D.dtype != torch.float32
-              or I.dtype != torch.int64 or not D.is_contiguous() or not I.is_contiguous()):
-            raise ValueError(f"D / I must be contiguous float32 / int64 [{nq}, {k}] tensors")
-        self.last_chunks = 0
-        if n == 0:
-            D.fill_(-FLT_MAX); I.fill_(-1)
-            return D, I
-        L, st = _lib.lib(), _lib.stream_ptr(self.device)
-        for lo, m in query_chunks(nq, exhaustive_chunk(n, 4)):
-            ws = self._ws.get(L.sss_jaccard_topk_workspace_bytes(m, n))
-            rc = L.sss_jaccard_topk(q.ptr.data_ptr() + 8 * lo, _ptr_of(q.items), m, self._ptr.data_ptr(), _ptr_of(self._items), n, k,
-                                    self.id_offset, D.data_ptr() + 4 * lo * k, I.data_ptr() + 8 * lo * k, ws.data_ptr(), ws.numel(), st)
-            _lib.check(rc, "sss_jaccard_topk")
-            self.last_chunks += 1
-        return D, I
+    def _topk(self, L, q, lo, m, n, k, d_ptr, i_ptr, st):
+        ws = self._ws.get(L.sss_jaccard_topk_workspace_bytes(m, n))
+        rc = L.sss_jaccard_topk(q.ptr.data_ptr() + 8 * lo, _ptr_of(q.items), m, self._ptr.data_ptr(), _ptr_of(self._items), n, k,
+                                self.id_offset, d_ptr, i_ptr, ws.data_ptr(), ws.numel(), st)
+        _lib.check(rc, "sss_jaccard_topk")
 
     def search(self, sets, k: int):
         return self.search_device(self._take(sets, "search"), k)
@@ -135,12 +91,13 @@ class JaccardIndex:
             return counts, first
         L, st = _lib.lib(), _lib.stream_ptr(self.device)
         host_edges = (ctypes.c_double * e.size)(*e.tolist())
-        for lo, m in query_chunks(nq, MAX_QUERIES):
+
+        def call(lo, m):
             rc = L.sss_jaccard_bands(q.ptr.data_ptr() + 8 * lo, _ptr_of(q.items), m, self._ptr.data_ptr(), _ptr_of(self._items), n,
                                      ctypes.addressof(host_edges), e.size, self.id_offset, counts.data_ptr() + 8 * lo * nb,
                                      first.data_ptr() + 8 * lo * nb, st)
             _lib.check(rc, "sss_jaccard_bands")
-            self.last_chunks += 1
+        self._each_piece(query_chunks(nq, MAX_QUERIES), call)
         return counts, first
 
 

@@ -151,11 +151,17 @@ def csr_to_vectors(m, device=None) -> SessionVectors:
     return _device_triple(m.indptr, m.indices, m.data, _dev(device))
 
 
-class SparseSessionIndex:
-    """Exact top-k over sparse session vectors: ``add(vectors)``, ``search(vectors, k) -> (D float32 [nq, k], I int64
-    [nq, k])`` by (score desc, id asc), ids = row + ``id_offset``, padding (-FLT_MAX, -1) when ``ntotal < k``.  The score
-    is the float64 sum of the products of the stored float32 weights over the shared items in ascending item order,
-    rounded once to float32; rows scoring 0 are ordinary results.  k <= 1024."""
+def query_pieces(nq: int, per: int):
+    """The (first query, queries) pieces of a batch of ``nq`` at ``per`` a call."""
+    return [(lo, min(per, nq - lo)) for lo in range(0, nq, per)]
+
+
+class CsrIndex:
+    """What the exact indexes over CSR rows share (``SparseSessionIndex``, ``jaccard.JaccardIndex``): the corpus on the
+    device, with a weights column when ``weighted``, and the top-k call in query pieces.  A subclass gives ``_take(v, what)
+    -> SessionVectors`` (checked), ``_pieces(nq, n)`` -- in its own module: the tests patch each module's
+    ``exhaustive_chunk`` -- and ``_topk``, its one library call."""
+    weighted = True
 
     def __init__(self, n_items: int, device=None):
         if not 0 < int(n_items) < 2 ** 31:
@@ -163,47 +169,43 @@ class SparseSessionIndex:
         self.n_items = int(n_items)
         self.device = _dev(device)
         self.id_offset = 0
-        self._v = _device_triple(np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float32), self.device)
+        self._ptr = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._items = torch.zeros(1, dtype=torch.int32, device=self.device)[:0]      # never NULL
+        self._weights = torch.zeros(1, dtype=torch.float32, device=self.device)[:0] if self.weighted else None
         self._ws = Workspace(self.device)
-        self.last_chunks = 0                             # query chunks of the last search
+        self.last_chunks = 0                             # query pieces of the last search (or bands)
 
     @property
     def ntotal(self) -> int:
-        return len(self._v)
-
-    @property
-    def vectors(self) -> SessionVectors:
-        return self._v
-
-    def _take(self, v, what) -> SessionVectors:
-        if isinstance(v, np.ndarray):
-            if v.ndim != 2 or v.shape[1] != self.n_items:
-                raise ValueError(f"{what}: expected [rows, {self.n_items}], got {v.shape}")
-            return dense_to_vectors(v, self.device)
-        if not isinstance(v, SessionVectors):
-            raise TypeError(f"{what}: expected SessionVectors or a dense [rows, n_items] numpy array")
-        _lib.require_cuda(v.ptr, "ptr", torch.int64)
-        _lib.require_cuda(v.items, "items", torch.int32)
-        _lib.require_cuda(v.weights, "weights", torch.float32)
-        return v.check(self.n_items)
+        return int(self._ptr.shape[0] - 1)
 
     def add(self, vectors):
         v = self._take(vectors, "add")
         if len(v) == 0:
             return self
-        old = self._v
         lo, hi = int(v.ptr[0].item()), int(v.ptr[-1].item())         # the entries these rows own (v may be a slice of a larger batch)
-        nnz_old, nnz = int(old.items.numel()), hi - lo
-        items = torch.zeros(nnz_old + nnz + 1, dtype=torch.int32, device=self.device)
-        weights = torch.zeros(nnz_old + nnz + 1, dtype=torch.float32, device=self.device)
-        items[:nnz_old] = old.items; items[nnz_old:nnz_old + nnz] = v.items[lo:hi].to(self.device)
-        weights[:nnz_old] = old.weights; weights[nnz_old:nnz_old + nnz] = v.weights[lo:hi].to(self.device)
-        ptr = torch.cat([old.ptr, v.ptr[1:].to(self.device) - lo + nnz_old])
-        self._v = SessionVectors(ptr, items[:nnz_old + nnz], weights[:nnz_old + nnz])
+        nnz_old, nnz = int(self._items.numel()), hi - lo
+
+        def grown(old, new):                             # one spare entry: zero entries still have an allocation behind them
+            t = torch.zeros(nnz_old + nnz + 1, dtype=old.dtype, device=self.device)
+            t[:nnz_old] = old; t[nnz_old:nnz_old + nnz] = new[lo:hi].to(self.device)
+            return t[:nnz_old + nnz]
+        self._ptr = torch.cat([self._ptr, v.ptr[1:].to(self.device) - lo + nnz_old])
+        self._items = grown(self._items, v.items)
+        if self.weighted:
+            self._weights = grown(self._weights, v.weights)
         return self
 
+    def _each_piece(self, pieces, call):
+        """``call(lo, m)`` per piece of the query batch, counted in ``last_chunks``."""
+        self.last_chunks = 0
+        for lo, m in pieces:
+            call(lo, m)
+            self.last_chunks += 1
+
     def search_device(self, q: SessionVectors, k: int, D: torch.Tensor | None = None, I: torch.Tensor | None = None):
-        """``search`` for device vectors, into ``D`` / ``I`` when given; no host sync."""
+        """``search`` for device vectors, into ``D`` / ``I`` when given; no host sync.  Queries go in pieces under the
+        exhaustive score budget."""
         k = int(k)
         if not 0 < k <= 1024:
             raise ValueError("k must be in 1..1024")
@@ -220,18 +222,46 @@ class SparseSessionIndex:
             return D, I
         if nq == 0:
             return D, I
-        L, st, c = _lib.lib(), _lib.stream_ptr(self.device), self._v
-        # items / weights of an all-empty batch: zero entries, but sliced from a one-entry allocation (never NULL)
-        per = exhaustive_chunk(n, 4)
-        for lo in range(0, nq, per):
-            m = min(per, nq - lo)
-            ws = self._ws.get(L.sss_sparse_topk_workspace_bytes(m, n))
-            rc = L.sss_sparse_topk(q.ptr.data_ptr() + 8 * lo, _ptr_of(q.items), _ptr_of(q.weights), m, c.ptr.data_ptr(),
-                                   _ptr_of(c.items), _ptr_of(c.weights), n, k, self.id_offset, D.data_ptr() + 4 * lo * k,
-                                   I.data_ptr() + 8 * lo * k, ws.data_ptr(), ws.numel(), st)
-            _lib.check(rc, "sss_sparse_topk")
-            self.last_chunks += 1
+        L, st = _lib.lib(), _lib.stream_ptr(self.device)
+
+        def call(lo, m):
+            self._topk(L, q, lo, m, n, k, D.data_ptr() + 4 * lo * k, I.data_ptr() + 8 * lo * k, st)
+        self._each_piece(self._pieces(nq, n), call)
         return D, I
+
+
+class SparseSessionIndex(CsrIndex):
+    """Exact top-k over sparse session vectors: ``add(vectors)``, ``search(vectors, k) -> (D float32 [nq, k], I int64
+    [nq, k])`` by (score desc, id asc), ids = row + ``id_offset``, padding (-FLT_MAX, -1) when ``ntotal < k``.  The score
+    is the float64 sum of the products of the stored float32 weights over the shared items in ascending item order,
+    rounded once to float32; rows scoring 0 are ordinary results.  k <= 1024."""
+
+    @property
+    def vectors(self) -> SessionVectors:
+        return SessionVectors(self._ptr, self._items, self._weights)
+
+    def _take(self, v, what) -> SessionVectors:
+        if isinstance(v, np.ndarray):
+            if v.ndim != 2 or v.shape[1] != self.n_items:
+                raise ValueError(f"{what}: expected [rows, {self.n_items}], got {v.shape}")
+            return dense_to_vectors(v, self.device)
+        if not isinstance(v, SessionVectors):
+            raise TypeError(f"{what}: expected SessionVectors or a dense [rows, n_items] numpy array")
+        _lib.require_cuda(v.ptr, "ptr", torch.int64)
+        _lib.require_cuda(v.items, "items", torch.int32)
+        _lib.require_cuda(v.weights, "weights", torch.float32)
+        return v.check(self.n_items)
+
+    def _pieces(self, nq, n):
+        return query_pieces(nq, exhaustive_chunk(n, 4))
+
+    def _topk(self, L, q, lo, m, n, k, d_ptr, i_ptr, st):
+        # items / weights of an all-empty batch: zero entries, but sliced from a one-entry allocation (never NULL)
+        ws = self._ws.get(L.sss_sparse_topk_workspace_bytes(m, n))
+        rc = L.sss_sparse_topk(q.ptr.data_ptr() + 8 * lo, _ptr_of(q.items), _ptr_of(q.weights), m, self._ptr.data_ptr(),
+                               _ptr_of(self._items), _ptr_of(self._weights), n, k, self.id_offset, d_ptr, i_ptr, ws.data_ptr(),
+                               ws.numel(), st)
+        _lib.check(rc, "sss_sparse_topk")
 
     def search(self, vectors, k: int):
         """Device ``SessionVectors`` -> device tensors; a dense [nq, n_items] numpy query -> numpy arrays."""
