@@ -8,6 +8,7 @@ Drop-in surface of the reference's path:
                                                                   util_amazon_filtered.sequence_to_graph)
   get_prediction_by_knn, get_p_r, SessionItems    (retrieval.py <- test_amazon_filterd.py:59-85)
   HeteroSAGE, GraphPooling, AttentionPooling, ... (variants.py  <- model/gnn.py, model/model.py variants)
+  HGT, hgt_fold_weights                           (variants.py  <- model/gnn.py HGT: the two-tower model's encoder)
   SparseSessionIndex, session_vectors, find_K_sparse_dense
                                                   (sparse.py    <- test_amazon_filterd.py SKNN / STAN item-vector baselines)
   evaluate, query_parts, item_overlap, get_*_jaccard, get_*_recall, get_*_map, get_ave_score, get_recall
@@ -29,6 +30,8 @@ __all__ = ["SssError", "build", "exported_symbols", "lib", "SessionVectors", "Sp
 _EVALUATION = frozenset(__all__[8:])
 _JACCARD = ("JaccardIndex", "mine_triples", "neighbourhood_recall")
 __all__ += list(_JACCARD)
+_HGT = ("HGT", "hgt_fold_weights")
+__all__ += list(_HGT)
 
 
 def __getattr__(name):
@@ -42,4 +45,7 @@ def __getattr__(name):
     if name in _JACCARD:                                 # the ground-truth index: lazily, for the same reason
         from . import jaccard
         return getattr(jaccard, name)
+    if name in _HGT:                                     # the HGT encoder: lazily, for the same reason
+        from . import variants
+        return getattr(variants, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -179,6 +179,12 @@ _JACCARD_SIGNATURES = {
                                   c_void_p, c_void_p]),
 }
 
+# include/sss_hgt.h one to one (the HGT encoder: HGTConv's attention aggregation on CSR by target and its skip connection)
+_HGT_SIGNATURES = {
+    "sss_hgt_aggregate": (c_int, [c_void_p, c_void_p]),
+    "sss_hgt_skip": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_float, c_int64, c_int, c_void_p]),
+}
+
 
 # header of include/ -> its signature table: what lib() binds, and every *_symbols() view below
 HEADERS = {
@@ -190,6 +196,7 @@ HEADERS = {
     "sss_graph.h": _GRAPH_SIGNATURES,
     "sss_eval.h": _EVAL_SIGNATURES,
     "sss_jaccard.h": _JACCARD_SIGNATURES,
+    "sss_hgt.h": _HGT_SIGNATURES,
 }
 
 
@@ -216,6 +223,17 @@ class LayerArgs(ctypes.Structure):
                 ("out_q", c_void_p), ("ld_out_q", c_int64), ("nq", c_int64), ("n_self_loop", c_int64),
                 ("row_p", c_void_p), ("row_q", c_void_p), ("x0_p", c_void_p), ("ld_x0_p", c_int64),
                 ("xq_table", c_void_p), ("ld_xq", c_int64), ("x0_q", c_void_p), ("ld_x0_q", c_int64)]
+
+
+class HgtSlot(ctypes.Structure):
+    """``sss_hgt_slot`` of include/sss_hgt.h."""
+    _fields_ = [("k", c_void_p), ("ld_k", c_int64), ("v", c_void_p), ("ld_v", c_int64), ("rowptr", c_void_p), ("col", c_void_p)]
+
+
+class HgtArgs(ctypes.Structure):
+    """``sss_hgt_args`` of include/sss_hgt.h."""
+    _fields_ = [("q", c_void_p), ("ld_q", c_int64), ("slot", HgtSlot * 2), ("n_slots", c_int32), ("n_dst", c_int64),
+                ("heads", c_int32), ("head_dim", c_int32), ("gelu", c_int32), ("out", c_void_p), ("ld_out", c_int64)]
 
 
 def exported_symbols():
@@ -255,6 +273,11 @@ def eval_symbols():
 def jaccard_symbols():
     """The entry points of include/sss_jaccard.h."""
     return sorted(HEADERS["sss_jaccard.h"])
+
+
+def hgt_symbols():
+    """The entry points of include/sss_hgt.h."""
+    return sorted(HEADERS["sss_hgt.h"])
 
 
 def build(verbose: bool = False) -> str:

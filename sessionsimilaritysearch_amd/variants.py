@@ -3,6 +3,8 @@ CSR-by-target + segment kernels:
 
 * ``HeteroSAGE``        <- ``GNN`` = 3 x ``SAGEConv((-1,-1), h)`` made heterogeneous with ``to_hetero``
                            (``model/gnn.py:83-121``; aggr = 'sum' over edge types, ``config.py:18``)
+* ``HGT``               <- ``HGT`` = relu(Linear) + 3 x ``HGTConv(h, h, heads, group='sum')``, every layer's output
+                           concatenated (``model/gnn.py:9-41``; the two-tower session / sub-session model)
 * ``GraphPooling``      <- ``model/gnn.py:123-143`` (mean / add / max + Linear; dropout is identity in eval)
 * ``AttentionPooling``  <- ``model/gnn.py:145-161`` (row-wise dot instead of the dense [n_nodes, B] matrix)
 * ``SRGNNPooling``      <- ``model/gnn.py:164-181``
@@ -15,12 +17,15 @@ CSR-by-target + segment kernels:
                            take (fine_tune_ours.py:839-843)
 
 Every arithmetic step runs in ``libsss.so`` (``sss_csr_mean``, ``sss_segment_reduce``,
-``sss_attention_dot_pool``, ``sss_pool_attention``, ``sss_linear_grouped``); torch owns memory only.
+``sss_attention_dot_pool``, ``sss_pool_attention``, ``sss_linear_grouped``, ``sss_hgt_aggregate``, ``sss_hgt_skip``);
+torch owns memory only.
 Weights are flat ``{name: tensor}`` dicts; conv / pool widths are multiples of 32 up to 2048 (the reference runs them at
 ``gnn_nout = 800``, config.py:15-16: rows wider than 256 floats are walked in column chunks), the MLP / binarize heads
 take any width (the reference's 1600 -> 3000 -> 2000 -> 250).
 """
 from __future__ import annotations
+
+import ctypes
 
 import torch
 
@@ -109,13 +114,135 @@ class HeteroSAGE:
         return {"query": x_q, "product": x_p}
 
 
+# HGT: the column blocks (h wide each) of a layer's two node transforms; every source row carries the K^e | V^e pair of
+# each edge type it feeds side by side (qp: query -> product, pq: product -> query, pp: product -> product)
+HGT_BLOCKS = {"product": ("q", "pq.k", "pq.v", "pp.k", "pp.v"), "query": ("q", "qp.k", "qp.v")}
+
+
+def hgt_fold_weights(weights, n_heads, n_layers):
+    """Host-side, device-free, float64: the weights of ``HGT`` with everything that is linear folded into the two GEMMs
+    of a layer.  Per layer and node type ``t``:
+
+    * ``w [len(HGT_BLOCKS[t]) * h, h]``, ``b``: the blocks of ``HGT_BLOCKS[t]`` stacked -- ``q`` is ``q_lin_t``; ``e.k`` is
+      ``k_lin_t`` followed per head by ``a_rel_e[eta] * p_rel_e[eta] / sqrt(D)`` (so the kernel's score is a plain dot
+      product); ``e.v`` is ``v_lin_t`` followed per head by ``m_rel_e[eta]``; the biases go through the same maps;
+    * ``a_w``, ``a_b``: ``sigmoid(skip_t) * a_lin_t``;  ``beta = 1 - sigmoid(skip_t)``.
+
+    Returns ``{"h", "heads", "lin": {t: (w, b)}, "layers": [{t: {"w", "b", "a_w", "a_b", "beta"}}]}``."""
+    f64 = lambda name: weights[name].detach().to("cpu", torch.float64)
+    h = int(weights["hgt.lin.query.w"].shape[0])
+    H = int(n_heads)
+    if H < 1 or h % H:
+        raise ValueError(f"hidden width {h} is not a multiple of n_heads = {n_heads}")
+    D = h // H
+    out = {"h": h, "heads": H, "lin": {t: (f64(f"hgt.lin.{t}.w"), f64(f"hgt.lin.{t}.b")) for t in ("query", "product")},
+           "layers": []}
+    for l in range(n_layers):
+        layer = {}
+        for t, blocks in HGT_BLOCKS.items():
+            ws, bs = [], []
+            for blk in blocks:
+                if blk == "q":
+                    ws.append(f64(f"hgt.{l}.{t}.q.w"))
+                    bs.append(f64(f"hgt.{l}.{t}.q.b"))
+                    continue
+                e, kind = blk.split(".")
+                rel = f64(f"hgt.{l}.{e}.{'a_rel' if kind == 'k' else 'm_rel'}").reshape(H, D, D)
+                if kind == "k":
+                    rel = rel * (f64(f"hgt.{l}.{e}.p_rel").reshape(H, 1, 1) / float(D) ** 0.5)
+                w = f64(f"hgt.{l}.{t}.{kind}.w").reshape(H, D, h)
+                b = f64(f"hgt.{l}.{t}.{kind}.b").reshape(H, D)
+                # row vector times matrix per head: (x W^T + b)[eta] @ rel[eta]
+                ws.append(torch.einsum("hde,hdk->hek", rel, w).reshape(h, h))
+                bs.append(torch.einsum("hd,hde->he", b, rel).reshape(h))
+            sig = torch.sigmoid(f64(f"hgt.{l}.{t}.skip").reshape(()))
+            layer[t] = {"w": torch.cat(ws, 0), "b": torch.cat(bs, 0), "a_w": sig * f64(f"hgt.{l}.{t}.a.w"),
+                        "a_b": sig * f64(f"hgt.{l}.{t}.a.b"), "beta": float(1.0 - sig)}
+        out["layers"].append(layer)
+    return out
+
+
+def hgt_aggregate(q, slots, n_heads, out, gelu=True):
+    """``sss_hgt_aggregate`` on 2-D float32 device views: ``slots`` = one or two ``(k, v, rowptr, col)`` by target."""
+    args = _lib.HgtArgs(q=q.data_ptr(), ld_q=q.stride(0), n_slots=len(slots), n_dst=q.shape[0], heads=n_heads,
+                        head_dim=q.shape[1] // n_heads, gelu=int(gelu), out=out.data_ptr(), ld_out=out.stride(0))
+    for i, (k, v, rowptr, col) in enumerate(slots[:2]):
+        args.slot[i] = _lib.HgtSlot(k=k.data_ptr(), ld_k=k.stride(0), v=v.data_ptr(), ld_v=v.stride(0),
+                                    rowptr=rowptr.data_ptr(), col=col.data_ptr())
+    _lib.check(_lib.lib().sss_hgt_aggregate(ctypes.byref(args), _st(q.device)), "sss_hgt_aggregate")
+    return out
+
+
+class HGT:
+    """``HGT`` (model/gnn.py:9-41): ``x0_t = relu(lin_t(x_t))``, then ``n_layers`` x ``HGTConv(h, h, heads, group='sum')``;
+    returns every layer's node features side by side, ``{'query': [Nq, h (L + 1)], 'product': [Np, h (L + 1)]}``.
+    weights: ``hgt.lin.{query|product}.{w,b}``, ``hgt.{l}.{query|product}.{k,q,v,a}.{w,b}``,
+    ``hgt.{l}.{query|product}.skip``, ``hgt.{l}.{qp|pq|pp}.{a_rel [H, D, D], m_rel [H, D, D], p_rel [H]}``.
+    Per layer: one grouped GEMM (all Q / K^e / V^e of both node types), ``sss_hgt_aggregate`` per target type, one
+    grouped ``a_lin`` GEMM into the next slice of the output, ``sss_hgt_skip`` per type: 1 + 6 L launches."""
+
+    def __init__(self, weights, n_heads=4, n_layers=3, device=None):
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        f = hgt_fold_weights(weights, n_heads, n_layers)
+        self.h, self.heads, self.n_layers = f["h"], f["heads"], n_layers
+        if self.heads not in (1, 2, 4, 8) or (self.h // self.heads) % 4 or self.h % 32 or self.h > 2048:
+            raise ValueError(f"HGT needs n_heads in (1, 2, 4, 8), h / n_heads % 4 == 0, h % 32 == 0 and h <= 2048; "
+                             f"got h = {self.h}, n_heads = {n_heads}")
+        dev = self.device
+        self.lin = {t: (_pad_cols(w, dev), _d(b, dev)) for t, (w, b) in f["lin"].items()}
+        self.layers = [{t: {n: (v if n == "beta" else _d(v, dev)) for n, v in lay[t].items()} for t in lay} for lay in f["layers"]]
+
+    def _grouped(self, probs, k):
+        arr = (_lib.LinearProblem * len(probs))(*probs)
+        _lib.check(_lib.lib().sss_linear_grouped(arr, len(probs), k, _st(self.device)), "sss_linear_grouped")
+
+    @torch.no_grad()
+    def forward(self, x_q, x_p, csr_qp, csr_pq, csr_pp):
+        """``csr_*`` = (rowptr, col) int32 by target: qp -> products, pq -> queries, pp -> products."""
+        L, dev, h, H = _lib.lib(), self.device, self.h, self.heads
+        n = {"query": x_q.shape[0], "product": x_p.shape[0]}
+        out = {t: torch.empty((n[t], h * (self.n_layers + 1)), dtype=torch.float32, device=dev) for t in n}
+        probs = {}
+        for t, x in (("product", x_p), ("query", x_q)):
+            w, b = self.lin[t]
+            if x.shape[1] != w.shape[1] or x.stride(1) != 1 or x.stride(0) % 4:       # the GEMM's K is a multiple of 32
+                buf = torch.zeros((n[t], w.shape[1]), dtype=torch.float32, device=dev)
+                buf[:, :x.shape[1]] = x
+                x = buf
+            probs[t] = (_prob(x, w, b, out[t][:, :h], n[t], h, act=1), w.shape[1])
+        if probs["product"][1] == probs["query"][1]:
+            self._grouped([probs["product"][0], probs["query"][0]], probs["query"][1])
+        else:                                                                        # K differs per node type: two launches
+            for t in probs:
+                self._grouped([probs[t][0]], probs[t][1])
+        y = {t: torch.empty((n[t], len(HGT_BLOCKS[t]) * h), dtype=torch.float32, device=dev) for t in n}
+        agg = {t: torch.empty((n[t], h), dtype=torch.float32, device=dev) for t in n}
+        blk = lambda t, name: y[t][:, HGT_BLOCKS[t].index(name) * h:(HGT_BLOCKS[t].index(name) + 1) * h]
+        kv = lambda src, e, csr: (blk(src, e + ".k"), blk(src, e + ".v"), csr[0], csr[1])
+        for l, lay in enumerate(self.layers):
+            cur = {t: out[t][:, l * h:(l + 1) * h] for t in n}                       # read in place through ldx
+            nxt = {t: out[t][:, (l + 1) * h:(l + 2) * h] for t in n}
+            self._grouped([_prob(cur[t], lay[t]["w"], lay[t]["b"], y[t], n[t], y[t].shape[1]) for t in ("product", "query")], h)
+            hgt_aggregate(blk("product", "q"), [kv("query", "qp", csr_qp), kv("product", "pp", csr_pp)], H, agg["product"])
+            hgt_aggregate(blk("query", "q"), [kv("product", "pq", csr_pq)], H, agg["query"])
+            self._grouped([_prob(agg[t], lay[t]["a_w"], lay[t]["a_b"], nxt[t], n[t], h) for t in ("product", "query")], h)
+            for t in ("product", "query"):
+                rc = L.sss_hgt_skip(nxt[t].data_ptr(), nxt[t].stride(0), cur[t].data_ptr(), cur[t].stride(0), lay[t]["beta"],
+                                    n[t], h, _st(dev))
+                _lib.check(rc, "sss_hgt_skip")
+        return out
+
+
 def segment_reduce(x, ptr, mode, weight=None):
-    """Per-graph mean / add / max (mode 0 / 1 / 2) of node rows sorted by graph; ``ptr`` int32 [B+1]."""
-    B = ptr.shape[0] - 1
-    out = torch.empty((B, x.shape[1]), dtype=torch.float32, device=x.device)
-    rc = _lib.lib().sss_segment_reduce(x.data_ptr(), x.stride(0), 0 if weight is None else weight.data_ptr(), ptr.data_ptr(),
-                                       B, x.shape[1], mode, out.data_ptr(), out.stride(0), _st(x.device))
-    _lib.check(rc, "sss_segment_reduce")
+    """Per-graph mean / add / max (mode 0 / 1 / 2) of node rows sorted by graph; ``ptr`` int32 [B+1].  The kernel takes
+    rows of up to 2048 floats; wider ones (the HGT's h (L + 1) = 3200) go through it in column blocks of that width."""
+    B, d = ptr.shape[0] - 1, x.shape[1]
+    out = torch.empty((B, d), dtype=torch.float32, device=x.device)
+    for c in range(0, d, 2048):
+        xv, ov = x[:, c:c + 2048], out[:, c:c + 2048]
+        rc = _lib.lib().sss_segment_reduce(xv.data_ptr(), x.stride(0), 0 if weight is None else weight.data_ptr(), ptr.data_ptr(),
+                                           B, xv.shape[1], mode, ov.data_ptr(), out.stride(0), _st(x.device))
+        _lib.check(rc, "sss_segment_reduce")
     return out
 
 
