@@ -17,6 +17,9 @@ Drop-in surface of the reference's path:
   JaccardIndex, mine_triples, neighbourhood_recall
                                                   (jaccard.py   <- fine_tune_ours.py get_score :42-55 over the whole corpus,
                                                                   the triple mining :187-235: the ground truth)
+  NodeTextTransformer, pack_tokens, text_fold_weights, TokenRows
+                                                  (text.py      <- model/NodeEmbedding.py NodeTextTransformer: the two-tower
+                                                                  model's query text encoder, eval mode)
   ShardedFlatIndex, ShardedBinaryIndex, ShardedSparseIndex, ShardedJaccardIndex
                                                   (distributed.py: corpus row-sharded over RCCL)
   SessionBatch, build_batch, synthetic_actions    (sessions.py  <- sequence_to_graph + Batch.from_data_list, host side)
@@ -32,6 +35,8 @@ _JACCARD = ("JaccardIndex", "mine_triples", "neighbourhood_recall")
 __all__ += list(_JACCARD)
 _HGT = ("HGT", "hgt_fold_weights")
 __all__ += list(_HGT)
+_TEXT = ("NodeTextTransformer", "pack_tokens", "text_fold_weights", "TokenRows")
+__all__ += list(_TEXT)
 
 
 def __getattr__(name):
@@ -48,4 +53,7 @@ def __getattr__(name):
     if name in _HGT:                                     # the HGT encoder: lazily, for the same reason
         from . import variants
         return getattr(variants, name)
+    if name in _TEXT:                                    # the query text encoder: lazily, for the same reason
+        from . import text
+        return getattr(text, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

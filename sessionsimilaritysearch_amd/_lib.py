@@ -185,6 +185,15 @@ _HGT_SIGNATURES = {
     "sss_hgt_skip": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_float, c_int64, c_int, c_void_p]),
 }
 
+# include/sss_text.h one to one (the query text encoder: token embedding, attention inside packed sequences, add + LayerNorm)
+_TEXT_SIGNATURES = {
+    "sss_text_embed": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_int64,
+                               c_void_p, c_void_p]),
+    "sss_seq_attention": (c_int, [c_void_p, c_void_p]),
+    "sss_add_layernorm": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_int64, c_int, c_void_p, c_int64,
+                                  c_void_p]),
+}
+
 
 # header of include/ -> its signature table: what lib() binds, and every *_symbols() view below
 HEADERS = {
@@ -197,6 +206,7 @@ HEADERS = {
     "sss_eval.h": _EVAL_SIGNATURES,
     "sss_jaccard.h": _JACCARD_SIGNATURES,
     "sss_hgt.h": _HGT_SIGNATURES,
+    "sss_text.h": _TEXT_SIGNATURES,
 }
 
 
@@ -234,6 +244,13 @@ class HgtArgs(ctypes.Structure):
     """``sss_hgt_args`` of include/sss_hgt.h."""
     _fields_ = [("q", c_void_p), ("ld_q", c_int64), ("slot", HgtSlot * 2), ("n_slots", c_int32), ("n_dst", c_int64),
                 ("heads", c_int32), ("head_dim", c_int32), ("gelu", c_int32), ("out", c_void_p), ("ld_out", c_int64)]
+
+
+class SeqAttentionArgs(ctypes.Structure):
+    """``sss_seq_attention_args`` of include/sss_text.h."""
+    _fields_ = [("qkv", c_void_p), ("ld_qkv", c_int64), ("ptr", c_void_p), ("key_ok", c_void_p), ("n_rows", c_int64),
+                ("n_seq", c_int64), ("heads", c_int32), ("head_dim", c_int32), ("max_len", c_int32), ("out", c_void_p),
+                ("ld_out", c_int64)]
 
 
 def exported_symbols():
@@ -278,6 +295,11 @@ def jaccard_symbols():
 def hgt_symbols():
     """The entry points of include/sss_hgt.h."""
     return sorted(HEADERS["sss_hgt.h"])
+
+
+def text_symbols():
+    """The entry points of include/sss_text.h."""
+    return sorted(HEADERS["sss_text.h"])
 
 
 def build(verbose: bool = False) -> str:
