@@ -307,7 +307,7 @@ typedef struct {
     const int64_t* ids; const float* table; float* xcopy; int64_t ld_xcopy;
     const float* w; int64_t ldw; const float* bias;
     float* y; int64_t ldy;
-    int64_t n; int32_t m; int32_t act;      /* epilogue activation: 0 none, 1 relu, 2 tanh, 3 sign, 4 tanh(tanh(.)) */
+    int64_t n; int32_t m; int32_t act;      /* epilogue activation: 0 none, 1 relu, 2 tanh, 3 sign, 4 tanh(tanh(.)), 5 gelu */
     const float* post_scale;                /* optional [m] (both or neither): after the activation, per output   */
     const float* post_shift;                /* column v = relu(v * post_scale + post_shift) -- BatchNorm1d in eval */
                                             /* mode + the relu the reference MLP applies to it (model/model.py:63-65) */

@@ -20,6 +20,9 @@ Drop-in surface of the reference's path:
   NodeTextTransformer, pack_tokens, text_fold_weights, TokenRows
                                                   (text.py      <- model/NodeEmbedding.py NodeTextTransformer: the two-tower
                                                                   model's query text encoder, eval mode)
+  BertNodeEncoder, bert_fold_weights, bert_pack_rows, BertRows
+                                                  (text.py      <- model/NodeEmbedding.py PretrainedQAEAEncoder: the deployed
+                                                                  model's node text encoder, BERT + masked mean + Linear)
   ShardedFlatIndex, ShardedBinaryIndex, ShardedSparseIndex, ShardedJaccardIndex
                                                   (distributed.py: corpus row-sharded over RCCL)
   SessionBatch, build_batch, synthetic_actions    (sessions.py  <- sequence_to_graph + Batch.from_data_list, host side)
@@ -35,7 +38,8 @@ _JACCARD = ("JaccardIndex", "mine_triples", "neighbourhood_recall")
 __all__ += list(_JACCARD)
 _HGT = ("HGT", "hgt_fold_weights")
 __all__ += list(_HGT)
-_TEXT = ("NodeTextTransformer", "pack_tokens", "text_fold_weights", "TokenRows")
+_TEXT = ("NodeTextTransformer", "pack_tokens", "text_fold_weights", "TokenRows", "BertNodeEncoder", "bert_fold_weights",
+         "bert_pack_rows", "BertRows")
 __all__ += list(_TEXT)
 
 

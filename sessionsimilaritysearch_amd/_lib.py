@@ -194,6 +194,12 @@ _TEXT_SIGNATURES = {
                                   c_void_p]),
 }
 
+# include/sss_bert.h one to one (the node text encoder: BERT's embedding stage; the rest of its forward is bound above)
+_BERT_SIGNATURES = {
+    "sss_bert_embed": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_float, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+}
+
 
 # header of include/ -> its signature table: what lib() binds, and every *_symbols() view below
 HEADERS = {
@@ -207,6 +213,7 @@ HEADERS = {
     "sss_jaccard.h": _JACCARD_SIGNATURES,
     "sss_hgt.h": _HGT_SIGNATURES,
     "sss_text.h": _TEXT_SIGNATURES,
+    "sss_bert.h": _BERT_SIGNATURES,
 }
 
 
@@ -300,6 +307,11 @@ def hgt_symbols():
 def text_symbols():
     """The entry points of include/sss_text.h."""
     return sorted(HEADERS["sss_text.h"])
+
+
+def bert_symbols():
+    """The entry points of include/sss_bert.h."""
+    return sorted(HEADERS["sss_bert.h"])
 
 
 def build(verbose: bool = False) -> str:

@@ -512,6 +512,7 @@ __global__ __launch_bounds__(256, 2) void k_linear_grouped(const LinBatch B) {
             else if (act == 2) v = tanhf(v);
             else if (act == 3) v = v > 0.f ? 1.f : v < 0.f ? -1.f : v;     // torch.sign (0 and NaN pass through)
             else if (act == 4) v = tanhf(tanhf(v));
+            else if (act == 5) v = gelu_erf(v);                             // exact GELU: gelu(0) = 0, NaN passes through
             if (post_s) {
 #pragma clang fp contract(off)                                               // multiply, round, add, round: no fused fma here
                 v = fmaxf(v * ps + pt, 0.f);                                // bn(x) in eval mode as scale / shift, then relu
@@ -904,8 +905,8 @@ extern "C" int sss_linear_grouped(const sss_linear_problem* problems, int n_prob
         p.x = s.x; p.ldx = s.ldx; p.ids = s.ids; p.table = s.table; p.xcopy = s.xcopy;
         p.ld_xcopy = s.ld_xcopy; p.w = s.w; p.ldw = s.ldw; p.bias = s.bias; p.y = s.y; p.ldy = s.ldy; p.n = s.n; p.m = s.m;
         p.act = s.act; p.post_scale = s.post_scale; p.post_shift = s.post_shift; p.tiles_m = 0; p.tile_begin = 0;
-        if (s.act < 0 || s.act > 4 || (s.post_scale == nullptr) != (s.post_shift == nullptr)) {
-            set_error("linear_grouped: problem %d: act must be 0..4, post_scale / post_shift come together", i);
+        if (s.act < 0 || s.act > 5 || (s.post_scale == nullptr) != (s.post_shift == nullptr)) {
+            set_error("linear_grouped: problem %d: act must be 0..5, post_scale / post_shift come together", i);
             return SSS_EINVAL;
         }
     }

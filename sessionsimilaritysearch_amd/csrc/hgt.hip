@@ -16,8 +16,6 @@
 
 namespace sss {
 
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
-
 template <int LPR, int NCH>
 __global__ __launch_bounds__(256) void k_hgt_aggregate(const sss_hgt_args A) {
     const int sub = threadIdx.x % LPR;

@@ -54,4 +54,7 @@ __device__ __host__ __forceinline__ uint64_t make_key(float s, int32_t id) {
 __device__ __host__ __forceinline__ float key_score(uint64_t k) { return ord2f((uint32_t)(k >> 32)); }
 __device__ __host__ __forceinline__ int32_t key_id(uint64_t k) { return (int32_t)(~(uint32_t)k); }
 
+// Exact GELU (torch's approximate='none', HF's "gelu"): k_hgt_aggregate's way out and act = 5 of k_linear_grouped.
+__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
+
 }  // namespace sss

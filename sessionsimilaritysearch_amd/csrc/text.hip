@@ -13,6 +13,7 @@
 // softmax, the idiom of k_hgt_aggregate).  At T = 20 a wave has 20 of 64 lanes at work; see DESIGN.md 5.9.
 #include <math.h>
 
+#include "layernorm_dev.h"
 #include "sss_common.h"
 #include "../../include/sss_text.h"
 
@@ -146,37 +147,12 @@ __global__ __launch_bounds__(256) void k_add_layernorm(const float* x, long ld_x
             const float4 a = *reinterpret_cast<const float4*>(x + r * ld_x + c);
             const float4 b = *reinterpret_cast<const float4*>(res + r * ld_res + c);
             v[j] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-            sum += (v[j].x + v[j].y) + (v[j].z + v[j].w);
+            sum += ln_lane_sum(v[j]);
         }
     }
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    const float mean = sum / (float)e;
-    float sq = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if ((lane + 64 * j) * 4 < e) {
-            v[j].x -= mean; v[j].y -= mean; v[j].z -= mean; v[j].w -= mean;
-            sq += (v[j].x * v[j].x + v[j].y * v[j].y) + (v[j].z * v[j].z + v[j].w * v[j].w);
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-    const float rstd = 1.f / sqrtf(sq / (float)e + eps);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = (lane + 64 * j) * 4;
-        if (c < e) {
-            const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-            const float4 b = *reinterpret_cast<const float4*>(beta + c);
-            *reinterpret_cast<float4*>(y + r * ld_y + c) = make_float4(v[j].x * rstd * g.x + b.x, v[j].y * rstd * g.y + b.y,
-                                                                       v[j].z * rstd * g.z + b.z, v[j].w * rstd * g.w + b.w);
-        }
-    }
-    for (int c = e + lane * 4; c < ld_y; c += 256) *reinterpret_cast<float4*>(y + r * ld_y + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+    ln_row_store(v, sum, gamma, beta, eps, e, lane, y + r * ld_y, ld_y);   // layernorm_dev.h: shared with k_bert_embed
 }
 
-static bool aligned16(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static bool ok_ld(int64_t ld, int width) { return ld % 4 == 0 && ld >= width; }
-static bool ok_count(int64_t n) { return n >= 0 && n < (1ll << 31); }
 static unsigned capped_grid(long blocks) { return (unsigned)(blocks < (1 << 20) ? blocks : (1 << 20)); }
 
 extern "C" int sss_text_embed(const float* table, int64_t n_token, const float* pe, int64_t n_pos, const int64_t* tok,

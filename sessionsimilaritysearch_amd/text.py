@@ -20,6 +20,18 @@ THE TWO PADDING RULES.  The refere
 Every arithmetic step runs in ``libsss.so``: ``sss_text_embed``, ``sss_seq_attention``, ``sss_add_layernorm``
 (include/sss_text.h), ``sss_linear_grouped`` for the four GEMMs of a layer and ``sss_segment_reduce`` for the pooling;
 torch owns memory only.  A layer is 7 launches, a forward ``7 * nlayers + 2`` per chunk of rows.
+
+The second half of the module is the deployed model's node text encoder, ``PretrainedQAEAEncoder``
+(``model/NodeEmbedding.py:100-125``): a BERT encoder without its pooling layer, a masked mean over the tokens and an
+optional ``Linear``, on the same packed rows and the same layer launches:
+
+* ``bert_pack_rows``         host side, numpy, device-free: ids, token types and attention mask -> packed rows + pool weights
+* ``unique_rows``            host side, numpy, device-free: the distinct ``(ids, types, mask)`` rows, each encoded once
+* ``bert_fold_weights``      host side, float64, device-free: ``query | key | value`` as one ``in_proj``, the same folds and pads
+* ``BertNodeEncoder``        the drop-in: ``enc(input_ids, token_type_ids, attention_mask, get_token=False)``
+
+Its embedding stage is ``sss_bert_embed`` (include/sss_bert.h), its feed-forward activation ``act = 5`` (exact GELU) of
+``sss_linear_grouped``; de-duplicated rows are scattered with ``sss_gather_rows``.
 """
 from __future__ import annotations
 
@@ -145,7 +157,40 @@ def split_chunks(ptr, chunk_rows):
     return out
 
 
-class NodeTextTransformer:
+class _PackedEncoder:
+    """What the two encoders on packed token rows share: the launches of a post-norm transformer layer.  A subclass sets
+    ``device``, ``eps``, ``ninp``, ``nhead`` and ``layers`` (the per-layer dicts of ``text_fold_weights``)."""
+
+    def _linear(self, x, w, b, y, n, act=0):
+        from . import _lib
+        from .variants import _prob
+        arr = (_lib.LinearProblem * 1)(_prob(x, w, b, y, n, w.shape[0], act))
+        _lib.check(_lib.lib().sss_linear_grouped(arr, 1, w.shape[1], _lib.stream_ptr(self.device)), "sss_linear_grouped")
+
+    def _add_layernorm(self, x, res, gamma, beta, n):
+        from . import _lib
+        rc = _lib.lib().sss_add_layernorm(x.data_ptr(), x.stride(0), res.data_ptr(), res.stride(0), gamma.data_ptr(), beta.data_ptr(),
+                                          self.eps, n, self.ninp, x.data_ptr(), x.stride(0), _lib.stream_ptr(self.device))
+        _lib.check(rc, "sss_add_layernorm")
+
+    def _run_layers(self, x, qkv, att, proj, hid, ptr, key_ok, n, n_seq, T, act):
+        """Every layer on the ``n`` packed rows of ``x`` (in place): 7 launches each; ``act`` is the feed-forward block's."""
+        from . import _lib
+        args = _lib.SeqAttentionArgs(qkv=qkv.data_ptr(), ld_qkv=qkv.stride(0), ptr=ptr.data_ptr(), key_ok=key_ok.data_ptr(),
+                                     n_rows=n, n_seq=n_seq, heads=self.nhead, head_dim=self.ninp // self.nhead, max_len=T,
+                                     out=att.data_ptr(), ld_out=att.stride(0))
+        L, st = _lib.lib(), _lib.stream_ptr(self.device)
+        for lay in self.layers:
+            self._linear(x, lay["in_w"], lay["in_b"], qkv, n)
+            _lib.check(L.sss_seq_attention(ctypes.byref(args), st), "sss_seq_attention")
+            self._linear(att, lay["out_w"], lay["out_b"], proj, n)
+            self._add_layernorm(x, proj, lay["n1_w"], lay["n1_b"], n)
+            self._linear(x, lay["l1_w"], lay["l1_b"], hid, n, act=act)
+            self._linear(hid, lay["l2_w"], lay["l2_b"], proj, n)
+            self._add_layernorm(x, proj, lay["n2_w"], lay["n2_b"], n)
+
+
+class NodeTextTransformer(_PackedEncoder):
     """Drop-in for the reference's ``NodeTextTransformer`` in eval mode: ``forward(src [B, T], mask [B, T]) -> [B, ninp]``
     float32 on the device -- ``x_q`` of ``variants.HGT.forward``, or ``data['query'].feat`` of ``SessionEncoder``.
 
@@ -185,18 +230,6 @@ class NodeTextTransformer:
         eps = module.transformer_encoder.layers[0].norm1.eps
         return cls({k: v for k, v in module.state_dict().items()}, nhead, eps=eps, **kw)
 
-    def _linear(self, x, w, b, y, n, act=0):
-        from . import _lib
-        from .variants import _prob
-        arr = (_lib.LinearProblem * 1)(_prob(x, w, b, y, n, w.shape[0], act))
-        _lib.check(_lib.lib().sss_linear_grouped(arr, 1, w.shape[1], _lib.stream_ptr(self.device)), "sss_linear_grouped")
-
-    def _add_layernorm(self, x, res, gamma, beta, n):
-        from . import _lib
-        rc = _lib.lib().sss_add_layernorm(x.data_ptr(), x.stride(0), res.data_ptr(), res.stride(0), gamma.data_ptr(), beta.data_ptr(),
-                                          self.eps, n, self.ninp, x.data_ptr(), x.stride(0), _lib.stream_ptr(self.device))
-        _lib.check(rc, "sss_add_layernorm")
-
     def forward(self, src, mask):
         import torch
         from . import _lib
@@ -225,17 +258,7 @@ class NodeTextTransformer:
                 rc = L.sss_text_embed(self.table.data_ptr(), self.ntoken, self.pe.data_ptr(), self.pe.shape[0], tok.data_ptr(),
                                       pos.data_ptr(), n, e, self.scale, x.data_ptr(), x.stride(0), err.data_ptr(), st)
                 _lib.check(rc, "sss_text_embed")
-                args = _lib.SeqAttentionArgs(qkv=qkv.data_ptr(), ld_qkv=qkv.stride(0), ptr=ptr.data_ptr(), key_ok=key_ok.data_ptr(),
-                                             n_rows=n, n_seq=s1 - s0, heads=self.nhead, head_dim=e // self.nhead, max_len=T,
-                                             out=att.data_ptr(), ld_out=att.stride(0))
-                for lay in self.layers:
-                    self._linear(x, lay["in_w"], lay["in_b"], qkv, n)
-                    _lib.check(L.sss_seq_attention(ctypes.byref(args), st), "sss_seq_attention")
-                    self._linear(att, lay["out_w"], lay["out_b"], proj, n)
-                    self._add_layernorm(x, proj, lay["n1_w"], lay["n1_b"], n)
-                    self._linear(x, lay["l1_w"], lay["l1_b"], hid, n, act=1)
-                    self._linear(hid, lay["l2_w"], lay["l2_b"], proj, n)
-                    self._add_layernorm(x, proj, lay["n2_w"], lay["n2_b"], n)
+                self._run_layers(x, qkv, att, proj, hid, ptr, key_ok, n, s1 - s0, T, act=1)
                 view = out[s0:s1]
                 rc = L.sss_segment_reduce(x.data_ptr(), x.stride(0), inv_t.data_ptr(), ptr.data_ptr(), s1 - s0, e, 1,
                                           view.data_ptr(), out.stride(0), st)
@@ -243,5 +266,246 @@ class NodeTextTransformer:
             if int(err.item()):                                              # one read per forward
                 raise IndexError("a token id or position was out of range on the device (sss_text_embed wrote zero rows)")
         return out
+
+    __call__ = forward
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# The node text encoder of the deployed model: PretrainedQAEAEncoder (model/NodeEmbedding.py:100-125), a BERT encoder without
+# its pooling layer + a masked mean over the tokens + an optional Linear.  DESIGN.md section 5.10.
+BERT_LAYER = "encoder.layer.{}."
+BERT_POOLS = ("masked", "mean")
+
+BertRows = namedtuple("BertRows", "rows tt w")
+BertRows.__doc__ = """Packed rows of a BERT batch: ``rows`` the ``TokenRows`` (``tok`` = input id, ``pos`` = index in the padded row,
+``key_ok`` = attention mask), ``tt`` int32 [n] the token type of each row, ``w`` float32 [n] the weight of each row in its
+sequence's pooled sum (``1 / len`` on attended rows and 0 elsewhere for ``"masked"``, ``1 / T`` for ``"mean"``)."""
+
+
+def bert_pack_rows(input_ids, token_type_ids, attention_mask, pool="masked", all_rows=False, n_word=None, n_type=None):
+    """``[B, T]`` ids, token types and attention mask (non-zero = attended) -> ``BertRows``.
+
+    Under ``pool="masked"`` without ``all_rows`` the padded rows are dropped: they are neither keys nor pooled, so the valid
+    rows and the pooled output are exactly what they are with them.  Under ``pool="mean"`` or ``all_rows`` (``get_token``)
+    every one of the ``T`` rows is kept; a padded row attends over the valid keys only and is never a key (HF's additive
+    mask).  Raises as ``pack_tokens`` does, and ``IndexError`` for a token type outside ``[0, n_type)``."""
+    if pool not in BERT_POOLS:
+        raise ValueError(f"pool must be 'masked' or 'mean', got {pool!r}")
+    ids, tt, am = _host(input_ids), _host(token_type_ids), _host(attention_mask)
+    if tt.shape != ids.shape or am.shape != ids.shape:
+        raise ValueError(f"input_ids, token_type_ids and attention_mask must share one [B, T] shape; got {ids.shape}, {tt.shape}, {am.shape}")
+    if not np.issubdtype(tt.dtype, np.integer):
+        raise ValueError(f"token_type_ids must hold integers, got dtype {tt.dtype}")
+    pad = am == 0
+    keep_all = pool == "mean" or all_rows
+    rows = pack_tokens(ids, pad, "compute" if keep_all else "zero", n_word)
+    if n_type is not None and tt.size and (int(tt.min()) < 0 or int(tt.max()) >= n_type):
+        raise IndexError(f"token type out of range [0, {n_type})")
+    B, T = ids.shape
+    counts = np.diff(rows.ptr)
+    b = np.repeat(np.arange(B), counts)
+    if pool == "mean":
+        w = np.full(len(b), 1.0 / T if T else 0.0, dtype=np.float32)
+    else:
+        w = (np.float32(1.0) / (~pad).sum(axis=1).astype(np.float32))[b] * rows.key_ok.astype(np.float32)
+    return BertRows(rows, tt[b, rows.pos].astype(np.int32), w.astype(np.float32))
+
+
+def unique_rows(ids, tt, am):
+    """``(first int64 [U], inverse int64 [B])`` of the distinct ``(ids, types, mask)`` rows of ``[B, T]`` integer arrays whose
+    values fit int32: ``first`` indexes one representative of each, ``row b == row first[inverse[b]]``.  One ``np.unique``
+    over the rows as byte strings (int32 ids and types, uint8 mask: 9 bytes per position), four times as fast as ``axis=0``
+    over int64 columns; the order of the distinct rows is the byte order, which no result depends on."""
+    key = np.concatenate([ids.astype(np.int32), tt.astype(np.int32)], axis=1).view(np.uint8)
+    key = np.ascontiguousarray(np.concatenate([key, (am != 0).astype(np.uint8)], axis=1))
+    _, first, inverse = np.unique(key.view(np.dtype((np.void, key.shape[1]))).reshape(-1), return_index=True, return_inverse=True)
+    return first.astype(np.int64), inverse.reshape(-1).astype(np.int64)
+
+
+def bert_fold_weights(weights, num_heads):
+    """Host-side, device-free, float64: the weights of a ``BertModel`` without its pooling layer (HF's own ``state_dict()``
+    names) as the kernels take them, after ``text_fold_weights``: ``query | key | value`` become one ``in_w [3 e, K]`` with
+    ``1 / sqrt(D)`` folded into the q rows and bias, every GEMM's K is padded with zero columns to a multiple of 32, and
+    ``intermediate.dense`` with zero rows and zero bias to ``pad32(inter)`` outputs: ``gelu(0) = 0``, so the pad columns
+    ``output.dense`` reads are exact zeros.  Optional ``lin.weight`` / ``lin.bias`` (the reference's ``Linear(768, nout)``).
+
+    Returns ``{"e", "heads", "inter", "nlayers", "word" [n_word, e], "pos" [n_pos, e], "type" [n_type, e], "emb_g", "emb_b",
+    "layers": [the keys of text_fold_weights], "lin_w" [nout, K] or None, "lin_b"}`` with ``K = pad32(e)``."""
+    import torch
+    f64 = lambda name: weights[name].detach().to("cpu", torch.float64)
+    word = f64("embeddings.word_embeddings.weight")
+    e, H = int(word.shape[1]), int(num_heads)
+    if H < 1 or e % H:
+        raise ValueError(f"hidden size {e} is not a multiple of num_heads = {num_heads}")
+    D = e // H
+    nlayers = 0
+    while BERT_LAYER.format(nlayers) + "attention.self.query.weight" in weights:
+        nlayers += 1
+    if nlayers == 0:
+        raise ValueError("weights hold no encoder.layer.0.attention.self.query.weight")
+    inter = int(weights[BERT_LAYER.format(0) + "intermediate.dense.weight"].shape[0])
+    K, Hp = _pad32(e), _pad32(inter)
+
+    def pad(w, rows, cols):
+        out = torch.zeros((rows, cols), dtype=torch.float64)
+        out[:w.shape[0], :w.shape[1]] = w
+        return out
+
+    layers = []
+    for l in range(nlayers):
+        g = lambda n: f64(BERT_LAYER.format(l) + n)
+        in_w = torch.cat([g("attention.self.query.weight") / math.sqrt(D), g("attention.self.key.weight"), g("attention.self.value.weight")])
+        in_b = torch.cat([g("attention.self.query.bias") / math.sqrt(D), g("attention.self.key.bias"), g("attention.self.value.bias")])
+        l1_b = torch.zeros(Hp, dtype=torch.float64)
+        l1_b[:inter] = g("intermediate.dense.bias")
+        layers.append({"in_w": pad(in_w, 3 * e, K), "in_b": in_b, "out_w": pad(g("attention.output.dense.weight"), e, K),
+                       "out_b": g("attention.output.dense.bias"), "l1_w": pad(g("intermediate.dense.weight"), Hp, K), "l1_b": l1_b,
+                       "l2_w": pad(g("output.dense.weight"), e, Hp), "l2_b": g("output.dense.bias"),
+                       "n1_w": g("attention.output.LayerNorm.weight"), "n1_b": g("attention.output.LayerNorm.bias"),
+                       "n2_w": g("output.LayerNorm.weight"), "n2_b": g("output.LayerNorm.bias")})
+    lin_w = lin_b = None
+    if "lin.weight" in weights:
+        lin_w = pad(f64("lin.weight"), int(weights["lin.weight"].shape[0]), K)
+        lin_b = f64("lin.bias") if "lin.bias" in weights else torch.zeros(lin_w.shape[0], dtype=torch.float64)
+    return {"e": e, "heads": H, "inter": inter, "nlayers": nlayers, "word": word, "pos": f64("embeddings.position_embeddings.weight"),
+            "type": f64("embeddings.token_type_embeddings.weight"), "emb_g": f64("embeddings.LayerNorm.weight"),
+            "emb_b": f64("embeddings.LayerNorm.bias"), "layers": layers, "lin_w": lin_w, "lin_b": lin_b}
+
+
+class BertNodeEncoder(_PackedEncoder):
+    """Drop-in for the reference's ``PretrainedQAEAEncoder``: ``enc(input_ids, token_type_ids, attention_mask, get_token=False)``
+    -> ``[B, e]`` (``[B, nout]`` with a ``lin`` head) float32 on the device, the pooled ``last_hidden_state`` of a BERT encoder
+    without its pooling layer -- ``data['query'].feat`` / ``data['product'].feat`` of ``SessionEncoder``.  With
+    ``get_token=True`` it also returns ``last_hidden_state [B, T, e]``.
+
+    ``weights``: flat ``{name: tensor}`` under HF's own ``state_dict()`` names (``embeddings.word_embeddings.weight``,
+    ``embeddings.position_embeddings.weight``, ``embeddings.token_type_embeddings.weight``, ``embeddings.LayerNorm.*``,
+    ``encoder.layer.{l}.attention.self.query|key|value.*``, ``attention.output.dense|LayerNorm.*``, ``intermediate.dense.*``,
+    ``output.dense|LayerNorm.*``), optionally ``lin.weight`` / ``lin.bias``.  ``pool``: ``"masked"`` is the reference's
+    ``sum(token_emb * mask) / sum(mask)``, ``"mean"`` the plain ``mean(dim=1)`` of ``main2('QAEA')``.  ``hidden_act`` and
+    ``position_embedding_type`` are the config's, taken only to be refused when the kernels do not compute them.
+
+    ``dedup``: identical ``(ids, types, mask)`` rows are encoded once (host ``np.unique``) and scattered with
+    ``sss_gather_rows``; the result is bit-equal with it on and off.  The unique sequences are walked in chunks of whole
+    sequences of at most ``chunk_rows`` packed rows.  The default, 32768 rows, keeps the widest buffer (``rows x 3072`` floats
+    at bert-base) at 0.40 GB and the five row buffers together (``rows x 7680`` floats) at 1.0 GB; the result does not
+    depend on it.
+
+    Limits: ``e % 4 == 0``, ``e <= 1024``, head width ``e / num_heads <= 64``, ``T <= 64`` and ``<= max_position_embeddings``.
+    Not here: tokenisation, ELECTRA's ``embeddings_project``, relative position embeddings, a reduced-precision GEMM."""
+
+    def __init__(self, weights, num_heads, pool="masked", eps=1e-12, device=None, chunk_rows=32768, dedup=True, hidden_act="gelu",
+                 position_embedding_type="absolute"):
+        import torch
+        if pool not in BERT_POOLS:
+            raise ValueError(f"pool must be 'masked' or 'mean', got {pool!r}")
+        if hidden_act != "gelu":
+            raise ValueError(f"hidden_act must be 'gelu' (the exact erf GELU), got {hidden_act!r}")
+        if position_embedding_type not in (None, "absolute"):
+            raise ValueError(f"position embeddings must be absolute, got {position_embedding_type!r}")
+        if "embeddings_project.weight" in weights:
+            raise ValueError("an embeddings_project (ELECTRA with embedding_size != hidden_size) is not supported")
+        e = int(weights["embeddings.word_embeddings.weight"].shape[1])
+        if int(num_heads) < 1 or e % int(num_heads) or e % 4 or e > 1024 or e // int(num_heads) > 64:
+            raise ValueError(f"BertNodeEncoder needs e % 4 == 0, e <= 1024, e a multiple of num_heads and e / num_heads <= 64; "
+                             f"got e = {e}, num_heads = {num_heads}")
+        if int(chunk_rows) < MAX_LEN:
+            raise ValueError(f"chunk_rows must be at least {MAX_LEN} (one whole sequence), got {chunk_rows}")
+        if not float(eps) > 0.0:
+            raise ValueError(f"eps must be positive, got {eps}")
+        f = bert_fold_weights(weights, num_heads)
+        self.pool, self.chunk_rows, self.eps, self.dedup = pool, int(chunk_rows), float(eps), bool(dedup)
+        self.ninp, self.nhead, self.inter, self.nlayers = e, f["heads"], f["inter"], f["nlayers"]
+        self.n_word, self.n_pos, self.n_type = int(f["word"].shape[0]), int(f["pos"].shape[0]), int(f["type"].shape[0])
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        d = lambda t: t.to(device=self.device, dtype=torch.float32).contiguous()
+        self.word, self.pos, self.type, self.emb_g, self.emb_b = (d(f[n]) for n in ("word", "pos", "type", "emb_g", "emb_b"))
+        self.layers = [{n: d(v) for n, v in lay.items()} for lay in f["layers"]]
+        self.lin_w, self.lin_b = (None, None) if f["lin_w"] is None else (d(f["lin_w"]), d(f["lin_b"]))
+        self.nout = e if self.lin_w is None else int(self.lin_w.shape[0])
+
+    @classmethod
+    def from_transformers(cls, model, lin=None, **kw):
+        """From a live ``transformers.BertModel(config, add_pooling_layer=False)`` and, optionally, the ``nn.Linear`` head;
+        ``num_attention_heads``, ``layer_norm_eps``, ``hidden_act`` and the position embedding type are read from its config."""
+        cfg = model.config
+        w = {k: v for k, v in model.state_dict().items()}
+        if lin is not None:
+            w["lin.weight"] = lin.weight
+            if lin.bias is not None:
+                w["lin.bias"] = lin.bias
+        kw.setdefault("eps", cfg.layer_norm_eps)
+        return cls(w, cfg.num_attention_heads, hidden_act=cfg.hidden_act,
+                   position_embedding_type=getattr(cfg, "position_embedding_type", None), **kw)
+
+    def forward(self, input_ids, token_type_ids, attention_mask, get_token=False):
+        import torch
+        from . import _lib
+        ids, tt, am = _host(input_ids), _host(token_type_ids), _host(attention_mask)
+        if ids.ndim != 2 or tt.shape != ids.shape or am.shape != ids.shape:
+            raise ValueError(f"input_ids, token_type_ids and attention_mask must share one [B, T] shape; got {ids.shape}, {tt.shape}, {am.shape}")
+        B, T = ids.shape
+        if T > MAX_LEN or T > self.n_pos:
+            raise ValueError(f"T = {T} positions: at most {min(MAX_LEN, self.n_pos)} are supported (the attention kernel takes {MAX_LEN}, "
+                             f"the position table has {self.n_pos})")
+        am = (am != 0).astype(np.uint8)
+        inv = None
+        if self.dedup and B > 1:                                             # encode each distinct (ids, types, mask) row once
+            for a, hi, what in ((ids, self.n_word, "token id"), (tt, self.n_type, "token type")):     # before int32 can alias an id
+                if a.size and (not np.issubdtype(a.dtype, np.integer) or int(a.min()) < 0 or int(a.max()) >= hi):
+                    raise IndexError(f"{what} out of range [0, {hi}) (or not an integer)")
+            first, inverse = unique_rows(ids, tt, am)
+            if len(first) < B:
+                ids, tt, am, inv = ids[first], tt[first], am[first], inverse
+        packed = bert_pack_rows(ids, tt, am, self.pool, get_token, self.n_word, self.n_type)
+        rows = packed.rows
+        U, e, dev = len(rows.ptr) - 1, self.ninp, self.device
+        with torch.no_grad():
+            L, st = _lib.lib(), _lib.stream_ptr(dev)
+            K = self.layers[0]["in_w"].shape[1]
+            pooled = torch.zeros((U, K), dtype=torch.float32, device=dev)     # pad columns stay zero: the lin head's K operand
+            tokens = torch.empty((U * T, e), dtype=torch.float32, device=dev) if get_token else None
+            if U:
+                chunks = split_chunks(rows.ptr, self.chunk_rows)
+                cap = max(int(rows.ptr[s1] - rows.ptr[s0]) for s0, s1 in chunks)
+                buf = lambda width: torch.empty((cap, width), dtype=torch.float32, device=dev)
+                x, qkv, att, proj, hid = buf(K), buf(3 * e), buf(K), buf(e), buf(self.layers[0]["l1_w"].shape[0])
+                err = torch.zeros(1, dtype=torch.int32, device=dev)
+                up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                for s0, s1 in chunks:
+                    r0, r1 = int(rows.ptr[s0]), int(rows.ptr[s1])
+                    n = r1 - r0
+                    tok, pos, typ, key_ok, w = (up(a[r0:r1]) for a in (rows.tok, rows.pos, packed.tt, rows.key_ok, packed.w))
+                    ptr = up(rows.ptr[s0:s1 + 1] - np.int32(r0))
+                    rc = L.sss_bert_embed(self.word.data_ptr(), self.n_word, self.type.data_ptr(), self.n_type, self.pos.data_ptr(),
+                                          self.n_pos, tok.data_ptr(), typ.data_ptr(), pos.data_ptr(), self.emb_g.data_ptr(),
+                                          self.emb_b.data_ptr(), self.eps, n, e, x.data_ptr(), x.stride(0), err.data_ptr(), st)
+                    _lib.check(rc, "sss_bert_embed")
+                    self._run_layers(x, qkv, att, proj, hid, ptr, key_ok, n, s1 - s0, T, act=5)
+                    view = pooled[s0:s1]
+                    rc = L.sss_segment_reduce(x.data_ptr(), x.stride(0), w.data_ptr(), ptr.data_ptr(), s1 - s0, e, 1, view.data_ptr(),
+                                              pooled.stride(0), st)
+                    _lib.check(rc, "sss_segment_reduce")
+                    if get_token:                                            # every sequence kept all T rows
+                        tokens[s0 * T:s1 * T].copy_(x[:n, :e])
+                if int(err.item()):                                          # one read per call
+                    raise IndexError("a token id, token type or position was out of range on the device (sss_bert_embed wrote zero rows)")
+            if inv is not None:                                              # scatter the distinct rows back to the batch
+                d_inv = torch.from_numpy(inv).to(dev)
+                full = torch.zeros((B, K), dtype=torch.float32, device=dev)
+                _lib.check(L.sss_gather_rows(pooled.data_ptr(), d_inv.data_ptr(), B, K, full.data_ptr(), K, st), "sss_gather_rows")
+                pooled = full
+                if get_token:
+                    t_ids = torch.from_numpy((inv[:, None] * T + np.arange(T)[None, :]).reshape(-1)).to(dev)
+                    full_t = torch.empty((B * T, e), dtype=torch.float32, device=dev)
+                    _lib.check(L.sss_gather_rows(tokens.data_ptr(), t_ids.data_ptr(), B * T, e, full_t.data_ptr(), e, st), "sss_gather_rows")
+                    tokens = full_t
+            if self.lin_w is not None:
+                out = torch.empty((B, self.nout), dtype=torch.float32, device=dev)
+                if B:
+                    self._linear(pooled, self.lin_w, self.lin_b, out, B)
+            else:
+                out = pooled[:, :e] if K == e else pooled[:, :e].contiguous()
+        return (out, tokens.view(B, T, e)) if get_token else out
 
     __call__ = forward
