@@ -256,7 +256,7 @@ WIDE = (260, 800, 1600)                                                         
 
 
 def lanes_for(width):
-    """Lane-group size the launchers of csrc/gnn.hip pick for a row of `width` floats (for the case tables only)."""
+    """Lane-group size the launchers pick (csrc/lane_group.h: lanes_for) for a row of `width` floats (for the case tables only)."""
     l = 1
     while l < width // 4 and l < 64:
         l <<= 1

@@ -72,7 +72,7 @@ int oracle_search_fp32(const float* q, int64_t nq, const float* c, int64_t n, in
     return search_impl(q, nq, c, n, d, k, id_offset, D, I, threads, 1);
 }
 
-/* The gfx950 grouped GEMM's arithmetic (k_linear_grouped, gnn.hip), element by element:
+/* The gfx950 grouped GEMM's arithmetic (k_linear_grouped, linear.hip), element by element:
  * out[r][c] = fl(chain(r, c) + bias[c]) with chain one correctly rounded fmaf per k, starting from +0,
  * in the kernel's k order.  Per 32-wide K chunk k0 the kernel issues, for u = 0..3, four
  * v_mfma_f32_32x32x2_f32 steps (a.x, a.y, a.z, a.w); the lanes with h = 0 hold k0+8u+0..3 and the

@@ -224,6 +224,23 @@ class LinearProblem(ctypes.Structure):
                 ("ldy", c_int64), ("n", c_int64), ("m", c_int32), ("act", c_int32), ("post_scale", c_void_p), ("post_shift", c_void_p)]
 
 
+def linear_problem(x, w, bias, y, n, m, act=0, post=None, ids=None, table=None, xcopy=None):
+    """One problem of ``sss_linear_grouped``: ``y[:n, :m] = act(x w^T + bias)`` on 2-D device tensors (row strides are taken
+    from them), ``post = (scale, shift)`` the second epilogue stage.  Gather mode: ``x = None``, ``ids`` / ``table`` the
+    rows' source and ``xcopy`` (optional) where the gathered rows are also written."""
+    ptr = lambda t: 0 if t is None else t.data_ptr()
+    ld = lambda t: 0 if t is None else t.stride(0)
+    return LinearProblem(x=ptr(x), ldx=ld(x), ids=ptr(ids), table=ptr(table), xcopy=ptr(xcopy), ld_xcopy=ld(xcopy),
+                         w=w.data_ptr(), ldw=w.stride(0), bias=ptr(bias), y=y.data_ptr(), ldy=y.stride(0), n=n, m=m, act=act,
+                         post_scale=0 if post is None else post[0].data_ptr(),
+                         post_shift=0 if post is None else post[1].data_ptr())
+
+
+def pad32(n):
+    """``n`` rounded up to the multiple of 32 that the GEMM's K has to be."""
+    return (n + 31) // 32 * 32
+
+
 class GraphOut(ctypes.Structure):
     """``sss_graph_out`` of include/sss.h."""
     _fields_ = [(n, c_void_p) for n in ("q_x", "q_batch", "q_pos", "p_x", "p_batch", "p_cnt", "rowptr_qp", "col_qp",

@@ -3,9 +3,9 @@
 //   k_bert_embed      x = LayerNorm((word[tok] + type[tt]) + pos[p]) * gamma + beta, pad columns zeroed
 // One wave per row, four rows per workgroup, a lane holds the float4 columns lane, lane + 64, ... -- the lane map of
 // k_add_layernorm (text.hip), with which it shares the row statistics and the store (layernorm_dev.h).  The rest of a BERT
-// layer is k_linear_grouped (gnn.hip; act = 5 is the exact GELU), k_seq_attention and k_add_layernorm (text.hip).
+// layer is k_linear_grouped (linear.hip; act = 5 is the exact GELU), k_seq_attention and k_add_layernorm (text.hip).
+#include "lane_group.h"
 #include "layernorm_dev.h"
-#include "sss_common.h"
 #include "../../include/sss_bert.h"
 
 namespace sss {
@@ -57,7 +57,7 @@ extern "C" int sss_bert_embed(const float* word, int64_t n_word, const float* ty
         set_error("bert_embed: need non-null 16-byte aligned word / type / pos / gamma / beta / x and non-null tok / tt / p / err");
         return SSS_EINVAL;
     }
-    hipLaunchKernelGGL(k_bert_embed, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, word, (long)n_word, type, (long)n_type, pos,
+    hipLaunchKernelGGL(k_bert_embed, dim3(grid_blocks(n, 4, GRID_ALL)), dim3(256), 0, st, word, (long)n_word, type, (long)n_type, pos,
                        (long)n_pos, reinterpret_cast<const long*>(tok), tt, p, gamma, beta, eps, (long)n, e, x, (long)ld_x, err);
     return check_launch("k_bert_embed");
 }

@@ -27,7 +27,6 @@
 // session without clicks), 0.0 elsewhere -- data['product'].last_click_mask of :203-216 -- and last_node int32 [S],
 // that node's batch-global id.
 #include "sss_common.h"
-#include "kargs.h"
 
 namespace sss {
 
@@ -160,7 +159,7 @@ template <bool IQ>
 __global__ __launch_bounds__(256) void k_session_fill(const long* __restrict__ sess_ptr,
                                                       const unsigned char* __restrict__ is_search,
                                                       const long* __restrict__ item_id, const long* __restrict__ query_tok,
-                                                      long S, const int* __restrict__ bases, const GraphOut O,
+                                                      long S, const int* __restrict__ bases, const sss_graph_out O,
                                                       float* __restrict__ last_click_mask, int* __restrict__ last_node) {
     const long s = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int t = threadIdx.x & 63;
@@ -265,7 +264,7 @@ static int graph_counts(const long* sess_ptr, const unsigned char* is_search, co
 
 // last_click_mask [Np] / last_node [S]: optional (NULL = not written); query_tok is not read under ignore_query
 static int graph_fill(const long* sess_ptr, const unsigned char* is_search, const long* item_id, const long* query_tok, long S,
-                      bool ignore_query, const int* bases, const GraphOut& out, float* last_click_mask, int* last_node, hipStream_t st) {
+                      bool ignore_query, const int* bases, const sss_graph_out& out, float* last_click_mask, int* last_node, hipStream_t st) {
     if (S <= 0) { set_error("graph_fill: need at least one session"); return SSS_EINVAL; }
     const unsigned nb = (unsigned)((S * 64 + 255) / 256);
     if (ignore_query)
@@ -277,15 +276,6 @@ static int graph_fill(const long* sess_ptr, const unsigned char* is_search, cons
     return check_launch("k_session_fill");
 }
 
-static GraphOut graph_out(const sss_graph_out* o) {
-    GraphOut g;
-    g.q_x = o->q_x; g.q_batch = o->q_batch; g.q_pos = o->q_pos;
-    g.p_x = o->p_x; g.p_batch = o->p_batch; g.p_cnt = o->p_cnt;
-    g.rowptr_qp = o->rowptr_qp; g.col_qp = o->col_qp; g.rowptr_pq = o->rowptr_pq; g.col_pq = o->col_pq;
-    g.rowptr_pp = o->rowptr_pp; g.col_pp = o->col_pp; g.w_pp = o->w_pp; g.src_row = o->src_row; g.pos_id = o->pos_id;
-    return g;
-}
-
 extern "C" int sss_graph_counts(const int64_t* sess_ptr, const uint8_t* is_search, const int64_t* item_id, int64_t n_sessions, int32_t* bases,
                                 int32_t* scratch, int32_t* err, void* stream) {
     return graph_counts(sess_ptr, is_search, item_id, n_sessions, false, bases, scratch, err, static_cast<hipStream_t>(stream));
@@ -294,7 +284,7 @@ extern "C" int sss_graph_counts(const int64_t* sess_ptr, const uint8_t* is_searc
 extern "C" int sss_graph_fill(const int64_t* sess_ptr, const uint8_t* is_search, const int64_t* item_id, const int64_t* query_tok,
                               int64_t n_sessions, const int32_t* bases, const sss_graph_out* out, void* stream) {
     if (!out) { set_error("graph_fill: null outputs"); return SSS_EINVAL; }
-    return graph_fill(sess_ptr, is_search, item_id, query_tok, n_sessions, false, bases, graph_out(out), nullptr, nullptr,
+    return graph_fill(sess_ptr, is_search, item_id, query_tok, n_sessions, false, bases, *out, nullptr, nullptr,
                       static_cast<hipStream_t>(stream));
 }
 
@@ -315,7 +305,7 @@ extern "C" int sss_graph_fill_ex(const int64_t* sess_ptr, const uint8_t* is_sear
     if (flags & ~SSS_GRAPH_IGNORE_QUERY) { set_error("graph_fill_ex: unknown flags 0x%x", flags); return SSS_EINVAL; }
     if (n_sessions <= 0) { set_error("graph_fill_ex: need at least one session"); return SSS_EINVAL; }
     if (!sess_ptr || !bases || !out) { set_error("graph_fill_ex: null sess_ptr / bases / outputs"); return SSS_EINVAL; }
-    return graph_fill(sess_ptr, is_search, item_id, query_tok, n_sessions, (flags & SSS_GRAPH_IGNORE_QUERY) != 0, bases, graph_out(out),
+    return graph_fill(sess_ptr, is_search, item_id, query_tok, n_sessions, (flags & SSS_GRAPH_IGNORE_QUERY) != 0, bases, *out,
                       last_click_mask, last_node, static_cast<hipStream_t>(stream));
 }
 

@@ -11,7 +11,7 @@
 // and the k | v pair in flight is the register bound behind heads * D <= 2048.
 #include <math.h>
 
-#include "sss_common.h"
+#include "lane_group.h"
 #include "../../include/sss_hgt.h"
 
 namespace sss {
@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void k_hgt_aggregate(const sss_hgt_args A) {
 #pragma unroll
             for (int o = 32; o >= LPR; o >>= 1) cmax = max(cmax, __shfl_xor(cmax, o));
         }
-        // one pass (online softmax, the idiom of gat_row in gnn.hip): a new maximum rescales what has been summed so
+        // one pass (online softmax, the idiom of gat_row in gnn_fused.hip): a new maximum rescales what has been summed so
         // far, so every edge's index and k | v row are loaded exactly once
         float mx = -INFINITY, den = 0.f;
         float4 acc[NCH];
@@ -112,11 +112,9 @@ __global__ __launch_bounds__(256) void k_hgt_skip(float* __restrict__ y, long ld
     }
 }
 
-static bool aligned16(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static bool ok_ld(int64_t ld, int width) { return ld % 4 == 0 && ld >= width; }
-
+// one lane group per target, no grid-stride: every target gets its group
 #define SSS_HGT_LAUNCH(L, N) \
-    hipLaunchKernelGGL((k_hgt_aggregate<L, N>), dim3((unsigned)((a.n_dst + 256 / L - 1) / (256 / L))), dim3(256), 0, st, a)
+    hipLaunchKernelGGL((k_hgt_aggregate<L, N>), dim3(grid_blocks(a.n_dst, 256 / L, GRID_ALL)), dim3(256), 0, st, a)
 
 extern "C" int sss_hgt_aggregate(const sss_hgt_args* args, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -128,7 +126,7 @@ extern "C" int sss_hgt_aggregate(const sss_hgt_args* args, void* stream) {
         set_error("hgt_aggregate: need head_dim %% 4 == 0 and heads * head_dim <= 2048, got %d x %d", a.heads, a.head_dim);
         return SSS_EINVAL;
     }
-    if (a.n_dst < 0 || a.n_dst >= (1ll << 31)) { set_error("hgt_aggregate: need 0 <= n_dst < 2^31"); return SSS_EINVAL; }
+    if (!ok_count(a.n_dst)) { set_error("hgt_aggregate: need 0 <= n_dst < 2^31"); return SSS_EINVAL; }
     if (a.n_dst == 0) return SSS_OK;
     const int width = a.heads * a.head_dim;
     bool ok = aligned16(a.q) && aligned16(a.out) && ok_ld(a.ld_q, width) && ok_ld(a.ld_out, width);
@@ -137,20 +135,10 @@ extern "C" int sss_hgt_aggregate(const sss_hgt_args* args, void* stream) {
         ok = ok && aligned16(s.k) && aligned16(s.v) && s.rowptr && s.col && ok_ld(s.ld_k, width) && ok_ld(s.ld_v, width);
     }
     if (!ok) { set_error("hgt_aggregate: need non-null 16-byte aligned q / k / v / out, non-null rowptr / col, leading dimensions %% 4 == 0 and >= heads * head_dim"); return SSS_EINVAL; }
-    int lpr = 1;
-    while (lpr < width / 4 && lpr < 64) lpr <<= 1;
+    const int lpr = lanes_for(width);
     const int lh = lpr / a.heads;                            // >= 1: width / 4 >= heads
     const int steps = (a.head_dim / 4 + lh - 1) / lh;        // float4 columns per lane: 1 below 64 lanes, <= 8 at 64
-    if (lpr < 64) {
-        switch (lpr) {
-            case 1: SSS_HGT_LAUNCH(1, 1); break;
-            case 2: SSS_HGT_LAUNCH(2, 1); break;
-            case 4: SSS_HGT_LAUNCH(4, 1); break;
-            case 8: SSS_HGT_LAUNCH(8, 1); break;
-            case 16: SSS_HGT_LAUNCH(16, 1); break;
-            default: SSS_HGT_LAUNCH(32, 1); break;
-        }
-    } else if (steps <= 1) SSS_HGT_LAUNCH(64, 1);
+    if (lpr < 64 || steps <= 1) { SSS_LPR_SWITCH(lpr, SSS_HGT_LAUNCH(L, 1)); }
     else if (steps <= 2) SSS_HGT_LAUNCH(64, 2);
     else if (steps <= 4) SSS_HGT_LAUNCH(64, 4);
     else SSS_HGT_LAUNCH(64, 8);
@@ -160,15 +148,13 @@ extern "C" int sss_hgt_aggregate(const sss_hgt_args* args, void* stream) {
 
 extern "C" int sss_hgt_skip(float* y, int64_t ld_y, const float* x, int64_t ld_x, float beta, int64_t n, int h, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (h <= 0 || h % 4 || n < 0 || n >= (1ll << 31)) { set_error("hgt_skip: need h %% 4 == 0 and 0 <= n < 2^31"); return SSS_EINVAL; }
+    if (h <= 0 || h % 4 || !ok_count(n)) { set_error("hgt_skip: need h %% 4 == 0 and 0 <= n < 2^31"); return SSS_EINVAL; }
     if (n == 0) return SSS_OK;
     if (!aligned16(y) || !aligned16(x) || !ok_ld(ld_y, h) || !ok_ld(ld_x, h)) {
         set_error("hgt_skip: need non-null 16-byte aligned y / x, leading dimensions %% 4 == 0 and >= h");
         return SSS_EINVAL;
     }
-    const long blocks = (n * (h / 4) + 255) / 256;
-    hipLaunchKernelGGL(k_hgt_skip, dim3((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(256), 0, st, y, ld_y, x, ld_x, beta,
-                       (long)n, h / 4);
+    hipLaunchKernelGGL(k_hgt_skip, dim3(grid_blocks(n * (h / 4), 256, 1 << 20)), dim3(256), 0, st, y, ld_y, x, ld_x, beta, (long)n, h / 4);
     return check_launch("k_hgt_skip");
 }
 

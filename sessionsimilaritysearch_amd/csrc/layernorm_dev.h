@@ -38,9 +38,4 @@ __device__ __forceinline__ void ln_row_store(float4 (&v)[4], float sum, const fl
     for (int c = e + lane * 4; c < ld_y; c += 256) *reinterpret_cast<float4*>(yrow + c) = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// the argument checks the row kernels share
-static inline bool aligned16(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static inline bool ok_ld(int64_t ld, int width) { return ld % 4 == 0 && ld >= width; }
-static inline bool ok_count(int64_t n) { return n >= 0 && n < (1ll << 31); }
-
 }  // namespace sss

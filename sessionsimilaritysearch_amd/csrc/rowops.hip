@@ -6,15 +6,9 @@
 // Each row is owned by a group of LPR lanes that move 16 bytes per lane per access (coalesced
 // 16 B x LPR segments); reductions are butterflies inside the lane group.
 #include "elem.h"
+#include "lane_group.h"
 
 namespace sss {
-
-template <int LPR, typename T>
-__device__ __forceinline__ T group_sum(T v) {
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 template <int LPR>
 __global__ __launch_bounds__(256) void k_normalize_rows(float* __restrict__ x, long n, int d, long ld,
@@ -322,29 +316,8 @@ __global__ __launch_bounds__(256) void k_gather_concat_rows(const float* __restr
     }
 }
 
-static int lanes_per_row(int d) {
-    const int nv = d / 4;
-    int l = 1;
-    while (l < nv && l < 64) l <<= 1;
-    return l;
-}
-static unsigned grid_for(long n, int lpr) {
-    const long rpb = 256 / lpr;
-    long g = (n + rpb - 1) / rpb;
-    if (g > 256 * 8) g = 256 * 8;   // ~8 blocks per CU, grid-stride the rest
-    return (unsigned)(g < 1 ? 1 : g);
-}
-
-#define SSS_DISPATCH_LPR(lpr, CALL) \
-    switch (lpr) {                  \
-        case 1: { constexpr int L = 1; CALL; } break;   \
-        case 2: { constexpr int L = 2; CALL; } break;   \
-        case 4: { constexpr int L = 4; CALL; } break;   \
-        case 8: { constexpr int L = 8; CALL; } break;   \
-        case 16: { constexpr int L = 16; CALL; } break; \
-        case 32: { constexpr int L = 32; CALL; } break; \
-        default: { constexpr int L = 64; CALL; } break; \
-    }
+// the lane-group kernels here grid-stride over their rows: ~8 workgroups per CU
+constexpr long GRID_CAP = 256 * 8;
 
 extern "C" int sss_normalize_rows(float* x, int64_t n, int d, int64_t ld, float eps, int rule, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -353,8 +326,8 @@ extern "C" int sss_normalize_rows(float* x, int64_t n, int d, int64_t ld, float 
         return SSS_EINVAL;
     }
     if (n == 0) return SSS_OK;
-    const int lpr = lanes_per_row(d);
-    SSS_DISPATCH_LPR(lpr, hipLaunchKernelGGL(k_normalize_rows<L>, dim3(grid_for(n, L)), dim3(256), 0, st, x, n, d, ld, eps, rule));
+    const int lpr = lanes_for(d);
+    SSS_LPR_SWITCH(lpr, hipLaunchKernelGGL(k_normalize_rows<L>, dim3(grid_blocks(n, 256 / L, GRID_CAP)), dim3(256), 0, st, x, n, d, ld, eps, rule));
     return check_launch("k_normalize_rows");
 }
 
@@ -368,9 +341,9 @@ extern "C" int sss_row_norm_max(const void* x, int64_t n, int d, int dtype, floa
     with_dtype(dtype, [&](auto dt) {
         constexpr int DT = decltype(dt)::value;
         if constexpr (DT == DT_F32) {
-            SSS_DISPATCH_LPR(lanes_per_row(d), hipLaunchKernelGGL((k_row_norm_max<DT, L>), dim3(grid_for(n, L)), dim3(256), 0, st, x, n, d, out));
+            SSS_LPR_SWITCH(lanes_for(d), hipLaunchKernelGGL((k_row_norm_max<DT, L>), dim3(grid_blocks(n, 256 / L, GRID_CAP)), dim3(256), 0, st, x, n, d, out));
         } else {
-            hipLaunchKernelGGL((k_row_norm_max<DT, 64>), dim3(grid_for(n, 64)), dim3(256), 0, st, x, n, d, out);
+            hipLaunchKernelGGL((k_row_norm_max<DT, 64>), dim3(grid_blocks(n, 256 / 64, GRID_CAP)), dim3(256), 0, st, x, n, d, out);
         }
     });
     return check_launch("k_row_norm_max");
@@ -380,9 +353,7 @@ extern "C" int sss_f32_to_bf16(const float* x, int64_t count, uint16_t* y, void*
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (count < 0 || count % 8) { set_error("f32_to_bf16: element count must be a multiple of 8"); return SSS_EINVAL; }
     if (count == 0) return SSS_OK;
-    long blocks = (count / 8 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)blocks), dim3(256), 0, st, x, count / 8, y);
+    hipLaunchKernelGGL(k_f32_to_bf16, dim3(grid_blocks(count / 8, 256, 4096)), dim3(256), 0, st, x, count / 8, y);
     return check_launch("k_f32_to_bf16");
 }
 
@@ -390,9 +361,7 @@ extern "C" int sss_split_bf16(const float* x, int64_t n, int d, uint16_t* y, voi
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n < 0 || d <= 0 || d % 8) { set_error("split_bf16: need n >= 0, d %% 8 == 0"); return SSS_EINVAL; }
     if (n == 0) return SSS_OK;
-    long blocks = (n * (d / 8) + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_split_bf16, dim3((unsigned)blocks), dim3(256), 0, st, x, n, d / 8, y);
+    hipLaunchKernelGGL(k_split_bf16, dim3(grid_blocks(n * (d / 8), 256, 8192)), dim3(256), 0, st, x, n, d / 8, y);
     return check_launch("k_split_bf16");
 }
 
@@ -400,9 +369,7 @@ extern "C" int sss_abs_max(const float* x, int64_t count, float* out, void* stre
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (count < 0 || count % 4) { set_error("abs_max: element count must be a multiple of 4"); return SSS_EINVAL; }
     if (count == 0) return SSS_OK;
-    long blocks = (count / 4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_abs_max, dim3((unsigned)blocks), dim3(256), 0, st, x, count / 4, out);
+    hipLaunchKernelGGL(k_abs_max, dim3(grid_blocks(count / 4, 256, 4096)), dim3(256), 0, st, x, count / 4, out);
     return check_launch("k_abs_max");
 }
 
@@ -411,9 +378,7 @@ extern "C" int sss_scale_f16(const float* x, int64_t count, int shift, uint16_t*
     if (count < 0 || count % 8) { set_error("scale_f16: element count must be a multiple of 8"); return SSS_EINVAL; }
     if (shift < -160 || shift > 160) { set_error("scale_f16: shift out of range"); return SSS_EINVAL; }
     if (count == 0) return SSS_OK;
-    long blocks = (count / 8 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_scale_f16, dim3((unsigned)blocks), dim3(256), 0, st, x, count / 8, shift, y);
+    hipLaunchKernelGGL(k_scale_f16, dim3(grid_blocks(count / 8, 256, 8192)), dim3(256), 0, st, x, count / 8, shift, y);
     return check_launch("k_scale_f16");
 }
 
@@ -421,9 +386,7 @@ extern "C" int sss_f16_resid_max(const float* x, const uint16_t* y, int64_t n, i
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n < 0 || d <= 0 || shift < -160 || shift > 160) { set_error("f16_resid_max: bad arguments"); return SSS_EINVAL; }
     if (n == 0) return SSS_OK;
-    long blocks = (n + 3) / 4;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(k_f16_resid_max, dim3((unsigned)blocks), dim3(256), 0, st, x, reinterpret_cast<const _Float16*>(y), n,
+    hipLaunchKernelGGL(k_f16_resid_max, dim3(grid_blocks(n, 4, 16384)), dim3(256), 0, st, x, reinterpret_cast<const _Float16*>(y), n,
                        d, shift, out);
     return check_launch("k_f16_resid_max");
 }
@@ -434,17 +397,13 @@ static int check_pad_rows(const char* what, const void* x, const void* y, long n
         set_error("%s: need n >= 0, 0 < d <= ds, d %% 4 == 0, ds %% 8 == 0 (d %d, ds %d)", what, d, ds);
         return SSS_EINVAL;
     }
-    if (n > 0 && (!x || !y || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y) & 15))) {
+    if (n > 0 && (!aligned16(x) || !aligned16(y))) {
         set_error("%s: rows and output are required, 16-byte aligned", what);
         return SSS_EINVAL;
     }
     return SSS_OK;
 }
-static unsigned pad_grid(long chunks) {
-    long blocks = (chunks + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    return (unsigned)blocks;
-}
+static unsigned pad_grid(long chunks) { return grid_blocks(chunks, 256, 8192); }
 
 extern "C" int sss_pad_rows_f32(const float* x, int64_t n, int d, int ds, float* y, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -478,9 +437,7 @@ extern "C" int sss_pad_f16_resid_max(const float* x, const uint16_t* y, int64_t 
     if (rc) return rc;
     if (shift < -160 || shift > 160 || (n > 0 && !out)) { set_error("pad_f16_resid_max: shift out of range or no output"); return SSS_EINVAL; }
     if (n == 0) return SSS_OK;
-    long blocks = (n + 15) / 16;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(k_pad_f16_resid_max, dim3((unsigned)blocks), dim3(256), 0, st, x, reinterpret_cast<const _Float16*>(y), n, d / 4,
+    hipLaunchKernelGGL(k_pad_f16_resid_max, dim3(grid_blocks(n, 16, 16384)), dim3(256), 0, st, x, reinterpret_cast<const _Float16*>(y), n, d / 4,
                        ds / 8, shift, out);
     return check_launch("k_pad_f16_resid_max");
 }
@@ -489,7 +446,7 @@ extern "C" int sss_l2_row_bias(const float* corpus, int64_t n, int d, float* bia
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n < 0 || d <= 0 || d % 4 || (n > 0 && (!corpus || !bias))) { set_error("l2_row_bias: need n >= 0, d %% 4 == 0, rows and bias"); return SSS_EINVAL; }
     if (n == 0) return SSS_OK;
-    hipLaunchKernelGGL(k_row_bias, dim3(grid_for(n, 4)), dim3(256), 0, st, corpus, n, d, bias);
+    hipLaunchKernelGGL(k_row_bias, dim3(grid_blocks(n, 256 / 4, GRID_CAP)), dim3(256), 0, st, corpus, n, d, bias);
     return check_launch("k_row_bias");
 }
 
@@ -500,8 +457,8 @@ extern "C" int sss_gather_rows(const float* table, const int64_t* ids, int64_t n
         return SSS_EINVAL;
     }
     if (n == 0) return SSS_OK;
-    const int lpr = lanes_per_row(d);
-    SSS_DISPATCH_LPR(lpr, hipLaunchKernelGGL(k_gather_rows<L>, dim3(grid_for(n, L)), dim3(256), 0, st, table, ids, n, d, out, ld_out));
+    const int lpr = lanes_for(d);
+    SSS_LPR_SWITCH(lpr, hipLaunchKernelGGL(k_gather_rows<L>, dim3(grid_blocks(n, 256 / L, GRID_CAP)), dim3(256), 0, st, table, ids, n, d, out, ld_out));
     return check_launch("k_gather_rows");
 }
 
@@ -514,8 +471,8 @@ extern "C" int sss_gather_concat_rows(const float* table, const int64_t* ids, in
         return SSS_EINVAL;
     }
     if (n == 0) return SSS_OK;
-    const int lpr = lanes_per_row(d_id + d_feat + d_pad);
-    SSS_DISPATCH_LPR(lpr, hipLaunchKernelGGL(k_gather_concat_rows<L>, dim3(grid_for(n, L)), dim3(256), 0, st, table, ids, d_id, feat,
+    const int lpr = lanes_for(d_id + d_feat + d_pad);
+    SSS_LPR_SWITCH(lpr, hipLaunchKernelGGL(k_gather_concat_rows<L>, dim3(grid_blocks(n, 256 / L, GRID_CAP)), dim3(256), 0, st, table, ids, d_id, feat,
                                              ld_feat, d_feat, d_pad, n, out, ld_out));
     return check_launch("k_gather_concat_rows");
 }

@@ -1,6 +1,6 @@
 // The row kernels of the query text encoder (gfx950; include/sss_text.h states each computation, DESIGN.md section 5.9
 // derives them from the reference's NodeTextTransformer, model/NodeEmbedding.py:62-98) on packed token rows.  The GEMMs of
-// a layer are k_linear_grouped (gnn.hip); these three are what is left between them:
+// a layer are k_linear_grouped (linear.hip); these three are what is left between them:
 //   k_text_embed      x = table[tok] * sqrt(e) + pe[pos], two roundings, pad columns zeroed
 //   k_seq_attention   multi-head softmax attention inside each packed sequence of at most 64 rows
 //   k_add_layernorm   y = LayerNorm(x + res) * gamma + beta, two-pass variance, in place allowed
@@ -13,8 +13,8 @@
 // softmax, the idiom of k_hgt_aggregate).  At T = 20 a wave has 20 of 64 lanes at work; see DESIGN.md 5.9.
 #include <math.h>
 
+#include "lane_group.h"
 #include "layernorm_dev.h"
-#include "sss_common.h"
 #include "../../include/sss_text.h"
 
 namespace sss {
@@ -153,8 +153,6 @@ __global__ __launch_bounds__(256) void k_add_layernorm(const float* x, long ld_x
     ln_row_store(v, sum, gamma, beta, eps, e, lane, y + r * ld_y, ld_y);   // layernorm_dev.h: shared with k_bert_embed
 }
 
-static unsigned capped_grid(long blocks) { return (unsigned)(blocks < (1 << 20) ? blocks : (1 << 20)); }
-
 extern "C" int sss_text_embed(const float* table, int64_t n_token, const float* pe, int64_t n_pos, const int64_t* tok,
                               const int32_t* pos, int64_t n, int e, float scale, float* x, int64_t ld_x, int32_t* err, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -165,7 +163,7 @@ extern "C" int sss_text_embed(const float* table, int64_t n_token, const float* 
         set_error("text_embed: need non-null 16-byte aligned table / pe / x and non-null tok / pos / err");
         return SSS_EINVAL;
     }
-    hipLaunchKernelGGL(k_text_embed, dim3(capped_grid((n * (ld_x / 4) + 255) / 256)), dim3(256), 0, st, table, (long)n_token, pe,
+    hipLaunchKernelGGL(k_text_embed, dim3(grid_blocks(n * (ld_x / 4), 256, 1 << 20)), dim3(256), 0, st, table, (long)n_token, pe,
                        (long)n_pos, reinterpret_cast<const long*>(tok), pos, (long)n, e, scale, x, (long)ld_x, err);
     return check_launch("k_text_embed");
 }
@@ -213,7 +211,7 @@ extern "C" int sss_add_layernorm(const float* x, int64_t ld_x, const float* res,
         return SSS_EINVAL;
     }
     if (y == x && ld_y != ld_x) { set_error("add_layernorm: in place (y == x) needs ld_y == ld_x"); return SSS_EINVAL; }
-    hipLaunchKernelGGL(k_add_layernorm, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, x, (long)ld_x, res, (long)ld_res, gamma, beta, eps,
+    hipLaunchKernelGGL(k_add_layernorm, dim3(grid_blocks(n, 4, GRID_ALL)), dim3(256), 0, st, x, (long)ld_x, res, (long)ld_res, gamma, beta, eps,
                        (long)n, e, y, (long)ld_y);
     return check_launch("k_add_layernorm");
 }

@@ -9,7 +9,7 @@
 //                          last_click_mask product of SRGNN_Pooling, model/gnn.py:172)
 //   k_attention_dot_pool<- AttentionPooling (model/gnn.py:145-161): att_i = <x_i, mean_g>, as a
 //                          row-wise dot instead of the reference's dense [n_nodes, n_graphs] matrix
-#include "sss_common.h"
+#include "lane_group.h"
 
 namespace sss {
 
@@ -97,8 +97,7 @@ __global__ __launch_bounds__(256) void k_attention_dot_pool(const float* __restr
             if (in_g && t < cnt && c4 < d) v[j] = *reinterpret_cast<const float4*>(x + (long)(r0 + t) * ld_x + c4);
             part += v[j].x * m[j].x + v[j].y * m[j].y + v[j].z * m[j].z + v[j].w * m[j].w;
         }
-#pragma unroll
-        for (int o = LPR / 2; o > 0; o >>= 1) part += __shfl_xor(part, o);
+        part = group_sum<LPR>(part);
 #pragma unroll
         for (int j = 0; j < NCH; ++j) { acc[j].x += part * v[j].x; acc[j].y += part * v[j].y; acc[j].z += part * v[j].z; acc[j].w += part * v[j].w; }
     }
@@ -110,33 +109,15 @@ __global__ __launch_bounds__(256) void k_attention_dot_pool(const float* __restr
     }
 }
 
-static int lanes4(int d) {
-    const int nv = d / 4;
-    int l = 1;
-    while (l < nv && l < 64) l <<= 1;
-    return l;
-}
-#define SSS_LPRV(lpr, CALL)                             \
-    switch (lpr) {                                      \
-        case 1: { constexpr int L = 1; CALL; } break;   \
-        case 2: { constexpr int L = 2; CALL; } break;   \
-        case 4: { constexpr int L = 4; CALL; } break;   \
-        case 8: { constexpr int L = 8; CALL; } break;   \
-        case 16: { constexpr int L = 16; CALL; } break; \
-        case 32: { constexpr int L = 32; CALL; } break; \
-        default: { constexpr int L = 64; CALL; } break; \
-    }
 constexpr int MAX_WIDTH = 2048;     // 8 column chunks of 64 lanes x 4 floats (k_attention_dot_pool keeps them in registers)
-static bool ok_rows(int d, long a, long b) { return d > 0 && d % 4 == 0 && d <= MAX_WIDTH && a % 4 == 0 && b % 4 == 0 && a >= d && b >= d; }
+static bool ok_rows(int d, long a, long b) { return d > 0 && d % 4 == 0 && d <= MAX_WIDTH && ok_ld(a, d) && ok_ld(b, d); }
 
 extern "C" int sss_csr_mean(const float* x, int64_t ld_x, const int32_t* rowptr, const int32_t* col, int64_t n_dst, int d, float* out,
                             int64_t ld_out, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_dst < 0 || !ok_rows(d, ld_x, ld_out)) { set_error("csr_mean: need d %% 4 == 0, d <= 2048, 16-byte aligned row strides"); return SSS_EINVAL; }
     if (n_dst == 0) return SSS_OK;
-    const int lpr = lanes4(d);
-    const long per = 256 / lpr;
-    SSS_LPRV(lpr, hipLaunchKernelGGL(k_csr_mean<L>, dim3((unsigned)((n_dst + per - 1) / per)), dim3(256), 0, st, x, ld_x, rowptr, col, n_dst, d, out, ld_out));
+    SSS_LPR_SWITCH(lanes_for(d), hipLaunchKernelGGL(k_csr_mean<L>, dim3(grid_blocks(n_dst, 256 / L, GRID_ALL)), dim3(256), 0, st, x, ld_x, rowptr, col, n_dst, d, out, ld_out));
     return check_launch("k_csr_mean");
 }
 extern "C" int sss_segment_reduce(const float* x, int64_t ld_x, const float* w, const int32_t* ptr, int64_t n_graphs, int d, int mode,
@@ -144,9 +125,7 @@ extern "C" int sss_segment_reduce(const float* x, int64_t ld_x, const float* w, 
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_graphs < 0 || mode < 0 || mode > 2 || !ok_rows(d, ld_x, ld_out)) { set_error("segment_reduce: need mode in {0,1,2}, d %% 4 == 0, d <= 2048"); return SSS_EINVAL; }
     if (n_graphs == 0) return SSS_OK;
-    const int lpr = lanes4(d);
-    const long per = 256 / lpr;
-    SSS_LPRV(lpr, hipLaunchKernelGGL(k_segment_reduce<L>, dim3((unsigned)((n_graphs + per - 1) / per)), dim3(256), 0, st, x, ld_x, w, ptr, n_graphs, d, mode, out, ld_out));
+    SSS_LPR_SWITCH(lanes_for(d), hipLaunchKernelGGL(k_segment_reduce<L>, dim3(grid_blocks(n_graphs, 256 / L, GRID_ALL)), dim3(256), 0, st, x, ld_x, w, ptr, n_graphs, d, mode, out, ld_out));
     return check_launch("k_segment_reduce");
 }
 extern "C" int sss_attention_dot_pool(const float* x, int64_t ld_x, const int32_t* ptr, int64_t n_graphs, int d, float* out,
@@ -154,12 +133,10 @@ extern "C" int sss_attention_dot_pool(const float* x, int64_t ld_x, const int32_
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_graphs < 0 || !ok_rows(d, ld_x, ld_out)) { set_error("attention_dot_pool: need d %% 4 == 0, d <= 2048"); return SSS_EINVAL; }
     if (n_graphs == 0) return SSS_OK;
-    const int lpr = lanes4(d);
-    const long per = 256 / lpr;
     if (d <= 256) {
-        SSS_LPRV(lpr, hipLaunchKernelGGL((k_attention_dot_pool<L, 1>), dim3((unsigned)((n_graphs + per - 1) / per)), dim3(256), 0, st, x, ld_x, ptr, n_graphs, d, out, ld_out));
+        SSS_LPR_SWITCH(lanes_for(d), hipLaunchKernelGGL((k_attention_dot_pool<L, 1>), dim3(grid_blocks(n_graphs, 256 / L, GRID_ALL)), dim3(256), 0, st, x, ld_x, ptr, n_graphs, d, out, ld_out));
     } else {
-        hipLaunchKernelGGL((k_attention_dot_pool<64, 8>), dim3((unsigned)((n_graphs + 3) / 4)), dim3(256), 0, st, x, ld_x, ptr, n_graphs, d, out, ld_out);
+        hipLaunchKernelGGL((k_attention_dot_pool<64, 8>), dim3(grid_blocks(n_graphs, 4, GRID_ALL)), dim3(256), 0, st, x, ld_x, ptr, n_graphs, d, out, ld_out);
     }
     return check_launch("k_attention_dot_pool");
 }

@@ -532,12 +532,8 @@ class SessionEncoder:
             else:
                 Yp = torch.empty((ni, 7 * h + ALPHA_PAD), dtype=torch.float32, device=self.device)
                 Yq = torch.empty((nqy, h + ALPHA_PAD), dtype=torch.float32, device=self.device)
-                P_ = _lib.LinearProblem
-                mk = lambda x, w, b, y, n, m: P_(x=x.data_ptr(), ldx=x.stride(0), ids=0, table=0, xcopy=0, ld_xcopy=0,
-                                                 w=w.data_ptr(), ldw=w.stride(0), bias=0 if b is None else b.data_ptr(),
-                                                 y=y.data_ptr(), ldy=y.stride(0), n=n, m=m, act=0)
-                arr = (P_ * 2)(mk(self.item_table, lw["w7"], lw["b7"], Yp, ni, 7 * h + 2),
-                               mk(self.query_table, lw["wq"], None, Yq, nqy, h + 2))
+                arr = (_lib.LinearProblem * 2)(_lib.linear_problem(self.item_table, lw["w7"], lw["b7"], Yp, ni, 7 * h + 2),
+                                               _lib.linear_problem(self.query_table, lw["wq"], None, Yq, nqy, h + 2))
                 _lib.check(_lib.lib().sss_linear_grouped(arr, 2, lw["din"], self._st()), "sss_linear_grouped")
                 self._tabs = (Yp, Yq)
         return self._tabs or None
@@ -551,14 +547,7 @@ class SessionEncoder:
         cfg = self.cfg
         h, D, P, W = cfg.h, cfg.d_out, cfg.max_seq_len, cfg.node_width
         NQ, NP, Yp, Yq = ws["NQ"], ws["NP"], ws["Yp"], ws["Yq"]
-        P_ = _lib.LinearProblem
-
-        def prob(x, w, bias, y, n, m, ids=None, table=None, xcopy=None):
-            return P_(x=0 if x is None else x.data_ptr(), ldx=0 if x is None else x.stride(0),
-                      ids=0 if ids is None else ids.data_ptr(), table=0 if table is None else table.data_ptr(),
-                      xcopy=0 if xcopy is None else xcopy.data_ptr(), ld_xcopy=0 if xcopy is None else xcopy.stride(0),
-                      w=w.data_ptr(), ldw=w.stride(0), bias=0 if bias is None else bias.data_ptr(),
-                      y=y.data_ptr(), ldy=y.stride(0), n=n, m=m, act=0)
+        P_, prob = _lib.LinearProblem, _lib.linear_problem
 
         steps, keep = [], []
         tabs = self._layer0_tables() if gather else None      # layer-0 transforms of the feature TABLES (weights only)
@@ -570,8 +559,8 @@ class SessionEncoder:
             if table0:
                 arr = None                                     # no per-batch transform: nodes read their table row's
             elif l == 0 and gather:
-                pp = prob(None, lw["w7"], lw["b7"], Yp, pb.Np, 7 * h + 2, pb.p_ids, self.item_table, xin_p)
-                pq = prob(None, lw["wq"], None, Yq, pb.Nq, h + 2, pb.q_ids, self.query_table, xin_q)
+                pp = prob(None, lw["w7"], lw["b7"], Yp, pb.Np, 7 * h + 2, ids=pb.p_ids, table=self.item_table, xcopy=xin_p)
+                pq = prob(None, lw["wq"], None, Yq, pb.Nq, h + 2, ids=pb.q_ids, table=self.query_table, xcopy=xin_q)
                 arr = (P_ * 2)(pp, pq)
             else:
                 pp = prob(xin_p, lw["w7"], lw["b7"], Yp, pb.Np, 7 * h + 2)
@@ -604,9 +593,8 @@ class SessionEncoder:
         pw, pt = self.pool, self.pool_tab
         Dl = D - P
         T, AC = ws["T"], ws["AC"]
-        pp, pq = prob(NP, pw["wp"], pw["bp"], T[:pb.Np], pb.Np, Dl), prob(NQ, pw["wq"], pw["bq"], T[pb.Np:], pb.Nq, Dl)
-        pp.act = pq.act = 2                                   # T = tanh(lin)
-        arr = (P_ * 2)(pp, pq)
+        arr = (P_ * 2)(prob(NP, pw["wp"], pw["bp"], T[:pb.Np], pb.Np, Dl, act=2),      # T = tanh(lin)
+                       prob(NQ, pw["wq"], pw["bq"], T[pb.Np:], pb.Nq, Dl, act=2))
         steps.append(("lin", arr, 2, W))
         arr2 = (P_ * 1)(prob(T, pt["wnc"], None, AC, pb.Np + pb.Nq, 2 * D))      # [A1 | C1]
         steps.append(("lin", arr2, 1, pt["KT"]))

@@ -41,6 +41,8 @@ from collections import namedtuple
 
 import numpy as np
 
+from ._lib import pad32 as _pad32
+
 MAX_LEN = 64                                 # rows per sequence sss_seq_attention takes: one lane per query row
 PAD_RULES = ("compute", "zero")
 
@@ -92,11 +94,49 @@ def pack_tokens(src, mask, pad_rule="compute", ntoken=None):
     return TokenRows(src[b, t].astype(np.int64), t.astype(np.int32), ptr, (~mask[b, t]).astype(np.uint8), T)
 
 
-def _pad32(n):
-    return (n + 31) // 32 * 32
-
-
 LAYER = "transformer_encoder.layers.{}."
+# the keys of a folded layer -> the tensor's name under LAYER; in_w / in_b arrive as q | k | v rows of one tensor
+LAYER_NAMES = {"in_w": "self_attn.in_proj_weight", "in_b": "self_attn.in_proj_bias", "out_w": "self_attn.out_proj.weight",
+               "out_b": "self_attn.out_proj.bias", "l1_w": "linear1.weight", "l1_b": "linear1.bias", "l2_w": "linear2.weight",
+               "l2_b": "linear2.bias", "n1_w": "norm1.weight", "n1_b": "norm1.bias", "n2_w": "norm2.weight", "n2_b": "norm2.bias"}
+
+
+def _pad(w, rows, cols):
+    import torch
+    out = torch.zeros((rows, cols), dtype=torch.float64)
+    out[:w.shape[0], :w.shape[1]] = w
+    return out
+
+
+def _fold_layers(weights, prefix, names, stacked, e, D):
+    """The layers of both folds, float64: ``(layers, inner)`` with ``layers`` the per-layer dicts ``text_fold_weights``
+    documents and ``inner`` the feed-forward width.  ``names`` maps the twelve keys of such a dict to the tensor's name under
+    ``prefix.format(l)``; ``stacked``: ``in_w`` / ``in_b`` name one tensor of q | k | v rows, otherwise the three of them.  The
+    layers are counted by probing the first of these names; q is divided by ``sqrt(D)`` first, padded second."""
+    import torch
+    probe = prefix + (names["in_w"] if stacked else names["in_w"][0])
+    nlayers = 0
+    while probe.format(nlayers) in weights:
+        nlayers += 1
+    if nlayers == 0:
+        raise ValueError(f"weights hold no {probe.format(0)}")
+    inner = int(weights[prefix.format(0) + names["l1_w"]].shape[0])
+    K, Hp = _pad32(e), _pad32(inner)
+    layers = []
+    for l in range(nlayers):
+        f64 = lambda name: weights[prefix.format(l) + name].detach().to("cpu", torch.float64)
+        g = lambda key: f64(names[key])
+
+        def qkv(key):
+            t = g(key) if stacked else torch.cat([f64(name) for name in names[key]])
+            return torch.cat([t[:e] / math.sqrt(D), t[e:]])
+
+        l1_b = torch.zeros(Hp, dtype=torch.float64)
+        l1_b[:inner] = g("l1_b")
+        layers.append({"in_w": _pad(qkv("in_w"), 3 * e, K), "in_b": qkv("in_b"), "out_w": _pad(g("out_w"), e, K), "out_b": g("out_b"),
+                       "l1_w": _pad(g("l1_w"), Hp, K), "l1_b": l1_b, "l2_w": _pad(g("l2_w"), e, Hp), "l2_b": g("l2_b"),
+                       "n1_w": g("n1_w"), "n1_b": g("n1_b"), "n2_w": g("n2_w"), "n2_b": g("n2_b")})
+    return layers, inner
 
 
 def text_fold_weights(weights, nhead):
@@ -117,32 +157,8 @@ def text_fold_weights(weights, nhead):
         raise ValueError(f"ninp = {e} is not a multiple of nhead = {nhead}")
     D = e // H
     pe = f64("pos_encoder.pe").reshape(-1, e)[:MAX_LEN].contiguous()
-    nlayers = 0
-    while LAYER.format(nlayers) + "self_attn.in_proj_weight" in weights:
-        nlayers += 1
-    if nlayers == 0:
-        raise ValueError("weights hold no transformer_encoder.layers.0.self_attn.in_proj_weight")
-    nhid = int(weights[LAYER.format(0) + "linear1.weight"].shape[0])
-    K, Hp = _pad32(e), _pad32(nhid)
-
-    def pad(w, rows, cols):
-        out = torch.zeros((rows, cols), dtype=torch.float64)
-        out[:w.shape[0], :w.shape[1]] = w
-        return out
-
-    layers = []
-    for l in range(nlayers):
-        g = lambda n: f64(LAYER.format(l) + n)
-        in_w, in_b = g("self_attn.in_proj_weight").clone(), g("self_attn.in_proj_bias").clone()
-        in_w[:e] /= math.sqrt(D)
-        in_b[:e] /= math.sqrt(D)
-        l1_b = torch.zeros(Hp, dtype=torch.float64)
-        l1_b[:nhid] = g("linear1.bias")
-        layers.append({"in_w": pad(in_w, 3 * e, K), "in_b": in_b, "out_w": pad(g("self_attn.out_proj.weight"), e, K),
-                       "out_b": g("self_attn.out_proj.bias"), "l1_w": pad(g("linear1.weight"), Hp, K), "l1_b": l1_b,
-                       "l2_w": pad(g("linear2.weight"), e, Hp), "l2_b": g("linear2.bias"), "n1_w": g("norm1.weight"),
-                       "n1_b": g("norm1.bias"), "n2_w": g("norm2.weight"), "n2_b": g("norm2.bias")})
-    return {"ninp": e, "nhead": H, "nhid": nhid, "nlayers": nlayers, "table": table, "pe": pe,
+    layers, nhid = _fold_layers(weights, LAYER, LAYER_NAMES, True, e, D)
+    return {"ninp": e, "nhead": H, "nhid": nhid, "nlayers": len(layers), "table": table, "pe": pe,
             "scale": float(np.float32(math.sqrt(e))), "layers": layers}
 
 
@@ -163,8 +179,7 @@ class _PackedEncoder:
 
     def _linear(self, x, w, b, y, n, act=0):
         from . import _lib
-        from .variants import _prob
-        arr = (_lib.LinearProblem * 1)(_prob(x, w, b, y, n, w.shape[0], act))
+        arr = (_lib.LinearProblem * 1)(_lib.linear_problem(x, w, b, y, n, w.shape[0], act))
         _lib.check(_lib.lib().sss_linear_grouped(arr, 1, w.shape[1], _lib.stream_ptr(self.device)), "sss_linear_grouped")
 
     def _add_layernorm(self, x, res, gamma, beta, n):
@@ -188,6 +203,41 @@ class _PackedEncoder:
             self._linear(x, lay["l1_w"], lay["l1_b"], hid, n, act=act)
             self._linear(hid, lay["l2_w"], lay["l2_b"], proj, n)
             self._add_layernorm(x, proj, lay["n2_w"], lay["n2_b"], n)
+
+    def _encode(self, rows, embed, act, pool_w, out, err_msg, extra=None, tokens=None):
+        """The chunk walk over packed ``rows`` (``TokenRows``, at least one sequence), whole sequences of at most
+        ``self.chunk_rows`` rows at a time: ``embed(tok, pos, extra, n, x, err)`` launches the subclass's embedding of the
+        chunk's ``n`` rows into ``x`` (``extra``: its slice of that host array, uploaded), then every layer, then
+        ``out[s] = sum_r pool_w[r] x[r]`` over the rows of sequence ``s`` -- ``pool_w`` one float for all rows or a host float32
+        array.  ``tokens`` (``[B * T, e]``, every sequence kept all ``T`` rows) also receives the rows.  ``err`` (int32 [1], set
+        by the embedding kernel on an index out of range) is read once, at the end: ``IndexError(err_msg)``."""
+        import torch
+        from . import _lib
+        e, dev, T = self.ninp, self.device, rows.T
+        L, st = _lib.lib(), _lib.stream_ptr(dev)
+        chunks = split_chunks(rows.ptr, self.chunk_rows)
+        cap = max(int(rows.ptr[s1] - rows.ptr[s0]) for s0, s1 in chunks)
+        K, Hp = self.layers[0]["in_w"].shape[1], self.layers[0]["l1_w"].shape[0]
+        buf = lambda width: torch.empty((cap, width), dtype=torch.float32, device=dev)
+        x, qkv, att, proj, hid = buf(K), buf(3 * e), buf(K), buf(e), buf(Hp)
+        same_w = None if isinstance(pool_w, np.ndarray) else torch.full((cap,), pool_w, dtype=torch.float32, device=dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        for s0, s1 in chunks:
+            r0, r1 = int(rows.ptr[s0]), int(rows.ptr[s1])
+            n = r1 - r0
+            tok, pos, key_ok = up(rows.tok[r0:r1]), up(rows.pos[r0:r1]), up(rows.key_ok[r0:r1])
+            w = up(pool_w[r0:r1]) if same_w is None else same_w
+            ptr = up(rows.ptr[s0:s1 + 1] - np.int32(r0))
+            embed(tok, pos, None if extra is None else up(extra[r0:r1]), n, x, err)
+            self._run_layers(x, qkv, att, proj, hid, ptr, key_ok, n, s1 - s0, T, act)
+            rc = L.sss_segment_reduce(x.data_ptr(), x.stride(0), w.data_ptr(), ptr.data_ptr(), s1 - s0, e, 1, out[s0:s1].data_ptr(),
+                                      out.stride(0), st)
+            _lib.check(rc, "sss_segment_reduce")
+            if tokens is not None:
+                tokens[s0 * T:s1 * T].copy_(x[:n, :e])
+        if int(err.item()):                                                  # one read per forward
+            raise IndexError(err_msg)
 
 
 class NodeTextTransformer(_PackedEncoder):
@@ -242,29 +292,14 @@ class NodeTextTransformer(_PackedEncoder):
             if B == 0:
                 return out
             L, st = _lib.lib(), _lib.stream_ptr(dev)
-            chunks = split_chunks(rows.ptr, self.chunk_rows)
-            cap = max(int(rows.ptr[s1] - rows.ptr[s0]) for s0, s1 in chunks)
-            K, Hp = self.layers[0]["in_w"].shape[1], self.layers[0]["l1_w"].shape[0]
-            buf = lambda width: torch.empty((cap, width), dtype=torch.float32, device=dev)
-            x, qkv, att, proj, hid = buf(K), buf(3 * e), buf(K), buf(e), buf(Hp)
-            inv_t = torch.full((cap,), 1.0 / T, dtype=torch.float32, device=dev)       # the mean divides by the padded length
-            err = torch.zeros(1, dtype=torch.int32, device=dev)
-            for s0, s1 in chunks:
-                r0, r1 = int(rows.ptr[s0]), int(rows.ptr[s1])
-                n = r1 - r0
-                up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-                tok, pos, key_ok = up(rows.tok[r0:r1]), up(rows.pos[r0:r1]), up(rows.key_ok[r0:r1])
-                ptr = up(rows.ptr[s0:s1 + 1] - np.int32(r0))
+
+            def embed(tok, pos, _, n, x, err):
                 rc = L.sss_text_embed(self.table.data_ptr(), self.ntoken, self.pe.data_ptr(), self.pe.shape[0], tok.data_ptr(),
                                       pos.data_ptr(), n, e, self.scale, x.data_ptr(), x.stride(0), err.data_ptr(), st)
                 _lib.check(rc, "sss_text_embed")
-                self._run_layers(x, qkv, att, proj, hid, ptr, key_ok, n, s1 - s0, T, act=1)
-                view = out[s0:s1]
-                rc = L.sss_segment_reduce(x.data_ptr(), x.stride(0), inv_t.data_ptr(), ptr.data_ptr(), s1 - s0, e, 1,
-                                          view.data_ptr(), out.stride(0), st)
-                _lib.check(rc, "sss_segment_reduce")
-            if int(err.item()):                                              # one read per forward
-                raise IndexError("a token id or position was out of range on the device (sss_text_embed wrote zero rows)")
+
+            self._encode(rows, embed, 1, 1.0 / T, out,          # relu in the feed-forward block; the mean divides by the padded length
+                         "a token id or position was out of range on the device (sss_text_embed wrote zero rows)")
         return out
 
     __call__ = forward
@@ -274,6 +309,12 @@ class NodeTextTransformer(_PackedEncoder):
 # The node text encoder of the deployed model: PretrainedQAEAEncoder (model/NodeEmbedding.py:100-125), a BERT encoder without
 # its pooling layer + a masked mean over the tokens + an optional Linear.  DESIGN.md section 5.10.
 BERT_LAYER = "encoder.layer.{}."
+BERT_LAYER_NAMES = {"in_w": tuple(f"attention.self.{n}.weight" for n in ("query", "key", "value")),
+                    "in_b": tuple(f"attention.self.{n}.bias" for n in ("query", "key", "value")),
+                    "out_w": "attention.output.dense.weight", "out_b": "attention.output.dense.bias",
+                    "l1_w": "intermediate.dense.weight", "l1_b": "intermediate.dense.bias", "l2_w": "output.dense.weight",
+                    "l2_b": "output.dense.bias", "n1_w": "attention.output.LayerNorm.weight", "n1_b": "attention.output.LayerNorm.bias",
+                    "n2_w": "output.LayerNorm.weight", "n2_b": "output.LayerNorm.bias"}
 BERT_POOLS = ("masked", "mean")
 
 BertRows = namedtuple("BertRows", "rows tt w")
@@ -338,36 +379,12 @@ def bert_fold_weights(weights, num_heads):
     if H < 1 or e % H:
         raise ValueError(f"hidden size {e} is not a multiple of num_heads = {num_heads}")
     D = e // H
-    nlayers = 0
-    while BERT_LAYER.format(nlayers) + "attention.self.query.weight" in weights:
-        nlayers += 1
-    if nlayers == 0:
-        raise ValueError("weights hold no encoder.layer.0.attention.self.query.weight")
-    inter = int(weights[BERT_LAYER.format(0) + "intermediate.dense.weight"].shape[0])
-    K, Hp = _pad32(e), _pad32(inter)
-
-    def pad(w, rows, cols):
-        out = torch.zeros((rows, cols), dtype=torch.float64)
-        out[:w.shape[0], :w.shape[1]] = w
-        return out
-
-    layers = []
-    for l in range(nlayers):
-        g = lambda n: f64(BERT_LAYER.format(l) + n)
-        in_w = torch.cat([g("attention.self.query.weight") / math.sqrt(D), g("attention.self.key.weight"), g("attention.self.value.weight")])
-        in_b = torch.cat([g("attention.self.query.bias") / math.sqrt(D), g("attention.self.key.bias"), g("attention.self.value.bias")])
-        l1_b = torch.zeros(Hp, dtype=torch.float64)
-        l1_b[:inter] = g("intermediate.dense.bias")
-        layers.append({"in_w": pad(in_w, 3 * e, K), "in_b": in_b, "out_w": pad(g("attention.output.dense.weight"), e, K),
-                       "out_b": g("attention.output.dense.bias"), "l1_w": pad(g("intermediate.dense.weight"), Hp, K), "l1_b": l1_b,
-                       "l2_w": pad(g("output.dense.weight"), e, Hp), "l2_b": g("output.dense.bias"),
-                       "n1_w": g("attention.output.LayerNorm.weight"), "n1_b": g("attention.output.LayerNorm.bias"),
-                       "n2_w": g("output.LayerNorm.weight"), "n2_b": g("output.LayerNorm.bias")})
+    layers, inter = _fold_layers(weights, BERT_LAYER, BERT_LAYER_NAMES, False, e, D)
     lin_w = lin_b = None
     if "lin.weight" in weights:
-        lin_w = pad(f64("lin.weight"), int(weights["lin.weight"].shape[0]), K)
+        lin_w = _pad(f64("lin.weight"), int(weights["lin.weight"].shape[0]), _pad32(e))
         lin_b = f64("lin.bias") if "lin.bias" in weights else torch.zeros(lin_w.shape[0], dtype=torch.float64)
-    return {"e": e, "heads": H, "inter": inter, "nlayers": nlayers, "word": word, "pos": f64("embeddings.position_embeddings.weight"),
+    return {"e": e, "heads": H, "inter": inter, "nlayers": len(layers), "word": word, "pos": f64("embeddings.position_embeddings.weight"),
             "type": f64("embeddings.token_type_embeddings.weight"), "emb_g": f64("embeddings.LayerNorm.weight"),
             "emb_b": f64("embeddings.LayerNorm.bias"), "layers": layers, "lin_w": lin_w, "lin_b": lin_b}
 
@@ -466,30 +483,14 @@ class BertNodeEncoder(_PackedEncoder):
             pooled = torch.zeros((U, K), dtype=torch.float32, device=dev)     # pad columns stay zero: the lin head's K operand
             tokens = torch.empty((U * T, e), dtype=torch.float32, device=dev) if get_token else None
             if U:
-                chunks = split_chunks(rows.ptr, self.chunk_rows)
-                cap = max(int(rows.ptr[s1] - rows.ptr[s0]) for s0, s1 in chunks)
-                buf = lambda width: torch.empty((cap, width), dtype=torch.float32, device=dev)
-                x, qkv, att, proj, hid = buf(K), buf(3 * e), buf(K), buf(e), buf(self.layers[0]["l1_w"].shape[0])
-                err = torch.zeros(1, dtype=torch.int32, device=dev)
-                up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-                for s0, s1 in chunks:
-                    r0, r1 = int(rows.ptr[s0]), int(rows.ptr[s1])
-                    n = r1 - r0
-                    tok, pos, typ, key_ok, w = (up(a[r0:r1]) for a in (rows.tok, rows.pos, packed.tt, rows.key_ok, packed.w))
-                    ptr = up(rows.ptr[s0:s1 + 1] - np.int32(r0))
+                def embed(tok, pos, typ, n, x, err):
                     rc = L.sss_bert_embed(self.word.data_ptr(), self.n_word, self.type.data_ptr(), self.n_type, self.pos.data_ptr(),
                                           self.n_pos, tok.data_ptr(), typ.data_ptr(), pos.data_ptr(), self.emb_g.data_ptr(),
                                           self.emb_b.data_ptr(), self.eps, n, e, x.data_ptr(), x.stride(0), err.data_ptr(), st)
                     _lib.check(rc, "sss_bert_embed")
-                    self._run_layers(x, qkv, att, proj, hid, ptr, key_ok, n, s1 - s0, T, act=5)
-                    view = pooled[s0:s1]
-                    rc = L.sss_segment_reduce(x.data_ptr(), x.stride(0), w.data_ptr(), ptr.data_ptr(), s1 - s0, e, 1, view.data_ptr(),
-                                              pooled.stride(0), st)
-                    _lib.check(rc, "sss_segment_reduce")
-                    if get_token:                                            # every sequence kept all T rows
-                        tokens[s0 * T:s1 * T].copy_(x[:n, :e])
-                if int(err.item()):                                          # one read per call
-                    raise IndexError("a token id, token type or position was out of range on the device (sss_bert_embed wrote zero rows)")
+
+                self._encode(rows, embed, 5, packed.w, pooled, "a token id, token type or position was out of range on the device "
+                             "(sss_bert_embed wrote zero rows)", extra=packed.tt, tokens=tokens)      # 5: the exact GELU
             if inv is not None:                                              # scatter the distinct rows back to the batch
                 d_inv = torch.from_numpy(inv).to(dev)
                 full = torch.zeros((B, K), dtype=torch.float32, device=dev)

@@ -37,11 +37,8 @@ def _st(dev):
     return _lib.stream_ptr(dev)
 
 
-def _prob(x, w, bias, y, n, m, act=0, post=None):
-    return _lib.LinearProblem(x=x.data_ptr(), ldx=x.stride(0), ids=0, table=0, xcopy=0, ld_xcopy=0, w=w.data_ptr(),
-                              ldw=w.stride(0), bias=0 if bias is None else bias.data_ptr(), y=y.data_ptr(), ldy=y.stride(0),
-                              n=n, m=m, act=act, post_scale=0 if post is None else post[0].data_ptr(),
-                              post_shift=0 if post is None else post[1].data_ptr())
+_prob = _lib.linear_problem      # (x, w, bias, y, n, m, act=0, post=None)
+_pad32 = _lib.pad32
 
 
 def linear(x, w, bias=None, act=0, out=None, post=None):
@@ -55,10 +52,6 @@ def linear(x, w, bias=None, act=0, out=None, post=None):
     arr = (_lib.LinearProblem * 1)(_prob(x, w, bias, out, n, m, act, post))
     _lib.check(_lib.lib().sss_linear_grouped(arr, 1, k, _st(x.device)), "sss_linear_grouped")
     return out
-
-
-def _pad32(n):
-    return (n + 31) // 32 * 32
 
 
 def _pad_cols(w, dev):

@@ -154,6 +154,30 @@ def test_fold_weights(geometry):
         bert_fold_weights(wt, 7)
 
 
+def test_both_folds_give_the_same_layers():
+    """bert_fold_weights and text_fold_weights share one layer fold: BERT layers re-keyed under the transformer's names, with
+    query | key | value stacked into one in_proj, fold to bit-equal layer dicts (96 / 4: 1 / sqrt(24) is not a power of two,
+    intermediate 100 needs row and column pads)."""
+    from sessionsimilaritysearch_amd.text import LAYER, bert_fold_weights, text_fold_weights
+    heads = 4
+    wb = {k: torch.as_tensor(v) for k, v in br.seeded_weights(6, 40, 96, heads, 100, 2, 16).items()}
+    wt = {"embedding.weight": wb["embeddings.word_embeddings.weight"], "pos_encoder.pe": wb["embeddings.position_embeddings.weight"]}
+    names = {"attention.output.dense": "self_attn.out_proj", "intermediate.dense": "linear1", "output.dense": "linear2",
+             "attention.output.LayerNorm": "norm1", "output.LayerNorm": "norm2"}
+    for l in range(2):
+        pb, pt = br.LAYER.format(l), LAYER.format(l)
+        for kind, to in (("weight", "in_proj_weight"), ("bias", "in_proj_bias")):
+            wt[pt + "self_attn." + to] = torch.cat([wb[pb + f"attention.self.{n}.{kind}"] for n in ("query", "key", "value")])
+        for a, b in names.items():
+            wt[pt + b + ".weight"], wt[pt + b + ".bias"] = wb[pb + a + ".weight"], wb[pb + a + ".bias"]
+    fb, ft = bert_fold_weights(wb, heads), text_fold_weights(wt, heads)
+    assert (ft["nlayers"], ft["nhid"], ft["ninp"]) == (fb["nlayers"], fb["inter"], fb["e"]) == (2, 100, 96)
+    for lb, lt in zip(fb["layers"], ft["layers"]):
+        assert lb.keys() == lt.keys() and len(lb) == 12
+        for k in lb:
+            assert lb[k].dtype == lt[k].dtype == torch.float64 and torch.equal(lb[k], lt[k]), k
+
+
 # ------------------------------------------------------------------------------------------------ bert_pack_rows
 def _pack_np(ids, tt, am, pool, all_rows):
     tok, typ, pos, key, w, ptr = [], [], [], [], [], [0]

@@ -1,4 +1,4 @@
-"""The fused encoder kernels of csrc/gnn.hip at their shape and structure edges, through the C ABI, each case against the
+"""The fused encoder kernels of csrc/gnn_fused.hip at their shape and structure edges, through the C ABI, each case against the
 float64 restatement of oracle/encoder_kernels_ref.py (itself pinned to oracle/gnn_ref64.py on the CPU by
 tests/test_encoder_kernels_ref_cpu.py, which also proves every case generated here well formed).
 

@@ -1,4 +1,4 @@
-"""sss_linear_grouped (k_linear_grouped, csrc/gnn.hip) bit for bit against the exact fma-chain oracle.
+"""sss_linear_grouped (k_linear_grouped, csrc/linear.hip) bit for bit against the exact fma-chain oracle.
 
 Every output element of the grouped GEMM is one k-ordered float32 fma chain (v_mfma_f32_32x32x2_f32 is an fmaf chain,
 bitwise), followed by a float32 bias add and the epilogue.  ``oracle.search_ref.linear_chain`` restates that chain with C
