@@ -1,5 +1,6 @@
-/* libsss, ground truth -- the similarity the session encoder is trained to approximate, over the WHOLE corpus: the
- * item-set kinds of the reference's get_score (fine_tune_ours.py:42-55, 'all_jaccard' and 'cur_jaccard'), its exact top-k,
+/* libsss, ground truth -- a similarity the session encoder can be trained to approximate, over the WHOLE corpus: the
+ * item-set kinds of the reference's get_score (fine_tune_ours.py:42-55, 'all_jaccard' and 'cur_jaccard'; the kind
+ * CFG.sim_type is set to, 'all_product_type_score', is include/sss_ptype.h's), its exact top-k,
  * and the band counts / first rows that the fine-tuning triple mining (fine_tune_ours.py:187-235) and a thresholded recall
  * need.  Same library (libsss.so) and the same conventions as include/sss.h and include/sss_sparse.h:
  *

@@ -17,13 +17,15 @@ Drop-in surface of the reference's path:
   JaccardIndex, mine_triples, neighbourhood_recall
                                                   (jaccard.py   <- fine_tune_ours.py get_score :42-55 over the whole corpus,
                                                                   the triple mining :187-235: the ground truth)
+  ProductTypeIndex, type_bags                     (product_types.py <- fine_tune_ours.py get_score :66-85, the kind of
+                                                                  CFG.sim_type = 'all_product_type_score', over the whole corpus)
   NodeTextTransformer, pack_tokens, text_fold_weights, TokenRows
                                                   (text.py      <- model/NodeEmbedding.py NodeTextTransformer: the two-tower
                                                                   model's query text encoder, eval mode)
   BertNodeEncoder, bert_fold_weights, bert_pack_rows, BertRows
                                                   (text.py      <- model/NodeEmbedding.py PretrainedQAEAEncoder: the deployed
                                                                   model's node text encoder, BERT + masked mean + Linear)
-  ShardedFlatIndex, ShardedBinaryIndex, ShardedSparseIndex, ShardedJaccardIndex
+  ShardedFlatIndex, ShardedBinaryIndex, ShardedSparseIndex, ShardedJaccardIndex, ShardedProductTypeIndex
                                                   (distributed.py: corpus row-sharded over RCCL)
   SessionBatch, build_batch, synthetic_actions    (sessions.py  <- sequence_to_graph + Batch.from_data_list, host side)
 """
@@ -36,6 +38,8 @@ __all__ = ["SssError", "build", "exported_symbols", "lib", "SessionVectors", "Sp
 _EVALUATION = frozenset(__all__[8:])
 _JACCARD = ("JaccardIndex", "mine_triples", "neighbourhood_recall")
 __all__ += list(_JACCARD)
+_PTYPE = ("ProductTypeIndex", "type_bags")
+__all__ += list(_PTYPE)
 _HGT = ("HGT", "hgt_fold_weights")
 __all__ += list(_HGT)
 _TEXT = ("NodeTextTransformer", "pack_tokens", "text_fold_weights", "TokenRows", "BertNodeEncoder", "bert_fold_weights",
@@ -54,6 +58,9 @@ def __getattr__(name):
     if name in _JACCARD:                                 # the ground-truth index: lazily, for the same reason
         from . import jaccard
         return getattr(jaccard, name)
+    if name in _PTYPE:                                   # the product-type index: lazily, for the same reason
+        from . import product_types
+        return getattr(product_types, name)
     if name in _HGT:                                     # the HGT encoder: lazily, for the same reason
         from . import variants
         return getattr(variants, name)

@@ -179,6 +179,21 @@ _JACCARD_SIGNATURES = {
                                   c_void_p, c_void_p]),
 }
 
+# include/sss_ptype.h one to one (ground truth under the product-type kind: type bags, their exact top-k, band counts and
+# pair scores; `edges` of sss_ptype_bands is a HOST pointer, as sss_jaccard_bands')
+_PTYPE_SIGNATURES = {
+    "sss_type_bags_count": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sss_type_bags_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
+    "sss_ptype_topk_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "sss_ptype_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64,
+                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "sss_ptype_bands": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int64,
+                                c_void_p, c_void_p, c_void_p]),
+    "sss_ptype_pair_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int,
+                                      c_int64, c_void_p, c_void_p, c_void_p]),
+}
+
 # include/sss_hgt.h one to one (the HGT encoder: HGTConv's attention aggregation on CSR by target and its skip connection)
 _HGT_SIGNATURES = {
     "sss_hgt_aggregate": (c_int, [c_void_p, c_void_p]),
@@ -211,6 +226,7 @@ HEADERS = {
     "sss_graph.h": _GRAPH_SIGNATURES,
     "sss_eval.h": _EVAL_SIGNATURES,
     "sss_jaccard.h": _JACCARD_SIGNATURES,
+    "sss_ptype.h": _PTYPE_SIGNATURES,
     "sss_hgt.h": _HGT_SIGNATURES,
     "sss_text.h": _TEXT_SIGNATURES,
     "sss_bert.h": _BERT_SIGNATURES,
@@ -314,6 +330,11 @@ def eval_symbols():
 def jaccard_symbols():
     """The entry points of include/sss_jaccard.h."""
     return sorted(HEADERS["sss_jaccard.h"])
+
+
+def ptype_symbols():
+    """The entry points of include/sss_ptype.h."""
+    return sorted(HEADERS["sss_ptype.h"])
 
 
 def hgt_symbols():

@@ -7,12 +7,11 @@
 //
 //   k_jaccard_scores    writes float32(inter / uni) for every pair and the identity query selection; topk_of_scores
 //                       (exhaustive.hip, metric 0) is the unchanged tail
-//   k_jaccard_bands     no matrix: per query one ballot per band over the wave (the popcount is the count; the lowest set
-//                       lane is the lowest row, rows ascend with the lane); the four waves' words of JC_QRUN queries meet in
-//                       LDS and one thread per (query, band) adds the workgroup's total with integer atomics
+//   k_jaccard_bands     no matrix: the band counts of band_count.h (a ballot per band over the wave, an LDS flush, integer
+//                       atomics), shared with ptype.hip
 #include <math.h>
 
-#include "csr_walk.h"
+#include "band_count.h"
 #include "scan.h"
 
 namespace sss {
@@ -21,12 +20,7 @@ namespace sss {
 // Every row session_vectors builds from the benchmark corpora (at most 19 actions) and all but the longest real sessions
 // then take the LDS form; 64 would cover the builder's limit but leaves 2 workgroups a CU (64 KiB each) where 32 leaves 4.
 constexpr int JC_D = 32;
-constexpr int JC_QRUN = 32;           // queries between two flushes of k_jaccard_bands: 256 threads = 32 queries x 8 bands
-constexpr int JC_MAX_EDGES = 7;
-constexpr int JC_BANDS = JC_MAX_EDGES + 1;
 constexpr int JC_MAX_K = 1024;        // k_topk_radix's RS_MAX_K
-
-struct JcEdges { double e[JC_MAX_EDGES]; };     // unused edges are +inf: no ratio reaches them
 
 // |Q & C| of the query entries [q0, q1) and the thread's row
 template <class View>
@@ -57,60 +51,33 @@ __global__ __launch_bounds__(CSR_ROWS) void k_jaccard_scores(const long* __restr
     });
 }
 
-// counts / first: [nq][nb] with nb = edges + 1, zeroed / set to all ones (int64 -1 = the largest unsigned value, so an
-// unsigned atomicMin of row + id_offset >= 0 leaves -1 exactly where a band has no row) by the entry point.
+// The band counts of band_count.h (its ballot and its flush) over the score (double)inter / (double)uni.
 __global__ __launch_bounds__(CSR_ROWS) void k_jaccard_bands(const long* __restrict__ qptr, const int* __restrict__ qitems, int nq,
                                                             int q_per, const long* __restrict__ cptr, const int* __restrict__ citems,
-                                                            long n, const JcEdges E, int nb, long id_offset,
+                                                            long n, const BandEdges E, int nb, long id_offset,
                                                             unsigned long long* __restrict__ counts,
                                                             unsigned long long* __restrict__ first_out) {
     __shared__ int r_it[JC_D * CSR_ROWS];
-    __shared__ int s_tot[CSR_ROWS / 64][JC_QRUN][JC_BANDS];      // (rows of the band in the wave) << 8 | its lowest lane; 0: none
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __shared__ BandWords s_tot;
+    const int tid = threadIdx.x;
     const long row0 = (long)blockIdx.x * CSR_ROWS, row = row0 + tid;
     CsrRow<JC_D, false> R{citems, nullptr, r_it, nullptr, tid};
     R.stage(cptr, row, n);
     const int f_lo = blockIdx.y * q_per, f_hi = f_lo + q_per < nq ? f_lo + q_per : nq;
-    for (int f0 = f_lo; f0 < f_hi; f0 += JC_QRUN) {              // workgroup-uniform: the barriers below are met by all
-        const int fe = f0 + JC_QRUN < f_hi ? f0 + JC_QRUN : f_hi;
+    for (int f0 = f_lo; f0 < f_hi; f0 += BD_QRUN) {              // workgroup-uniform: band_flush's barriers are met by all
+        const int fe = f0 + BD_QRUN < f_hi ? f0 + BD_QRUN : f_hi;
         R.each_space([&](auto V) {
             for (int f = f0; f < fe; ++f) {
                 const long q0 = qptr[f], q1 = q0 + csr_len(q0, qptr[f + 1]);
                 const int acc = jc_inter(qitems, q0, q1, V);
                 const long uni = (q1 - q0) + R.lr - acc;
                 const double s = uni ? __ddiv_rn((double)acc, (double)uni) : 0.0;
-                int band = 0;
-#pragma unroll
-                for (int e = 0; e < JC_MAX_EDGES; ++e) band += s >= E.e[e] ? 1 : 0;
-                int mine = 0;                                    // lane b: band b's word for this wave
-                for (int b = 0; b < nb; ++b) {
-                    const unsigned long long m = __builtin_amdgcn_ballot_w64(row < n && band == b);
-                    if (lane == b && m) mine = (__builtin_popcountll(m) << 8) | __builtin_ctzll(m);
-                }
-                if (lane < JC_BANDS) s_tot[wv][f - f0][lane] = mine;
+                band_ballot(s_tot, f - f0, row < n, s, E, nb);
             }
         });
-        __syncthreads();
-        const int q = tid >> 3, b = tid & 7;                     // CSR_ROWS = JC_QRUN * JC_BANDS: one thread per (query, band)
-        if (f0 + q < fe && b < nb) {
-            int cnt = 0, lo = -1;
-            for (int w = 0; w < CSR_ROWS / 64; ++w) {            // waves ascend with the rows: the first hit is the lowest
-                const int t = s_tot[w][q][b];
-                if (t) {
-                    cnt += t >> 8;
-                    if (lo < 0) lo = w * 64 + (t & 255);
-                }
-            }
-            if (cnt) {
-                const size_t at = (size_t)(f0 + q) * nb + b;
-                atomicAdd(&counts[at], (unsigned long long)cnt);
-                atomicMin(&first_out[at], (unsigned long long)(row0 + lo + id_offset));
-            }
-        }
-        __syncthreads();
+        band_flush(s_tot, f0, fe, nb, row0, id_offset, counts, first_out);
     }
 }
-static_assert(CSR_ROWS == JC_QRUN * JC_BANDS, "the flush maps one thread to one (query, band)");
 
 // ------------------------------------------------------------------------------ host launchers
 static int jc_sets_ok(const char* what, const void* q_ptr, const void* q_items, long nq, const void* c_ptr, const void* c_items, long n) {
@@ -153,32 +120,12 @@ extern "C" int sss_jaccard_bands(const int64_t* q_ptr, const int32_t* q_items, i
     hipStream_t st = static_cast<hipStream_t>(stream);
     int rc = jc_sets_ok("jaccard_bands", q_ptr, q_items, nq, c_ptr, c_items, n);
     if (rc) return rc;
-    if (n_edges < 1 || n_edges > JC_MAX_EDGES) { set_error("jaccard_bands: need 1 <= n_edges <= 7"); return SSS_EINVAL; }
-    if (!edges || !counts || !first) {
-        set_error("jaccard_bands: a null pointer (edges, counts and first are required)");
-        return SSS_EINVAL;
-    }
-    if (id_offset < 0 || id_offset > INT64_MAX - n) {
-        set_error("jaccard_bands: need 0 <= id_offset <= 2^63 - 1 - n (-1 marks a band without a row)");
-        return SSS_EINVAL;
-    }
-    JcEdges E;
-    for (int e = 0; e < JC_MAX_EDGES; ++e) {
-        E.e[e] = e < n_edges ? edges[e] : (double)INFINITY;
-        if (e < n_edges && (!isfinite(E.e[e]) || (e > 0 && !(E.e[e] > E.e[e - 1])))) {
-            set_error("jaccard_bands: edges must be finite and strictly ascending (edge %d)", e);
-            return SSS_EINVAL;
-        }
-    }
-    const int nb = n_edges + 1;
-    const size_t bytes = (size_t)nq * nb * sizeof(int64_t);
-    if (hipMemsetAsync(counts, 0, bytes, st) != hipSuccess || hipMemsetAsync(first, 0xFF, bytes, st) != hipSuccess) {
-        set_error("jaccard_bands: memset failed");
-        return SSS_EHIP;
-    }
+    BandEdges E;
+    rc = band_args("jaccard_bands", edges, n_edges, id_offset, nq, n, counts, first, &E, st);
+    if (rc) return rc;
     int q_per = 0;
     const dim3 grid = csr_grid(nq, n, &q_per);
-    hipLaunchKernelGGL(k_jaccard_bands, grid, dim3(CSR_ROWS), 0, st, q_ptr, q_items, (int)nq, q_per, c_ptr, c_items, n, E, nb, id_offset,
+    hipLaunchKernelGGL(k_jaccard_bands, grid, dim3(CSR_ROWS), 0, st, q_ptr, q_items, (int)nq, q_per, c_ptr, c_items, n, E, n_edges + 1, id_offset,
                        reinterpret_cast<unsigned long long*>(counts), reinterpret_cast<unsigned long long*>(first));
     return check_launch("k_jaccard_bands");
 }

@@ -13,7 +13,8 @@ every rank would be the Amdahl term of strong scaling.
 Every index kind shards this way.  ``ShardedFlatIndex`` serves both metrics and every d / k of ``FlatIndex``
 (shapes without a fused scan run the shard's exhaustive kernels) and ``range_search``; ``ShardedBinaryIndex``
 serves ``BinaryFlatIndex``; ``ShardedSparseIndex`` serves ``SparseSessionIndex``; ``ShardedJaccardIndex`` serves
-``JaccardIndex`` (its band counts by two all-reduces).  All of them merge through the one ``sss_topk_merge`` -- (score desc, id asc) --
+``JaccardIndex`` and ``ShardedProductTypeIndex`` ``ProductTypeIndex`` (their band counts by two all-reduces).  All of
+them merge through the one ``sss_topk_merge`` -- (score desc, id asc) --
 so a contract that orders ascending (L2, Hamming) crosses the exchange NEGATED: float negation is exact and
 ``(-dist desc, id asc)`` is ``(dist asc, id asc)``.
 
@@ -148,6 +149,10 @@ class JaccardEngine(_Engine):
     def local_bands(self, sets, edges):
         """This shard's (counts, first) int64 [nq, len(edges) + 1] with global ids in ``first`` (-1: none)."""
         return self.index.bands(sets, edges)
+
+
+class ProductTypeEngine(JaccardEngine):
+    """Local search, bands + merge of a ``ProductTypeIndex`` shard through libsss: ``JaccardEngine``'s calls, over bags."""
 
 
 def range_chunk_words(m: int) -> int:
@@ -368,3 +373,8 @@ class ShardedJaccardIndex(ShardedSparseIndex):
         dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
         dist.all_reduce(first, op=dist.ReduceOp.MIN, group=self.group)
         return counts, torch.where(first == INT64_MAX, torch.full_like(first, -1), first)
+
+
+class ShardedProductTypeIndex(ShardedJaccardIndex):
+    """``ProductTypeIndex`` over type bags row-sharded across ``dist`` ranks, over a ``ProductTypeEngine``:
+    ``ShardedJaccardIndex``'s shape -- top-k merged by ``sss_topk_merge``, bands by the all-reduce SUM and MIN."""

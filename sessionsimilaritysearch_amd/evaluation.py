@@ -13,8 +13,9 @@ reference's names and argument order, with ``test_data`` a ``QueryParts`` and ``
 Deviations from the reference (DESIGN.md "Scoring a result"): an id of -1 in ``I`` is a missing neighbour (it scores 0
 and is never a hit, but keeps its rank; the reference would wrap to the last session), and ``get_cur_map`` /
 ``get_all_map`` apply ``get_future_map``'s rule to the ``cur`` / ``all`` item sets (the reference's two index an older
-dataset layout).  The string metrics (``get_query_metric``, the Levenshtein and product-type kinds of ``get_score``) are
-out of scope.
+dataset layout).  ``get_ave_score`` / ``get_recall`` also take ``'all_product_type_score'``, the kind the reference is
+configured with, over type bags (``product_types.type_bags``; score of record: ``include/sss_ptype.h``).  The string
+metrics (``get_query_metric``, the Levenshtein kinds of ``get_score``) are out of scope.
 """
 from __future__ import annotations
 
@@ -30,6 +31,7 @@ from .sparse import SessionVectors, _ptr_of, session_vectors
 MAX_K = 1024
 PARTS = ("cur", "future", "all")
 _SIM_PART = {"cur_jaccard": "cur", "all_jaccard": "all"}
+PRODUCT_TYPE = "all_product_type_score"
 
 
 class QueryParts(NamedTuple):
@@ -187,20 +189,37 @@ for _name, _ref in (("get_cur_jaccard", "286-297"), ("get_future_jaccard", "331-
 
 def _sim_part(sim_type: str) -> str:
     if sim_type not in _SIM_PART:
-        raise ValueError(f"sim_type must be 'all_jaccard' or 'cur_jaccard' (the string metrics are out of scope), got {sim_type!r}")
+        raise ValueError(f"sim_type must be 'all_jaccard', 'cur_jaccard' or '{PRODUCT_TYPE}' (the string metrics are out of scope), "
+                         f"got {sim_type!r}")
     return _SIM_PART[sim_type]
+
+
+def _type_scores32(I, test_bags, train_bags) -> torch.Tensor:
+    """float32 of the product-type score of record of every pair, a missing neighbour scoring 0: what the reference's
+    ``gt = np.zeros_like(I, dtype=np.float32)`` holds."""
+    from .product_types import bag_pair_scores
+    return torch.nan_to_num(bag_pair_scores(I, test_bags, train_bags), nan=0.0).float()
 
 
 def get_ave_score(I, test_data, train_data, sim_type) -> float:
     """Drop-in for the reference's ``get_ave_score`` (fine_tune_ours.py:90-97) for the two item-set kinds of
     ``get_score``: 'all_jaccard' (raises ZeroDivisionError on an empty union, as the reference does) and 'cur_jaccard'
-    (an empty union scores 0)."""
+    (an empty union scores 0); and for 'all_product_type_score', the kind the reference is configured with: ``test_data`` is
+    then the type bags of ``seq[i] + tar[i]`` (``product_types.type_bags(ActionTable.concat(seq, tar), ...)``) and
+    ``train_data`` the corpus bags.  Every pair score is rounded to float32 first, their mean is taken in float64."""
+    if sim_type == PRODUCT_TYPE:
+        s = _type_scores32(I, test_data, train_data)
+        return float(s.double().sum().item()) / s.numel() if s.numel() else float("nan")
     return _ave_score(part_scores(I, _part(test_data, _sim_part(sim_type)), train_data), sim_type)
 
 
 def get_recall(test_data, train_data, I, sim_type, thres) -> float:
     """Drop-in for the reference's ``get_recall`` (test_amazon_filterd.py:443-450): the share of the K neighbours whose
-    float32 pair score exceeds ``thres``, averaged over the queries."""
+    float32 pair score exceeds ``thres``, averaged over the queries.  'all_product_type_score': as ``get_ave_score``."""
+    if sim_type == PRODUCT_TYPE:
+        s = _type_scores32(I, test_data, train_data)
+        above = (s > torch.tensor(float(thres), dtype=torch.float32, device=s.device)).sum(1)
+        return _mean(above.cpu().numpy()) / s.shape[1]
     return _above(part_scores(I, _part(test_data, _sim_part(sim_type)), train_data, thres), sim_type)
 
 
