@@ -9,7 +9,7 @@ popularity from a seeded table, a tenth of the items none.  Prints one JSON line
   mine_triples_ms            mine_triples: bands, one pair-score launch and the copies to the host; wall clock, median
 and "ratio": ptype / jaccard of each figure.  The weighted walk stages 16 (type, count) entries a row where the item-set walk
 stages 32 items; type bags are shorter than item sets (several items share a type), which the two nnz figures show.
-A report, not a gate."""
+A report, not a gate.  --lib PATH times another build of libsss.so with the same C ABI (another commit's)."""
 import argparse
 import json
 import os
@@ -22,7 +22,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench_jaccard import event_median_ms, kernel_medians_ms, wall_median_ms  # noqa: E402
-from sessionsimilaritysearch_amd import jaccard, product_types, sparse  # noqa: E402
+from sessionsimilaritysearch_amd import _lib, jaccard, product_types, sparse  # noqa: E402
 from sessionsimilaritysearch_amd.sessions import ASIN_NUM, synthetic_actions  # noqa: E402
 
 
@@ -63,12 +63,16 @@ def main():
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--types", type=int, default=500)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--lib", default=None)
     a = ap.parse_args()
+    if a.lib:
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     dev = torch.device("cuda", 0)
     edges = (0.2, 0.8)
     ca, qa = synthetic_actions(a.n, 1), synthetic_actions(a.nq, 2)
     ty = torch.from_numpy(type_table(a.types, 3)).to(dev)
-    out = {"n": a.n, "nq": a.nq, "k": a.k, "edges": edges, "n_items": ASIN_NUM, "n_types": a.types, "reps": a.reps}
+    out = {"n": a.n, "nq": a.nq, "k": a.k, "edges": edges, "n_items": ASIN_NUM, "n_types": a.types, "reps": a.reps,
+           "lib": _lib.LIB_PATH if a.lib else "default"}
     cb, qb = product_types.type_bags(ca, ty, a.types, dev), product_types.type_bags(qa, ty, a.types, dev)
     cs, qs = sparse.session_vectors(ca, "binary", device=dev), sparse.session_vectors(qa, "binary", device=dev)
     pi = product_types.ProductTypeIndex(a.types, dev).add(cb)

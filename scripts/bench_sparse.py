@@ -8,7 +8,8 @@ Prints one JSON line, per mode:
                             find_K_sparse_dense does it; single-threaded, as scipy's product is) on the first
                             --host-queries queries, scaled to the batch
 and for the builder the device time of its two kernels (binary, 1M sessions) beside the wall time of
-session_vectors, which also uploads the action table and reads the total back (medians after warm-up, both)."""
+session_vectors, which also uploads the action table and reads the total back (medians after warm-up, both).
+--lib PATH times another build of libsss.so with the same C ABI (another commit's: DESIGN.md 5.11)."""
 import argparse
 import json
 import os
@@ -21,7 +22,7 @@ import torch
 from torch.profiler import ProfilerActivity, profile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from sessionsimilaritysearch_amd import sparse  # noqa: E402
+from sessionsimilaritysearch_amd import _lib, sparse  # noqa: E402
 from sessionsimilaritysearch_amd.sessions import ASIN_NUM, synthetic_actions  # noqa: E402
 
 HBM_BYTES_PER_S = 8.0e12
@@ -67,10 +68,13 @@ def main():
     ap.add_argument("--lammy", type=float, default=1.04)
     ap.add_argument("--host-queries", type=int, default=8)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--lib", default=None)
     a = ap.parse_args()
+    if a.lib:
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     dev = torch.device("cuda", 0)
     corpus_actions, query_actions = synthetic_actions(a.n, 1), synthetic_actions(a.nq, 2)
-    out = {"n": a.n, "nq": a.nq, "k": a.k, "n_items": ASIN_NUM, "reps": a.reps}
+    out = {"n": a.n, "nq": a.nq, "k": a.k, "n_items": ASIN_NUM, "reps": a.reps, "lib": _lib.LIB_PATH if a.lib else "default"}
     build = lambda: sparse.session_vectors(corpus_actions, "binary", device=dev)
     kb = kernel_medians_ms(build, 1, 3)
     out["builder_kernels_ms"] = {k: round(v, 4) for k, v in kb.items() if "k_svec" in k}

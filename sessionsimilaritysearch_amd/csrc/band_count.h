@@ -1,6 +1,6 @@
-// Internal: the band counts of the ground-truth kernels (k_jaccard_bands in jaccard.hip, k_ptype_bands in ptype.hip).  Both
-// walk csr_walk.h's rows, turn every (query, row) pair into one float64 score, and need, per query, the rows of every band
-// and the lowest row in it.  What differs is the walk and the score; the ballot and the flush after it are here, once.
+// Internal: the band kernels of the ground-truth kinds (k_jaccard_bands in jaccard.hip, k_ptype_bands in ptype.hip).  Both
+// walk csr_walk.h's rows, turn every (query, row) pair into one float64 score (their Kind's pair), and need, per query, the
+// rows of every band and the lowest row in it.  The frame (csr_bands), the ballot and the flush are here, once.
 //
 //   per query one ballot per band over the wave (the popcount is the count; the lowest set lane is the lowest row, rows
 //   ascend with the lane); the four waves' words of BD_QRUN queries meet in LDS and one thread per (query, band) adds the
@@ -22,14 +22,6 @@ struct BandEdges { double e[BD_MAX_EDGES]; };   // unused edges are +inf: no sco
 // (rows of the band in the wave) << 8 | its lowest lane; 0: none.  One per workgroup, in LDS.
 using BandWords = int[CSR_ROWS / 64][BD_QRUN][BD_BANDS];
 
-// A band kernel walks its queries in runs of BD_QRUN (workgroup-uniform bounds: band_flush's barriers are met by all):
-//
-//     for (int f0 = f_lo; f0 < f_hi; f0 += BD_QRUN) {
-//         const int fe = min(f0 + BD_QRUN, f_hi);
-//         R.each_space([&](auto V) { for (int f = f0; f < fe; ++f) band_ballot(s_tot, f - f0, row < n, <score of (f, row)>, E, nb); });
-//         band_flush(s_tot, f0, fe, nb, row0, id_offset, counts, first_out);
-//     }
-//
 // band_ballot: the band of the thread's score (the number of edges it reaches, a float64 >=), one ballot per band over the
 // wave, lane b keeping band b's word in the run's slot.  `live`: the thread's row exists.
 __device__ __forceinline__ void band_ballot(BandWords& s_tot, int slot, bool live, double s, const BandEdges& E, int nb) {
@@ -72,33 +64,39 @@ __device__ __forceinline__ void band_flush(BandWords& s_tot, int f0, int fe, int
     __syncthreads();
 }
 
-// ------------------------------------------------------------------------------ host
-// The band arguments every entry point takes, checked (messages start with `what`), the edges copied into *E, and counts /
-// first initialised on the stream.  SSS_OK, SSS_EINVAL or SSS_EHIP.
-static int band_args(const char* what, const double* edges, int n_edges, long id_offset, long nq, long n, int64_t* counts,
-                     int64_t* first, BandEdges* E, hipStream_t st) {
-    if (n_edges < 1 || n_edges > BD_MAX_EDGES) { set_error("%s: need 1 <= n_edges <= 7", what); return SSS_EINVAL; }
-    if (!edges || !counts || !first) {
-        set_error("%s: a null pointer (edges, counts and first are required)", what);
-        return SSS_EINVAL;
+// THE BAND FRAME: the band counts and first rows of the workgroup's rows and queries under Kind::pair, the queries in runs
+// of BD_QRUN (workgroup-uniform bounds: band_flush's barriers are met by all).  grid: csr_grid's.
+template <class Kind>
+__device__ __forceinline__ void csr_bands(const CsrSets& Q, int nq, int q_per, const CsrSets& C, long n, const BandEdges& E, int nb,
+                                          long id_offset, unsigned long long* __restrict__ counts,
+                                          unsigned long long* __restrict__ first_out) {
+    __shared__ int cols[CSR_LDS_WORDS];
+    __shared__ BandWords s_tot;
+    const long row0 = (long)blockIdx.x * CSR_ROWS, row = row0 + threadIdx.x;
+    const auto R = csr_stage<Kind>(cols, C, row, n);
+    const auto state = Kind::row_state(R);
+    int f_lo;
+    const int f_hi = csr_query_range(nq, q_per, &f_lo);
+    for (int f0 = f_lo; f0 < f_hi; f0 += BD_QRUN) {
+        const int fe = f0 + BD_QRUN < f_hi ? f0 + BD_QRUN : f_hi;
+        R.each_space([&](auto V) {
+            for (int f = f0; f < fe; ++f) {
+                const long q0 = Q.ptr[f];
+                band_ballot(s_tot, f - f0, row < n, Kind::pair(Q, q0, csr_len(q0, Q.ptr[f + 1]), V, state), E, nb);
+            }
+        });
+        band_flush(s_tot, f0, fe, nb, row0, id_offset, counts, first_out);
     }
-    if (id_offset < 0 || id_offset > INT64_MAX - n) {
-        set_error("%s: need 0 <= id_offset <= 2^63 - 1 - n (-1 marks a band without a row)", what);
-        return SSS_EINVAL;
-    }
-    for (int e = 0; e < BD_MAX_EDGES; ++e) {
-        E->e[e] = e < n_edges ? edges[e] : (double)INFINITY;
-        if (e < n_edges && (!isfinite(E->e[e]) || (e > 0 && !(E->e[e] > E->e[e - 1])))) {
-            set_error("%s: edges must be finite and strictly ascending (edge %d)", what, e);
-            return SSS_EINVAL;
-        }
-    }
-    const size_t bytes = (size_t)nq * (n_edges + 1) * sizeof(int64_t);
-    if (hipMemsetAsync(counts, 0, bytes, st) != hipSuccess || hipMemsetAsync(first, 0xFF, bytes, st) != hipSuccess) {
-        set_error("%s: memset failed", what);
-        return SSS_EHIP;
-    }
-    return SSS_OK;
 }
+
+// ------------------------------------------------------------------------------ host (defined in jaccard.hip)
+// A kind's band kernel: (qptr, qitems, qw, nq, q_per, cptr, citems, cw, n, E, nb, id_offset, counts, first), on csr_grid's grid.
+using BandKernel = void (*)(const long*, const int*, const float*, int, int, const long*, const int*, const float*, long, BandEdges, int,
+                            long, unsigned long long*, unsigned long long*);
+// A *_bands entry point: csr_args_ok, the band arguments (1..7 finite ascending edges, no null pointer, an id_offset that
+// leaves -1 free), counts / first initialised on the stream, the launch of `kernel` (`name`) and its status.  Messages start
+// with `what`.
+int band_counts(const char* what, const char* name, BandKernel kernel, const CsrSets& Q, long nq, const CsrSets& C, long n, bool weighted,
+                const double* edges, int n_edges, long id_offset, int64_t* counts, int64_t* first, hipStream_t st);
 
 }  // namespace sss

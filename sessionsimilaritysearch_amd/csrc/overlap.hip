@@ -65,16 +65,7 @@ __global__ __launch_bounds__(OV_WAVES * 64) void k_item_overlap(const long* __re
             const int j = jb + lane;
             long c0 = 0;
             int len = -1, cnt = 0;
-            if (j < K) {
-                const long id = I[(size_t)i * K + j];
-                const unsigned long r = (unsigned long)id - (unsigned long)id_offset;
-                if (id != -1 && r < (unsigned long)n) {
-                    c0 = cptr[r];
-                    len = csr_len(c0, cptr[r + 1]);
-                } else if (id != -1) {
-                    bad = true;
-                }
-            }
+            if (j < K) len = csr_neighbour(cptr, n, I[(size_t)i * K + j], id_offset, &c0, &bad);
             if (len <= OV_LONG && ql > 0)
                 for (int e = 0; e < len; ++e) cnt += has(citems[c0 + e]) ? 1 : 0;
             for (unsigned long long todo = __builtin_amdgcn_ballot_w64(len > OV_LONG && ql > 0); todo; todo &= todo - 1) {

@@ -27,9 +27,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._device import exhaustive_chunk
 from .evaluation import item_overlap
-from .sparse import CsrIndex, SessionVectors, _ptr_of, query_pieces
+from .sparse import CsrIndex, SessionVectors, _ptr_of, device_vectors, query_pieces
 
 MAX_EDGES = 7
 MAX_QUERIES = 65535                  # per call of either entry point (include/sss_jaccard.h)
@@ -88,14 +87,7 @@ class JaccardIndex(BandIndex):
         return SessionVectors(self._ptr, self._items, torch.zeros(self._items.numel(), dtype=torch.float32, device=self.device))
 
     def _take(self, v, what) -> SessionVectors:
-        if not isinstance(v, SessionVectors):
-            raise TypeError(f"{what}: expected SessionVectors, got {type(v).__name__}")
-        _lib.require_cuda(v.ptr, "ptr", torch.int64)
-        _lib.require_cuda(v.items, "items", torch.int32)
-        return v.check(self.n_items)
-
-    def _pieces(self, nq, n):
-        return query_chunks(nq, exhaustive_chunk(n, 4))
+        return device_vectors(v, what, weighted=False).check(self.n_items)
 
     def _topk(self, L, q, lo, m, n, k, d_ptr, i_ptr, st):
         ws = self._ws.get(L.sss_jaccard_topk_workspace_bytes(m, n))

@@ -19,11 +19,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._device import exhaustive_chunk
 from .index import _dev
 from .jaccard import BandIndex, mine_triples, neighbourhood_recall, query_chunks  # noqa: F401  (the two functions: re-exported)
 from .sessions import ActionTable
-from .sparse import MAX_ITEMS, SessionVectors, _ptr_of
+from .sparse import MAX_ITEMS, SessionVectors, _ptr_of, device_vectors, rows_of_sessions
 
 MAX_K = 1024
 MAX_NORM2 = 2 ** 26                  # a row's sum of squared counts (include/sss_ptype.h): dot < 2^31, nq2 * nc2 <= 2^52
@@ -46,48 +45,19 @@ def type_bags(actions: ActionTable, item_type, n_types: int | None = None, devic
         raise ValueError("n_types must be in (0, 2^31)")
     n_types, n_items = int(n_types), int(ty.numel())
     dev = _dev(device)
-    S = actions.num_sessions
-    if S == 0:
-        return SessionVectors(torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
-                              torch.zeros(0, dtype=torch.float32, device=dev))
-    L, st = _lib.lib(), _lib.stream_ptr(dev)
     ty = ty.to(dev).clamp(-2, 2 ** 31 - 1).to(torch.int32).contiguous()       # an int64 id beyond int32 stays out of range
-    sp = torch.from_numpy(np.ascontiguousarray(actions.sess_ptr, dtype=np.int64)).to(dev)
-    T = max(1, int(actions.is_search.shape[0]))
-    isr = torch.zeros(T, dtype=torch.uint8, device=dev)
-    item = torch.zeros(T, dtype=torch.int64, device=dev)
-    isr[:actions.is_search.shape[0]] = torch.from_numpy(np.ascontiguousarray(actions.is_search, dtype=np.uint8)).to(dev)
-    item[:actions.item_id.shape[0]] = torch.from_numpy(np.ascontiguousarray(actions.item_id, dtype=np.int64)).to(dev)
-    counts = torch.empty(S, dtype=torch.int32, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(L.sss_type_bags_count(sp.data_ptr(), isr.data_ptr(), item.data_ptr(), S, ty.data_ptr(), n_items, n_types,
-                                     counts.data_ptr(), err.data_ptr(), st), "sss_type_bags_count")
-    ptr = torch.zeros(S + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(counts, 0, out=ptr[1:])
-    nnz = int(ptr[-1].item())                            # the one host read: sizes the output
-    items = torch.empty(nnz + 1, dtype=torch.int32, device=dev)
-    weights = torch.empty(nnz + 1, dtype=torch.float32, device=dev)
-    _lib.check(L.sss_type_bags_fill(sp.data_ptr(), isr.data_ptr(), item.data_ptr(), S, ty.data_ptr(), n_items, n_types, ptr.data_ptr(),
-                                    items.data_ptr(), weights.data_ptr(), err.data_ptr(), st), "sss_type_bags_fill")
-    flags = int(err.item())
-    if flags & 1:
-        raise _lib.SssError(f"type_bags: a session has more than {MAX_ITEMS} item actions")
-    if flags & 2:
-        raise _lib.SssError(f"type_bags: an item id lies outside [0, {n_items})")
-    if flags & 4:
-        raise _lib.SssError(f"type_bags: item_type holds a type id outside [-1, {n_types})")
-    return SessionVectors(ptr, items[:nnz], weights[:nnz])
+    args = (ty.data_ptr(), n_items, n_types)
+    return rows_of_sessions(actions, dev, "sss_type_bags_count", args, "sss_type_bags_fill", args,
+                            {1: f"type_bags: a session has more than {MAX_ITEMS} item actions",
+                             2: f"type_bags: an item id lies outside [0, {n_items})",
+                             4: f"type_bags: item_type holds a type id outside [-1, {n_types})"})
 
 
 def check_bags(v, n_types: int | None = None, what: str = "bags") -> SessionVectors:
     """``v`` as a checked batch of type bags, or TypeError / SssError / ValueError: device ``SessionVectors``, well formed
     (``SessionVectors.check``), every count a positive integer and every row's sum of squared counts ``<= 2^26`` -- the
     range in which the score of record is exact integer arithmetic.  Device reductions and one host read, once per batch."""
-    if not isinstance(v, SessionVectors):
-        raise TypeError(f"{what}: expected SessionVectors (product_types.type_bags), got {type(v).__name__}")
-    _lib.require_cuda(v.ptr, "ptr", torch.int64)
-    _lib.require_cuda(v.items, "items", torch.int32)
-    _lib.require_cuda(v.weights, "weights", torch.float32)
+    device_vectors(v, what, expected="SessionVectors (product_types.type_bags)")
     if n_types is not None or not getattr(v, "_checked", ()):                # checked against any vocabulary: well formed
         v.check(n_types)
     if getattr(v, "_bags_checked", False):
@@ -160,9 +130,6 @@ class ProductTypeIndex(BandIndex):
 
     def _take(self, v, what) -> SessionVectors:
         return check_bags(v, self.n_items, what)
-
-    def _pieces(self, nq, n):
-        return query_chunks(nq, exhaustive_chunk(n, 4))
 
     def _topk(self, L, q, lo, m, n, k, d_ptr, i_ptr, st):
         ws = self._ws.get(L.sss_ptype_topk_workspace_bytes(m, n))

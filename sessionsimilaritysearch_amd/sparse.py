@@ -88,17 +88,24 @@ def _device_triple(ptr, items, weights, device) -> SessionVectors:
     return SessionVectors(torch.from_numpy(np.ascontiguousarray(ptr, dtype=np.int64)).to(device), it[:nnz], w[:nnz])
 
 
-def session_vectors(actions: ActionTable, mode: str = "binary", lammy=None, device=None, n_items: int | None = None) -> SessionVectors:
-    """All sessions of ``actions`` as sparse vectors: ``mode="binary"`` (SKNN queries and every corpus row,
-    ``sequence_to_binary_vec`` + ``normalize``) or ``mode="stan"`` (``sequence_to_stan_vec``; ``lammy`` is required --
-    the reference's ``CFG.STAN_lammy`` is commented out, there is no default).  Batched replacement of the reference's
-    per-session ``sequence_to_*_vec`` calls.  ``n_items``: the vocabulary the ids are checked against (default: any
-    non-negative int32)."""
-    if mode not in _MODES:
-        raise ValueError(f"mode must be 'binary' or 'stan', got {mode!r}")
-    if mode == "stan" and (lammy is None or not np.isfinite(lammy) or lammy <= 0):
-        raise ValueError("mode='stan' needs a finite lammy > 0")
-    dev = _dev(device)
+def device_vectors(v, what: str, weighted: bool = True, expected: str = "SessionVectors") -> SessionVectors:
+    """``v``, a ``SessionVectors`` of contiguous CUDA tensors of the C ABI's dtypes (the weights only when ``weighted``), or
+    TypeError (it names ``expected``) / SssError.  What every index checks before ``SessionVectors.check``; no host sync."""
+    if not isinstance(v, SessionVectors):
+        raise TypeError(f"{what}: expected {expected}, got {type(v).__name__}")
+    _lib.require_cuda(v.ptr, "ptr", torch.int64)
+    _lib.require_cuda(v.items, "items", torch.int32)
+    if weighted:
+        _lib.require_cuda(v.weights, "weights", torch.float32)
+    return v
+
+
+def rows_of_sessions(actions: ActionTable, dev, count: str, count_args, fill: str, fill_args, messages) -> SessionVectors:
+    """One CSR row per session of ``actions`` by a pair of builder entry points (``count`` / ``fill``, by name): the
+    ``ActionTable`` staged on the device (``sess_ptr``, ``is_search``, ``item_id``; at least one entry, so an action-free
+    table still has an allocation behind its pointers), then the two sweeps -- count, prefix sum, the one host read that
+    sizes the output, fill -- and the err word: ``messages`` maps its bits to the ``SssError`` text, the lowest bit first.
+    ``count_args`` / ``fill_args``: what each call takes between the session count and its outputs."""
     S = actions.num_sessions
     if S == 0:
         return SessionVectors(torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
@@ -110,25 +117,38 @@ def session_vectors(actions: ActionTable, mode: str = "binary", lammy=None, devi
     item = torch.zeros(T, dtype=torch.int64, device=dev)
     isr[:actions.is_search.shape[0]] = torch.from_numpy(np.ascontiguousarray(actions.is_search, dtype=np.uint8)).to(dev)
     item[:actions.item_id.shape[0]] = torch.from_numpy(np.ascontiguousarray(actions.item_id, dtype=np.int64)).to(dev)
-    vocab = int(n_items) if n_items is not None else 2 ** 31 - 1
+    head = (sp.data_ptr(), isr.data_ptr(), item.data_ptr(), S)
     counts = torch.empty(S, dtype=torch.int32, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(L.sss_session_vectors_count(sp.data_ptr(), isr.data_ptr(), item.data_ptr(), S, vocab, counts.data_ptr(),
-                                           err.data_ptr(), st), "sss_session_vectors_count")
+    _lib.check(getattr(L, count)(*head, *count_args, counts.data_ptr(), err.data_ptr(), st), count)
     ptr = torch.zeros(S + 1, dtype=torch.int64, device=dev)
     torch.cumsum(counts, 0, out=ptr[1:])
     nnz = int(ptr[-1].item())                            # the one host read: sizes the output
     items = torch.empty(nnz + 1, dtype=torch.int32, device=dev)
     weights = torch.empty(nnz + 1, dtype=torch.float32, device=dev)
-    _lib.check(L.sss_session_vectors_fill(sp.data_ptr(), isr.data_ptr(), item.data_ptr(), S, vocab, _MODES[mode],
-                                          float(lammy) if mode == "stan" else 0.0, ptr.data_ptr(), items.data_ptr(),
-                                          weights.data_ptr(), err.data_ptr(), st), "sss_session_vectors_fill")
+    _lib.check(getattr(L, fill)(*head, *fill_args, ptr.data_ptr(), items.data_ptr(), weights.data_ptr(), err.data_ptr(), st), fill)
     flags = int(err.item())
-    if flags & 1:
-        raise _lib.SssError(f"session_vectors: a session has more than {MAX_ITEMS} item actions")
-    if flags & 2:
-        raise _lib.SssError(f"session_vectors: an item id lies outside [0, {vocab})")
+    for bit, text in messages.items():
+        if flags & bit:
+            raise _lib.SssError(text)
     return SessionVectors(ptr, items[:nnz], weights[:nnz])
+
+
+def session_vectors(actions: ActionTable, mode: str = "binary", lammy=None, device=None, n_items: int | None = None) -> SessionVectors:
+    """All sessions of ``actions`` as sparse vectors: ``mode="binary"`` (SKNN queries and every corpus row,
+    ``sequence_to_binary_vec`` + ``normalize``) or ``mode="stan"`` (``sequence_to_stan_vec``; ``lammy`` is required --
+    the reference's ``CFG.STAN_lammy`` is commented out, there is no default).  Batched replacement of the reference's
+    per-session ``sequence_to_*_vec`` calls.  ``n_items``: the vocabulary the ids are checked against (default: any
+    non-negative int32)."""
+    if mode not in _MODES:
+        raise ValueError(f"mode must be 'binary' or 'stan', got {mode!r}")
+    if mode == "stan" and (lammy is None or not np.isfinite(lammy) or lammy <= 0):
+        raise ValueError("mode='stan' needs a finite lammy > 0")
+    vocab = int(n_items) if n_items is not None else 2 ** 31 - 1
+    return rows_of_sessions(actions, _dev(device), "sss_session_vectors_count", (vocab,), "sss_session_vectors_fill",
+                            (vocab, _MODES[mode], float(lammy) if mode == "stan" else 0.0),
+                            {1: f"session_vectors: a session has more than {MAX_ITEMS} item actions",
+                             2: f"session_vectors: an item id lies outside [0, {vocab})"})
 
 
 def dense_to_vectors(x: np.ndarray, device=None) -> SessionVectors:
@@ -157,10 +177,10 @@ def query_pieces(nq: int, per: int):
 
 
 class CsrIndex:
-    """What the exact indexes over CSR rows share (``SparseSessionIndex``, ``jaccard.JaccardIndex``): the corpus on the
-    device, with a weights column when ``weighted``, and the top-k call in query pieces.  A subclass gives ``_take(v, what)
-    -> SessionVectors`` (checked), ``_pieces(nq, n)`` -- in its own module: the tests patch each module's
-    ``exhaustive_chunk`` -- and ``_topk``, its one library call."""
+    """What the exact indexes over CSR rows share (``SparseSessionIndex``, ``jaccard.JaccardIndex``,
+    ``product_types.ProductTypeIndex``): the corpus on the device, with a weights column when ``weighted``, and the top-k
+    call in query pieces under the exhaustive score budget.  A subclass gives ``_take(v, what) -> SessionVectors`` (checked)
+    and ``_topk``, its one library call."""
     weighted = True
 
     def __init__(self, n_items: int, device=None):
@@ -195,6 +215,9 @@ class CsrIndex:
         if self.weighted:
             self._weights = grown(self._weights, v.weights)
         return self
+
+    def _pieces(self, nq, n):
+        return query_pieces(nq, exhaustive_chunk(n, 4))                  # at most the 65535 queries a call takes
 
     def _each_piece(self, pieces, call):
         """``call(lo, m)`` per piece of the query batch, counted in ``last_chunks``."""
@@ -245,15 +268,7 @@ class SparseSessionIndex(CsrIndex):
             if v.ndim != 2 or v.shape[1] != self.n_items:
                 raise ValueError(f"{what}: expected [rows, {self.n_items}], got {v.shape}")
             return dense_to_vectors(v, self.device)
-        if not isinstance(v, SessionVectors):
-            raise TypeError(f"{what}: expected SessionVectors or a dense [rows, n_items] numpy array")
-        _lib.require_cuda(v.ptr, "ptr", torch.int64)
-        _lib.require_cuda(v.items, "items", torch.int32)
-        _lib.require_cuda(v.weights, "weights", torch.float32)
-        return v.check(self.n_items)
-
-    def _pieces(self, nq, n):
-        return query_pieces(nq, exhaustive_chunk(n, 4))
+        return device_vectors(v, what, expected="SessionVectors or a dense [rows, n_items] numpy array").check(self.n_items)
 
     def _topk(self, L, q, lo, m, n, k, d_ptr, i_ptr, st):
         # items / weights of an all-empty batch: zero entries, but sliced from a one-entry allocation (never NULL)

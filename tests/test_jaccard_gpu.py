@@ -277,7 +277,7 @@ def test_query_chunks_of_seven(cuda, monkeypatch):
     G = gold(cuda)
     D1, I1 = (t.clone() for t in G.index.search(G.parts.all, 20))
     assert G.index.last_chunks == 1
-    monkeypatch.setattr(jaccard, "exhaustive_chunk", lambda n, bytes_per_score: 7)
+    monkeypatch.setattr(sparse, "exhaustive_chunk", lambda n, bytes_per_score: 7)       # CsrIndex._pieces reads it
     D7, I7 = G.index.search(G.parts.all, 20)
     assert G.index.last_chunks == 7 and torch.equal(D1, D7) and torch.equal(I1, I7)
     G.index.bands(G.parts.all, (0.2, 0.8))

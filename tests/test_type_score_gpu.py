@@ -389,7 +389,7 @@ def test_query_chunks_of_seven(cuda, monkeypatch):
     G = gold(cuda)
     D1, I1 = (x.clone() for x in G.index.search(G.bags, 20))
     assert G.index.last_chunks == 1
-    monkeypatch.setattr(pt, "exhaustive_chunk", lambda n, bytes_per_score: 7)
+    monkeypatch.setattr(sparse, "exhaustive_chunk", lambda n, bytes_per_score: 7)       # CsrIndex._pieces reads it
     D7, I7 = G.index.search(G.bags, 20)
     assert G.index.last_chunks == 7 and torch.equal(D1, D7) and torch.equal(I1, I7)
     G.index.bands(G.bags, (0.2, 0.8))
@@ -497,7 +497,15 @@ def raw_bags(tab, item_type, n_types, want, stream=None):
 def builder_sessions():
     """Sessions at the builder's edges over 40 items: empty, searches only, untyped items only, one type through three items
     and three times through one (a count of 3 either way), exactly 64 item actions of one type (a count of 64), 64 item
-    actions among 90 actions (more than one 64-action step), every type once, and 300 random ones."""
+    actions among 90 actions (more than one 64-action step), every type once, 64 item actions among exactly 128 and among 129
+    actions, the last action an item action (two full steps; a third step of one action), and 300 random ones."""
+
+    def spread(n_raw):
+        r = np.random.default_rng(n_raw)
+        s = [None] * n_raw
+        for at in (*r.choice(n_raw - 1, 63, replace=False), n_raw - 1):
+            s[at] = int(r.integers(0, 40))
+        return s
     rng = np.random.default_rng(64)
     item_type = rng.integers(0, 9, 40).astype(np.int32)
     item_type[[3, 11, 30]] = -1
@@ -506,7 +514,7 @@ def builder_sessions():
     mixed = [None] * 90
     for i, at in enumerate(np.sort(rng.choice(90, 64, replace=False))):
         mixed[at] = int(rng.integers(0, 40))
-    fixed = [[], [None, None], [3, 11, 30, 3], [0, 1, 2], [2, 2, None, 2], [39] * 64, mixed, list(range(40))]
+    fixed = [[], [None, None], [3, 11, 30, 3], [0, 1, 2], [2, 2, None, 2], [39] * 64, mixed, list(range(40)), spread(128), spread(129)]
     rand = [[None if rng.random() < 0.3 else int((rng.zipf(1.3) - 1) % 40) for _ in range(int(rng.integers(1, 20)))] for _ in range(300)]
     return fixed + rand, item_type
 
