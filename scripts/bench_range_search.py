@@ -3,6 +3,8 @@
 Two radii: one keeping about 10 rows per query, one about 1000 (picked from the scores of the first queries' top 1024).
 Device events around each call (warmed up), median of --iters calls.  Prints one JSON line: ms per call, results per
 query, the route and the overflow count of every range search.
+--metric l2 has no fused range route: it times the exhaustive range kernels (scores, count, scan, compact).
+--lib PATH times another build of libsss.so with the same C ABI (another commit's).
 """
 import argparse
 import json
@@ -14,6 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from sessionsimilaritysearch_amd import _lib  # noqa: E402
 from sessionsimilaritysearch_amd.index import FlatIndex, normalize_  # noqa: E402
 
 
@@ -39,7 +42,11 @@ def main():
     ap.add_argument("--nq", type=int, default=1024)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--metric", choices=("ip", "l2"), default="ip")
+    ap.add_argument("--lib", default=None)
     a = ap.parse_args()
+    if a.lib:
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev)
     g.manual_seed(7)
@@ -47,10 +54,10 @@ def main():
     normalize_(c)
     q = torch.randn((a.nq, a.d), device=dev, generator=g)
     normalize_(q)
-    idx = FlatIndex(a.d, "ip", dev).adopt(c)
+    idx = FlatIndex(a.d, a.metric, dev).adopt(c)
 
-    out = {"n": a.n, "d": a.d, "nq": a.nq, "iters": a.iters}
-    # radii: the 10th / 1000th best score, averaged over the first 64 queries (the index's own exact search)
+    out = {"n": a.n, "d": a.d, "nq": a.nq, "iters": a.iters, "metric": a.metric, "lib": _lib.LIB_PATH if a.lib else "default"}
+    # radii: the 10th / 1000th best score (smallest distance), averaged over the first 64 queries (the index's own exact search)
     Dk, _ = idx.search(q[:64], 1024)
     radii = {"r10": float(Dk[:, 9].mean()), "r1000": float(Dk[:, 999].mean())}
     for name, r in radii.items():

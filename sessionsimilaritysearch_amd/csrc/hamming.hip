@@ -28,7 +28,7 @@
 // split (id / 256) % S at every width, S = sss_hamming_topk_capacity / 16; sub-tiles of one tile stay in one list.
 // Registers per thread at NW = 64: query 64 + stage 16 + list 32 + the row words in flight; no scratch (see
 // DESIGN.md for the compiler's figures and the occupancy).
-#include "sss_common.h"
+#include "block_select.h"
 
 namespace sss {
 
@@ -227,19 +227,7 @@ __global__ __launch_bounds__(HSEL_THREADS) void k_hamming_select(const unsigned 
     if (tid == 0) s_minlast = ~0ull;
     __syncthreads();
     atomicMin(&s_minlast, minlast);
-    for (int kk = 2; kk <= M2; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < M2; i += HSEL_THREADS) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long a = hkeys[i], b = hkeys[ixj];
-                    const bool asc = (i & kk) == 0;
-                    if (asc ? a > b : a < b) { hkeys[i] = b; hkeys[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    sort_keys<HSEL_THREADS, false>(hkeys, M2, tid);      // ascending; padding keys are ~0
     for (int i = tid; i < k; i += HSEL_THREADS) {
         const unsigned long long v = i < M2 ? hkeys[i] : ~0ull;
         if (v != ~0ull) { D_out[(size_t)q * k + i] = (int)(v >> 32); I_out[(size_t)q * k + i] = (long)(unsigned)v + id_offset; }

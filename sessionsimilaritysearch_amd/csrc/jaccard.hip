@@ -6,7 +6,7 @@
 // Both kernels are a frame under JaccardKind, the walk of csr_walk.h over items alone, counting the hits.
 //
 //   k_jaccard_scores    csr_walk.h's score frame: float32(inter / uni) for every pair and the identity query selection;
-//                       topk_of_scores (exhaustive.hip, metric 0) is the unchanged tail
+//                       topk_of_scores (topk_scores.hip, metric 0) is the unchanged tail
 //   k_jaccard_bands     band_count.h's band frame: no matrix, a ballot per band over the wave, an LDS flush, integer atomics
 //
 // The host piece band_count.h declares for the two *_bands entry points (this one and ptype.hip's) is below.

@@ -10,7 +10,7 @@
 //                                (through item_type), the multiplicity counted over equal types
 //   k_ptype_scores               csr_walk.h's score frame under PtypeKind, the walk over (type, count) entries: a thread
 //                                owns a corpus row and takes its nc2 once after staging; the query's nq2 is wave-uniform;
-//                                float32(score) and the identity query selection; topk_of_scores (exhaustive.hip, metric 0)
+//                                float32(score) and the identity query selection; topk_of_scores (topk_scores.hip, metric 0)
 //                                is the unchanged tail
 //   k_ptype_bands                band_count.h's band frame under PtypeKind: no matrix, the float64 score itself
 //   k_ptype_pair_scores          one wave per query, lane l owns the neighbours j = l, l + 64, ... (as k_item_overlap): one

@@ -162,7 +162,14 @@ int check_scan_source(const char* what, int exact_dtype, int scan_dtype, int d, 
 ThrArgs thr_args(const void* q, const void* c_exact, int exact_dtype, int scan_dtype, int corpus_shift, float corpus_resid,
                  float corpus_max_norm, const int* qsel, long nsel, long n, int d, int k, int cap, long id_offset);
 
-// the exact top-k of a finished [nsel][n] score matrix (exhaustive.hip): the tail of the exhaustive search, also sparse.hip's
+// a float32 [nsel][n] score matrix at the head of a workspace, up to the next 256-byte boundary
+static inline size_t score_matrix_bytes(long nsel, long n) { return al256((size_t)nsel * n * 4); }
+// scores [nsel][n] of the selected queries against every row (exhaustive.hip: k_exact_scores_rows where the shape has it, else
+// k_exact_scores); lb / lb_by_row: the optional pre-test bound of k_exact_scores_rows (inner product only).
+int launch_exact_scores(const void* q, const int* qsel, long nsel, const void* c, long n, int d, int dtype, int metric, float* scores,
+                        const float* lb, int lb_by_row, hipStream_t st);
+// the exact top-k of a finished [nsel][n] score matrix (topk_scores.hip): the tail of the exhaustive search, also sparse.hip's
+constexpr int RS_MAX_K = 1024;
 size_t topk_of_scores_bytes(long nsel, long n);
 int topk_of_scores(const float* scores, const int* qsel, long nsel, long n, int k, long id_offset, int metric, float* D_out,
                    long* I_out, void* tail, hipStream_t st);

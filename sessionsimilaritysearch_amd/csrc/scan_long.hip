@@ -371,7 +371,6 @@ constexpr int LONG_MAX_K = 1024;    // what the exhaustive kernels -- the path o
 // k_select_all keeps 2 x cap keys + the exact query row + its staging tile in LDS: rows beyond 10240 bytes
 // (f32 d > 2560, bf16 d > 5120) leave room for half the capacity only.
 static int long_cap(int d, int exact_dtype) { return d * elem_bytes(exact_dtype) > 10240 ? LONG_CAP / 2 : LONG_CAP; }
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 extern "C" size_t sss_ip_topk_long_workspace_bytes(int64_t nq, int64_t n, int d, int dtype) {
     if (nq <= 0 || n <= 0 || !long_shape_ok(d, dtype, long_scan_dtype(dtype))) return 0;

@@ -2,6 +2,7 @@
 // form: rung, long rows, range search): wave primitives, the canonical float64 re-score, the scan's error bound
 // (err_bound), the proof window and the per-query bound every proof of exactness rests on, radix selection and sort.
 #pragma once
+#include "block_select.h"
 #include "scan.h"
 
 namespace sss {
@@ -360,51 +361,10 @@ __device__ __forceinline__ void query_bound(const Args& A, const char* qrow, int
 }
 
 // The k-th largest score ordinal (high word of the keys) among keys[0 .. M), k <= M, by the whole workgroup of
-// SORT_THREADS = 256 threads: a radix descent, eight bits a pass -- a 256-bin histogram (LDS atomics) of the keys
-// that still match the prefix, then the bin holding the k-th from the top (one wave: four bins a lane, a suffix
-// sum by shuffles) -- four passes over the keys instead of a sort of up to 8192 of them (round 3; it was 32 one-bit
-// passes, 3 barriers each).  s_hist: 260 shared words; every thread returns the same value.
-template <typename OrdAt>
-__device__ __forceinline__ unsigned kth_largest_of(OrdAt ord_at, int M, int k, int tid, unsigned* s_hist) {
-    unsigned prefix = 0u, mask = 0u;
-    unsigned kk = (unsigned)k;                      // rank, from the top, inside the bucket that matches the prefix
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        s_hist[tid] = 0u;
-        __syncthreads();
-        for (int x = tid; x < M; x += SORT_THREADS) {
-            const unsigned o = ord_at(x);
-            if ((o & mask) == prefix) atomicAdd(&s_hist[(o >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        if (tid < 64) {
-            const unsigned h0 = s_hist[4 * tid], h1 = s_hist[4 * tid + 1], h2 = s_hist[4 * tid + 2], h3 = s_hist[4 * tid + 3];
-            const unsigned mine = h0 + h1 + h2 + h3;
-            unsigned suf = mine;                    // sum over this lane and every higher one
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned v = (unsigned)__shfl_down((int)suf, o);
-                if (tid + o < 64) suf += v;
-            }
-            const unsigned above = suf - mine;
-            if (above < kk && suf >= kk) {          // the k-th from the top falls into this lane's four bins (exactly one lane)
-                unsigned cum = above;
-                int b = 3;
-                if (cum + h3 < kk) { cum += h3; b = 2; if (cum + h2 < kk) { cum += h2; b = 1; if (cum + h1 < kk) { cum += h1; b = 0; } } }
-                s_hist[256] = (unsigned)(4 * tid + b);
-                s_hist[257] = kk - cum;
-            }
-        }
-        __syncthreads();
-        prefix |= s_hist[256] << shift;
-        mask |= 255u << shift;
-        kk = s_hist[257];
-        __syncthreads();                            // (the two words are rewritten in the next pass)
-    }
-    return prefix;
-}
-
+// SORT_THREADS = 256 threads (block_select.h: kth_largest_of).  s_hist: RADIX_HIST_WORDS shared words; every thread
+// returns the same value.
 __device__ __forceinline__ unsigned kth_largest_ord(const unsigned long long* keys, int M, int k, int tid, unsigned* s_hist) {
-    return kth_largest_of([&](int x) { return (unsigned)(keys[x] >> 32); }, M, k, tid, s_hist);
+    return kth_largest_of<SORT_THREADS>([&](int x) { return (unsigned)(keys[x] >> 32); }, M, k, tid, s_hist);
 }
 
 // The k-th largest 64-bit KEY among keys[0 .. M) (keys are unique: score ordinal << 32 | ~row id), k <= M: the k-th largest
@@ -412,7 +372,7 @@ __device__ __forceinline__ unsigned kth_largest_ord(const unsigned long long* ke
 // result.  Whole workgroup; s_cnt: one shared word.
 __device__ __forceinline__ unsigned long long kth_largest_key(const unsigned long long* keys, int M, int k, int tid, unsigned* s_hist,
                                                               unsigned* s_cnt) {
-    const unsigned sk = kth_largest_of([&](int x) { return (unsigned)(keys[x] >> 32); }, M, k, tid, s_hist);
+    const unsigned sk = kth_largest_of<SORT_THREADS>([&](int x) { return (unsigned)(keys[x] >> 32); }, M, k, tid, s_hist);
     if (tid == 0) *s_cnt = 0u;
     __syncthreads();
     unsigned gt = 0u;
@@ -421,27 +381,13 @@ __device__ __forceinline__ unsigned long long kth_largest_key(const unsigned lon
     __syncthreads();
     const int need_eq = k - (int)*s_cnt;                                // >= 1: the k-th itself has ordinal sk
     __syncthreads();
-    const unsigned lowk = kth_largest_of([&](int x) { const unsigned long long kx = keys[x]; return (unsigned)(kx >> 32) == sk ? (unsigned)kx : 0u; },
+    const unsigned lowk = kth_largest_of<SORT_THREADS>([&](int x) { const unsigned long long kx = keys[x]; return (unsigned)(kx >> 32) == sk ? (unsigned)kx : 0u; },
                                          M, need_eq, tid, s_hist);
     return ((unsigned long long)sk << 32) | lowk;
 }
 
 // descending bitonic sort of keys[0 .. M2) (M2 a power of two) by the whole workgroup
-__device__ __forceinline__ void sort_desc(unsigned long long* keys, int M2, int tid) {
-    for (int kk = 2; kk <= M2; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int x = tid; x < M2; x += SORT_THREADS) {
-                const int ixj = x ^ j;
-                if (ixj > x) {
-                    const unsigned long long a = keys[x], b = keys[ixj];
-                    const bool desc = (x & kk) == 0;
-                    if (desc ? a < b : a > b) { keys[x] = b; keys[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
+__device__ __forceinline__ void sort_desc(unsigned long long* keys, int M2, int tid) { sort_keys<SORT_THREADS, true>(keys, M2, tid); }
 
 // Canonical re-score of the kept rows surv[0 .. keep) (scan keys: only their ids are read) by a workgroup of SORT_THREADS,
 // one thread per row for the strictly sequential float64 chain -- but rows of 1024 bytes and more come in through LDS:

@@ -194,7 +194,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_bound_prepare(const ThrArgs A)
         const unsigned long long* ck = A.cand + (size_t)i * A.cap;
         for (int x = tid; x < (int)M; x += SORT_THREADS) ords[x] = (unsigned)(ck[x] >> 32);
         __syncthreads();
-        sk = kth_largest_of([&](int x) { return ords[x]; }, (int)M, k, tid, s_hist);
+        sk = kth_largest_of<SORT_THREADS>([&](int x) { return ords[x]; }, (int)M, k, tid, s_hist);
     }
     if (tid >= 64) return;
     double B, unscale, off;

@@ -12,7 +12,7 @@
 //                                      weights
 //   k_sparse_scores                    csr_walk.h's score frame under SparseKind: one thread per corpus row, stores
 //                                      coalesced across rows
-//   topk_of_scores (exhaustive.hip)    the exact top-k of the score matrix, shared with the dense exhaustive search
+//   topk_of_scores (topk_scores.hip)   the exact top-k of the score matrix, shared with the dense exhaustive search
 //
 // The host pieces csr_walk.h declares for the three *_topk entry points (this one, jaccard.hip's, ptype.hip's) are below.
 #include <math.h>
@@ -167,12 +167,11 @@ dim3 csr_grid(long nq, long n, int* q_per) {
     return dim3((unsigned)nbx, (unsigned)ny);
 }
 
-static size_t ws_scores_bytes(long nq, long n) { return ((size_t)nq * n * 4 + 255) & ~(size_t)255; }
-static size_t ws_qsel_bytes(long nq) { return ((size_t)nq * 4 + 255) & ~(size_t)255; }
+static size_t ws_qsel_bytes(long nq) { return al256((size_t)nq * 4); }
 
 size_t score_ws_bytes(long nq, long n) {
     if (nq <= 0 || n <= 0) return 0;
-    return ws_scores_bytes(nq, n) + ws_qsel_bytes(nq) + topk_of_scores_bytes(nq, n);
+    return score_matrix_bytes(nq, n) + ws_qsel_bytes(nq) + topk_of_scores_bytes(nq, n);
 }
 
 int score_topk(const char* what, const char* name, ScoreKernel kernel, const CsrSets& Q, long nq, const CsrSets& C, long n,
@@ -190,7 +189,7 @@ int score_topk(const char* what, const char* name, ScoreKernel kernel, const Csr
         return SSS_EWORKSPACE;
     }
     float* scores = reinterpret_cast<float*>(workspace);
-    int* qsel = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + ws_scores_bytes(nq, n));
+    int* qsel = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + score_matrix_bytes(nq, n));
     void* tail = reinterpret_cast<char*>(qsel) + ws_qsel_bytes(nq);
     int q_per = 0;
     const dim3 grid = csr_grid(nq, n, &q_per);

@@ -37,6 +37,9 @@ int opt_in_lds(const void* kernel, const char* name, size_t bytes);
 constexpr int MAX_DEVICES = 64;
 int current_device();
 
+// workspace sections start on 256-byte boundaries
+static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+
 // float -> uint32 whose unsigned order equals the float order (-inf lowest, +inf highest).
 __device__ __host__ __forceinline__ uint32_t f2ord(float f) {
     uint32_t u = __builtin_bit_cast(uint32_t, f);

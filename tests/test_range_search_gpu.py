@@ -161,6 +161,41 @@ def test_shapes_without_a_scan(cuda, d, n):
     _check(got, _expected(q, c, r))
 
 
+SLAB = 16384                                                     # rows per workgroup of the exhaustive count / compaction
+
+
+def _slab_edge_case(metric, n):
+    """(c, q, per-query radii, the copies of row 7) for the exhaustive-only route at d = 96: one call whose five queries
+    keep every row, about half of them, about 20, none, and -- the radius exactly the score of a row copied to the last
+    row of the first slab and the first row of the second (where n has them) -- neither copy."""
+    rng = np.random.default_rng(65)
+    if metric == "ip":
+        c, q = _unit(rng, n, 96), _unit(rng, 5, 96)
+    else:
+        c, q = rng.standard_normal((n, 96)).astype(np.float32), rng.standard_normal((5, 96)).astype(np.float32)
+    dup = [r for r in (100, SLAB - 1, SLAB) if r < n]
+    c[dup] = c[7]
+    score = sr.canonical_scores if metric == "ip" else sr.canonical_l2
+    half = np.float32(0.0) if metric == "ip" else _radius_for(q[1:2], c, n // 2, "l2")
+    everything, nothing = (-np.inf, np.inf) if metric == "ip" else (np.inf, -np.inf)
+    r = np.array([everything, half, _radius_for(q[2:3], c, 20, metric), nothing, score(q[4:5], c[7:8])[0, 0]], np.float32)
+    return c, q, r, [7] + dup
+
+
+@pytest.mark.parametrize("metric, n", (("ip", SLAB - 1), ("ip", SLAB), ("ip", SLAB + 1), ("ip", 2 * SLAB + 1), ("l2", SLAB + 1)))
+def test_exhaustive_route_at_slab_edges(cuda, metric, n):
+    c, q, r, copies = _slab_edge_case(metric, n)
+    exp = _expected(q, c, r, metric)
+    counts = np.diff(exp[0])
+    assert counts[0] == n and n // 4 < counts[1] < 3 * n // 4 and 0 < counts[2] < 200 and counts[3] == 0 and counts[4] > 0
+    idx = build_index(c, metric, cuda)
+    lims, D, I = idx.range_search(q, r)
+    assert idx.last_range_scan == "" and idx.last_range_overflow_queries == 0
+    _check((lims, D, I), exp)
+    assert np.array_equal(I[:n], np.arange(n))                   # the query that keeps every row
+    assert not set(I[lims[4]:lims[5]].tolist()) & set(copies)    # strict: a row AT the radius does not pass
+
+
 # ------------------------------------------------------------------------------------------ 5. magnitudes
 @pytest.mark.parametrize("kind", ("auto", "split", "f32", "bf16"))
 def test_scaled_rows_and_queries(cuda, kind):
