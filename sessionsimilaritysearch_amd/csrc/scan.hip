@@ -27,7 +27,9 @@
 //   * the score matrix is never written: each lane owns one query column of the 32x32
 //     accumulators and keeps a sorted top-KP list (scores + row ids) in registers.  The scan runs
 //     in 64-row steps: a HOT loop (MFMAs, one v_max3 tree, one compare) that never writes the list
-//     state, left for a RARE insert path only when some lane's step maximum beats its threshold;
+//     state, left for a RARE insert path only when some lane's step maximum beats its threshold.  (The f32 list form
+//     for 512-byte rows decides the two 32-row halves of a step apart, each under the other half's MFMAs and across
+//     the step boundary: two exits, one per half -- scan_kernel.h, "F32S");
 //   * ADMISSION THRESHOLD shared by all workgroups of a query: every lane list belongs to one of J
 //     classes (J >= K2); slot[q][class] holds, by atomic max, the best score any list of that class
 //     has seen (cert == 1) or the largest cert-th best of such a list (cert > 1).  Classes

@@ -2,6 +2,7 @@
 // it -- scan.hip (the inner-product scans, MET = 0, and the host side) and scan_l2.hip (the L2 scans, MET = 1) -- so the
 // two sets of kernels compile side by side.  The kernel's description is at the top of scan.hip.  gfx950 only.
 #pragma once
+#include <type_traits>
 #include "scan.h"
 #include "scan_dev.h"
 
@@ -11,9 +12,11 @@
 // The f32 list form's step order for 512-byte rows (k_scan, "F32S"): 0 = the order every scan shares; bit 0 = its own loop
 // (fragments prefetched across the step boundary, tile hand-over in front of the last k-group, step scalars behind
 // k-group 0), bit 1 = the next tile's DMA one piece per k-group, bit 2 = half the max tree under the other accumulator's
-// last MFMAs.  (A/B builds: DESIGN.md 5.1.)
+// last MFMAs, bit 3 = the half-step skew: each accumulator's tree, compare and rare path under the other's MFMAs, across
+// the step boundary (needs bit 2), bit 4 = static priority 1 for waves 4-7 (not in the default: DESIGN.md 5.1).
+// (A/B builds: DESIGN.md 5.1.)
 #ifndef SSS_F32_SCHED
-#define SSS_F32_SCHED 7
+#define SSS_F32_SCHED 15
 #endif
 
 namespace sss {
@@ -651,18 +654,69 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
         //    of the next tile has landed: exactly what the barrier at the end of the step guaranteed.  The last k-group's
         //    512 cycles then cover the next tile's first fragment reads and the threshold read-back.
         //    The bootstrap tile keeps the old order (publish behind its tree, wait, barrier, bounded poll): once a launch.
-        constexpr bool SPREAD = (SSS_F32_SCHED & 2) != 0, EARLY_TREE = (SSS_F32_SCHED & 4) != 0;
+        //  * THE HALF-STEP SKEW (bit 3): each accumulator's tree, compare and rare path run under the OTHER accumulator's
+        //    MFMAs, across the step boundary.  acc0(t)'s tree and compare sit behind the second of acc1's last four MFMAs
+        //    of step t; acc0's four MFMAs of k-group 0 of step t + 1 then overwrite it (its decision is made) and acc1(t)'s
+        //    tree and compare sit behind the second of THOSE -- at least 128 pipe cycles after acc1's last MFMA was issued,
+        //    so no wait states -- followed by acc1's four MFMAs of k-group 0.  Between the last MFMA of a step and the first
+        //    of the next the plain path issues scalar instructions only.  The hot loop has two exits, one per half
+        //    (insert_block of that accumulator alone; it re-enters where it left); every accumulator's k order is what it
+        //    was.  The bootstrap tile's steps keep the whole step (nothing of them is compared); the last step's second
+        //    half is drained behind the loop.
+        constexpr bool SPREAD = (SSS_F32_SCHED & 2) != 0, EARLY_TREE = (SSS_F32_SCHED & 4) != 0, SKEW = (SSS_F32_SCHED & 8) != 0;
+        static_assert(!SKEW || EARLY_TREE, "bit 3 carries bit 2 across the step boundary");
         static_assert(LOADS_PER_WAVE + 1 < NU, "a DMA piece per k-group, behind k-groups 1 .. LOADS_PER_WAVE");
         const unsigned frag_lane = (unsigned)(r * CH) * 16u;          // (the chunk term is added per k-group: compile-time xor)
         f32x4 nf0 = {0}, nf1 = {0};
+        [[maybe_unused]] float nb0 = 0.f;                         // SKEW, L2: the bias acc0 starts the next step from
         auto frag_ptr = [&](unsigned step_off, int u) -> const f32x4* {
             const int c = (2 * u) ^ x;                          // == (2u + h) ^ (r & 15)
             return reinterpret_cast<const f32x4*>(smem + step_off + frag_lane + c * 16);
         };
-        auto read_first = [&](unsigned step_off) { const f32x4* p = frag_ptr(step_off, 0); nf0 = p[0]; nf1 = p[32 * CH]; };
+        // first fragments of the step at step_off, sub-step nsub of its tile (whose biases bcur holds by now)
+        auto read_first = [&](unsigned step_off, [[maybe_unused]] int nsub) {
+            const f32x4* p = frag_ptr(step_off, 0); nf0 = p[0]; nf1 = p[32 * CH];
+            if constexpr (MET && SKEW) {
+                nb0 = bcur[0];
+#pragma unroll
+                for (int s = 1; s < H; ++s) nb0 = nsub == s ? bcur[2 * s] : nb0;
+            }
+        };
         float tm0 = -INFINITY;                                    // acc0's half of the tree (EARLY_TREE)
-        // MFMAs of step t (and, inside its last k-group, the hand-over when it ends a tile); returns the lane's maximum
-        auto step = [&](int t) -> float {
+        bool hit = false;                                         // SKEW: some lane of the half just decided passes
+        // SKEW, point 3: acc0's four MFMAs of k-group 0 of the step that follows step `row0_of_step`, and behind the second
+        // of them the decision on that step's acc1 (whose last MFMA is two MFMA times back at the least)
+        auto head = [&]() {
+            const f32x4 a0 = nf0;
+            const f32x16 zero = {0};
+            const bool ragged_prev = row0_of_step + 64 > n;
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (MET) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(nb0, bscale, zero, 0, 0, 0);
+            else acc0 = zero;
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, qc[0].x, acc0, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, qc[0].y, acc0, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (ragged_prev) {
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    if ((int)row0_of_step + 32 + 4 * h + (j & 3) + 8 * (j >> 2) >= n) acc1[j] = -INFINITY;
+            }
+            float m1 = vmax3(acc1[0], acc1[1], acc1[2]);
+#pragma unroll
+            for (int j = 3; j < 15; j += 2) m1 = vmax3(m1, acc1[j], acc1[j + 1]);
+            rmax = vmax3(m1, acc1[15], rmax);
+            m1 = vmax3(m1, acc1[15], acc1[15]);
+            hit = __builtin_amdgcn_ballot_w64(m1 > thr) != 0;
+            __builtin_amdgcn_sched_barrier(0);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, qc[0].z, acc0, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, qc[0].w, acc0, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        // MFMAs of step t (and, inside its last k-group, the hand-over when it ends a tile); returns the lane's maximum.
+        // TAIL (SKEW): the step from point 4 on -- head() has issued acc0's share of k-group 0 -- up to the decision on acc0,
+        // which it leaves in `hit`; acc1 stays undecided
+        auto step = [&](int t, auto tail_c) -> float {
+            constexpr bool TAIL = decltype(tail_c)::value;
             const int i = (int)((unsigned)t / (unsigned)H), sub = (int)((unsigned)t % (unsigned)H);
             const unsigned off = (unsigned)((i & 1) * TILE_BYTES + sub * (64 * RB));
             f32x4 as0[NU], as1[NU];
@@ -672,10 +726,11 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
                 float b0 = bcur[0], b1 = bcur[1];
 #pragma unroll
                 for (int s = 1; s < H; ++s) { b0 = sub == s ? bcur[2 * s] : b0; b1 = sub == s ? bcur[2 * s + 1] : b1; }
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, bscale, zero, 0, 0, 0);
+                if constexpr (!TAIL) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, bscale, zero, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, bscale, zero, 0, 0, 0);
             } else {
-                acc0 = zero; acc1 = zero;
+                if constexpr (!TAIL) acc0 = zero;
+                acc1 = zero;
             }
             auto fetch = [&](int u) { const f32x4* p = frag_ptr(off, u); as0[u] = p[0]; as1[u] = p[32 * CH]; };
             auto mfma8 = [&](int u) {
@@ -693,7 +748,17 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
             };
             // ---- k-group 0: its fragments came with the previous step; behind its MFMAs, whatever the step needs besides
             fetch(1);
-            mfma8(0);
+            if constexpr (!TAIL) {
+                mfma8(0);
+            } else {
+                const f32x4 a1 = as1[0];
+                __builtin_amdgcn_sched_barrier(0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, qc[0].x, acc1, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, qc[0].y, acc1, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, qc[0].z, acc1, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, qc[0].w, acc1, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             if (sub == 0) tile_top(i);
             const int next_tile = (sub == 0 && i + 1 < niter && !(two_ahead && i == 0)) ? tile_of(i + 1) : -1;
             const long nrow0 = (long)next_tile * TR;
@@ -722,7 +787,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
                 tile_end(i);
             }
             if (t + 1 < T && (sub < H - 1 || ends_tile))
-                read_first(sub == H - 1 ? (unsigned)(((i + 1) & 1) * TILE_BYTES) : off + 64 * RB);
+                read_first(sub == H - 1 ? (unsigned)(((i + 1) & 1) * TILE_BYTES) : off + 64 * RB, sub == H - 1 ? 0 : sub + 1);
             if constexpr (!EARLY_TREE) {
                 mfma8(u);
             } else {
@@ -750,10 +815,15 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
                 tm0 = vmax3(acc0[0], acc0[1], acc0[2]);
 #pragma unroll
                 for (int j = 3; j < 15; j += 2) tm0 = vmax3(tm0, acc0[j], acc0[j + 1]);
+                if constexpr (TAIL) {       // acc0 is decided here; head() overwrites it
+                    rmax = vmax3(tm0, acc0[15], rmax);
+                    hit = __builtin_amdgcn_ballot_w64(vmax3(tm0, acc0[15], acc0[15]) > thr) != 0;
+                }
                 __builtin_amdgcn_sched_barrier(0);
                 acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, qc[u].z, acc1, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, qc[u].w, acc1, 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
+                if constexpr (TAIL) return 0.f;
             }
             if (ragged_step) {
 #pragma unroll
@@ -771,24 +841,72 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
             rmax = vmax3(m, acc1[15], rmax);
             return vmax3(m, acc1[15], acc1[15]);
         };
-        if (T > 0) read_first(0);
-        while (t < T) {
-            bool rare = false;
-            for (; t < T; ++t) {                // ---- hot loop (never writes the list state, like the one below)
-                const float m = step(t);
-                if (t < t_live) {               // bootstrap tile: lane maximum only; its end in the old order
-                    if (t == t_live - 1) {
-                        tile_end(0);
-                        if (t + 1 < T) read_first((unsigned)TILE_BYTES);
-                    }
-                    continue;
+        constexpr std::false_type whole{};
+        if constexpr ((SSS_F32_SCHED & 16) != 0) {
+            // the younger half of every SIMD pair ahead of its partner, once and for good (no flips inside the loop)
+            if (wave >= 4) __builtin_amdgcn_s_setprio(1);
+        }
+        if (T > 0) read_first(0, 0);
+        if constexpr (SKEW) {
+            constexpr std::true_type tail{};
+            for (; t < t_live; ++t) {           // bootstrap tile: lane maximum only; its end in the old order
+                step(t, whole);
+                if (t == t_live - 1) {
+                    tile_end(0);
+                    if (t + 1 < T) read_first((unsigned)TILE_BYTES, 0);
                 }
-                if (__builtin_amdgcn_ballot_w64(m > thr) != 0) { rare = true; break; }
             }
-            if (!rare) break;
-            insert_block(acc0, (int)row0_of_step + 4 * h);
-            insert_block(acc1, (int)row0_of_step + 32 + 4 * h);
-            ++t;
+            if (t < T) {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) acc1[j] = -INFINITY;     // no second half waits for its decision yet
+                head();                         // (decides nothing: the hot loop is entered at point 4)
+                for (;;) {
+                    int rare = 0;
+                    for (;;) {                  // ---- hot loop (never writes the list state)
+                        step(t, tail);
+                        ++t;
+                        if (hit) { rare = 2; break; }
+                        if (t == T) break;
+                        head();
+                        if (hit) { rare = 1; break; }
+                    }
+                    // (row0_of_step is the first row of the step both exits decide on: it moves behind k-group 0)
+                    if (rare == 2) {
+                        insert_block(acc0, (int)row0_of_step + 4 * h);
+                        if (t == T) break;
+                        head();                 // point 3, outside the hot loop this once
+                        if (hit) rare = 1;
+                    }
+                    if (rare == 1) insert_block(acc1, (int)row0_of_step + 32 + 4 * h);
+                    if (t == T) break;
+                }
+                // the last step's second half (insert_block tests it itself)
+                if (row0_of_step + 64 > n) {
+#pragma unroll
+                    for (int j = 0; j < 16; ++j)
+                        if ((int)row0_of_step + 32 + 4 * h + (j & 3) + 8 * (j >> 2) >= n) acc1[j] = -INFINITY;
+                }
+                insert_block(acc1, (int)row0_of_step + 32 + 4 * h);
+            }
+        } else {
+            while (t < T) {
+                bool rare = false;
+                for (; t < T; ++t) {                // ---- hot loop (never writes the list state, like the one below)
+                    const float m = step(t, whole);
+                    if (t < t_live) {               // bootstrap tile: lane maximum only; its end in the old order
+                        if (t == t_live - 1) {
+                            tile_end(0);
+                            if (t + 1 < T) read_first((unsigned)TILE_BYTES, 0);
+                        }
+                        continue;
+                    }
+                    if (__builtin_amdgcn_ballot_w64(m > thr) != 0) { rare = true; break; }
+                }
+                if (!rare) break;
+                insert_block(acc0, (int)row0_of_step + 4 * h);
+                insert_block(acc1, (int)row0_of_step + 32 + 4 * h);
+                ++t;
+            }
         }
     }
     while (!F32S && t < T) {
