@@ -113,7 +113,7 @@ int sss_ip_topk_split(const float* q, int64_t nq, const float* corpus, const uin
  * Every search entry point checks what it scans the same way, before its workspace: a missing or not 16-byte aligned
  * image (the corpus itself for sss_ip_topk), corpus_shift outside [-160, 160] or a negative / NaN corpus_resid_norm
  * for an f16 image: -1. */
-int sss_abs_max(const float* x, int64_t count, float* out, void* stream);   /* max |x_i| -> *out (device, caller zeroes); count % 4 == 0 */
+int sss_abs_max(const float* x, int64_t count, float* out, void* stream);   /* max |x_i| -> *out (device, caller zeroes); count % 4 == 0.  NaNs are ignored, +-inf gives +inf. */
 int sss_f16_shift(float amax);                                              /* host helper: the shift for a largest magnitude */
 int sss_scale_f16(const float* x, int64_t count, int shift, uint16_t* y, void* stream);   /* count % 8 == 0 */
 int sss_f16_resid_max(const float* x, const uint16_t* y, int64_t n, int d, int shift, float* out, void* stream);   /* *out: device float, caller zeroes */

@@ -13,6 +13,9 @@ use the tolerances of tests/test_encoder_gpu.py and tests/test_variants_gpu.py.
 """
 import ctypes
 import itertools
+import math
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -24,6 +27,9 @@ from oracle import search_ref as sr
 from sessionsimilaritysearch_amd import _lib
 from sessionsimilaritysearch_amd import sessions as S
 from sessionsimilaritysearch_amd.encoder import EncoderConfig, SessionEncoder, init_weights
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import bound_inputs_ref as bir  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -642,8 +648,11 @@ def test_row_norm_max(cuda, dtype):
     out = Buf(1, torch.float32, zero=True)
     assert L().sss_row_norm_max(xt.data_ptr(), n, d, dtype, out.ptr, _st()) == 0
     torch.cuda.synchronize()
-    ref = float(xt[:n].double().norm(dim=1).max())
-    assert out.guards_ok() and abs(float(out.t[0]) - ref) <= 2e-6 * ref
+    norms = xt[:n].double().norm(dim=1)
+    ref = float(norms.max())
+    exact = math.sqrt(math.fsum(float(v) * float(v) for v in xt[int(norms.argmax())].float().cpu().numpy()))
+    assert abs(ref - exact) <= 1e-12 * exact
+    assert out.guards_ok() and ref <= float(out.t[0]) <= ref * (1 + 2e-6)       # an upper bound: never below the norm
 
 
 def test_image_conversions(cuda):
@@ -684,9 +693,9 @@ def test_image_maxima(cuda):
     res = Buf(1, torch.float32, zero=True)
     assert L().sss_f16_resid_max(x.data_ptr(), img.data_ptr(), n, d, shift, res.ptr, _st()) == 0
     torch.cuda.synchronize()
-    ref = float((img[:n].double() * 2.0 ** -shift - x[:n].double()).norm(dim=1).max())
+    S = bir.max_resid_sumsq_exact(x[:n].cpu().numpy(), img[:n].cpu().numpy(), shift)      # exact: no float64 norm that may round either way
     got = float(res.t[0])
-    assert res.guards_ok() and ref * (1 - 1e-6) <= got <= ref * (1 + 1e-5)
+    assert res.guards_ok() and bir.is_upper_bound(got, S) and got <= math.sqrt(float(S)) * (1 + 1e-5)
 
 
 # ------------------------------------------------------------------------------------------------ encoder pieces

@@ -8,12 +8,17 @@ The two seeded corpora: "gauss" (standard normal rows) and "varnorm" (directions
 with a missing, mis-indexed or mis-scaled row bias cannot pass by way of the re-score: its candidates would be the wrong
 rows."""
 import ctypes
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import search_ref as sr
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import bound_inputs_ref  # noqa: E402
 
 SCANS = ("f32", "split", "f16")
 KS = (1, 10, 16, 17, 100, 500)
@@ -349,8 +354,8 @@ def test_l2_abi_row_bias(cuda):
     assert bool((t["bias"] == 5.0).all())
     assert L.sss_l2_row_bias(t["c"].data_ptr(), n, d, t["bias"].data_ptr(), None) == 0
     got = t["bias"].cpu().numpy()
-    want = (-0.5 * (c_h.astype(np.float64) ** 2).sum(1)).astype(np.float32)
-    assert np.allclose(got[:n], want, rtol=3e-7, atol=0) and (got[n:] == 5.0).all()            # nothing behind row n - 1
+    want = bound_inputs_ref.bias_ref_rows(c_h)                                                 # ONE rounding of the exact -|c|^2 / 2
+    assert np.array_equal(got[:n], want) and (got[n:] == 5.0).all()                            # nothing behind row n - 1
 
 
 @pytest.mark.gpu
