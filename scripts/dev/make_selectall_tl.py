@@ -1,6 +1,8 @@
 """Dev helper (not product): csrc/select_tl.hip = csrc/select_thr.hip + phase stamps in k_select_all (symbol sss_debug_selall:
 [1024 workgroups][8] s_memtime values: start, keys loaded, cut known, survivors compacted, re-scored, sorted/written; words 6, 7 =
-kept rows, survivors).  Build as make_selectfast_tl.py says, with select_tl.o in place of select_thr.o."""
+kept rows, survivors).  Build (after `make` in csrc, which leaves the other units' objects there):
+  cd sessionsimilaritysearch_amd/csrc && hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -c select_tl.hip -o select_tl.o &&
+  hipcc --offload-arch=gfx950 -shared -o ../../scripts/dev/libsss_satl.so select_tl.o $(ls *.o | grep -v -e '^select_thr\.o$' -e '^select_tl\.o$')"""
 import os
 root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 src = open(os.path.join(root, "sessionsimilaritysearch_amd/csrc/select_thr.hip")).read()

@@ -55,6 +55,59 @@ __device__ __forceinline__ void hlist_insert(unsigned (&ld)[N], int (&li)[N], un
     }
 }
 
+// ---- what the two scan kernels (and, for the distance, the backstop) share
+template <int NW>
+__device__ __forceinline__ void load_code(const unsigned* __restrict__ Q, int q_ld, unsigned (&qw)[NW]) {
+#pragma unroll
+    for (int w = 0; w < NW; ++w) qw[w] = Q[(size_t)q_ld * NW + w];
+}
+// Hamming distance of the code at `row` (NW words, 16-byte reads) from the query words qw
+template <int NW>
+__device__ __forceinline__ unsigned hamming_dist(const unsigned* __restrict__ row, const unsigned (&qw)[NW]) {
+    unsigned d = 0;
+#pragma unroll
+    for (int w = 0; w < NW; w += 4) {
+        const uint4 c4 = *reinterpret_cast<const uint4*>(row + w);
+        d += __builtin_popcount(c4.x ^ qw[w]) + __builtin_popcount(c4.y ^ qw[w + 1]) +
+             __builtin_popcount(c4.z ^ qw[w + 2]) + __builtin_popcount(c4.w ^ qw[w + 3]);
+    }
+    return d;
+}
+__device__ __forceinline__ void hlist_init(unsigned (&ld)[HK], int (&li)[HK]) {
+#pragma unroll
+    for (int i = 0; i < HK; ++i) { ld[i] = 0xFFFFFFFFu; li[i] = -1; }
+}
+// The rows [0, nrows) of the LDS tile `tl` (ids row0 + r) against the thread's query, into its list.  Every lane reads
+// the same address: broadcast.  Four rows per trip: the LDS broadcasts overlap the popcounts.
+template <int NW>
+__device__ __forceinline__ void scan_rows(const unsigned* tl, int nrows, int row0, const unsigned (&qw)[NW], unsigned (&ld)[HK],
+                                          int (&li)[HK]) {
+    auto dist_of = [&](int r) { return hamming_dist<NW>(tl + r * NW, qw); };
+    int r = 0;
+    for (; r + 4 <= nrows; r += 4) {
+        const unsigned d0 = dist_of(r), d1 = dist_of(r + 1), d2 = dist_of(r + 2), d3 = dist_of(r + 3);
+        const unsigned dm = min(min(d0, d1), min(d2, d3));
+        if (__builtin_amdgcn_ballot_w64(dm < ld[HK - 1]) != 0) {     // rare after the first tiles
+            if (d0 < ld[HK - 1]) hlist_insert<HK>(ld, li, d0, row0 + r);
+            if (d1 < ld[HK - 1]) hlist_insert<HK>(ld, li, d1, row0 + r + 1);
+            if (d2 < ld[HK - 1]) hlist_insert<HK>(ld, li, d2, row0 + r + 2);
+            if (d3 < ld[HK - 1]) hlist_insert<HK>(ld, li, d3, row0 + r + 3);
+        }
+    }
+    for (; r < nrows; ++r) {
+        const unsigned d = dist_of(r);
+        if (d < ld[HK - 1]) hlist_insert<HK>(ld, li, d, row0 + r);
+    }
+}
+// the list of (query q, split) as keys (distance << 32 | id; ~0: empty slot)
+__device__ __forceinline__ void hlist_store(unsigned long long* __restrict__ cand, int q, int S, int split, const unsigned (&ld)[HK],
+                                            const int (&li)[HK]) {
+    unsigned long long* dst = cand + ((size_t)q * S + split) * HK;
+#pragma unroll
+    for (int i = 0; i < HK; ++i)
+        dst[i] = li[i] >= 0 ? (((unsigned long long)ld[i] << 32) | (unsigned)li[i]) : ~0ull;
+}
+
 template <int NW>       // 32-bit words per code (4, 8, 16 -> 128, 256, 512 bits; 32 and 64: k_hamming_scan_wide)
 __global__ __launch_bounds__(256) void k_hamming_scan(const unsigned* __restrict__ Q, int nq, const unsigned* __restrict__ C,
                                                       int n, int S, unsigned long long* __restrict__ cand) {
@@ -64,12 +117,10 @@ __global__ __launch_bounds__(256) void k_hamming_scan(const unsigned* __restrict
     const int q = g * 256 + tid;
     const int q_ld = q < nq ? q : nq - 1;
     unsigned qw[NW];
-#pragma unroll
-    for (int w = 0; w < NW; ++w) qw[w] = Q[(size_t)q_ld * NW + w];
+    load_code<NW>(Q, q_ld, qw);
     unsigned ld[HK];
     int li[HK];
-#pragma unroll
-    for (int i = 0; i < HK; ++i) { ld[i] = 0xFFFFFFFFu; li[i] = -1; }
+    hlist_init(ld, li);
     const int total_tiles = (n + HT_ROWS - 1) / HT_ROWS;
     // register staging of the next tile (thread t loads row t), written to LDS after the barrier
     unsigned stage[NW];
@@ -90,40 +141,10 @@ __global__ __launch_bounds__(256) void k_hamming_scan(const unsigned* __restrict
         if (t + S < total_tiles) fetch(t + S);       // next tile's loads fly under this tile's popcounts
         const int row0 = t * HT_ROWS;
         const int nrows = min(HT_ROWS, n - row0);
-        const unsigned* tl = tile[buf];
-        auto dist_of = [&](int r) {
-            unsigned d = 0;
-#pragma unroll
-            for (int w = 0; w < NW; w += 4) {
-                const uint4 c4 = *reinterpret_cast<const uint4*>(tl + r * NW + w);   // same address in every lane: broadcast
-                d += __builtin_popcount(c4.x ^ qw[w]) + __builtin_popcount(c4.y ^ qw[w + 1]) +
-                     __builtin_popcount(c4.z ^ qw[w + 2]) + __builtin_popcount(c4.w ^ qw[w + 3]);
-            }
-            return d;
-        };
-        int r = 0;
-        for (; r + 4 <= nrows; r += 4) {             // four rows per trip: the LDS broadcasts overlap the popcounts
-            const unsigned d0 = dist_of(r), d1 = dist_of(r + 1), d2 = dist_of(r + 2), d3 = dist_of(r + 3);
-            const unsigned dm = min(min(d0, d1), min(d2, d3));
-            if (__builtin_amdgcn_ballot_w64(dm < ld[HK - 1]) != 0) {     // rare after the first tiles
-                if (d0 < ld[HK - 1]) hlist_insert<HK>(ld, li, d0, row0 + r);
-                if (d1 < ld[HK - 1]) hlist_insert<HK>(ld, li, d1, row0 + r + 1);
-                if (d2 < ld[HK - 1]) hlist_insert<HK>(ld, li, d2, row0 + r + 2);
-                if (d3 < ld[HK - 1]) hlist_insert<HK>(ld, li, d3, row0 + r + 3);
-            }
-        }
-        for (; r < nrows; ++r) {
-            const unsigned d = dist_of(r);
-            if (d < ld[HK - 1]) hlist_insert<HK>(ld, li, d, row0 + r);
-        }
+        scan_rows<NW>(tile[buf], nrows, row0, qw, ld, li);
         buf ^= 1;
     }
-    if (q < nq) {
-        unsigned long long* dst = cand + ((size_t)q * S + split) * HK;
-#pragma unroll
-        for (int i = 0; i < HK; ++i)
-            dst[i] = li[i] >= 0 ? (((unsigned long long)ld[i] << 32) | (unsigned)li[i]) : ~0ull;
-    }
+    if (q < nq) hlist_store(cand, q, S, split, ld, li);
 }
 
 // Rows of 128 / 256 bytes (NW = 32 / 64): the same scan over sub-tiles of SUB_ROWS rows (file header).  Thread tid
@@ -143,12 +164,10 @@ __global__ __launch_bounds__(256) void k_hamming_scan_wide(const unsigned* __res
     const int q = g * 256 + tid;
     const int q_ld = q < nq ? q : nq - 1;
     unsigned qw[NW];
-#pragma unroll
-    for (int w = 0; w < NW; ++w) qw[w] = Q[(size_t)q_ld * NW + w];
+    load_code<NW>(Q, q_ld, qw);
     unsigned ld[HK];
     int li[HK];
-#pragma unroll
-    for (int i = 0; i < HK; ++i) { ld[i] = 0xFFFFFFFFu; li[i] = -1; }
+    hlist_init(ld, li);
     const int total_tiles = (n + HT_ROWS - 1) / HT_ROWS;
     u32x4 stage[PIECE / 4];                          // (native vectors, not words cast to uint4: those park the array in scratch)
     auto fetch = [&](int t, int s) {                 // rows past the end re-read row n - 1 (never scored: nrows below)
@@ -171,41 +190,11 @@ __global__ __launch_bounds__(256) void k_hamming_scan_wide(const unsigned* __res
             else if (t + S < total_tiles) fetch(t + S, 0);
             const int row0 = t * HT_ROWS + s * SUB_ROWS;
             const int nrows = min(SUB_ROWS, n - row0);       // <= 0 in the sub-tiles past a ragged last tile's end
-            const unsigned* tl = tile[buf];
-            auto dist_of = [&](int r) {
-                unsigned d = 0;
-#pragma unroll
-                for (int w = 0; w < NW; w += 4) {
-                    const uint4 c4 = *reinterpret_cast<const uint4*>(tl + r * NW + w);   // same address in every lane: broadcast
-                    d += __builtin_popcount(c4.x ^ qw[w]) + __builtin_popcount(c4.y ^ qw[w + 1]) +
-                         __builtin_popcount(c4.z ^ qw[w + 2]) + __builtin_popcount(c4.w ^ qw[w + 3]);
-                }
-                return d;
-            };
-            int r = 0;
-            for (; r + 4 <= nrows; r += 4) {
-                const unsigned d0 = dist_of(r), d1 = dist_of(r + 1), d2 = dist_of(r + 2), d3 = dist_of(r + 3);
-                const unsigned dm = min(min(d0, d1), min(d2, d3));
-                if (__builtin_amdgcn_ballot_w64(dm < ld[HK - 1]) != 0) {
-                    if (d0 < ld[HK - 1]) hlist_insert<HK>(ld, li, d0, row0 + r);
-                    if (d1 < ld[HK - 1]) hlist_insert<HK>(ld, li, d1, row0 + r + 1);
-                    if (d2 < ld[HK - 1]) hlist_insert<HK>(ld, li, d2, row0 + r + 2);
-                    if (d3 < ld[HK - 1]) hlist_insert<HK>(ld, li, d3, row0 + r + 3);
-                }
-            }
-            for (; r < nrows; ++r) {
-                const unsigned d = dist_of(r);
-                if (d < ld[HK - 1]) hlist_insert<HK>(ld, li, d, row0 + r);
-            }
+            scan_rows<NW>(tile[buf], nrows, row0, qw, ld, li);
             buf ^= 1;
         }
     }
-    if (q < nq) {
-        unsigned long long* dst = cand + ((size_t)q * S + split) * HK;
-#pragma unroll
-        for (int i = 0; i < HK; ++i)
-            dst[i] = li[i] >= 0 ? (((unsigned long long)ld[i] << 32) | (unsigned)li[i]) : ~0ull;
-    }
+    if (q < nq) hlist_store(cand, q, S, split, ld, li);
 }
 
 // One workgroup per query: bitonic sort (ascending) of its S * HK candidate keys, write the first
@@ -248,17 +237,9 @@ __global__ __launch_bounds__(256) void k_hamming_dists(const unsigned* __restric
                                                        const unsigned* __restrict__ C, long n, unsigned short* __restrict__ dist) {
     const int f = blockIdx.y;
     unsigned qw[NW];
-#pragma unroll
-    for (int w = 0; w < NW; ++w) qw[w] = Q[(size_t)qsel[f] * NW + w];
+    load_code<NW>(Q, qsel[f], qw);
     for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < n; r += (long)gridDim.x * 256) {
-        unsigned d = 0;
-#pragma unroll
-        for (int w = 0; w < NW; w += 4) {
-            const uint4 c4 = *reinterpret_cast<const uint4*>(C + (size_t)r * NW + w);
-            d += __builtin_popcount(c4.x ^ qw[w]) + __builtin_popcount(c4.y ^ qw[w + 1]) +
-                 __builtin_popcount(c4.z ^ qw[w + 2]) + __builtin_popcount(c4.w ^ qw[w + 3]);
-        }
-        dist[(size_t)f * n + r] = (unsigned short)d;
+        dist[(size_t)f * n + r] = (unsigned short)hamming_dist<NW>(C + (size_t)r * NW, qw);
     }
 }
 __global__ __launch_bounds__(1024) void k_hamming_topk_full(const unsigned short* __restrict__ dist, const int* __restrict__ qsel,

@@ -40,6 +40,85 @@ __device__ __forceinline__ float vmax3_settled(float a, float b, float c) {
     return r;
 }
 
+// Maximum of elements 0 .. 14 of an accumulator, a chain of seven v_max3 (element 15 goes into the v_max3 the caller
+// finishes with).  SETTLED: the chain starts right behind the MFMA that wrote `a`.
+template <bool SETTLED = false>
+__device__ __forceinline__ float acc_max15(const f32x16& a) {
+    float m = SETTLED ? vmax3_settled(a[0], a[1], a[2]) : vmax3(a[0], a[1], a[2]);
+#pragma unroll
+    for (int j = 3; j < 15; j += 2) m = vmax3(m, a[j], a[j + 1]);
+    return m;
+}
+// ... of two accumulators, the chains interleaved
+__device__ __forceinline__ void acc_max15(const f32x16& a0, const f32x16& a1, float& m0, float& m1) {
+    m0 = vmax3(a0[0], a0[1], a0[2]); m1 = vmax3(a1[0], a1[1], a1[2]);
+#pragma unroll
+    for (int j = 3; j < 15; j += 2) { m0 = vmax3(m0, a0[j], a0[j + 1]); m1 = vmax3(m1, a1[j], a1[j + 1]); }
+}
+
+// Element j of a lane's 16 values of a 32x32 MFMA accumulator is row acc_row(j) + 4 * (lane >> 5) of the unit's 32
+// (acc_row(j, first): counted from the row `first` of the lane's element 0).
+__device__ __forceinline__ constexpr int acc_row(int j, int first = 0) { return first + (j & 3) + 8 * (j >> 2); }
+
+// Ragged last tile: the elements of an accumulator whose corpus row lies at or beyond n become -inf (`first`: the corpus
+// row of the lane's element 0).  (n and, below, bias_of's sub-step by reference: the callers are lambdas that reach them
+// through their captures, and with a by-value copy hipcc compiles the f32 step-order kernels differently.)
+__device__ __forceinline__ void mask_rows(f32x16& a, int first, const int& n) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        if (acc_row(j, first) >= n) a[j] = -INFINITY;
+}
+// ... of the two accumulators of a step, a1's rows 32 further
+__device__ __forceinline__ void mask_rows(f32x16& a0, f32x16& a1, int first, const int& n) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int rr = acc_row(j, first);
+        if (rr >= n) a0[j] = -INFINITY;
+        if (rr + 32 >= n) a1[j] = -INFINITY;
+    }
+}
+
+// One LDS-DMA wave-instruction: 64 lanes x 16 bytes from `base` (wave-uniform: an SGPR pair) + the lane's byte offset to
+// the 1 KiB of LDS at the wave-uniform address lds_dst, lane-linear.  SC1: agent scope (not served from this CU's L1).
+// (Inline asm, so hipcc neither counts it nor drains vmcnt(0) at the next ds_read.  M0 is written without a save /
+//  restore: hipcc has no use of its own for M0 in the scan kernels -- no dynamic register indexing, no LDS-direct / GWS /
+//  sendmsg; every M0 reference in their ISA comes from this statement.)
+template <bool SC1 = false, class Base>
+__device__ __forceinline__ void lds_dma16(unsigned lane_off, unsigned lds_dst, Base base) {
+    if constexpr (SC1)
+        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2 sc1" : : "v"(lane_off), "s"(lds_dst), "s"(base) : "memory");
+    else
+        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2" : : "v"(lane_off), "s"(lds_dst), "s"(base) : "memory");
+}
+
+// One k-group of the f32 scans: the 16-byte chunk of a row of each accumulator's 32 (a0, a1) against the query's (q) --
+// eight v_mfma_f32_32x32x2_f32, the two accumulators' chains interleaved, each in the k order x, y, z, w.
+__device__ __forceinline__ void mfma_f32_group(f32x16& acc0, f32x16& acc1, const f32x4& a0, const f32x4& a1, const f32x4& q) {
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, q.x, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, q.x, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, q.y, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, q.y, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, q.z, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, q.z, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, q.w, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, q.w, acc1, 0, 0, 0);
+}
+// Half of one accumulator's share of a k-group: two of its four MFMAs, where a step issues the halves apart.
+__device__ __forceinline__ void mfma_f32_pair(f32x16& acc, float a_lo, float a_hi, float q_lo, float q_hi) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a_lo, q_lo, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a_hi, q_hi, acc, 0, 0, 0);
+}
+
+// L2 scans: the bias of accumulator k (0, 1) in sub-step `sub` of the current tile, bcur[2 sub + k], by a select chain over
+// the H compile-time sub-steps (a runtime index would send bcur to scratch).
+template <int H, int N>
+__device__ __forceinline__ float bias_of(const float (&bcur)[N], const int& sub, int k) {
+    float b = bcur[k];
+#pragma unroll
+    for (int s = 1; s < H; ++s) b = sub == s ? bcur[2 * s + k] : b;
+    return b;
+}
+
 // Two 16-byte agent-scope (sc1: not served from this CU's L1) loads + their wait, as ONE asm
 // statement so the destinations are never touched before the data has landed.
 __device__ __forceinline__ unsigned min8_sc1(const unsigned* p) {

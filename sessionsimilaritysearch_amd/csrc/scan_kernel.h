@@ -6,19 +6,6 @@
 #include "scan.h"
 #include "scan_dev.h"
 
-#ifndef SSS_STAGGER
-#define SSS_STAGGER 1
-#endif
-// The f32 list form's step order for 512-byte rows (k_scan, "F32S"): 0 = the order every scan shares; bit 0 = its own loop
-// (fragments prefetched across the step boundary, tile hand-over in front of the last k-group, step scalars behind
-// k-group 0), bit 1 = the next tile's DMA one piece per k-group, bit 2 = half the max tree under the other accumulator's
-// last MFMAs, bit 3 = the half-step skew: each accumulator's tree, compare and rare path under the other's MFMAs, across
-// the step boundary (needs bit 2), bit 4 = static priority 1 for waves 4-7 (not in the default: DESIGN.md 5.1).
-// (A/B builds: DESIGN.md 5.1.)
-#ifndef SSS_F32_SCHED
-#define SSS_F32_SCHED 15
-#endif
-
 namespace sss {
 
 // NW = waves per workgroup: 8 (two per SIMD, 256 VGPRs each) or, for 1024-byte rows whose resident
@@ -49,7 +36,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
     constexpr int WGQ = NW * 32;                      // queries per workgroup
     constexpr bool PRECOMP = RB <= 512 && !AP;        // keep the DMA lane offsets in VGPRs (register budget; not at 128 VGPRs)
     constexpr int TAU_LDS = 2 * TILE_BYTES;           // [8 waves][32 queries][16 slots] u32 behind the two tile buffers
-    constexpr bool F32S = (SSS_F32_SCHED & 1) && DT == DT_F32 && !AP && !THR && RB == 512;   // (the loop is in front of the split loop, below)
+    constexpr bool F32S = DT == DT_F32 && !AP && !THR && RB == 512;   // (the loop is in front of the split loop, below)
     static_assert(CH <= 64, "row longer than one LDS-DMA instruction");
     static_assert(LOADS_PER_WAVE >= 1, "a tile is at least one DMA piece per wave");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -120,11 +107,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
     // pair publishes ONE value -- the better of its two lane maxima, by lane h = 0: half the agent-scope atomics (at the
     // bootstrap 128 instead of 256 per query line, which all arrive within a microsecond and serialise at the line's
     // memory channel).  cert > 1: a class per lane list, as the lists certify `cert` rows each.
-#ifdef SSS_EXP_NOPAIR
-    const bool pair_pub = false;
-#else
     const bool pair_pub = A.cert == 1;
-#endif
     if (use_tau) {
         // (split + split / 16: with the append form's 128 splits the low four bits of `split` alone would put the workgroups
         //  dispatched first -- the lower half of the grid, one per CU -- in classes 0-7 and their co-resident partners,
@@ -162,10 +145,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
             if (qi > nq - 1) qi = nq - 1;
             const unsigned off = (unsigned)qi * (unsigned)(SLOT_STRIDE * 4) + (unsigned)(ln & 3) * 16u;
             const unsigned dst = __builtin_amdgcn_readfirstlane(tau_lds + j * 1024);
-            // (M0 is written without a save / restore: hipcc has no use of its own for M0 in this kernel -- no dynamic
-            //  register indexing, no LDS-direct / GWS / sendmsg; every M0 reference in the ISA comes from these statements)
-            asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2 sc1"
-                         : : "v"(off), "s"(dst), "s"(A.slots) : "memory");
+            lds_dma16<true>(off, dst, A.slots);
         }
     };
     auto tau_read = [&]() -> unsigned {
@@ -244,8 +224,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
             if (grow > (long)n - 1) grow = (long)n - 1;
             off = (unsigned)((grow - row0) * RB) + (off - (unsigned)(lr * RB));
         }
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2"
-                     : : "v"(off), "s"(dst), "s"(tile_src) : "memory");
+        lds_dma16(off, dst, tile_src);
     };
     auto stage = [&](int buf, int tile_idx) {
 #pragma unroll
@@ -295,6 +274,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
         for (int u = 0; u < PF && u < NU; ++u) { const f32x4* p = lda(u); as0[u] = p[0]; as1[u] = p[32 * CH]; }
         const f32x16 zero = {0};
         if constexpr (MET) {
+            // (bias_of() written out: through the helper the kernels with four sub-steps a tile compile differently)
             float b0 = bcur[0], b1 = bcur[1];
 #pragma unroll
             for (int s = 1; s < H; ++s) { b0 = sub == s ? bcur[2 * s] : b0; b1 = sub == s ? bcur[2 * s + 1] : b1; }
@@ -310,14 +290,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
             const f32x4 a0 = as0[u], a1 = as1[u];
             __builtin_amdgcn_sched_barrier(0);   // keep the prefetch ABOVE this group's MFMAs
             if constexpr (DT == DT_F32) {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, qc[u].x, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, qc[u].x, acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, qc[u].y, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, qc[u].y, acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, qc[u].z, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, qc[u].z, acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, qc[u].w, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, qc[u].w, acc1, 0, 0, 0);
+                mfma_f32_group(acc0, acc1, a0, a1, qc[u]);
             } else if constexpr (DT == DT_BF16) {
                 const bf16x8 qb = __builtin_bit_cast(bf16x8, qc[u]);
                 acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a0), qb, acc0, 0, 0, 0);
@@ -385,7 +358,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
                     }
                     const bool still = a[j] > thr;
                     pend_s = still ? a[j] : pend_s;
-                    pend_i = still ? base + (j & 3) + 8 * (j >> 2) : pend_i;
+                    pend_i = still ? base + acc_row(j) : pend_i;
                 }
             }
         };
@@ -426,7 +399,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
 #pragma unroll
                     for (int i = E - 1; i > 0; --i) { es[i] = pass ? es[i - 1] : es[i]; ei[i] = pass ? ei[i - 1] : ei[i]; }
                     es[0] = pass ? a[j] : es[0];
-                    ei[0] = pass ? base + (j & 3) + 8 * (j >> 2) : ei[0];
+                    ei[0] = pass ? base + acc_row(j) : ei[0];
                     ecnt += pass ? 1 : 0;
                 }
             }
@@ -443,7 +416,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
         for (int j = 0; j < 16; ++j) {
             if (a[j] > thr) {
                 const unsigned pos = atomicAdd(A.cnt + q_glob, 1u);
-                if (pos < (unsigned)A.cap) A.cand[(size_t)q_glob * A.cap + pos] = make_key(a[j], base + (j & 3) + 8 * (j >> 2));
+                if (pos < (unsigned)A.cap) A.cand[(size_t)q_glob * A.cap + pos] = make_key(a[j], base + acc_row(j));
             }
         }
     };
@@ -548,20 +521,12 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
         const int next_tile = (i + 1 < niter && !(two_ahead && i == 0)) ? tile_of(i + 1) : -1;
         mfma_sub(i & 1, sub, next_tile);
         row0_of_step = (long)tile_of(i) * TR + sub * 64;
-        if (row0_of_step + 64 > n) {                        // wave-uniform, last tile only
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int rr = (int)row0_of_step + 4 * h + (j & 3) + 8 * (j >> 2);
-                if (rr >= n) acc0[j] = -INFINITY;
-                if (rr + 32 >= n) acc1[j] = -INFINITY;
-            }
-        }
+        if (row0_of_step + 64 > n) mask_rows(acc0, acc1, (int)row0_of_step + 4 * h, n);     // wave-uniform, last tile only
     };
     auto score_tree = [&]() -> float {
         // 16 v_max3 (as asm: fmaxf() adds a canonicalising v_max x, x per MFMA result it touches)
-        float m0 = vmax3(acc0[0], acc0[1], acc0[2]), m1 = vmax3(acc1[0], acc1[1], acc1[2]);
-#pragma unroll
-        for (int j = 3; j < 15; j += 2) { m0 = vmax3(m0, acc0[j], acc0[j + 1]); m1 = vmax3(m1, acc1[j], acc1[j + 1]); }
+        float m0, m1;
+        acc_max15(acc0, acc1, m0, m1);
         const float m = vmax3(m0, m1, acc0[15]);
         const float mm = vmax3(m, acc1[15], rmax);
         rmax = mm;
@@ -577,7 +542,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
     // to +1 % (their partners drift apart by themselves), so those keep the plain order.
     // (DT_H16 -- stored f16 rows -- and DT_I8 -- stored int8 rows -- are the bf16 kernel with another MFMA: they take the
     //  bf16 order)
-    const bool defer = SSS_STAGGER && NW == 8 && (DT == DT_SPLIT || DT == DT_BF16 || DT == DT_H16 || DT == DT_I8) && wave >= 4;
+    const bool defer = NW == 8 && (DT == DT_SPLIT || DT == DT_BF16 || DT == DT_H16 || DT == DT_I8) && wave >= 4;
     int t = 0;
     if constexpr (AP || THR) {
         // The forms WITHOUT lane lists (append, threshold) have no list state to keep out of the hot loop, so theirs is the
@@ -613,6 +578,8 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
                 mfma_sub(i & 1, sub, next_tile);
                 const int row0 = row_base + sub * 64;
                 if (ragged) {
+                    // (mask_rows(acc0, acc1, row0 + 4 * h, n) written out: through the helper, or with acc_row() for the row
+                    //  term, hipcc compiles every append and threshold kernel differently -- DESIGN.md 5.1, the refactor's table)
 #pragma unroll
                     for (int j = 0; j < 16; ++j) {
                         const int rr = row0 + 4 * h + (j & 3) + 8 * (j >> 2);
@@ -654,7 +621,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
         //    of the next tile has landed: exactly what the barrier at the end of the step guaranteed.  The last k-group's
         //    512 cycles then cover the next tile's first fragment reads and the threshold read-back.
         //    The bootstrap tile keeps the old order (publish behind its tree, wait, barrier, bounded poll): once a launch.
-        //  * THE HALF-STEP SKEW (bit 3): each accumulator's tree, compare and rare path run under the OTHER accumulator's
+        //  * THE HALF-STEP SKEW: each accumulator's tree, compare and rare path run under the OTHER accumulator's
         //    MFMAs, across the step boundary.  acc0(t)'s tree and compare sit behind the second of acc1's last four MFMAs
         //    of step t; acc0's four MFMAs of k-group 0 of step t + 1 then overwrite it (its decision is made) and acc1(t)'s
         //    tree and compare sit behind the second of THOSE -- at least 128 pipe cycles after acc1's last MFMA was issued,
@@ -663,12 +630,10 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
         //    (insert_block of that accumulator alone; it re-enters where it left); every accumulator's k order is what it
         //    was.  The bootstrap tile's steps keep the whole step (nothing of them is compared); the last step's second
         //    half is drained behind the loop.
-        constexpr bool SPREAD = (SSS_F32_SCHED & 2) != 0, EARLY_TREE = (SSS_F32_SCHED & 4) != 0, SKEW = (SSS_F32_SCHED & 8) != 0;
-        static_assert(!SKEW || EARLY_TREE, "bit 3 carries bit 2 across the step boundary");
         static_assert(LOADS_PER_WAVE + 1 < NU, "a DMA piece per k-group, behind k-groups 1 .. LOADS_PER_WAVE");
         const unsigned frag_lane = (unsigned)(r * CH) * 16u;          // (the chunk term is added per k-group: compile-time xor)
         f32x4 nf0 = {0}, nf1 = {0};
-        [[maybe_unused]] float nb0 = 0.f;                         // SKEW, L2: the bias acc0 starts the next step from
+        [[maybe_unused]] float nb0 = 0.f;                         // L2: the bias acc0 starts the next step from
         auto frag_ptr = [&](unsigned step_off, int u) -> const f32x4* {
             const int c = (2 * u) ^ x;                          // == (2u + h) ^ (r & 15)
             return reinterpret_cast<const f32x4*>(smem + step_off + frag_lane + c * 16);
@@ -676,15 +641,11 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
         // first fragments of the step at step_off, sub-step nsub of its tile (whose biases bcur holds by now)
         auto read_first = [&](unsigned step_off, [[maybe_unused]] int nsub) {
             const f32x4* p = frag_ptr(step_off, 0); nf0 = p[0]; nf1 = p[32 * CH];
-            if constexpr (MET && SKEW) {
-                nb0 = bcur[0];
-#pragma unroll
-                for (int s = 1; s < H; ++s) nb0 = nsub == s ? bcur[2 * s] : nb0;
-            }
+            if constexpr (MET) nb0 = bias_of<H>(bcur, nsub, 0);
         };
-        float tm0 = -INFINITY;                                    // acc0's half of the tree (EARLY_TREE)
-        bool hit = false;                                         // SKEW: some lane of the half just decided passes
-        // SKEW, point 3: acc0's four MFMAs of k-group 0 of the step that follows step `row0_of_step`, and behind the second
+        float tm0 = -INFINITY;                                    // acc0's half of the tree, taken under acc1's last MFMAs
+        bool hit = false;                                         // some lane of the half just decided passes
+        // The skew's first half: acc0's four MFMAs of k-group 0 of the step that follows step `row0_of_step`, and behind the second
         // of them the decision on that step's acc1 (whose last MFMA is two MFMA times back at the least)
         auto head = [&]() {
             const f32x4 a0 = nf0;
@@ -693,28 +654,22 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (MET) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(nb0, bscale, zero, 0, 0, 0);
             else acc0 = zero;
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, qc[0].x, acc0, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, qc[0].y, acc0, 0, 0, 0);
+            mfma_f32_pair(acc0, a0.x, a0.y, qc[0].x, qc[0].y);
             __builtin_amdgcn_sched_barrier(0);
-            if (ragged_prev) {
-#pragma unroll
-                for (int j = 0; j < 16; ++j)
-                    if ((int)row0_of_step + 32 + 4 * h + (j & 3) + 8 * (j >> 2) >= n) acc1[j] = -INFINITY;
-            }
-            float m1 = vmax3(acc1[0], acc1[1], acc1[2]);
-#pragma unroll
-            for (int j = 3; j < 15; j += 2) m1 = vmax3(m1, acc1[j], acc1[j + 1]);
+            if (ragged_prev) mask_rows(acc1, (int)row0_of_step + 32 + 4 * h, n);
+            float m1 = acc_max15(acc1);
             rmax = vmax3(m1, acc1[15], rmax);
             m1 = vmax3(m1, acc1[15], acc1[15]);
             hit = __builtin_amdgcn_ballot_w64(m1 > thr) != 0;
             __builtin_amdgcn_sched_barrier(0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, qc[0].z, acc0, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, qc[0].w, acc0, 0, 0, 0);
+            mfma_f32_pair(acc0, a0.z, a0.w, qc[0].z, qc[0].w);
             __builtin_amdgcn_sched_barrier(0);
         };
-        // MFMAs of step t (and, inside its last k-group, the hand-over when it ends a tile); returns the lane's maximum.
-        // TAIL (SKEW): the step from point 4 on -- head() has issued acc0's share of k-group 0 -- up to the decision on acc0,
-        // which it leaves in `hit`; acc1 stays undecided
+        // MFMAs of step t (and, inside its last k-group, the hand-over when it ends a tile).  Whole (the bootstrap tile): the
+        // lane's maximum over both accumulators goes into rmax, nothing is compared.
+        // TAIL: the step behind head(), which has issued acc0's share of k-group 0 -- up to the decision on acc0, which it
+        // leaves in `hit`; acc1 stays undecided.  (No caller reads the float it returns; it stays because a void step compiles
+        // to another register assignment in the four kernels of this loop.)
         auto step = [&](int t, auto tail_c) -> float {
             constexpr bool TAIL = decltype(tail_c)::value;
             const int i = (int)((unsigned)t / (unsigned)H), sub = (int)((unsigned)t % (unsigned)H);
@@ -723,11 +678,8 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
             as0[0] = nf0; as1[0] = nf1;
             const f32x16 zero = {0};
             if constexpr (MET) {
-                float b0 = bcur[0], b1 = bcur[1];
-#pragma unroll
-                for (int s = 1; s < H; ++s) { b0 = sub == s ? bcur[2 * s] : b0; b1 = sub == s ? bcur[2 * s + 1] : b1; }
-                if constexpr (!TAIL) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, bscale, zero, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, bscale, zero, 0, 0, 0);
+                if constexpr (!TAIL) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_of<H>(bcur, sub, 0), bscale, zero, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_of<H>(bcur, sub, 1), bscale, zero, 0, 0, 0);
             } else {
                 if constexpr (!TAIL) acc0 = zero;
                 acc1 = zero;
@@ -736,14 +688,7 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
             auto mfma8 = [&](int u) {
                 const f32x4 a0 = as0[u], a1 = as1[u];
                 __builtin_amdgcn_sched_barrier(0);   // keep the prefetch ABOVE this group's MFMAs
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, qc[u].x, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, qc[u].x, acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, qc[u].y, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, qc[u].y, acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, qc[u].z, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, qc[u].z, acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, qc[u].w, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, qc[u].w, acc1, 0, 0, 0);
+                mfma_f32_group(acc0, acc1, a0, a1, qc[u]);
                 __builtin_amdgcn_sched_barrier(0);
             };
             // ---- k-group 0: its fragments came with the previous step; behind its MFMAs, whatever the step needs besides
@@ -753,10 +698,8 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
             } else {
                 const f32x4 a1 = as1[0];
                 __builtin_amdgcn_sched_barrier(0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, qc[0].x, acc1, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, qc[0].y, acc1, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, qc[0].z, acc1, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, qc[0].w, acc1, 0, 0, 0);
+                mfma_f32_pair(acc1, a1.x, a1.y, qc[0].x, qc[0].y);
+                mfma_f32_pair(acc1, a1.z, a1.w, qc[0].z, qc[0].w);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (sub == 0) tile_top(i);
@@ -768,17 +711,13 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
             row0_of_step = (long)tile_of(i) * TR + sub * 64;
             const bool ragged_step = row0_of_step + 64 > n;                 // wave-uniform, last tile only
             const bool ends_tile = sub == H - 1 && !(boot && i == 0);       // (the bootstrap tile's end comes behind its tree)
-            if (next_tile >= 0 && (!dma_plain || !SPREAD)) stage((i & 1) ^ 1, next_tile);
+            if (next_tile >= 0 && !dma_plain) stage((i & 1) ^ 1, next_tile);
             // ---- k-groups 1 .. NU - 2, a DMA piece behind each of the first LOADS_PER_WAVE
 #pragma unroll
             for (int u = 1; u < NU - 1; ++u) {
                 fetch(u + 1);
                 mfma8(u);
-                if constexpr (SPREAD) {
-                    if (u <= LOADS_PER_WAVE && dma_plain)
-                        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2"
-                                     : : "v"(lane_off[u - 1]), "s"(dma_dst + (u - 1) * 1024), "s"(dma_src) : "memory");
-                }
+                if (u <= LOADS_PER_WAVE && dma_plain) lds_dma16(lane_off[u - 1], dma_dst + (u - 1) * 1024, dma_src);
             }
             // ---- the last k-group: the hand-over in front of its MFMAs when it ends a tile (see above)
             constexpr int u = NU - 1;
@@ -788,125 +727,72 @@ __global__ __launch_bounds__(NW * 64, AP ? 2 * (NW / 4) : NW / 4) void k_scan(co
             }
             if (t + 1 < T && (sub < H - 1 || ends_tile))
                 read_first(sub == H - 1 ? (unsigned)(((i + 1) & 1) * TILE_BYTES) : off + 64 * RB, sub == H - 1 ? 0 : sub + 1);
-            if constexpr (!EARLY_TREE) {
-                mfma8(u);
-            } else {
-                // acc0's chain first (back to back on one accumulator is free: 64-cycle issue = the dependent latency); its
-                // half of the tree goes in behind acc1's SECOND MFMA -- two MFMA times after acc0's last one was issued
-                const f32x4 a0 = as0[u], a1 = as1[u];
-                __builtin_amdgcn_sched_barrier(0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, qc[u].x, acc0, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, qc[u].y, acc0, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, qc[u].z, acc0, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, qc[u].w, acc0, 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);   // (acc0's last MFMA strictly in front of acc1's two: see the tree below)
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, qc[u].x, acc1, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, qc[u].y, acc1, 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                // (the tree is inline asm, which hipcc does not pad against the MFMA that wrote its operands: what keeps
-                //  acc0's readers clear of acc0's last MFMA is the order -- acc1's second MFMA cannot issue before the
-                //  first has had the pipe for its 64 cycles, and that one not before acc0's last has: 128 cycles, against
-                //  the 19 wait states (76 cycles) a 16-pass MFMA's result needs before a VALU reads it)
-                if (ragged_step) {
-#pragma unroll
-                    for (int j = 0; j < 16; ++j)
-                        if ((int)row0_of_step + 4 * h + (j & 3) + 8 * (j >> 2) >= n) acc0[j] = -INFINITY;
-                }
-                tm0 = vmax3(acc0[0], acc0[1], acc0[2]);
-#pragma unroll
-                for (int j = 3; j < 15; j += 2) tm0 = vmax3(tm0, acc0[j], acc0[j + 1]);
-                if constexpr (TAIL) {       // acc0 is decided here; head() overwrites it
-                    rmax = vmax3(tm0, acc0[15], rmax);
-                    hit = __builtin_amdgcn_ballot_w64(vmax3(tm0, acc0[15], acc0[15]) > thr) != 0;
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, qc[u].z, acc1, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, qc[u].w, acc1, 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (TAIL) return 0.f;
+            // acc0's chain first (back to back on one accumulator is free: 64-cycle issue = the dependent latency); its
+            // half of the tree goes in behind acc1's SECOND MFMA -- two MFMA times after acc0's last one was issued
+            const f32x4 a0 = as0[u], a1 = as1[u];
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_f32_pair(acc0, a0.x, a0.y, qc[u].x, qc[u].y);
+            mfma_f32_pair(acc0, a0.z, a0.w, qc[u].z, qc[u].w);
+            __builtin_amdgcn_sched_barrier(0);   // (acc0's last MFMA strictly in front of acc1's two: see the tree below)
+            mfma_f32_pair(acc1, a1.x, a1.y, qc[u].x, qc[u].y);
+            __builtin_amdgcn_sched_barrier(0);
+            // (the tree is inline asm, which hipcc does not pad against the MFMA that wrote its operands: what keeps
+            //  acc0's readers clear of acc0's last MFMA is the order -- acc1's second MFMA cannot issue before the
+            //  first has had the pipe for its 64 cycles, and that one not before acc0's last has: 128 cycles, against
+            //  the 19 wait states (76 cycles) a 16-pass MFMA's result needs before a VALU reads it)
+            if (ragged_step) mask_rows(acc0, (int)row0_of_step + 4 * h, n);
+            tm0 = acc_max15(acc0);
+            if constexpr (TAIL) {       // acc0 is decided here; head() overwrites it
+                rmax = vmax3(tm0, acc0[15], rmax);
+                hit = __builtin_amdgcn_ballot_w64(vmax3(tm0, acc0[15], acc0[15]) > thr) != 0;
             }
-            if (ragged_step) {
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const int rr = (int)row0_of_step + 4 * h + (j & 3) + 8 * (j >> 2);
-                    if (!EARLY_TREE && rr >= n) acc0[j] = -INFINITY;
-                    if (rr + 32 >= n) acc1[j] = -INFINITY;
-                }
-            }
-            if constexpr (!EARLY_TREE) return score_tree();
-            float m1 = vmax3_settled(acc1[0], acc1[1], acc1[2]);      // (acc1's last MFMA is the instruction in front of it)
-#pragma unroll
-            for (int j = 3; j < 15; j += 2) m1 = vmax3(m1, acc1[j], acc1[j + 1]);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_f32_pair(acc1, a1.z, a1.w, qc[u].z, qc[u].w);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (TAIL) return 0.f;
+            if (ragged_step) mask_rows(acc1, (int)row0_of_step + 32 + 4 * h, n);
+            const float m1 = acc_max15<true>(acc1);                   // (acc1's last MFMA is the instruction in front of it)
             const float m = vmax3(tm0, m1, acc0[15]);
             rmax = vmax3(m, acc1[15], rmax);
             return vmax3(m, acc1[15], acc1[15]);
         };
         constexpr std::false_type whole{};
-        if constexpr ((SSS_F32_SCHED & 16) != 0) {
-            // the younger half of every SIMD pair ahead of its partner, once and for good (no flips inside the loop)
-            if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-        }
+        constexpr std::true_type tail{};
         if (T > 0) read_first(0, 0);
-        if constexpr (SKEW) {
-            constexpr std::true_type tail{};
-            for (; t < t_live; ++t) {           // bootstrap tile: lane maximum only; its end in the old order
-                step(t, whole);
-                if (t == t_live - 1) {
-                    tile_end(0);
-                    if (t + 1 < T) read_first((unsigned)TILE_BYTES, 0);
-                }
+        for (; t < t_live; ++t) {           // bootstrap tile: lane maximum only; its end in the old order
+            step(t, whole);
+            if (t == t_live - 1) {
+                tile_end(0);
+                if (t + 1 < T) read_first((unsigned)TILE_BYTES, 0);
             }
-            if (t < T) {
+        }
+        if (t < T) {
 #pragma unroll
-                for (int j = 0; j < 16; ++j) acc1[j] = -INFINITY;     // no second half waits for its decision yet
-                head();                         // (decides nothing: the hot loop is entered at point 4)
-                for (;;) {
-                    int rare = 0;
-                    for (;;) {                  // ---- hot loop (never writes the list state)
-                        step(t, tail);
-                        ++t;
-                        if (hit) { rare = 2; break; }
-                        if (t == T) break;
-                        head();
-                        if (hit) { rare = 1; break; }
-                    }
-                    // (row0_of_step is the first row of the step both exits decide on: it moves behind k-group 0)
-                    if (rare == 2) {
-                        insert_block(acc0, (int)row0_of_step + 4 * h);
-                        if (t == T) break;
-                        head();                 // point 3, outside the hot loop this once
-                        if (hit) rare = 1;
-                    }
-                    if (rare == 1) insert_block(acc1, (int)row0_of_step + 32 + 4 * h);
+            for (int j = 0; j < 16; ++j) acc1[j] = -INFINITY;     // no second half waits for its decision yet
+            head();                         // (decides nothing: the hot loop is entered at its second half)
+            for (;;) {
+                int rare = 0;
+                for (;;) {                  // ---- hot loop (never writes the list state)
+                    step(t, tail);
+                    ++t;
+                    if (hit) { rare = 2; break; }
                     if (t == T) break;
+                    head();
+                    if (hit) { rare = 1; break; }
                 }
-                // the last step's second half (insert_block tests it itself)
-                if (row0_of_step + 64 > n) {
-#pragma unroll
-                    for (int j = 0; j < 16; ++j)
-                        if ((int)row0_of_step + 32 + 4 * h + (j & 3) + 8 * (j >> 2) >= n) acc1[j] = -INFINITY;
+                // (row0_of_step is the first row of the step both exits decide on: it moves behind k-group 0)
+                if (rare == 2) {
+                    insert_block(acc0, (int)row0_of_step + 4 * h);
+                    if (t == T) break;
+                    head();                 // outside the hot loop this once
+                    if (hit) rare = 1;
                 }
-                insert_block(acc1, (int)row0_of_step + 32 + 4 * h);
+                if (rare == 1) insert_block(acc1, (int)row0_of_step + 32 + 4 * h);
+                if (t == T) break;
             }
-        } else {
-            while (t < T) {
-                bool rare = false;
-                for (; t < T; ++t) {                // ---- hot loop (never writes the list state, like the one below)
-                    const float m = step(t, whole);
-                    if (t < t_live) {               // bootstrap tile: lane maximum only; its end in the old order
-                        if (t == t_live - 1) {
-                            tile_end(0);
-                            if (t + 1 < T) read_first((unsigned)TILE_BYTES, 0);
-                        }
-                        continue;
-                    }
-                    if (__builtin_amdgcn_ballot_w64(m > thr) != 0) { rare = true; break; }
-                }
-                if (!rare) break;
-                insert_block(acc0, (int)row0_of_step + 4 * h);
-                insert_block(acc1, (int)row0_of_step + 32 + 4 * h);
-                ++t;
-            }
+            // the last step's second half (insert_block tests it itself)
+            if (row0_of_step + 64 > n) mask_rows(acc1, (int)row0_of_step + 32 + 4 * h, n);
+            insert_block(acc1, (int)row0_of_step + 32 + 4 * h);
         }
     }
     while (!F32S && t < T) {

@@ -67,10 +67,7 @@ struct LongArgs {
 // (the f16 image of f32 queries -- scaled by the query's own power of two, scan.h: f16_shift -- is written by
 //  select_thr.hip: k_long_setup; the select side, query_bound / k_thr_prepare, re-derives the same shift)
 
-#ifndef SSS_LT_LOADERS
-#define SSS_LT_LOADERS 4
-#endif
-constexpr int LT_LOADERS = SSS_LT_LOADERS;             // loader waves per workgroup (one per SIMD), behind the 8 matrix waves
+constexpr int LT_LOADERS = 4;                          // loader waves per workgroup (one per SIMD), behind the 8 matrix waves
 constexpr int LT_NP = 32 / LT_LOADERS;                 // 1 KiB pieces of an operand slab per loader
 constexpr int LT_THREADS = (8 + LT_LOADERS) * 64;
 
@@ -173,8 +170,7 @@ __global__ __launch_bounds__(LT_THREADS, (LT_THREADS + 255) / 256) void k_scan_l
 #pragma unroll
             for (int i = 0; i < LT_NP; ++i) {
                 const unsigned dst = __builtin_amdgcn_readfirstlane(lds_base + slot_idx * LT_HALF + (lw + LT_LOADERS * i) * 1024);
-                asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2"
-                             : : "v"(off[i]), "s"(dst), "s"(bs) : "memory");
+                lds_dma16(off[i], dst, bs);
             }
         };
         int itile = tile, ifrac = tile_frac, islab = 0, ibuf = 0;   // next corpus slab to fetch and its ring slot
@@ -188,11 +184,10 @@ __global__ __launch_bounds__(LT_THREADS, (LT_THREADS + 255) / 256) void k_scan_l
         stage(q_base, off_q, 3, 0);
         if (total_steps > 1) issue_rows();
         int qslab = 1 % nslab;                                      // query slab of step + 1
+        static_assert(LT_NP == 8, "the wait below leaves one corpus slab's pieces of this loader in flight");
         for (int step = 0; step < total_steps; ++step) {
             if (step + 2 > total_steps - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if constexpr (LT_NP == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else if constexpr (LT_NP == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");    // all but the youngest LT_NP pieces (corpus, step + 2)
             __syncthreads();                                        // step's slabs are there; the slots of step - 1 are free
             if (step + 1 < total_steps) stage(q_base, off_q, 3 + ((step & 1) ^ 1), qslab);
             if (step + 2 < total_steps) issue_rows();               // into slot (step + 2) % 3, read last in step - 1
@@ -282,6 +277,8 @@ __global__ __launch_bounds__(LT_THREADS, (LT_THREADS + 255) / 256) void k_scan_l
         }
         // ---- tile epilogue: acc[b][s][jj] is (corpus row tile * 256 + 128 wr + 32 b + (jj & 3) + 8 (jj >> 2) + 4 h,
         // query r (s = 0) / 32 + r (s = 1) of the wave's 64)
+        const int qs[2] = {q0, q1};
+        const float thrs[2] = {thr0, thr1};
         float m0 = -INFINITY, m1 = -INFINITY;
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
@@ -299,14 +296,13 @@ __global__ __launch_bounds__(LT_THREADS, (LT_THREADS + 255) / 256) void k_scan_l
                 for (int b = 0; b < 4; ++b) {
 #pragma unroll
                     for (int jj = 0; jj < 16; ++jj) {
-                        const int row = row_base + 32 * b + (jj & 3) + 8 * (jj >> 2);
-                        if (acc[b][0][jj] > thr0 && row < n) {
-                            const unsigned pos = atomicAdd(A.cnt + q0, 1u);
-                            if (pos < (unsigned)A.cap) A.cand[(size_t)q0 * A.cap + pos] = make_key(acc[b][0][jj], row);
-                        }
-                        if (acc[b][1][jj] > thr1 && row < n) {
-                            const unsigned pos = atomicAdd(A.cnt + q1, 1u);
-                            if (pos < (unsigned)A.cap) A.cand[(size_t)q1 * A.cap + pos] = make_key(acc[b][1][jj], row);
+                        const int row = row_base + 32 * b + acc_row(jj);
+#pragma unroll
+                        for (int s = 0; s < 2; ++s) {
+                            if (acc[b][s][jj] > thrs[s] && row < n) {
+                                const unsigned pos = atomicAdd(A.cnt + qs[s], 1u);
+                                if (pos < (unsigned)A.cap) A.cand[(size_t)qs[s] * A.cap + pos] = make_key(acc[b][s][jj], row);
+                            }
                         }
                     }
                 }
@@ -316,43 +312,32 @@ __global__ __launch_bounds__(LT_THREADS, (LT_THREADS + 255) / 256) void k_scan_l
             // add per lane and query for all of them (count, reserve, store); one per row made the first level cost
             // four times its matrix work.  (On the last level the counting pass costs more than it saves: +9 %.)
             const int row_base = tile * LT_ROWS + wr * 128 + 4 * h;
-            unsigned n0 = 0u, n1 = 0u;
+            unsigned cnt[2] = {0u, 0u}, at[2] = {0u, 0u};
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
 #pragma unroll
                 for (int jj = 0; jj < 16; ++jj) {
-                    const bool in = row_base + 32 * b + (jj & 3) + 8 * (jj >> 2) < n;
-                    n0 += (acc[b][0][jj] > thr0 && in) ? 1u : 0u;
-                    n1 += (acc[b][1][jj] > thr1 && in) ? 1u : 0u;
+                    const bool in = row_base + 32 * b + acc_row(jj) < n;
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) cnt[s] += (acc[b][s][jj] > thrs[s] && in) ? 1u : 0u;
                 }
             }
-            unsigned at0 = 0u, at1 = 0u;
-            if (n0) at0 = atomicAdd(A.cnt + q0, n0);
-            if (n1) at1 = atomicAdd(A.cnt + q1, n1);
-            unsigned long long* c0 = A.cand + (size_t)q0 * A.cap;
-            unsigned long long* c1 = A.cand + (size_t)q1 * A.cap;
-            if (__builtin_amdgcn_ballot_w64(n0 != 0u) != 0) {
 #pragma unroll
-                for (int b = 0; b < 4; ++b) {
+            for (int s = 0; s < 2; ++s)
+                if (cnt[s]) at[s] = atomicAdd(A.cnt + qs[s], cnt[s]);
 #pragma unroll
-                    for (int jj = 0; jj < 16; ++jj) {
-                        const int row = row_base + 32 * b + (jj & 3) + 8 * (jj >> 2);
-                        if (acc[b][0][jj] > thr0 && row < n) {
-                            if (at0 < (unsigned)A.cap) c0[at0] = make_key(acc[b][0][jj], row);
-                            ++at0;
-                        }
-                    }
-                }
-            }
-            if (__builtin_amdgcn_ballot_w64(n1 != 0u) != 0) {
+            for (int s = 0; s < 2; ++s) {
+                unsigned long long* c = A.cand + (size_t)qs[s] * A.cap;
+                if (__builtin_amdgcn_ballot_w64(cnt[s] != 0u) != 0) {
 #pragma unroll
-                for (int b = 0; b < 4; ++b) {
+                    for (int b = 0; b < 4; ++b) {
 #pragma unroll
-                    for (int jj = 0; jj < 16; ++jj) {
-                        const int row = row_base + 32 * b + (jj & 3) + 8 * (jj >> 2);
-                        if (acc[b][1][jj] > thr1 && row < n) {
-                            if (at1 < (unsigned)A.cap) c1[at1] = make_key(acc[b][1][jj], row);
-                            ++at1;
+                        for (int jj = 0; jj < 16; ++jj) {
+                            const int row = row_base + 32 * b + acc_row(jj);
+                            if (acc[b][s][jj] > thrs[s] && row < n) {
+                                if (at[s] < (unsigned)A.cap) c[at[s]] = make_key(acc[b][s][jj], row);
+                                ++at[s];
+                            }
                         }
                     }
                 }

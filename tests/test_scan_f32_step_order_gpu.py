@@ -1,4 +1,4 @@
-"""The half-step skew of the f32 list scan for 512-byte rows (csrc/scan_kernel.h, "F32S", SSS_F32_SCHED bit 3): each
+"""The half-step skew of the f32 list scan for 512-byte rows (csrc/scan_kernel.h, "F32S", the half-step skew): each
 accumulator of a 64-row step is decided under the other accumulator's MFMAs, across the step boundary, and the hot loop
 has one exit per half.  None of it may change a result.
 
