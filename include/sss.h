@@ -55,7 +55,7 @@ int sss_f32_to_bf16(const float* x, int64_t count, uint16_t* y, void* stream);
  * are int8 like the rows, as the 16-bit dtypes put queries in the stored type), d in {256,512,1024} (int32 accumulate on
  * v_mfma_i32_32x32x32_i8; the stored int8 values are the rows of record and a scan score is the canonical score: error
  * bound 0, as |score| <= d 2^14 <= 2^24 is exact in float32).  The corpus dtype codes are 0, 1, 4 and 6 wherever a `dtype`
- * is taken; 2 and 3 name scan images of a float32 corpus (`scan` below), never a corpus, and 5 is unassigned: -1.
+ * is taken; 2 and 3 name scan images of a float32 corpus (`scan_dtype` below), never a corpus, and 5 is unassigned: -1.
  * k <= 500.  Writes D_out [nq, k] fp32 (descending) and I_out [nq, k] int64 = row + id_offset,
  * ordered by (score desc, id asc); missing results: I = -1, D = -FLT_MAX (faiss convention).
  * Scores are the canonical ones of DESIGN.md (float64 sequential dot of the stored elements,
@@ -78,7 +78,7 @@ int sss_ip_topk(const void* q, int64_t nq, const void* corpus, int64_t n, int d,
                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* The same search for a float32 corpus with the scan on the bf16 MFMA ("split" scan, the default of
- * the Python FlatIndex): corpus_split [n, 2d] bfloat16 is the image sss_split_bf16 makes of the
+ * the Python FlatIndex): scan_image [n, 2d] bfloat16 is the image sss_split_bf16 makes of the
  * corpus rows -- [hi(d) | lo(d)], hi = rne_bf16(x), lo = rne_bf16(x - hi), 4 bytes per element like
  * the f32 row.  The scan scores hi*hi + hi*lo + lo*hi (three bf16 MFMA passes, f32 accumulate:
  * 16/3 of the f32 MFMA rate) to pick the candidates; the candidates are re-scored from the float32
@@ -87,7 +87,7 @@ int sss_ip_topk(const void* q, int64_t nq, const void* corpus, int64_t n, int d,
  * identical results for every query with status 0.  q float32 [nq, d]; d in {64,128,256};
  * workspace: sss_ip_topk_workspace_bytes(nq, n, d, k, 0); state as above. */
 int sss_split_bf16(const float* x, int64_t n, int d, uint16_t* y, void* stream);
-int sss_ip_topk_split(const float* q, int64_t nq, const float* corpus, const uint16_t* corpus_split,
+int sss_ip_topk_split(const float* q, int64_t nq, const float* corpus, const uint16_t* scan_image,
                       int64_t n, int d, int k, int64_t id_offset, float corpus_max_norm, float* D_out,
                       int64_t* I_out, int32_t* status, int32_t* unproven_count, void* state,
                       size_t state_bytes, void* workspace, size_t workspace_bytes, void* stream);
@@ -95,7 +95,7 @@ int sss_ip_topk_split(const float* q, int64_t nq, const float* corpus, const uin
 /* The same search with the candidates found by ONE float16 MFMA pass over a scaled float16 image of
  * the float32 corpus (half the bytes, a third of the split scan's matrix work; the default of the
  * Python FlatIndex for d in {128,256,512}):
- *   corpus_f16 [n, d] float16 = round_to_nearest_even(corpus * 2^corpus_shift), made by
+ *   scan_image [n, d] float16 = round_to_nearest_even(corpus * 2^corpus_shift), made by
  *   sss_scale_f16; corpus_shift = sss_f16_shift(largest |element| of the corpus) (sss_abs_max), which
  *   puts that element in [2^12, 2^13) -- an exact scaling far from both ends of the f16 range.  A
  *   shift stays valid while every element times 2^shift is below 65504 (the index re-scales when
@@ -105,7 +105,7 @@ int sss_ip_topk_split(const float* q, int64_t nq, const float* corpus, const uin
  * unaffected, and the proof divides it out.  Error bound of a scan score:
  * Rc |q| + (|c| + Rc) Rq + (2^-25 sqrt(d) + d 2^-23) |q| |c|, with Rq the query's own rounding
  * residual norm (measured by the kernel) and Rc = corpus_resid_norm = the largest row norm of
- * (corpus_f16 * 2^-corpus_shift - corpus), measured by sss_f16_resid_max when the image is built
+ * (scan_image * 2^-corpus_shift - corpus), measured by sss_f16_resid_max when the image is built
  * (any upper bound is valid; the worst case is 2^-11 * corpus_max_norm).  Coarser than the other
  * scans (~4e-4 |q||c| at d = 128), so more near-ties are left unproven (status != 0) and go to
  * sss_ip_topk_exhaustive; results for status 0 are identical.
@@ -118,7 +118,7 @@ int sss_f16_shift(float amax);                                              /* h
 int sss_scale_f16(const float* x, int64_t count, int shift, uint16_t* y, void* stream);   /* count % 8 == 0 */
 int sss_f16_resid_max(const float* x, const uint16_t* y, int64_t n, int d, int shift, float* out, void* stream);   /* *out: device float, caller zeroes */
 size_t sss_ip_topk_f16_workspace_bytes(int64_t nq, int64_t n, int d, int k);
-int sss_ip_topk_f16(const float* q, int64_t nq, const float* corpus, const uint16_t* corpus_f16,
+int sss_ip_topk_f16(const float* q, int64_t nq, const float* corpus, const uint16_t* scan_image,
                     int corpus_shift, float corpus_resid_norm, int64_t n, int d, int k, int64_t id_offset, float corpus_max_norm,
                     float* D_out, int64_t* I_out, int32_t* status, int32_t* unproven_count, void* state,
                     size_t state_bytes, void* workspace, size_t workspace_bytes, void* stream);
@@ -130,15 +130,15 @@ int sss_ip_topk_f16(const float* q, int64_t nq, const float* corpus, const uint1
  * lies above (bound - scan error bound - one float32 ulp) and re-scores them all canonically (float64, from
  * `corpus`): exact for near ties and for exact ties (duplicate rows) alike.  Resolved queries get their rows of
  * D_out / I_out rewritten and status 0; a query with more than 8192 such rows (or NaNs) keeps its status and goes
- * to sss_ip_topk_exhaustive.  scan: 0 / 1 / 4 / 6 = the corpus itself (f32 / bf16 / f16 / int8 index: scan = dtype,
+ * to sss_ip_topk_exhaustive.  scan_dtype: 0 / 1 / 4 / 6 = the corpus itself (f32 / bf16 / f16 / int8 index: scan_dtype = dtype,
  * pass scan_image = corpus),
  * 2 = the [hi | lo] bf16 image (sss_split_bf16), 3 = the scaled float16 image (corpus_shift / corpus_resid_norm
  * as for sss_ip_topk_f16; ignored otherwise).  Serves the same result contract as the reference's
  * `index.search` (test_amazon_filterd.py:578).  workspace (256-byte aligned):
- * sss_ip_topk_threshold_workspace_bytes(nsel, n, d, scan). */
-size_t sss_ip_topk_threshold_workspace_bytes(int64_t nsel, int64_t n, int d, int scan);
+ * sss_ip_topk_threshold_workspace_bytes(nsel, n, d, scan_dtype). */
+size_t sss_ip_topk_threshold_workspace_bytes(int64_t nsel, int64_t n, int d, int scan_dtype);
 int sss_ip_topk_threshold(const void* q, const int32_t* qsel, int64_t nsel, const void* corpus, int dtype,
-                          const void* scan_image, int scan, int corpus_shift, float corpus_resid_norm, int64_t n,
+                          const void* scan_image, int scan_dtype, int corpus_shift, float corpus_resid_norm, int64_t n,
                           int d, int k, int64_t id_offset, float corpus_max_norm, float* D_out, int64_t* I_out,
                           int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -196,9 +196,9 @@ int sss_ip_topk_exhaustive_lb(const void* q, const int32_t* qsel, int64_t nsel, 
  * Fused route: the threshold rung's matrix-core scan (same shapes / scan codes / images as sss_ip_topk_threshold)
  * with each query's threshold derived from its radius, then a canonical re-score of every row the scan kept.
  * A query whose scan kept more than 8192 rows gets status 1 and count 0: run it through the exhaustive route.
- * workspace (256-byte aligned): sss_range_search_workspace_bytes(nq, n, d, scan), ~64 KB per query. */
-size_t sss_range_search_workspace_bytes(int64_t nq, int64_t n, int d, int scan);
-int sss_range_search_count(const void* q, int64_t nq, const void* corpus, int dtype, const void* scan_image, int scan,
+ * workspace (256-byte aligned): sss_range_search_workspace_bytes(nq, n, d, scan_dtype), ~64 KB per query. */
+size_t sss_range_search_workspace_bytes(int64_t nq, int64_t n, int d, int scan_dtype);
+int sss_range_search_count(const void* q, int64_t nq, const void* corpus, int dtype, const void* scan_image, int scan_dtype,
                            int corpus_shift, float corpus_resid_norm, int64_t n, int d, const float* radius,
                            float corpus_max_norm, int64_t* counts, int32_t* status, void* workspace,
                            size_t workspace_bytes, void* stream);

@@ -18,7 +18,7 @@
  * every kept row is re-scored canonically from the float32 rows.
  *
  * Rows: float32, d % 64 == 0, d <= 4096 (the limits of sss_ip_topk_long for float32 rows); 0 < n < 2^31 - 1024;
- * k <= 1024.  f16_image / corpus_shift / corpus_resid_norm: the scaled float16 image of the rows, as for
+ * k <= 1024.  scan_image / corpus_shift / corpus_resid_norm: the scaled float16 image of the rows, as for
  * sss_ip_topk_f16 (sss_scale_f16, sss_f16_resid_max), 16-byte aligned.  bias: n floats, 16-byte aligned.
  * corpus_max_norm: an upper bound of the largest row 2-norm; the caller takes this route only where
  * corpus_max_norm^2 / 2 is a finite, normal float32 (2^-60 <= corpus_max_norm <= 2^60 is what FlatIndex asks).
@@ -37,7 +37,7 @@ extern "C" {
  * upper bound of its true k-th distance, +FLT_MAX when none is known; the rest of the row is unspecified).
  * workspace: sss_l2_topk_long_workspace_bytes(nq, n, d) bytes, 256-byte aligned (0 for a shape this scan does not take). */
 size_t sss_l2_topk_long_workspace_bytes(int64_t nq, int64_t n, int d);
-int sss_l2_topk_long(const float* q, int64_t nq, const float* corpus, const void* f16_image, int corpus_shift,
+int sss_l2_topk_long(const float* q, int64_t nq, const float* corpus, const void* scan_image, int corpus_shift,
                      float corpus_resid_norm, const float* bias, int64_t n, int d, int k, int64_t id_offset, float corpus_max_norm,
                      float* D_out, int64_t* I_out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 

@@ -1,5 +1,6 @@
-"""ctypes binding of libsss.so: the C ABI declared in the headers of include/, one signature table per header
-(``HEADERS`` below names them all).
+"""ctypes binding of libsss.so, read from the C ABI's own declarations: the headers of include/ are the one place where
+an entry point's types and an argument struct's fields are written down (``HEADERS``, ``PARAMS`` and ``STRUCTS`` below
+are what the reader makes of them).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails, this
 module raises.  ``build()`` compiles the library in-tree with hipcc for gfx950.
@@ -8,236 +9,96 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import subprocess
-from ctypes import c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsss.so")
 CSRC = os.path.join(_HERE, "csrc")
+INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 _lib = None
 
-# name -> (restype, argtypes); mirrors include/sss.h one to one
-_SIGNATURES = {
-    "sss_version": (c_int, []),
-    "sss_last_error": (ctypes.c_char_p, []),
-    "sss_normalize_rows": (c_int, [c_void_p, c_int64, c_int, c_int64, c_float, c_int, c_void_p]),
-    "sss_row_norm_max": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "sss_f32_to_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
-    "sss_ip_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int, c_int]),
-    "sss_ip_topk_state_bytes": (c_size_t, [c_int64]),
-    "sss_ip_topk": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int64, c_float,
-                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
-    "sss_split_bf16": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
-    "sss_ip_topk_split": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_float,
-                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
-                                  c_void_p]),
-    "sss_abs_max": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
-    "sss_f16_shift": (c_int, [c_float]),
-    "sss_scale_f16": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
-    "sss_ip_topk_f16_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
-    "sss_f16_resid_max": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "sss_ip_topk_f16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_float, c_int64, c_int, c_int, c_int64, c_float,
-                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
-                                c_void_p]),
-    "sss_ip_topk_long_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
-    "sss_ip_topk_long": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_float, c_int64, c_int, c_int, c_int64,
-                                 c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "sss_ip_topk_threshold_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
-    "sss_ip_topk_threshold": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int64,
-                                      c_int, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                      c_void_p]),
-    "sss_ip_topk_exhaustive_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "sss_ip_topk_exhaustive": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int,
-                                       c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
-                                       c_void_p]),
-    "sss_ip_topk_exhaustive_lb": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int,
-                                          c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "sss_range_search_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
-    "sss_range_search_count": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int64, c_int, c_void_p,
-                                       c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "sss_range_search_fill": (c_int, [c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "sss_range_search_exhaustive_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "sss_range_search_exhaustive_count": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
-                                                  c_void_p, c_void_p, c_size_t, c_void_p]),
-    "sss_range_search_exhaustive_fill": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
-                                                 c_void_p, c_size_t, c_void_p]),
-    "sss_topk_merge": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_int, c_void_p, c_void_p,
-                               c_void_p]),
-    "sss_scan_boot_expired": (c_int, [c_int]),
-    "sss_profile_enable": (c_int, [c_int]),
-    "sss_profile_read": (c_int, [c_void_p, c_void_p]),
-    "sss_gather_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
-    "sss_gather_concat_rows": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_int64,
-                                       c_void_p]),
-    "sss_linear": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
-                           c_int, c_int, c_void_p]),
-    "sss_gat_aggregate": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
-                                  c_int64, c_int, c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p]),
-    "sss_csr_weighted_sum": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int,
-                                     c_void_p, c_int64, c_void_p]),
-    "sss_gru_combine": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p,
-                                c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p]),
-    "sss_pool_expand": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int,
-                                c_int, c_void_p, c_void_p, c_int64, c_void_p]),
-    "sss_segment_pool": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p,
-                                 c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
-    "sss_segment_ptr": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
-    "sss_pack_sign_bits": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p]),
-    "sss_hamming_topk_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "sss_hamming_topk_capacity": (c_int, [c_int64, c_int64]),
-    "sss_hamming_topk": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
-                                 c_void_p, c_size_t, c_void_p]),
-    "sss_hamming_topk_exhaustive_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "sss_hamming_topk_exhaustive": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int64,
-                                            c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "sss_graph_scratch_ints": (c_size_t, [c_int64]),
-    "sss_graph_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "sss_graph_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "sss_knn_item_vote": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int,
-                                  c_void_p, c_void_p, c_void_p, c_void_p]),
-    "sss_linear_grouped": (c_int, [c_void_p, c_int, c_int, c_void_p]),
-    "sss_hetero_layer_update": (c_int, [c_void_p, c_void_p]),
-    "sss_pool_expand_mean": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
-                                     c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
-    "sss_pool_attention": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                   c_int64, c_int64, c_int, c_int, c_float, c_int, c_void_p, c_int64, c_void_p]),
-    "sss_pool_attention_tab": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_float,
-                                       c_void_p, c_int64, c_void_p]),
-    "sss_csr_mean": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
-    "sss_segment_reduce": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
-    "sss_attention_dot_pool": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
-}
-
-# include/sss_sparse.h one to one (the sparse session index: its own header, bound from the same library)
-_SPARSE_SIGNATURES = {
-    "sss_session_vectors_count": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
-    "sss_session_vectors_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, ctypes.c_double, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_void_p]),
-    "sss_sparse_topk_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "sss_sparse_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64,
-                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-}
-
-# include/sss_l2.h one to one (L2 top-k on the matrix-core scans)
-_L2_SIGNATURES = {
-    "sss_l2_row_bias": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
-    "sss_l2_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int, c_int]),
-    "sss_l2_topk": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_int, c_int, c_int64,
-                            c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
-    "sss_l2_topk_threshold_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
-    "sss_l2_topk_threshold": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_int,
-                                      c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-}
-
-# include/sss_l2_long.h one to one (L2 top-k of long float32 rows on the K-tiled scan)
-_L2_LONG_SIGNATURES = {
-    "sss_l2_topk_long_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
-    "sss_l2_topk_long": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_float, c_void_p, c_int64, c_int, c_int, c_int64,
-                                 c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-}
-
-# include/sss_pad.h one to one (scans at the next supported width for float32 rows of any width d % 4 == 0)
-_PAD_SIGNATURES = {
-    "sss_pad_rows_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "sss_pad_scale_f16": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "sss_pad_split_bf16": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "sss_pad_f16_resid_max": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "sss_pad_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int, c_int, c_int]),
-    "sss_pad_topk": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_int, c_int, c_int,
-                             c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
-                             c_void_p]),
-    "sss_pad_topk_threshold_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int, c_int]),
-    "sss_pad_topk_threshold": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_int64,
-                                       c_int, c_int, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                       c_void_p]),
-}
-
-# include/sss_graph.h one to one (the graph builder with ignore_query and the last-click outputs)
-GRAPH_IGNORE_QUERY = 1      # SSS_GRAPH_IGNORE_QUERY
-_GRAPH_SIGNATURES = {
-    "sss_graph_counts_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "sss_graph_fill_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_void_p]),
-}
-
-# include/sss_eval.h one to one (scoring a search result: pair overlaps of item sets and their per-query sums)
-_EVAL_SIGNATURES = {
-    "sss_item_overlap": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p,
-                                 c_void_p, c_void_p]),
-    "sss_overlap_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p]),
-}
-
-# include/sss_jaccard.h one to one (ground truth: exact item-set Jaccard top-k and band counts over the whole corpus;
-# `edges` of sss_jaccard_bands is the one HOST pointer of the ABI)
-_JACCARD_SIGNATURES = {
-    "sss_jaccard_topk_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "sss_jaccard_topk": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p,
-                                 c_void_p, c_size_t, c_void_p]),
-    "sss_jaccard_bands": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int64, c_void_p,
-                                  c_void_p, c_void_p]),
-}
-
-# include/sss_ptype.h one to one (ground truth under the product-type kind: type bags, their exact top-k, band counts and
-# pair scores; `edges` of sss_ptype_bands is a HOST pointer, as sss_jaccard_bands')
-_PTYPE_SIGNATURES = {
-    "sss_type_bags_count": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
-    "sss_type_bags_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
-                                   c_void_p, c_void_p]),
-    "sss_ptype_topk_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "sss_ptype_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64,
-                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "sss_ptype_bands": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int64,
-                                c_void_p, c_void_p, c_void_p]),
-    "sss_ptype_pair_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int,
-                                      c_int64, c_void_p, c_void_p, c_void_p]),
-}
-
-# include/sss_hgt.h one to one (the HGT encoder: HGTConv's attention aggregation on CSR by target and its skip connection)
-_HGT_SIGNATURES = {
-    "sss_hgt_aggregate": (c_int, [c_void_p, c_void_p]),
-    "sss_hgt_skip": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_float, c_int64, c_int, c_void_p]),
-}
-
-# include/sss_text.h one to one (the query text encoder: token embedding, attention inside packed sequences, add + LayerNorm)
-_TEXT_SIGNATURES = {
-    "sss_text_embed": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_int64,
-                               c_void_p, c_void_p]),
-    "sss_seq_attention": (c_int, [c_void_p, c_void_p]),
-    "sss_add_layernorm": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_int64, c_int, c_void_p, c_int64,
-                                  c_void_p]),
-}
-
-# include/sss_bert.h one to one (the node text encoder: BERT's embedding stage; the rest of its forward is bound above)
-_BERT_SIGNATURES = {
-    "sss_bert_embed": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                               c_float, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
-}
+# ---------------------------------------------------------------------------------------------- the header reader
+# The headers are plain C in one style: no macros in declarations, these scalar types, and everything else a pointer.
+_SCALARS = {"int": c_int, "int32_t": c_int32, "int64_t": c_int64, "size_t": c_size_t, "float": c_float, "double": c_double}
+_DECLARATOR = re.compile(r"\s*(?:const\s+)?(\w+)\s*(\*?)\s*(\w+)\s*(?:\[(\d+)\])?\s*")
+_STRUCT = re.compile(r"typedef\s+struct\s*\{(.*?)\}\s*(sss_\w+)\s*;", re.S)
+_FUNCTION = re.compile(r"\b((?:const\s+)?\w+\s*\*?)\s*\b(sss_\w+)\s*\(([^()]*)\)\s*;")
 
 
-# header of include/ -> its signature table: what lib() binds, and every *_symbols() view below
-HEADERS = {
-    "sss.h": _SIGNATURES,
-    "sss_sparse.h": _SPARSE_SIGNATURES,
-    "sss_l2.h": _L2_SIGNATURES,
-    "sss_l2_long.h": _L2_LONG_SIGNATURES,
-    "sss_pad.h": _PAD_SIGNATURES,
-    "sss_graph.h": _GRAPH_SIGNATURES,
-    "sss_eval.h": _EVAL_SIGNATURES,
-    "sss_jaccard.h": _JACCARD_SIGNATURES,
-    "sss_ptype.h": _PTYPE_SIGNATURES,
-    "sss_hgt.h": _HGT_SIGNATURES,
-    "sss_text.h": _TEXT_SIGNATURES,
-    "sss_bert.h": _BERT_SIGNATURES,
-}
+def _declarator(text, where, structs=()):
+    """``(name, ctypes type)`` of one parameter or struct field; ``structs``: the struct types a field may nest."""
+    m = _DECLARATOR.fullmatch(text)
+    if not m:
+        raise ValueError(f"{where}: cannot read the declaration {text.strip()!r}")
+    base, star, name, count = m.groups()
+    if star:
+        t = c_void_p
+    elif base in _SCALARS:
+        t = _SCALARS[base]
+    elif base in structs:
+        t = structs[base]
+    else:
+        raise ValueError(f"{where}: type {base!r} of {text.strip()!r} is not one this binding knows")
+    return name, t * int(count) if count else t
 
 
+def read_header(text, header):
+    """What a header's text declares: ``({entry point: (restype, argtypes, parameter names)}, {struct: [field text]})``.
+    Comments and preprocessor lines are dropped first; a type outside ``_SCALARS`` that is no pointer raises, naming the
+    header and the declaration."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
+    structs = {name: [f for f in body.split(";") if f.strip()] for body, name in _STRUCT.findall(text)}
+    functions = {}
+    for ret, name, params in _FUNCTION.findall(_STRUCT.sub(" ", text)):
+        where = f"{header}: {name}"
+        ret = " ".join(ret.replace("*", " * ").split())
+        if ret == "const char *":
+            restype = c_char_p
+        elif ret in _SCALARS:
+            restype = _SCALARS[ret]
+        else:
+            raise ValueError(f"{where}: return type {ret!r} is not one this binding knows")
+        args = [] if params.strip() == "void" else [_declarator(p, where) for p in params.split(",")]
+        functions[name] = (restype, [t for _, t in args], tuple(n for n, _ in args))
+    return functions, structs
+
+
+def _read_include():
+    headers, params, fields = {}, {}, {}
+    for header in sorted(f for f in os.listdir(INCLUDE) if f.endswith(".h")):
+        with open(os.path.join(INCLUDE, header)) as f:
+            functions, structs = read_header(f.read(), header)
+        headers[header] = {n: sig[:2] for n, sig in functions.items()}
+        params.update({n: sig[2] for n, sig in functions.items()})
+        fields.update({n: (header, body) for n, body in structs.items()})
+    return headers, params, fields
+
+
+# HEADERS: header of include/ -> {entry point: (restype, argtypes)}, what lib() binds; PARAMS: entry point -> its
+# parameter names; STRUCTS: C struct name -> its ctypes.Structure below
+HEADERS, PARAMS, _STRUCT_FIELDS = _read_include()
+STRUCTS = {}
+GRAPH_IGNORE_QUERY = 1      # SSS_GRAPH_IGNORE_QUERY of include/sss_graph.h
+
+
+def _c_struct(name):
+    """Class decorator: the ``_fields_`` of struct ``name`` as its header declares them."""
+    def bind(cls):
+        header, body = _STRUCT_FIELDS[name]
+        cls._fields_ = [_declarator(f, f"{header}: {name}", STRUCTS) for f in body]
+        STRUCTS[name] = cls
+        return cls
+    return bind
+
+
+@_c_struct("sss_linear_problem")
 class LinearProblem(ctypes.Structure):
     """``sss_linear_problem`` of include/sss.h."""
-    _fields_ = [("x", c_void_p), ("ldx", c_int64), ("ids", c_void_p), ("table", c_void_p), ("xcopy", c_void_p),
-                ("ld_xcopy", c_int64), ("w", c_void_p), ("ldw", c_int64), ("bias", c_void_p), ("y", c_void_p),
-                ("ldy", c_int64), ("n", c_int64), ("m", c_int32), ("act", c_int32), ("post_scale", c_void_p), ("post_shift", c_void_p)]
 
 
 def linear_problem(x, w, bias, y, n, m, act=0, post=None, ids=None, table=None, xcopy=None):
@@ -257,99 +118,42 @@ def pad32(n):
     return (n + 31) // 32 * 32
 
 
+@_c_struct("sss_graph_out")
 class GraphOut(ctypes.Structure):
     """``sss_graph_out`` of include/sss.h."""
-    _fields_ = [(n, c_void_p) for n in ("q_x", "q_batch", "q_pos", "p_x", "p_batch", "p_cnt", "rowptr_qp", "col_qp",
-                                        "rowptr_pq", "col_pq", "rowptr_pp", "col_pp", "w_pp", "src_row", "pos_id")]
 
 
+@_c_struct("sss_layer_args")
 class LayerArgs(ctypes.Structure):
     """``sss_layer_args`` of include/sss.h."""
-    _fields_ = [("yp", c_void_p), ("ld_yp", c_int64), ("yq", c_void_p), ("ld_yq", c_int64), ("h", c_int32), ("d_x", c_int32),
-                ("rowptr_qp", c_void_p), ("col_qp", c_void_p), ("rowptr_pp", c_void_p), ("col_pp", c_void_p),
-                ("w_pp", c_void_p), ("bias_qp", c_void_p), ("b_ih", c_void_p),
-                ("xin_p", c_void_p), ("ld_xin", c_int64), ("out_p", c_void_p), ("ld_out_p", c_int64), ("np", c_int64),
-                ("rowptr_pq", c_void_p), ("col_pq", c_void_p), ("bias_pq", c_void_p),
-                ("out_q", c_void_p), ("ld_out_q", c_int64), ("nq", c_int64), ("n_self_loop", c_int64),
-                ("row_p", c_void_p), ("row_q", c_void_p), ("x0_p", c_void_p), ("ld_x0_p", c_int64),
-                ("xq_table", c_void_p), ("ld_xq", c_int64), ("x0_q", c_void_p), ("ld_x0_q", c_int64)]
 
 
+@_c_struct("sss_hgt_slot")
 class HgtSlot(ctypes.Structure):
     """``sss_hgt_slot`` of include/sss_hgt.h."""
-    _fields_ = [("k", c_void_p), ("ld_k", c_int64), ("v", c_void_p), ("ld_v", c_int64), ("rowptr", c_void_p), ("col", c_void_p)]
 
 
+@_c_struct("sss_hgt_args")
 class HgtArgs(ctypes.Structure):
     """``sss_hgt_args`` of include/sss_hgt.h."""
-    _fields_ = [("q", c_void_p), ("ld_q", c_int64), ("slot", HgtSlot * 2), ("n_slots", c_int32), ("n_dst", c_int64),
-                ("heads", c_int32), ("head_dim", c_int32), ("gelu", c_int32), ("out", c_void_p), ("ld_out", c_int64)]
 
 
+@_c_struct("sss_seq_attention_args")
 class SeqAttentionArgs(ctypes.Structure):
     """``sss_seq_attention_args`` of include/sss_text.h."""
-    _fields_ = [("qkv", c_void_p), ("ld_qkv", c_int64), ("ptr", c_void_p), ("key_ok", c_void_p), ("n_rows", c_int64),
-                ("n_seq", c_int64), ("heads", c_int32), ("head_dim", c_int32), ("max_len", c_int32), ("out", c_void_p),
-                ("ld_out", c_int64)]
+
+
+if set(STRUCTS) != set(_STRUCT_FIELDS):
+    raise ValueError(f"include/ declares structs with no ctypes.Structure here: {sorted(set(_STRUCT_FIELDS) - set(STRUCTS))}")
+
+
+def symbols(header):
+    """The entry points of include/<header>."""
+    return sorted(HEADERS[header])
 
 
 def exported_symbols():
-    return sorted(HEADERS["sss.h"])
-
-
-def sparse_symbols():
-    """The entry points of include/sss_sparse.h."""
-    return sorted(HEADERS["sss_sparse.h"])
-
-
-def l2_symbols():
-    """The entry points of include/sss_l2.h."""
-    return sorted(HEADERS["sss_l2.h"])
-
-
-def l2_long_symbols():
-    """The entry points of include/sss_l2_long.h."""
-    return sorted(HEADERS["sss_l2_long.h"])
-
-
-def pad_symbols():
-    """The entry points of include/sss_pad.h."""
-    return sorted(HEADERS["sss_pad.h"])
-
-
-def graph_symbols():
-    """The entry points of include/sss_graph.h."""
-    return sorted(HEADERS["sss_graph.h"])
-
-
-def eval_symbols():
-    """The entry points of include/sss_eval.h."""
-    return sorted(HEADERS["sss_eval.h"])
-
-
-def jaccard_symbols():
-    """The entry points of include/sss_jaccard.h."""
-    return sorted(HEADERS["sss_jaccard.h"])
-
-
-def ptype_symbols():
-    """The entry points of include/sss_ptype.h."""
-    return sorted(HEADERS["sss_ptype.h"])
-
-
-def hgt_symbols():
-    """The entry points of include/sss_hgt.h."""
-    return sorted(HEADERS["sss_hgt.h"])
-
-
-def text_symbols():
-    """The entry points of include/sss_text.h."""
-    return sorted(HEADERS["sss_text.h"])
-
-
-def bert_symbols():
-    """The entry points of include/sss_bert.h."""
-    return sorted(HEADERS["sss_bert.h"])
+    return symbols("sss.h")
 
 
 def build(verbose: bool = False) -> str:
@@ -379,6 +183,13 @@ def lib():
                 fn.restype, fn.argtypes = res, args
         _lib = h
     return _lib
+
+
+def call(name, values):
+    """Entry point ``name`` with each argument taken from ``values`` under the name its header gives the parameter (a
+    parameter ``values`` lacks: KeyError naming it).  For the once-per-search calls whose families differ in what they
+    take; the per-launch paths call positionally."""
+    return getattr(lib(), name)(*[values[p] for p in PARAMS[name]])
 
 
 class SssError(RuntimeError):

@@ -184,9 +184,9 @@ static int run_threshold_form(const ThrArgs& t, const void* c_scan, const ScanPl
 constexpr int THR_CAP = 8192;       // rows kept per query (64 KB of keys in LDS for the sort)
 static size_t thr_head_bytes(long nsel) { return ((size_t)nsel * 8 + 255) & ~(size_t)255; }
 
-extern "C" size_t sss_ip_topk_threshold_workspace_bytes(int64_t nsel, int64_t n, int d, int scan) {
-    if (nsel <= 0 || n <= 0 || !fused_shape_ok(d, scan)) return 0;
-    return thr_head_bytes(nsel) + make_thr_plan(nsel, n, d, scan, THR_CAP).total_bytes;
+extern "C" size_t sss_ip_topk_threshold_workspace_bytes(int64_t nsel, int64_t n, int d, int scan_dtype) {
+    if (nsel <= 0 || n <= 0 || !fused_shape_ok(d, scan_dtype)) return 0;
+    return thr_head_bytes(nsel) + make_thr_plan(nsel, n, d, scan_dtype, THR_CAP).total_bytes;
 }
 
 static int topk_threshold_impl(const char* what, const void* q, const int* qsel, long nsel, const void* c_exact, int exact_dtype,
@@ -213,11 +213,11 @@ static int topk_threshold_impl(const char* what, const void* q, const int* qsel,
 }
 
 extern "C" int sss_ip_topk_threshold(const void* q, const int32_t* qsel, int64_t nsel, const void* corpus, int dtype,
-                                     const void* scan_image, int scan, int corpus_shift, float corpus_resid_norm, int64_t n, int d,
+                                     const void* scan_image, int scan_dtype, int corpus_shift, float corpus_resid_norm, int64_t n, int d,
                                      int k, int64_t id_offset, float corpus_max_norm, float* D_out, int64_t* I_out, int32_t* status,
                                      void* workspace, size_t workspace_bytes, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return topk_threshold_impl("ip_topk_threshold", q, qsel, nsel, corpus, dtype, scan_image, scan, corpus_shift, corpus_resid_norm, n, d,
+    return topk_threshold_impl("ip_topk_threshold", q, qsel, nsel, corpus, dtype, scan_image, scan_dtype, corpus_shift, corpus_resid_norm, n, d,
                                k, id_offset, corpus_max_norm, D_out, I_out, status, workspace, workspace_bytes, st);
 }
 
@@ -227,27 +227,27 @@ extern "C" int sss_ip_topk_threshold(const void* q, const int32_t* qsel, int64_t
 static size_t range_head_bytes(long nq) { return thr_head_bytes(nq) + (((size_t)nq * 4 + 255) & ~(size_t)255); }
 static size_t range_cand_bytes(long nq) { return ((size_t)nq * THR_CAP * 8 + 255) & ~(size_t)255; }
 
-extern "C" size_t sss_range_search_workspace_bytes(int64_t nq, int64_t n, int d, int scan) {
-    if (nq <= 0 || n <= 0 || !fused_shape_ok(d, scan)) return 0;
-    return range_head_bytes(nq) + make_thr_plan(nq, n, d, scan, THR_CAP).total_bytes;
+extern "C" size_t sss_range_search_workspace_bytes(int64_t nq, int64_t n, int d, int scan_dtype) {
+    if (nq <= 0 || n <= 0 || !fused_shape_ok(d, scan_dtype)) return 0;
+    return range_head_bytes(nq) + make_thr_plan(nq, n, d, scan_dtype, THR_CAP).total_bytes;
 }
 
-extern "C" int sss_range_search_count(const void* q, int64_t nq, const void* corpus, int dtype, const void* scan_image, int scan,
+extern "C" int sss_range_search_count(const void* q, int64_t nq, const void* corpus, int dtype, const void* scan_image, int scan_dtype,
                                       int corpus_shift, float corpus_resid_norm, int64_t n, int d, const float* radius,
                                       float corpus_max_norm, int64_t* counts, int32_t* status, void* workspace, size_t workspace_bytes,
                                       void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (nq <= 0 || n <= 0) { set_error("range_search_count: nq, n must be positive"); return SSS_EINVAL; }
-    const int rc = check_scan_source("range_search_count", dtype, scan, d, false, scan_image, corpus_shift, corpus_resid_norm, n, nq);
+    const int rc = check_scan_source("range_search_count", dtype, scan_dtype, d, false, scan_image, corpus_shift, corpus_resid_norm, n, nq);
     if (rc) return rc;
     if (!q || !corpus || !radius || !counts || !status) { set_error("range_search_count: q, corpus, radius, counts and status are required"); return SSS_EINVAL; }
     if (reinterpret_cast<uintptr_t>(workspace) & 255) { set_error("range_search_count: workspace must be 256-byte aligned"); return SSS_EINVAL; }
-    const ScanPlan p = make_thr_plan(nq, n, d, scan, THR_CAP);
+    const ScanPlan p = make_thr_plan(nq, n, d, scan_dtype, THR_CAP);
     const size_t need = range_head_bytes(nq) + p.total_bytes;
     if (!workspace || workspace_bytes < need) { set_error("range_search_count: workspace %zu < %zu", workspace_bytes, need); return SSS_EWORKSPACE; }
     char* w = reinterpret_cast<char*>(workspace);
     int* qsel = reinterpret_cast<int*>(w + thr_head_bytes(nq));
-    ThrArgs t = thr_args(q, corpus, dtype, scan, corpus_shift, corpus_resid_norm, corpus_max_norm, qsel, nq, n, d, 1, p.cap, 0);
+    ThrArgs t = thr_args(q, corpus, dtype, scan_dtype, corpus_shift, corpus_resid_norm, corpus_max_norm, qsel, nq, n, d, 1, p.cap, 0);
     t.thr = reinterpret_cast<float*>(w);
     t.cnt = reinterpret_cast<unsigned*>(w + (size_t)nq * 4);
     t.cand = reinterpret_cast<unsigned long long*>(w + range_head_bytes(nq));
@@ -277,21 +277,21 @@ extern "C" int sss_ip_topk(const void* q, int64_t nq, const void* corpus, int64_
                         unproven_count, state, state_bytes, workspace, workspace_bytes, st);
 }
 
-extern "C" int sss_ip_topk_split(const float* q, int64_t nq, const float* corpus, const uint16_t* corpus_split, int64_t n, int d, int k,
+extern "C" int sss_ip_topk_split(const float* q, int64_t nq, const float* corpus, const uint16_t* scan_image, int64_t n, int d, int k,
                                  int64_t id_offset, float corpus_max_norm, float* D_out, int64_t* I_out, int32_t* status,
                                  int32_t* unproven_count, void* state, size_t state_bytes, void* workspace, size_t workspace_bytes,
                                  void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return ip_topk_impl("ip_topk_split", q, nq, corpus_split, DT_SPLIT, 0, 0.f, corpus, DT_F32, n, d, k, id_offset, corpus_max_norm, D_out,
+    return ip_topk_impl("ip_topk_split", q, nq, scan_image, DT_SPLIT, 0, 0.f, corpus, DT_F32, n, d, k, id_offset, corpus_max_norm, D_out,
                         I_out, status, unproven_count, state, state_bytes, workspace, workspace_bytes, st);
 }
 
-extern "C" int sss_ip_topk_f16(const float* q, int64_t nq, const float* corpus, const uint16_t* corpus_f16, int corpus_shift,
+extern "C" int sss_ip_topk_f16(const float* q, int64_t nq, const float* corpus, const uint16_t* scan_image, int corpus_shift,
                                float corpus_resid_norm, int64_t n, int d, int k, int64_t id_offset, float corpus_max_norm, float* D_out,
                                int64_t* I_out, int32_t* status, int32_t* unproven_count, void* state, size_t state_bytes,
                                void* workspace, size_t workspace_bytes, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return ip_topk_impl("ip_topk_f16", q, nq, corpus_f16, DT_F16, corpus_shift, corpus_resid_norm, corpus, DT_F32, n, d, k, id_offset, corpus_max_norm,
+    return ip_topk_impl("ip_topk_f16", q, nq, scan_image, DT_F16, corpus_shift, corpus_resid_norm, corpus, DT_F32, n, d, k, id_offset, corpus_max_norm,
                         D_out, I_out, status, unproven_count, state, state_bytes, workspace, workspace_bytes, st);
 }
 

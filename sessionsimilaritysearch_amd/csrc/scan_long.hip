@@ -511,14 +511,14 @@ extern "C" int sss_ip_topk_long(const void* q, int64_t nq, const void* corpus, i
 
 // L2 top-k of long float32 rows (include/sss_l2_long.h): the buffers an inner-product call does not have are checked
 // here, the shape / image / k / workspace checks are topk_long_impl's own -- all of them before the first launch.
-extern "C" int sss_l2_topk_long(const float* q, int64_t nq, const float* corpus, const void* f16_image, int corpus_shift,
+extern "C" int sss_l2_topk_long(const float* q, int64_t nq, const float* corpus, const void* scan_image, int corpus_shift,
                                 float corpus_resid_norm, const float* bias, int64_t n, int d, int k, int64_t id_offset,
                                 float corpus_max_norm, float* D_out, int64_t* I_out, int32_t* status, void* workspace,
                                 size_t workspace_bytes, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!bias || (reinterpret_cast<uintptr_t>(bias) & 15)) { set_error("l2_topk_long: row bias missing or not 16-byte aligned"); return SSS_EINVAL; }
     if (!q || !corpus || !D_out || !I_out || !status) { set_error("l2_topk_long: q, corpus, D_out, I_out and status are required"); return SSS_EINVAL; }
-    return topk_long_impl("l2_topk_long", bias, q, nq, corpus, DT_F32, f16_image, corpus_shift, corpus_resid_norm, n, d, k, id_offset, corpus_max_norm,
+    return topk_long_impl("l2_topk_long", bias, q, nq, corpus, DT_F32, scan_image, corpus_shift, corpus_resid_norm, n, d, k, id_offset, corpus_max_norm,
                           D_out, I_out, status, workspace, workspace_bytes, st);
 }
 

@@ -63,28 +63,15 @@ RANGE_CHUNK = 4096               # queries per fused range_search count / fill (
 _SCAN_CODE = {"split": 2, "f16": 3}                              # include/sss.h: scan image codes (else the dtype's own)
 
 
-class _Entry:
-    """The libsss entry point of one scan family: its name, the fields its argument list opens with (the rest -- bound,
-    outputs, workspace, stream -- is the same in every family) and the fields its workspace-size function takes."""
-    def __init__(self, name: str, lead: str, ws_lead: str, ws_name: str | None = None):
-        self.name, self.lead, self.ws_lead, self.ws_name = name, lead.split(), ws_lead.split(), ws_name or name + "_workspace_bytes"
-
-
-# Field names are those of FlatIndex._fields: "dtype" is the stored rows' code, "code" the scan image's, "id" the id offset.
-_TOPK = {                                # search_fused, by FlatIndex._family ("ip": by scan, else the index's own rows)
-    "pad": _Entry("sss_pad_topk", "q nq xb image code shift resid bias n d ds k id", "nq n d ds k code"),
-    "l2": _Entry("sss_l2_topk", "q nq xb image code shift resid bias n d k id", "nq n d k code"),
-    "ip_f16": _Entry("sss_ip_topk_f16", "q nq xb image shift resid n d k id", "nq n d k"),
-    "ip_split": _Entry("sss_ip_topk_split", "q nq xb image n d k id", "nq n d k dtype", "sss_ip_topk_workspace_bytes"),
-    "ip": _Entry("sss_ip_topk", "q nq xb n d k dtype id", "nq n d k dtype"),
-    "long_ip": _Entry("sss_ip_topk_long", "q nq xb dtype image shift resid n d k id", "nq n d dtype"),
-    "long_l2": _Entry("sss_l2_topk_long", "q nq xb image shift resid bias n d k id", "nq n d"),
+# Scan family (FlatIndex._family; "ip": by scan, else by the index's own rows) -> the entry point that serves it.  What a
+# family takes -- a row bias, a state buffer, an unproven count -- is read from its declaration (_lib.PARAMS); its workspace
+# is sized by <name>_workspace_bytes, with one exception.
+_TOPK = {                                # search_fused
+    "pad": "sss_pad_topk", "l2": "sss_l2_topk", "ip_f16": "sss_ip_topk_f16", "ip_split": "sss_ip_topk_split", "ip": "sss_ip_topk",
+    "long_ip": "sss_ip_topk_long", "long_l2": "sss_l2_topk_long",
 }
-_THRESHOLD = {                           # search_threshold (nq: the selected queries); long rows have no rung
-    "pad": _Entry("sss_pad_topk_threshold", "q sel nq xb image code shift resid bias n d ds k id", "nq n d ds code"),
-    "l2": _Entry("sss_l2_topk_threshold", "q sel nq xb image code shift resid bias n d k id", "nq n d code"),
-    "ip": _Entry("sss_ip_topk_threshold", "q sel nq xb dtype image code shift resid n d k id", "nq n d code"),
-}
+_THRESHOLD = {"pad": "sss_pad_topk_threshold", "l2": "sss_l2_topk_threshold", "ip": "sss_ip_topk_threshold"}   # search_threshold; long rows have no rung
+_WORKSPACE_BYTES = {"sss_ip_topk_split": "sss_ip_topk_workspace_bytes"}      # the split scan's workspace is the f32 scan's (dtype 0)
 
 
 def _dev(device=None):
@@ -509,28 +496,23 @@ class FlatIndex(ScanRouting):
         if mode == "":
             raise _lib.SssError("search_fused: this index / k has no fused path (use search)")
         family = self._family(mode)
-        entry = _TOPK.get(f"{family}_{mode}") or _TOPK[family]
-        v = self._fields(q, nq, source, k, mode)
-        ws = self._workspace(entry, v)
-        res = (self.corpus_max_norm(), D.data_ptr(), I.data_ptr(), status.data_ptr())
-        space = (ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
-        if mode == "long":
-            _lib.check(getattr(L, entry.name)(*[v[f] for f in entry.lead], *res, *space), entry.name)
-            if unproven_count is not None:
-                unproven_count += (status != 0).sum().to(torch.int32)
-            return D, I, status
-        sbytes = L.sss_ip_topk_state_bytes(nq)
-        if self._state is None or self._state.numel() < sbytes:
-            self._state = torch.zeros(sbytes, dtype=torch.uint8, device=self.device)
-        if self._pad:
-            # the scan reads the padded batch and the ds-wide image, the re-score the d-wide rows (include/sss_pad.h)
-            qp = self._padded_queries(q, v["ds"])
-            v["q"] = qp.data_ptr()
-        rc = getattr(L, entry.name)(*[v[f] for f in entry.lead], *res, 0 if unproven_count is None else unproven_count.data_ptr(),
-                                    self._state.data_ptr(), self._state.numel(), *space)
-        if rc != 0:
+        name = _TOPK.get(f"{family}_{mode}") or _TOPK[family]
+        v = self._values(source, k, mode, nq=nq, D_out=D.data_ptr(), I_out=I.data_ptr(), status=status.data_ptr(),
+                         unproven_count=0 if unproven_count is None else unproven_count.data_ptr())
+        self._set_workspace(name, v)
+        stateful = "state" in _lib.PARAMS[name]                 # the long-row entries keep no state and count no unproven queries
+        if stateful:
+            sbytes = L.sss_ip_topk_state_bytes(nq)
+            if self._state is None or self._state.numel() < sbytes:
+                self._state = torch.zeros(sbytes, dtype=torch.uint8, device=self.device)
+            v["state"], v["state_bytes"] = self._state.data_ptr(), self._state.numel()
+        self._set_queries(q, v)
+        rc = _lib.call(name, v)
+        if rc != 0 and stateful:
             self._state = None          # re-made (zeroed) on the next call
-        _lib.check(rc, entry.name)
+        _lib.check(rc, name)
+        if unproven_count is not None and "unproven_count" not in _lib.PARAMS[name]:
+            unproven_count += (status != 0).sum().to(torch.int32)
         return D, I, status
 
     def _family(self, mode: str) -> str:
@@ -539,15 +521,29 @@ class FlatIndex(ScanRouting):
             return "long_" + self.metric
         return "pad" if self._pad else self.metric
 
-    def _fields(self, q: torch.Tensor, nq: int, source, k: int, mode: str) -> dict:
-        """The values ``_Entry.lead`` names; ``source`` is ``_scan_image(mode)``'s, an L2 index's row bias up to date."""
+    def _values(self, source, k: int, mode: str, **call) -> dict:
+        """The arguments of a scan family's entry point under the names the headers give its parameters; ``source`` is
+        ``_scan_image(mode)``'s, an L2 index's row bias up to date, ``call`` what the one call adds (counts, outputs)."""
         image, code, shift, resid = source
-        return {"q": q.data_ptr(), "nq": nq, "xb": self._xb.data_ptr(), "dtype": self._fmt.code, "image": image.data_ptr(),
-                "code": code, "shift": shift, "resid": resid, "bias": self._bias.data_ptr() if self.metric == "l2" else None,
-                "n": self.ntotal, "d": self.d, "ds": self.scan_width(mode) if self._pad else 0, "k": k, "id": self.id_offset}
+        v = {"corpus": self._xb.data_ptr(), "dtype": self._fmt.code, "scan_image": image.data_ptr(), "scan_dtype": code,
+             "corpus_shift": shift, "corpus_resid_norm": resid, "bias": self._bias.data_ptr() if self.metric == "l2" else None,
+             "n": self.ntotal, "d": self.d, "k": k, "id_offset": self.id_offset, "corpus_max_norm": self.corpus_max_norm(),
+             "stream": _lib.stream_ptr(self.device), **call}
+        if self._pad:
+            v["d_row"], v["d_scan"] = self.d, self.scan_width(mode)
+        return v
 
-    def _workspace(self, entry: _Entry, v: dict) -> torch.Tensor:
-        return self._ws.get(getattr(_lib.lib(), entry.ws_name)(*[v[f] for f in entry.ws_lead]))
+    def _set_queries(self, q: torch.Tensor, v: dict):
+        """``v["q"]``: the batch -- on a ``pad_scan`` index zero-extended to the scan's width: the scan reads the padded
+        batch and the d_scan-wide image, the re-score the d-wide rows (include/sss_pad.h)."""
+        if self._pad:
+            q = v["padded q"] = self._padded_queries(q, v["d_scan"])       # (names no parameter: holds the batch for the call)
+        v["q"] = q.data_ptr()
+
+    def _set_workspace(self, name: str, v: dict):
+        """``v``'s workspace: the index's buffer at the size ``name``'s workspace function asks for on the values ``v``."""
+        ws = self._ws.get(_lib.call(_WORKSPACE_BYTES.get(name, name + "_workspace_bytes"), v))
+        v["workspace"], v["workspace_bytes"] = ws.data_ptr(), ws.numel()
 
     def search_threshold(self, q: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor, status: torch.Tensor, rows):
         """Threshold rung (``sss_ip_topk_threshold``) for the query rows ``rows`` a fused search left
@@ -561,16 +557,12 @@ class FlatIndex(ScanRouting):
         sel = rows.to(device=self.device, dtype=torch.int32).contiguous()
         if self.metric == "l2":
             self._ensure_bias()
-        entry = _THRESHOLD[self._family(mode)]
-        v = self._fields(q, sel.numel(), source, k, mode)
-        v["sel"] = sel.data_ptr()
-        if self._pad:
-            qp = self._padded_queries(q, v["ds"])
-            v["q"] = qp.data_ptr()
-        ws = self._workspace(entry, v)
-        rc = getattr(_lib.lib(), entry.name)(*[v[f] for f in entry.lead], self.corpus_max_norm(), D.data_ptr(), I.data_ptr(),
-                                             status.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device))
-        _lib.check(rc, entry.name)
+        name = _THRESHOLD[self._family(mode)]
+        v = self._values(source, k, mode, qsel=sel.data_ptr(), nsel=sel.numel(), D_out=D.data_ptr(), I_out=I.data_ptr(),
+                         status=status.data_ptr())
+        self._set_queries(q, v)
+        self._set_workspace(name, v)
+        _lib.check(_lib.call(name, v), name)
         return sel[status[sel.long()] != 0]
 
     def fix_unproven(self, q: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor, status: torch.Tensor) -> int:

@@ -4,12 +4,15 @@ thread-local."""
 import ast
 import os
 import re
+import sys
 import threading
 
 from sessionsimilaritysearch_amd import _lib
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from abi import declared  # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "sss.h")
 GPU_MODULE = os.path.join(ROOT, "tests", "test_abi_contract_gpu.py")
 
 # Host-only helpers and diagnostics: nothing is written to device buffers the caller owns.
@@ -22,12 +25,6 @@ EXEMPT = {
     "sss_scan_boot_expired": "diagnostic counter; read (not asserted) by the concurrency test",
 }
 _EXEMPT_PATTERNS = (r".*_bytes", r".*_capacity", r"sss_graph_scratch_ints")   # sizing queries: host arithmetic only
-
-
-def declared_entry_points():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return sorted(set(re.findall(r"\b(sss_\w+)\s*\(", text)))
 
 
 def _gpu_module():
@@ -43,7 +40,7 @@ def _exempt(name):
 
 
 def test_every_entry_point_is_covered_or_exempt():
-    names = declared_entry_points()
+    names = declared("sss.h")
     assert len(names) > 50
     table, tests = _gpu_module()
     missing = [n for n in names if n not in table and not _exempt(n)]
@@ -58,7 +55,7 @@ def test_every_entry_point_is_covered_or_exempt():
 
 
 def test_header_and_ctypes_binding_declare_the_same_entry_points():
-    assert declared_entry_points() == _lib.exported_symbols()
+    assert declared("sss.h") == _lib.exported_symbols()
 
 
 def test_last_error_is_thread_local():

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from abi import declared  # noqa: E402
 import bert_ref as br  # noqa: E402
 
 from sessionsimilaritysearch_amd import _lib  # noqa: E402
@@ -260,30 +261,23 @@ def test_unique_rows_partitions_like_numpy():
 
 
 # ------------------------------------------------------------------------------------------------ symbols
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return sorted(set(re.findall(r"\b(sss_\w+)\s*\(", text)))
-
-
 def test_bert_header_and_binding_declare_the_same_entry_point():
-    names = _declared("sss_bert.h")
-    assert names == _lib.bert_symbols() == ["sss_bert_embed"]
-    assert _lib.HEADERS["sss_bert.h"] is _lib._BERT_SIGNATURES
+    names = declared("sss_bert.h")
+    assert names == _lib.symbols("sss_bert.h") == ["sss_bert_embed"]
     L = _lib.lib()
-    assert L.sss_bert_embed.argtypes == _lib._BERT_SIGNATURES["sss_bert_embed"][1] and L.sss_bert_embed.restype is ctypes.c_int
+    assert L.sss_bert_embed.argtypes == _lib.HEADERS["sss_bert.h"]["sss_bert_embed"][1] and L.sss_bert_embed.restype is ctypes.c_int
     for header, table in _lib.HEADERS.items():
         if header != "sss_bert.h":
-            assert not set(names) & set(table) and not set(names) & set(_declared(header)), header
+            assert not set(names) & set(table) and not set(names) & set(declared(header)), header
     assert sorted(_lib.HEADERS) == sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h"))
-    assert _declared("sss.h") == _lib.exported_symbols() and len(_lib.exported_symbols()) == 60
+    assert declared("sss.h") == _lib.exported_symbols() and len(_lib.exported_symbols()) == 60
     text = open(os.path.join(ROOT, "include", "sss_bert.h")).read()
     for phrase in ("CALLER-OWNED DEVICE", "nothing is allocated", "no host synchronisation", "enqueued on `stream`",
                    "-1 bad argument", "-3 HIP error", "bert_embed:"):
         assert phrase in text, phrase
     plain = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     params = re.search(r"\bsss_bert_embed\s*\(([^)]*)\)", plain, re.S).group(1)
-    assert len(params.split(",")) == len(_lib._BERT_SIGNATURES["sss_bert_embed"][1])
+    assert len(params.split(",")) == len(_lib.HEADERS["sss_bert.h"]["sss_bert_embed"][1])
     assert "5 gelu" in open(os.path.join(ROOT, "include", "sss.h")).read()
 
 

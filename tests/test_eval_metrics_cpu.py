@@ -19,13 +19,13 @@ Bounds against the reference's recorded values (absolute; every term and every m
   get_recall                  counts: integers, the two means are of the same nq integers -- GAMMA(nq)."""
 import math
 import os
-import re
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from abi import declared  # noqa: E402
 import eval_ref as ev  # noqa: E402
 import sparse_ref as sp  # noqa: E402
 
@@ -118,21 +118,16 @@ def test_helper_canonical_loop_by_hand():
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(sss_\w+)\s*\(", text)))
-
-
 def test_eval_header_and_binding_declare_the_same_entry_points():
-    names = _declared("sss_eval.h")
-    assert names == _lib.eval_symbols() == ["sss_item_overlap", "sss_overlap_metrics"]
+    names = declared("sss_eval.h")
+    assert names == _lib.symbols("sss_eval.h") == ["sss_item_overlap", "sss_overlap_metrics"]
     L = _lib.lib()
     for n in names:
-        assert getattr(L, n).argtypes == _lib._EVAL_SIGNATURES[n][1] and getattr(L, n).restype is _lib._EVAL_SIGNATURES[n][0]
-    others = {"sss.h": _lib.exported_symbols(), "sss_sparse.h": _lib.sparse_symbols(), "sss_l2.h": _lib.l2_symbols(),
-              "sss_pad.h": _lib.pad_symbols(), "sss_graph.h": _lib.graph_symbols()}
+        assert getattr(L, n).argtypes == _lib.HEADERS["sss_eval.h"][n][1] and getattr(L, n).restype is _lib.HEADERS["sss_eval.h"][n][0]
+    others = {"sss.h": _lib.exported_symbols(), "sss_sparse.h": _lib.symbols("sss_sparse.h"), "sss_l2.h": _lib.symbols("sss_l2.h"),
+              "sss_pad.h": _lib.symbols("sss_pad.h"), "sss_graph.h": _lib.symbols("sss_graph.h")}
     for header, bound in others.items():
-        assert _declared(header) == bound and not set(names) & set(bound), header
+        assert declared(header) == bound and not set(names) & set(bound), header
     assert len(others["sss.h"]) == 60
     text = open(os.path.join(ROOT, "include", "sss_eval.h")).read()
     assert "CALLER-OWNED DEVICE" in text and "-3 HIP error" in text

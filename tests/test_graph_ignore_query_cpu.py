@@ -5,18 +5,17 @@ record with its mask `p_last`); and the header / ctypes table of the `_ex` build
 The subset collation of the fixture is test code (numpy offsets), as in tests/helpers/graph_np.py."""
 import itertools
 import os
-import re
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from abi import declared  # noqa: E402
 import graph_np as G  # noqa: E402
 from sessionsimilaritysearch_amd import _lib  # noqa: E402
 from sessionsimilaritysearch_amd import sessions as S  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NODE_KEYS = {"product": ("x", "batch", "cnt", "pos_emb_id", "last_click_mask"), "query": ("x", "batch", "pos_emb_id")}
 
 
@@ -138,21 +137,15 @@ def test_ignore_query_is_filtering_on_the_host(z, kind):
         assert not a["query"].pos_emb_id.any() and not a["product"].pos_emb_id.any()
 
 
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return sorted(set(re.findall(r"\b(sss_\w+)\s*\(", text)))
-
-
 def test_graph_header_library_and_ctypes_binding_name_the_same_entry_points():
-    names = _declared("sss_graph.h")
-    assert names == _lib.graph_symbols() == ["sss_graph_counts_ex", "sss_graph_fill_ex"]
+    names = declared("sss_graph.h")
+    assert names == _lib.symbols("sss_graph.h") == ["sss_graph_counts_ex", "sss_graph_fill_ex"]
     L = _lib.lib()
     for n in names:
-        assert getattr(L, n).argtypes == _lib._GRAPH_SIGNATURES[n][1]
-    others = set(_lib.exported_symbols()) | set(_lib.sparse_symbols()) | set(_lib.l2_symbols()) | set(_lib.pad_symbols())
+        assert getattr(L, n).argtypes == _lib.HEADERS["sss_graph.h"][n][1]
+    others = set(_lib.exported_symbols()) | set(_lib.symbols("sss_sparse.h")) | set(_lib.symbols("sss_l2.h")) | set(_lib.symbols("sss_pad.h"))
     assert not set(names) & others
-    assert _declared("sss.h") == _lib.exported_symbols() and len(_lib.exported_symbols()) == 60
+    assert declared("sss.h") == _lib.exported_symbols() and len(_lib.exported_symbols()) == 60
     # argument rules, checked before anything is launched (addresses that are never dereferenced)
     A = 1 << 20
     for flags in (2, 3, 4, -1, 1 << 16):

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from abi import declared  # noqa: E402
 import hgt_ref as hr  # noqa: E402
 
 from sessionsimilaritysearch_amd import _lib  # noqa: E402
@@ -115,22 +116,16 @@ def test_package_exports_the_hgt_encoder():
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return sorted(set(re.findall(r"\b(sss_\w+)\s*\(", text)))
-
-
 def test_hgt_header_and_binding_declare_the_same_entry_points():
-    names = _declared("sss_hgt.h")
-    assert names == _lib.hgt_symbols() == ["sss_hgt_aggregate", "sss_hgt_skip"]
+    names = declared("sss_hgt.h")
+    assert names == _lib.symbols("sss_hgt.h") == ["sss_hgt_aggregate", "sss_hgt_skip"]
     L = _lib.lib()
     for n in names:
-        assert getattr(L, n).argtypes == _lib._HGT_SIGNATURES[n][1] and getattr(L, n).restype is ctypes.c_int
+        assert getattr(L, n).argtypes == _lib.HEADERS["sss_hgt.h"][n][1] and getattr(L, n).restype is ctypes.c_int
     for header, table in _lib.HEADERS.items():
         if header != "sss_hgt.h":
-            assert not set(names) & set(table) and not set(names) & set(_declared(header)), header
-    assert _declared("sss.h") == _lib.exported_symbols()
+            assert not set(names) & set(table) and not set(names) & set(declared(header)), header
+    assert declared("sss.h") == _lib.exported_symbols()
     text = open(os.path.join(ROOT, "include", "sss_hgt.h")).read()
     for phrase in ("CALLER-OWNED DEVICE", "nothing is allocated", "no host synchronisation", "enqueued on `stream`",
                    "-1 bad argument", "-3 HIP error"):

@@ -15,12 +15,13 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from abi import declared  # noqa: E402
 import jaccard_ref as jr  # noqa: E402
 
 from sessionsimilaritysearch_amd import _lib  # noqa: E402
 from sessionsimilaritysearch_amd.distributed import ShardedJaccardIndex, shard_range  # noqa: E402
 from test_eval_metrics_cpu import golden, host_parts  # noqa: E402
-from test_sparse_index_cpu import OracleEngine as SparseOracle, _declared  # noqa: E402
+from test_sparse_index_cpu import OracleEngine as SparseOracle  # noqa: E402
 import sparse_ref  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -85,15 +86,15 @@ def test_float32_keeps_the_order_of_fractions_up_to_128():
 
 # ------------------------------------------------------------------------------------------------ the C ABI
 def test_jaccard_header_and_binding_declare_the_same_entry_points():
-    names = _declared("sss_jaccard.h")
-    assert names == _lib.jaccard_symbols() == ["sss_jaccard_bands", "sss_jaccard_topk", "sss_jaccard_topk_workspace_bytes"]
+    names = declared("sss_jaccard.h")
+    assert names == _lib.symbols("sss_jaccard.h") == ["sss_jaccard_bands", "sss_jaccard_topk", "sss_jaccard_topk_workspace_bytes"]
     L = _lib.lib()
     for n in names:
-        assert getattr(L, n).argtypes == _lib._JACCARD_SIGNATURES[n][1]
+        assert getattr(L, n).argtypes == _lib.HEADERS["sss_jaccard.h"][n][1]
     for header, table in _lib.HEADERS.items():
         if header != "sss_jaccard.h":
-            assert not set(names) & set(table) and not set(names) & set(_declared(header)), header
-    assert _declared("sss.h") == _lib.exported_symbols()
+            assert not set(names) & set(table) and not set(names) & set(declared(header)), header
+    assert declared("sss.h") == _lib.exported_symbols()
     text = open(os.path.join(ROOT, "include", "sss_jaccard.h")).read()
     assert "CALLER-OWNED DEVICE" in text and "-2 workspace too small" in text and "HOST array" in text and "2^-14" in text
 

@@ -1,38 +1,31 @@
 """L2 on the long-row scan without a device: include/sss_l2_long.h and its ctypes table agree and stay out of the other
 headers' lists, the workspace size is host arithmetic, and the routing policy of ``FlatIndex.l2_long_for`` is host logic."""
 import os
-import re
 import sys
 
 from sessionsimilaritysearch_amd import _lib, index as ix
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from abi import declared  # noqa: E402
 from routing_stub import make_routing  # noqa: E402
 NAMES = ["sss_l2_topk_long", "sss_l2_topk_long_workspace_bytes"]
 
 
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return sorted(set(re.findall(r"\b(sss_\w+)\s*\(", text)))
-
-
 def test_l2_long_header_and_ctypes_binding_declare_the_same_entry_points():
-    names = _declared("sss_l2_long.h")
-    assert names == _lib.l2_long_symbols() == NAMES
+    names = declared("sss_l2_long.h")
+    assert names == _lib.symbols("sss_l2_long.h") == NAMES
     L = _lib.lib()
     for n in names:
-        assert getattr(L, n).argtypes == _lib._L2_LONG_SIGNATURES[n][1]
-        assert getattr(L, n).restype == _lib._L2_LONG_SIGNATURES[n][0]
+        assert getattr(L, n).argtypes == _lib.HEADERS["sss_l2_long.h"][n][1]
+        assert getattr(L, n).restype == _lib.HEADERS["sss_l2_long.h"][n][0]
 
 
 def test_l2_long_names_are_in_no_other_list():
-    others = {"sss.h": _lib.exported_symbols(), "sss_sparse.h": _lib.sparse_symbols(), "sss_l2.h": _lib.l2_symbols(),
-              "sss_pad.h": _lib.pad_symbols(), "sss_graph.h": _lib.graph_symbols(), "sss_eval.h": _lib.eval_symbols()}
+    others = {"sss.h": _lib.exported_symbols(), "sss_sparse.h": _lib.symbols("sss_sparse.h"), "sss_l2.h": _lib.symbols("sss_l2.h"),
+              "sss_pad.h": _lib.symbols("sss_pad.h"), "sss_graph.h": _lib.symbols("sss_graph.h"), "sss_eval.h": _lib.symbols("sss_eval.h")}
     for header, listed in others.items():
         assert not set(NAMES) & set(listed), header
-        assert not set(NAMES) & set(_declared(header)), header
+        assert not set(NAMES) & set(declared(header)), header
 
 
 def test_l2_long_workspace_bytes_is_host_arithmetic():

@@ -1,38 +1,31 @@
 """L2 on the matrix-core scans without a device: the new header and its ctypes table agree, include/sss.h keeps its
 entry points, and the routing policy of ``FlatIndex.l2_scan_for`` is host logic."""
 import os
-import re
 import sys
 
 import pytest
 
 from sessionsimilaritysearch_amd import _lib, index as ix
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from abi import declared  # noqa: E402
 from routing_stub import make_routing  # noqa: E402
 
 
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return sorted(set(re.findall(r"\b(sss_\w+)\s*\(", text)))
-
-
 def test_l2_header_and_ctypes_binding_declare_the_same_entry_points():
-    names = _declared("sss_l2.h")
-    assert names == _lib.l2_symbols()
+    names = declared("sss_l2.h")
+    assert names == _lib.symbols("sss_l2.h")
     assert names == ["sss_l2_row_bias", "sss_l2_topk", "sss_l2_topk_threshold", "sss_l2_topk_threshold_workspace_bytes",
                      "sss_l2_topk_workspace_bytes"]
     L = _lib.lib()
     for n in names:
-        assert getattr(L, n).argtypes == _lib._L2_SIGNATURES[n][1]
+        assert getattr(L, n).argtypes == _lib.HEADERS["sss_l2.h"][n][1]
 
 
 def test_main_header_keeps_its_entry_points():
     """The L2 entry points live in their own header: include/sss.h declares what it declared (its coverage table is in a
     test file of its own) and none of the new names."""
-    main = _declared("sss.h")
+    main = declared("sss.h")
     assert main == _lib.exported_symbols() and len(main) == 60
     assert not [n for n in main if n.startswith("sss_l2_")]
 

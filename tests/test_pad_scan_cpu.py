@@ -3,15 +3,14 @@ float32 index of any width d % 4 == 0 up to 512 is host logic; include/sss_pad.h
 same entry points; and every argument rule of the new entry points is checked before anything is launched (calls with
 null or never-dereferenced pointers, as tests/test_abi_contract_cpu.py makes them)."""
 import os
-import re
 import sys
 
 import pytest
 
 from sessionsimilaritysearch_amd import _lib, index as ix
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from abi import declared  # noqa: E402
 from routing_stub import make_routing as Stub  # noqa: E402    (no device: only the policy)
 
 
@@ -128,24 +127,18 @@ def test_escalation_and_decay_as_at_a_native_width(d, native):
 
 
 # ------------------------------------------------------------------------------------------- ABI
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return sorted(set(re.findall(r"\b(sss_\w+)\s*\(", text)))
-
-
 PAD_NAMES = ["sss_pad_f16_resid_max", "sss_pad_rows_f32", "sss_pad_scale_f16", "sss_pad_split_bf16", "sss_pad_topk",
              "sss_pad_topk_threshold", "sss_pad_topk_threshold_workspace_bytes", "sss_pad_topk_workspace_bytes"]
 
 
 def test_pad_header_library_and_ctypes_binding_name_the_same_entry_points():
-    names = _declared("sss_pad.h")
-    assert names == _lib.pad_symbols() == PAD_NAMES
+    names = declared("sss_pad.h")
+    assert names == _lib.symbols("sss_pad.h") == PAD_NAMES
     L = _lib.lib()
     for n in names:
-        assert getattr(L, n).argtypes == _lib._PAD_SIGNATURES[n][1]
-    assert not [n for n in _declared("sss.h") if n.startswith("sss_pad_")]
-    assert not set(names) & (set(_lib.exported_symbols()) | set(_lib.l2_symbols()) | set(_lib.sparse_symbols()))
+        assert getattr(L, n).argtypes == _lib.HEADERS["sss_pad.h"][n][1]
+    assert not [n for n in declared("sss.h") if n.startswith("sss_pad_")]
+    assert not set(names) & (set(_lib.exported_symbols()) | set(_lib.symbols("sss_l2.h")) | set(_lib.symbols("sss_sparse.h")))
 
 
 def test_pad_sizing_queries():

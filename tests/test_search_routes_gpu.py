@@ -1,6 +1,7 @@
 """Routes of the search that the rest of the suite does not pin: scan plans with 8 to 15 active splits (large query
 batches, small corpora), the exhaustive path's compaction pre-pass for 500 < k <= 1024, and the threshold rung at
-selection sizes on wave and workgroup boundaries.  Ids and scores are compared with the oracle by array_equal."""
+selection sizes on wave and workgroup boundaries, and one small search per scan family ``FlatIndex`` calls by parameter
+name.  Ids and scores are compared with the oracle by array_equal."""
 import functools
 
 import numpy as np
@@ -215,3 +216,40 @@ def test_threshold_rung_selection_sizes(cuda, mode, d, nsel):
     Ic, Dc = I.cpu().numpy(), D.cpu().numpy()
     assert np.array_equal(Ic[done], Ir[done]) and np.array_equal(Dc[done], Dr[done])
     assert (Ic[~done] == -7).all() and np.array_equal(Dc[~sel], Ds[~sel])
+
+
+# ------------------------------------------------------------------------------- every scan family once, small
+# (family of index._TOPK / _THRESHOLD, metric, d, FlatIndex arguments, the scan it must run on)
+FAMILY_CASES = [("ip", "ip", 64, dict(scan="f32"), "f32"), ("ip_split", "ip", 128, dict(scan="split"), "split"),
+                ("ip_f16", "ip", 128, dict(scan="f16"), "f16"), ("l2", "l2", 64, dict(scan="f32"), "f32"),
+                ("pad", "ip", 200, dict(scan="f16", pad_scan=True), "f16"), ("long_ip", "ip", 320, {}, "long"),
+                ("long_l2", "l2", 320, {}, "long")]
+FAMILY_CASES = [(*c, False) for c in FAMILY_CASES] + [(*c, True) for c in FAMILY_CASES if c[0] in ("ip", "l2", "pad")]
+
+
+@pytest.mark.parametrize("family,metric,d,kwargs,scan,rung", FAMILY_CASES, ids=[f"{c[0]}-{'rung' if c[-1] else 'topk'}" for c in FAMILY_CASES])
+def test_every_scan_family_is_called_with_its_own_arguments(cuda, family, metric, d, kwargs, scan, rung):
+    """One search per entry point FlatIndex calls by parameter name, at the family's smallest width, with nq != nsel and
+    an id offset so that no two integer arguments can be swapped unseen.  ``rung``: 32 copies of each query in the corpus
+    (the construction of test_f16_index_gpu.test_duplicates_at_the_kth_place_go_through_the_rung) tie across rank k, which
+    no scan can prove: the family's threshold entry point resolves them."""
+    from sessionsimilaritysearch_amd.index import FlatIndex
+    rng = np.random.default_rng(500 + d)
+    n, nq, k, offset = 2000, 8, 10, 7
+    q, c = _unit(rng, nq, d), _unit(rng, n, d)
+    if rung:
+        for j in range(nq):
+            c[rng.choice(n, 32, replace=False)] = q[j]
+    if metric == "l2":
+        Dr, Ir = sr.topk_from_scores(sr.canonical_l2(q, c), k + 1, offset, largest=False)
+    else:
+        Dr, Ir = sr.search_exact(q, c, k + 1, offset)
+    assert (Dr[:, k - 1] == Dr[:, k]).all() if rung else (Dr[:, k - 1] != Dr[:, k]).all()
+    idx = FlatIndex(d, metric, cuda, **kwargs)
+    idx.add(c)
+    idx.id_offset = offset
+    D, I = idx.search(q, k)
+    assert idx.last_scan == scan and family in (idx._family(scan), f"{idx._family(scan)}_{scan}")
+    assert np.array_equal(I, Ir[:, :k]) and np.array_equal(D, Dr[:, :k])
+    if rung:
+        assert idx.last_rescan_queries > 0 and idx.last_fallback_queries == 0

@@ -7,7 +7,6 @@ Tolerances (relative, from the number formats): the reference normalises its flo
 weights (1e-6 each) and at most 19 positive terms summed in float32 (19 * 2^-24): 4e-6."""
 import ast
 import os
-import re
 import socket
 import sys
 
@@ -18,6 +17,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from abi import declared  # noqa: E402
 import sparse_ref as ref  # noqa: E402
 
 from sessionsimilaritysearch_amd import _lib  # noqa: E402
@@ -83,18 +83,13 @@ def test_oracle_binary_weights_and_order():
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(sss_\w+)\s*\(", text)))
-
-
 def test_sparse_header_and_binding_declare_the_same_entry_points():
-    names = _declared("sss_sparse.h")
-    assert names == _lib.sparse_symbols() and len(names) >= 4
+    names = declared("sss_sparse.h")
+    assert names == _lib.symbols("sss_sparse.h") and len(names) >= 4
     L = _lib.lib()
     for n in names:
-        assert getattr(L, n).argtypes == _lib._SPARSE_SIGNATURES[n][1]
-    assert _declared("sss.h") == _lib.exported_symbols()
+        assert getattr(L, n).argtypes == _lib.HEADERS["sss_sparse.h"][n][1]
+    assert declared("sss.h") == _lib.exported_symbols()
     assert not set(names) & set(_lib.exported_symbols())
     text = open(os.path.join(ROOT, "include", "sss_sparse.h")).read()
     assert "CALLER-OWNED DEVICE" in text and "-2 workspace too small" in text
@@ -105,7 +100,7 @@ def test_every_sparse_entry_point_has_a_guarded_gpu_test():
     table = next(ast.literal_eval(n.value) for n in tree.body
                  if isinstance(n, ast.Assign) and any(getattr(t, "id", None) == "COVERAGE" for t in n.targets))
     tests = {n.name for n in tree.body if isinstance(n, ast.FunctionDef)}
-    computing = [n for n in _declared("sss_sparse.h") if not n.endswith("_bytes")]
+    computing = [n for n in declared("sss_sparse.h") if not n.endswith("_bytes")]
     assert sorted(table) == computing and all(t in tests for t in table.values())
 
 

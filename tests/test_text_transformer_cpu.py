@@ -12,6 +12,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from abi import declared  # noqa: E402
 import text_ref as tr  # noqa: E402
 
 from sessionsimilaritysearch_amd import _lib  # noqa: E402
@@ -188,22 +189,16 @@ def test_package_exports_the_text_encoder():
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return sorted(set(re.findall(r"\b(sss_\w+)\s*\(", text)))
-
-
 def test_text_header_and_binding_declare_the_same_entry_points():
-    names = _declared("sss_text.h")
-    assert names == _lib.text_symbols() == ["sss_add_layernorm", "sss_seq_attention", "sss_text_embed"]
+    names = declared("sss_text.h")
+    assert names == _lib.symbols("sss_text.h") == ["sss_add_layernorm", "sss_seq_attention", "sss_text_embed"]
     L = _lib.lib()
     for n in names:
-        assert getattr(L, n).argtypes == _lib._TEXT_SIGNATURES[n][1] and getattr(L, n).restype is ctypes.c_int
+        assert getattr(L, n).argtypes == _lib.HEADERS["sss_text.h"][n][1] and getattr(L, n).restype is ctypes.c_int
     for header, table in _lib.HEADERS.items():
         if header != "sss_text.h":
-            assert not set(names) & set(table) and not set(names) & set(_declared(header)), header
-    assert _declared("sss.h") == _lib.exported_symbols() and len(_lib.exported_symbols()) == 60
+            assert not set(names) & set(table) and not set(names) & set(declared(header)), header
+    assert declared("sss.h") == _lib.exported_symbols() and len(_lib.exported_symbols()) == 60
     text = open(os.path.join(ROOT, "include", "sss_text.h")).read()
     for phrase in ("CALLER-OWNED DEVICE", "nothing is allocated", "no host synchronisation", "enqueued on `stream`",
                    "-1 bad argument", "-3 HIP error"):
@@ -214,7 +209,7 @@ def test_text_header_and_binding_declare_the_same_entry_points():
     assert re.findall(r"(\w+)\s*;", body) == [n for n, _ in _lib.SeqAttentionArgs._fields_]
     for n in names:
         params = re.search(r"\b" + n + r"\s*\(([^)]*)\)", plain, re.S).group(1)
-        assert len(params.split(",")) == len(_lib._TEXT_SIGNATURES[n][1]), n
+        assert len(params.split(",")) == len(_lib.HEADERS["sss_text.h"][n][1]), n
 
 
 _P = 1 << 20                                                          # a non-null, 16-byte aligned address; never dereferenced

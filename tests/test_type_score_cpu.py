@@ -20,12 +20,13 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from abi import declared  # noqa: E402
 import type_score_ref as tr  # noqa: E402
 
 from sessionsimilaritysearch_amd import _lib  # noqa: E402
 from sessionsimilaritysearch_amd.sessions import ActionTable  # noqa: E402
 from sessionsimilaritysearch_amd.distributed import ShardedProductTypeIndex, shard_range  # noqa: E402
-from test_eval_metrics_cpu import AVE_TOL, GAMMA, _declared, golden  # noqa: E402
+from test_eval_metrics_cpu import AVE_TOL, GAMMA, golden  # noqa: E402
 from test_sparse_index_cpu import OracleEngine as SparseOracle  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -134,16 +135,16 @@ def test_helper_by_hand():
 
 # ------------------------------------------------------------------------------------------------ the C ABI
 def test_ptype_header_and_binding_declare_the_same_entry_points():
-    names = _declared("sss_ptype.h")
-    assert names == _lib.ptype_symbols() == NAMES and _lib.HEADERS["sss_ptype.h"] is _lib._PTYPE_SIGNATURES
+    names = declared("sss_ptype.h")
+    assert names == _lib.symbols("sss_ptype.h") == NAMES
     L = _lib.lib()
     for n in names:
-        assert getattr(L, n).argtypes == _lib._PTYPE_SIGNATURES[n][1] and getattr(L, n).restype is _lib._PTYPE_SIGNATURES[n][0]
+        assert getattr(L, n).argtypes == _lib.HEADERS["sss_ptype.h"][n][1] and getattr(L, n).restype is _lib.HEADERS["sss_ptype.h"][n][0]
     for header, table in _lib.HEADERS.items():
         if header != "sss_ptype.h":
-            assert not set(names) & set(table) and not set(names) & set(_declared(header)), header
+            assert not set(names) & set(table) and not set(names) & set(declared(header)), header
     assert sorted(_lib.HEADERS) == sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h"))
-    assert _declared("sss.h") == _lib.exported_symbols() and len(_lib.exported_symbols()) == 60
+    assert declared("sss.h") == _lib.exported_symbols() and len(_lib.exported_symbols()) == 60
     text = open(os.path.join(ROOT, "include", "sss_ptype.h")).read()
     assert "CALLER-OWNED DEVICE" in text and "-2 workspace too small" in text and "HOST array" in text
     assert "SCORE OF RECORD" in text and "__dsqrt_rn" in text and "2^26" in text and "DEVIATION" in text
