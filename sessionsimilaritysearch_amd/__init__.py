@@ -25,6 +25,9 @@ Drop-in surface of the reference's path:
   BertNodeEncoder, bert_fold_weights, bert_pack_rows, BertRows
                                                   (text.py      <- model/NodeEmbedding.py PretrainedQAEAEncoder: the deployed
                                                                   model's node text encoder, BERT + masked mean + Linear)
+  StringTable, StringSequences, query_sequences, title_sequences, sequence_parts, seq_pair_scores, get_query_metric
+                                                  (strings.py   <- fine_tune_ours.py get_score :56-65, the Levenshtein.seqratio
+                                                                  kinds, and test_amazon_filterd.py get_query_metric :416-441)
   ShardedFlatIndex, ShardedBinaryIndex, ShardedSparseIndex, ShardedJaccardIndex, ShardedProductTypeIndex
                                                   (distributed.py: corpus row-sharded over RCCL)
   SessionBatch, build_batch, synthetic_actions    (sessions.py  <- sequence_to_graph + Batch.from_data_list, host side)
@@ -45,6 +48,9 @@ __all__ += list(_HGT)
 _TEXT = ("NodeTextTransformer", "pack_tokens", "text_fold_weights", "TokenRows", "BertNodeEncoder", "bert_fold_weights",
          "bert_pack_rows", "BertRows")
 __all__ += list(_TEXT)
+_STRINGS = ("StringTable", "StringSequences", "SequenceParts", "query_sequences", "title_sequences", "sequence_parts",
+            "seq_pair_scores", "seq_query_metric", "get_query_metric")
+__all__ += list(_STRINGS)
 
 
 def __getattr__(name):
@@ -67,4 +73,7 @@ def __getattr__(name):
     if name in _TEXT:                                    # the query text encoder: lazily, for the same reason
         from . import text
         return getattr(text, name)
+    if name in _STRINGS:                                 # the string metrics of a result: lazily, for the same reason
+        from . import strings
+        return getattr(strings, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,6 +1,7 @@
 """ctypes binding of libsss.so, read from the C ABI's own declarations: the headers of include/ are the one place where
 an entry point's types and an argument struct's fields are written down (``HEADERS``, ``PARAMS`` and ``STRUCTS`` below
-are what the reader makes of them).
+are what the reader makes of them).  The headers of include/ext/ are read the same way into tables of their own
+(``EXT_HEADERS``, ``EXT_PARAMS``): families added since the listing of include/ was pinned; ``lib()`` binds both.
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails, this
 module raises.  ``build()`` compiles the library in-tree with hipcc for gfx950.
@@ -68,10 +69,10 @@ def read_header(text, header):
     return functions, structs
 
 
-def _read_include():
+def _read_include(directory=INCLUDE):
     headers, params, fields = {}, {}, {}
-    for header in sorted(f for f in os.listdir(INCLUDE) if f.endswith(".h")):
-        with open(os.path.join(INCLUDE, header)) as f:
+    for header in sorted(f for f in os.listdir(directory) if f.endswith(".h")):
+        with open(os.path.join(directory, header)) as f:
             functions, structs = read_header(f.read(), header)
         headers[header] = {n: sig[:2] for n, sig in functions.items()}
         params.update({n: sig[2] for n, sig in functions.items()})
@@ -84,6 +85,21 @@ def _read_include():
 HEADERS, PARAMS, _STRUCT_FIELDS = _read_include()
 STRUCTS = {}
 GRAPH_IGNORE_QUERY = 1      # SSS_GRAPH_IGNORE_QUERY of include/sss_graph.h
+# the same two tables for include/ext/ (no header there declares a struct)
+EXT_INCLUDE = os.path.join(INCLUDE, "ext")
+EXT_HEADERS, EXT_PARAMS, _EXT_STRUCT_FIELDS = _read_include(EXT_INCLUDE)
+if _EXT_STRUCT_FIELDS or set(EXT_PARAMS) & set(PARAMS):
+    raise ValueError(f"include/ext/ declares a struct or repeats an entry point of include/: "
+                     f"{sorted(_EXT_STRUCT_FIELDS) + sorted(set(EXT_PARAMS) & set(PARAMS))}")
+
+
+def header_constant(path, name):
+    """The integer a header ``#define``s ``name`` as (``path`` below include/)."""
+    with open(os.path.join(INCLUDE, path)) as f:
+        m = re.search(rf"^[ \t]*#[ \t]*define[ \t]+{name}[ \t]+(-?\d+)\b", f.read(), flags=re.M)
+    if not m:
+        raise ValueError(f"include/{path} does not define {name} as an integer")
+    return int(m.group(1))
 
 
 def _c_struct(name):
@@ -177,7 +193,7 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C "
                 "sessionsimilaritysearch_amd/csrc`). There is no CPU fallback.")
         h = ctypes.CDLL(LIB_PATH)
-        for table in HEADERS.values():
+        for table in (*HEADERS.values(), *EXT_HEADERS.values()):
             for name, (res, args) in table.items():
                 fn = getattr(h, name)      # AttributeError if the .so lacks a declared symbol
                 fn.restype, fn.argtypes = res, args

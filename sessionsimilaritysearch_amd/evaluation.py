@@ -14,8 +14,8 @@ Deviations from the reference (DESIGN.md "Scoring a result"): an id of -1 in ``I
 and is never a hit, but keeps its rank; the reference would wrap to the last session), and ``get_cur_map`` /
 ``get_all_map`` apply ``get_future_map``'s rule to the ``cur`` / ``all`` item sets (the reference's two index an older
 dataset layout).  ``get_ave_score`` / ``get_recall`` also take ``'all_product_type_score'``, the kind the reference is
-configured with, over type bags (``product_types.type_bags``; score of record: ``include/sss_ptype.h``).  The string
-metrics (``get_query_metric``, the Levenshtein kinds of ``get_score``) are out of scope.
+configured with, over type bags (``product_types.type_bags``; score of record: ``include/sss_ptype.h``), and the two string kinds ``'all_query_score'`` / ``'all_product_title_score'`` over
+``strings.StringSequences`` (``Levenshtein.seqratio``; score of record: ``include/ext/sss_seqsim.h``).
 """
 from __future__ import annotations
 
@@ -27,11 +27,13 @@ import torch
 from . import _lib
 from .sessions import ActionTable
 from .sparse import SessionVectors, _ptr_of, session_vectors
+from .strings import StringSequences, seq_pair_scores
 
 MAX_K = 1024
 PARTS = ("cur", "future", "all")
 _SIM_PART = {"cur_jaccard": "cur", "all_jaccard": "all"}
 PRODUCT_TYPE = "all_product_type_score"
+QUERY_SCORE, TITLE_SCORE = "all_query_score", "all_product_title_score"
 
 
 class QueryParts(NamedTuple):
@@ -189,8 +191,8 @@ for _name, _ref in (("get_cur_jaccard", "286-297"), ("get_future_jaccard", "331-
 
 def _sim_part(sim_type: str) -> str:
     if sim_type not in _SIM_PART:
-        raise ValueError(f"sim_type must be 'all_jaccard', 'cur_jaccard' or '{PRODUCT_TYPE}' (the string metrics are out of scope), "
-                         f"got {sim_type!r}")
+        raise ValueError(f"sim_type must be 'all_jaccard', 'cur_jaccard', '{PRODUCT_TYPE}' or, over StringSequences, "
+                         f"'{QUERY_SCORE}' / '{TITLE_SCORE}', got {sim_type!r}")
     return _SIM_PART[sim_type]
 
 
@@ -201,25 +203,54 @@ def _type_scores32(I, test_bags, train_bags) -> torch.Tensor:
     return torch.nan_to_num(bag_pair_scores(I, test_bags, train_bags), nan=0.0).float()
 
 
+def _is_string_kind(sim_type, test_data, train_data) -> bool:
+    """A string kind over ``StringSequences`` on both sides; with anything else the kinds stay the ``ValueError`` of
+    ``_sim_part``."""
+    return sim_type in (QUERY_SCORE, TITLE_SCORE) and isinstance(test_data, StringSequences) and isinstance(train_data, StringSequences)
+
+
+def _seq_scores32(I, test_seqs, train_seqs, sim_type) -> torch.Tensor:
+    """float32 of ``seqratio`` of every pair, a missing neighbour scoring 0; 'all_query_score' scores 0 where either list
+    is empty (fine_tune_ours.py:59-60), the title kind does not (two empty lists score 1.0)."""
+    ratio, _, _, clen = seq_pair_scores(I, test_seqs, train_seqs)
+    s = torch.nan_to_num(ratio, nan=0.0)
+    if sim_type == QUERY_SCORE:
+        s = torch.where((test_seqs.lengths[:, None] == 0) | (clen == 0), torch.zeros((), dtype=torch.float64, device=s.device), s)
+    return s.float()
+
+
+def _mean32(s: torch.Tensor) -> float:
+    return float(s.double().sum().item()) / s.numel() if s.numel() else float("nan")
+
+
+def _above32(s: torch.Tensor, thres) -> float:
+    above = (s > torch.tensor(float(thres), dtype=torch.float32, device=s.device)).sum(1)
+    return _mean(above.cpu().numpy()) / s.shape[1]
+
+
 def get_ave_score(I, test_data, train_data, sim_type) -> float:
     """Drop-in for the reference's ``get_ave_score`` (fine_tune_ours.py:90-97) for the two item-set kinds of
     ``get_score``: 'all_jaccard' (raises ZeroDivisionError on an empty union, as the reference does) and 'cur_jaccard'
     (an empty union scores 0); and for 'all_product_type_score', the kind the reference is configured with: ``test_data`` is
     then the type bags of ``seq[i] + tar[i]`` (``product_types.type_bags(ActionTable.concat(seq, tar), ...)``) and
-    ``train_data`` the corpus bags.  Every pair score is rounded to float32 first, their mean is taken in float64."""
+    ``train_data`` the corpus bags; and for 'all_query_score' / 'all_product_title_score' when both are
+    ``strings.StringSequences`` (``query_sequences`` / ``title_sequences`` of ``ActionTable.concat(seq, tar)`` and of the
+    corpus).  Every pair score is rounded to float32 first, their mean is taken in float64."""
     if sim_type == PRODUCT_TYPE:
-        s = _type_scores32(I, test_data, train_data)
-        return float(s.double().sum().item()) / s.numel() if s.numel() else float("nan")
+        return _mean32(_type_scores32(I, test_data, train_data))
+    if _is_string_kind(sim_type, test_data, train_data):
+        return _mean32(_seq_scores32(I, test_data, train_data, sim_type))
     return _ave_score(part_scores(I, _part(test_data, _sim_part(sim_type)), train_data), sim_type)
 
 
 def get_recall(test_data, train_data, I, sim_type, thres) -> float:
     """Drop-in for the reference's ``get_recall`` (test_amazon_filterd.py:443-450): the share of the K neighbours whose
-    float32 pair score exceeds ``thres``, averaged over the queries.  'all_product_type_score': as ``get_ave_score``."""
+    float32 pair score exceeds ``thres``, averaged over the queries.  'all_product_type_score' and the two string kinds: as
+    ``get_ave_score``."""
     if sim_type == PRODUCT_TYPE:
-        s = _type_scores32(I, test_data, train_data)
-        above = (s > torch.tensor(float(thres), dtype=torch.float32, device=s.device)).sum(1)
-        return _mean(above.cpu().numpy()) / s.shape[1]
+        return _above32(_type_scores32(I, test_data, train_data), thres)
+    if _is_string_kind(sim_type, test_data, train_data):
+        return _above32(_seq_scores32(I, test_data, train_data, sim_type), thres)
     return _above(part_scores(I, _part(test_data, _sim_part(sim_type)), train_data, thres), sim_type)
 
 
