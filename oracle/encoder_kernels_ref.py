@@ -203,6 +203,21 @@ def pool_indices(batch):
     return src_row, pos_id, pptr, qptr, int(src_p.shape[0])
 
 
+def node_transforms(W, l, cp, cq):
+    """(yp, yq) of layer `l` from the raw weights `W` (flat dict of tensors in the dtype of the rows): the node transforms
+    of the product rows `cp` and the query rows `cq` in the column layout of sss_hetero_layer_update."""
+    g = lambda name: W[name.format(l)]
+    din = cp.shape[1]
+    xs_p, xs_q = cp @ g("gat_pq.{}.lin_src").T, cq @ g("gat_qp.{}.lin_src").T
+    u = cp @ (g("ggc.{}.weight")[:din] @ g("ggc.{}.w_ih").T)
+    gh = cp @ g("ggc.{}.w_hh")[:, :din].T + g("ggc.{}.b_hh")
+    yp = torch.cat([xs_p, u, gh, (xs_p @ g("gat_pq.{}.att_src"))[:, None],
+                    ((cp @ g("gat_qp.{}.lin_dst").T) @ g("gat_qp.{}.att_dst"))[:, None]], 1)
+    yq = torch.cat([xs_q, (xs_q @ g("gat_qp.{}.att_src"))[:, None],
+                    ((cq @ g("gat_pq.{}.lin_dst").T) @ g("gat_pq.{}.att_dst"))[:, None]], 1)
+    return yp, yq
+
+
 def encoder_forward(batch, w, n_layers, self_loops=True, tab=True, get_node=False):
     """The fused encoder as a chain of the restatements above, float64: per layer the node transforms in the column
     layout of sss_hetero_layer_update (yp = xs_p | u | gh | alpha_src(pq) alpha_dst(qp), yq = xs_q | alpha_src(qp)
@@ -222,15 +237,8 @@ def encoder_forward(batch, w, n_layers, self_loops=True, tab=True, get_node=Fals
     for l in range(n_layers):
         g = lambda name: W[name.format(l)]
         cp, cq = np_[-1], nq_[-1]
-        h, din = g("ggc.{}.weight").shape[0], cp.shape[1]
-        xs_p, xs_q = cp @ g("gat_pq.{}.lin_src").T, cq @ g("gat_qp.{}.lin_src").T
-        u = cp @ (g("ggc.{}.weight")[:din] @ g("ggc.{}.w_ih").T)
-        gh = cp @ g("ggc.{}.w_hh")[:, :din].T + g("ggc.{}.b_hh")
-        c.yp = torch.cat([xs_p, u, gh, (xs_p @ g("gat_pq.{}.att_src"))[:, None],
-                          ((cp @ g("gat_qp.{}.lin_dst").T) @ g("gat_qp.{}.att_dst"))[:, None]], 1)
-        c.yq = torch.cat([xs_q, (xs_q @ g("gat_qp.{}.att_src"))[:, None],
-                          ((cq @ g("gat_pq.{}.lin_dst").T) @ g("gat_pq.{}.att_dst"))[:, None]], 1)
-        c.h, c.xin, c.xq_tab = h, cp, cq
+        c.yp, c.yq = node_transforms(W, l, cp, cq)
+        c.h, c.xin, c.xq_tab = g("ggc.{}.weight").shape[0], cp, cq
         c.bias_qp, c.bias_pq, c.b_ih = g("gat_qp.{}.bias"), g("gat_pq.{}.bias"), g("ggc.{}.b_ih")
         out_p, out_q, _, _ = layer_update_ref(c)
         np_.append(out_p)

@@ -4,7 +4,8 @@ Drop-in surface of the reference's path:
   normalize, build_index, FlatIndex (f32 / bf16 / f16 / i8), quantize_i8
                                                   (index.py     <- test_amazon_filterd.py / util_amazon_filtered.py)
   BinaryFlatIndex, pack_sign_bits                 (index.py     <- fine_tune_ours.py IndexBinaryFlat branch)
-  SessionEncoder (+ prepare_actions)              (encoder.py   <- model/model.py UnifyPoolingGraphLevelEncoder,
+  SessionEncoder (+ prepare_actions), session_fold_weights
+                                                  (encoder.py   <- model/model.py UnifyPoolingGraphLevelEncoder,
                                                                   util_amazon_filtered.sequence_to_graph)
   get_prediction_by_knn, get_p_r, SessionItems    (retrieval.py <- test_amazon_filterd.py:59-85)
   HeteroSAGE, GraphPooling, AttentionPooling, ... (variants.py  <- model/gnn.py, model/model.py variants)
@@ -43,6 +44,8 @@ _JACCARD = ("JaccardIndex", "mine_triples", "neighbourhood_recall")
 __all__ += list(_JACCARD)
 _PTYPE = ("ProductTypeIndex", "type_bags")
 __all__ += list(_PTYPE)
+_ENCODER = ("session_fold_weights",)
+__all__ += list(_ENCODER)
 _HGT = ("HGT", "hgt_fold_weights")
 __all__ += list(_HGT)
 _TEXT = ("NodeTextTransformer", "pack_tokens", "text_fold_weights", "TokenRows", "BertNodeEncoder", "bert_fold_weights",
@@ -67,6 +70,9 @@ def __getattr__(name):
     if name in _PTYPE:                                   # the product-type index: lazily, for the same reason
         from . import product_types
         return getattr(product_types, name)
+    if name in _ENCODER:                                 # the session encoder's fold: lazily, for the same reason
+        from . import encoder
+        return getattr(encoder, name)
     if name in _HGT:                                     # the HGT encoder: lazily, for the same reason
         from . import variants
         return getattr(variants, name)

@@ -1,10 +1,20 @@
-"""Device-memory plumbing the index classes share: a scratch buffer that only grows, amortised row storage and the
-query chunking of the exhaustive kernels."""
+"""Device plumbing the models and index classes share: the device a model binds to and the upload of a weight; a scratch
+buffer that only grows, amortised row storage and the query chunking of the exhaustive kernels."""
 from __future__ import annotations
 
 import torch
 
 EXHAUSTIVE_WS_BYTES = 1 << 30       # budget of a [chunk, n] score matrix of the exhaustive kernels
+
+
+def model_device(device=None) -> torch.device:
+    """The device a model is bound to: ``device``, or the current HIP device when it is None."""
+    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+def upload_f32(t: torch.Tensor, device) -> torch.Tensor:
+    """``t`` as the kernels read a weight: detached, float32, contiguous, on ``device``."""
+    return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
 class Workspace:

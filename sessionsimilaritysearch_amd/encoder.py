@@ -6,23 +6,27 @@ Every arithmetic step runs in the HIP kernels of ``libsss.so`` through the C ABI
 (``include/sss.h``); torch owns device memory, the stream and the integer index preparation
 (CSR by target, repeat_interleave).  There is no CPU fallback.
 
-Out of scope, by design: the reference's BERT/ELECTRA text encoder
-(``model/NodeEmbedding.py:100-125``).  Node input features are rows of two tables --
-``item_table`` (``NodeAsinEmbedding``, ``model/NodeEmbedding.py:128-138``) and ``query_table``
-(stand-in for the text features of query nodes) -- or precomputed float features passed as
-``data[node_type].feat``.
+Node input features are either rows of two tables gathered by node id -- ``item_table``
+(``NodeAsinEmbedding``, ``model/NodeEmbedding.py:128-138``) and ``query_table`` -- or float rows
+passed as ``data[node_type].feat``: what the reference's text encoders
+(``model/NodeEmbedding.py:100-125``) produce, here ``text.BertNodeEncoder`` / ``text.NodeTextTransformer``.
+With ``d_id > 0`` (use_id_embedding) a product row is ``[id_table[x] | feat]``.
+
+The weights reach the kernels through ``session_fold_weights``: host-side and device-free, it stacks
+each layer's node transforms and forms the pooling tables; ``SessionEncoder`` only uploads its result.
 """
 from __future__ import annotations
 
 import ctypes
 import itertools
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._device import model_device, upload_f32
 from .sessions import ASIN_NUM, EDGE_PP, EDGE_PQ, EDGE_QP, MAX_SEQ_LEN, QUERY_VOCAB, ActionTable
 
 ALPHA_PAD = 32          # extra output columns of the fused node transforms (2 used: alpha_src, alpha_dst)
@@ -117,6 +121,111 @@ def init_weights(cfg: EncoderConfig, seed: int, random_bias: bool = True, tables
     return {k: v.float().contiguous() for k, v in w.items()}
 
 
+def _single_width_weights(cfg, w):
+    """Reference-shaped weights of a use_id_embedding model -> the single-width internal form: product rows are
+    [id embedding | text features] as the reference concatenates them (model/model.py:289), query rows
+    [text features | d_id zeros]."""
+    dq, did = cfg.d_in, cfg.d_id
+    pad_cols = lambda t: torch.cat([t, t.new_zeros(t.shape[0], did)], dim=1)
+    out = dict(w)
+    out["id_table"] = w["item_table"]                           # kept for batches that bring their own text features
+    if "item_text_table" in w:
+        out["item_table"] = torch.cat([w["item_table"], w["item_text_table"]], dim=1)
+    else:
+        del out["item_table"]
+    if "query_table" in w:
+        out["query_table"] = pad_cols(w["query_table"])
+    out["gat_qp.0.lin_src"] = pad_cols(w["gat_qp.0.lin_src"])   # reads query rows
+    out["gat_pq.0.lin_dst"] = pad_cols(w["gat_pq.0.lin_dst"])
+    ql = w["pool.query_lin.w"]
+    out["pool.query_lin.w"] = torch.cat([ql[:, :dq], ql.new_zeros(ql.shape[0], did), ql[:, dq:]], dim=1)
+    return out
+
+
+def session_fold_weights(cfg: EncoderConfig, weights: dict):
+    """Host-side, device-free: the flat reference-shaped weights (``init_weights``' names) as the kernels take them
+    ("Weight fold").  Products are formed in float64 and stored as float32; copied blocks are exact.
+
+    use_id_embedding (``d_id > 0``): BOTH node types run at the product width ``d_p = d_id + d_in`` -- query feature rows
+    are zero-padded behind their ``d_in`` columns and every weight that reads them gets zero columns there, which leaves
+    the arithmetic of the reference's mixed-width model unchanged (a zero column adds exact zeros) and lets every kernel
+    keep ONE input width.
+
+    Returns CPU float32 contiguous tensors and plain ints:
+
+    * ``"cfg"``: the internal single-width config (``d_in = d_p``, ``d_id = 0``);
+    * ``"tables"``: those of ``item_table`` / ``query_table`` / ``id_table`` (the ``[V, d_id]`` id embedding) the weights give;
+    * ``"layers"``: per layer, ``din`` and, ``ALPHA_PAD`` zero-padded rows (2 used) closing each stack,
+      ``wp [5h + 32, din]``, ``bp``: ``xs_p | m = x W_g | gh = W_hh x + b_hh | a_s(pq) a_d(qp)`` (per-op path),
+      ``w7 [7h + 32, din]``, ``b7``: ``xs_p | u = x (W_g W_ih^T) | gh | a_s(pq) a_d(qp)`` (fused path),
+      ``wq [h + 32, din]``: ``xs_q | a_s(qp) a_d(pq)``, and ``w_ih b_ih bias_qp bias_pq`` as given;
+    * ``"pool"``: ``wq bq wp bp pos wn bn wc watt`` as given;
+    * ``"pool_tab"``: ``KT = pad32(D - P)``, ``tanhpos = tanh(pos)``, ``a2 = tanhpos Wn[:, D-P:]^T + bn``,
+      ``c2 = tanhpos Wc[:, D-P:]^T``, ``wnc [2D, KT] = [Wn[:, :D-P] ; Wc[:, :D-P]]`` with zero pad columns."""
+    cfg.validate()
+    w = weights
+    if cfg.d_id:
+        w = _single_width_weights(cfg, w)
+        cfg = EncoderConfig(**{**cfg.__dict__, "d_in": cfg.d_p, "d_id": 0})
+    h = cfg.h
+    f64 = lambda t: t.detach().to(torch.float64)
+    d = lambda t: t.detach().to(device="cpu", dtype=torch.float32).contiguous()
+    layers = []
+    for l in range(cfg.n_layers):
+        qp = {k: w[f"gat_qp.{l}.{k}"] for k in ("lin_src", "lin_dst", "att_src", "att_dst", "bias")}
+        pq = {k: w[f"gat_pq.{l}.{k}"] for k in ("lin_src", "lin_dst", "att_src", "att_dst", "bias")}
+        # alpha_src[j] = <lin_src x_j, att_src> = x_j . (lin_src^T att_src): one extra output row
+        v = lambda lin, att: (f64(lin).T @ f64(att)).float()
+        din = qp["lin_src"].shape[1]
+        # product-side fused transform: [xs_p (p->q messages) | m = x Wg | gh = W_hh x | a_s(pq) | a_d(qp)]
+        wp = torch.zeros((5 * h + ALPHA_PAD, din))
+        wp[0:h] = pq["lin_src"]
+        wp[h:2 * h, :] = w[f"ggc.{l}.weight"].T[:, :din]     # m = pad(x) @ weight
+        wp[2 * h:5 * h, :] = w[f"ggc.{l}.w_hh"][:, :din]
+        wp[5 * h] = v(pq["lin_src"], pq["att_src"])
+        wp[5 * h + 1] = v(qp["lin_dst"], qp["att_dst"])
+        bp = torch.zeros(5 * h + ALPHA_PAD)
+        bp[2 * h:5 * h] = w[f"ggc.{l}.b_hh"]
+        # query-side fused transform: [xs_q (q->p messages) | a_s(qp) | a_d(pq)]
+        wq = torch.zeros((h + ALPHA_PAD, din))
+        wq[0:h] = qp["lin_src"]
+        wq[h] = v(qp["lin_src"], qp["att_src"])
+        wq[h + 1] = v(pq["lin_dst"], pq["att_dst"])
+        # fused-path product transform (k_layer_update's column layout):
+        #   [xs_p | u = x (W_g W_ih^T) (3h) | gh = W_hh x + b_hh (3h) | a_s(pq) a_d(qp)]
+        # the GRU input transform W_ih is applied BEFORE the neighbour sum (both are linear), so the
+        # layer needs no second GEMM: gi[i] = sum_j u[j] + b_ih.  Product formed in float64.
+        w7 = torch.zeros((7 * h + ALPHA_PAD, din))
+        w7[0:h] = pq["lin_src"]
+        w7[h:4 * h] = (f64(w[f"ggc.{l}.weight"])[:din, :] @ f64(w[f"ggc.{l}.w_ih"]).T).T.float()
+        w7[4 * h:7 * h] = w[f"ggc.{l}.w_hh"][:, :din]
+        w7[7 * h] = v(pq["lin_src"], pq["att_src"])
+        w7[7 * h + 1] = v(qp["lin_dst"], qp["att_dst"])
+        b7 = torch.zeros(7 * h + ALPHA_PAD)
+        b7[4 * h:7 * h] = w[f"ggc.{l}.b_hh"]
+        layers.append(dict(
+            wp=d(wp), bp=d(bp), wq=d(wq), w_ih=d(w[f"ggc.{l}.w_ih"]), b_ih=d(w[f"ggc.{l}.b_ih"]),
+            bias_qp=d(qp["bias"]), bias_pq=d(pq["bias"]), din=din, w7=d(w7), b7=d(b7)))
+    # fused pooling (sss_pool_attention_tab): per-position tables and the stacked node-side weights
+    P_, D_ = cfg.max_seq_len, cfg.d_out
+    Dl_ = D_ - P_
+    KT = _lib.pad32(Dl_)                            # T = tanh(lin) is stored KT wide (zero pad columns): a GEMM K
+    tp = torch.tanh(f64(w["pool.pos_emb"]))
+    wn, wc = f64(w["pool.node_lin.w"]), f64(w["pool.coarse_lin.w"])
+    wnc = torch.zeros((2 * D_, KT), dtype=torch.float64)
+    wnc[:D_, :Dl_] = wn[:, :Dl_]
+    wnc[D_:, :Dl_] = wc[:, :Dl_]
+    pool_tab = dict(KT=KT, tanhpos=d(tp.float()), a2=d((tp @ wn[:, Dl_:].T + f64(w["pool.node_lin.b"])).float()),
+                    c2=d((tp @ wc[:, Dl_:].T).float()), wnc=d(wnc.float()))
+    pool = dict(
+        wq=d(w["pool.query_lin.w"]), bq=d(w["pool.query_lin.b"]),
+        wp=d(w["pool.product_lin.w"]), bp=d(w["pool.product_lin.b"]),
+        pos=d(w["pool.pos_emb"]), wn=d(w["pool.node_lin.w"]), bn=d(w["pool.node_lin.b"]),
+        wc=d(w["pool.coarse_lin.w"]), watt=d(w["pool.att_lin.w"]))
+    tables = {k: d(w[k]) for k in ("item_table", "query_table", "id_table") if k in w}
+    return {"cfg": cfg, "tables": tables, "layers": layers, "pool": pool, "pool_tab": pool_tab}
+
+
 def save_weights(path, weights):
     """Flat weight file: named float32 arrays (``.npz``).  The reference pickles whole
     ``nn.Module`` tuples (pretrain_filtered_amazon.py:605-610), which cannot be loaded without
@@ -153,9 +262,36 @@ def build_csr(edge_index: torch.Tensor, n_dst: int, n_src: int = 0, self_loops: 
     return rowptr, col, wv
 
 
+@dataclass(eq=False, repr=False)    # identity comparison, hashing and the short repr stay: the generated ones walk the tensors
 class PreparedBatch:
-    """Device-resident batch: feature ids + CSR adjacencies + pooling index arrays
-    (``SessionEncoder.prepare``)."""
+    """Device-resident batch: feature ids + CSR adjacencies + pooling index arrays, built by ``SessionEncoder.prepare``
+    (from a ``SessionBatch``) or ``SessionEncoder.prepare_actions`` (from an action table).  A field its builder does not
+    produce is None."""
+    Nq: int = None                  # query nodes
+    Np: int = None                  # product nodes
+    B: int = None                   # graphs (sessions)
+    n_clicks: int = None            # expanded product rows of the pooling: sum(cnt)
+    q_ids: torch.Tensor = None      # int64 [Nq] query_table rows (None: q_feat given)
+    p_ids: torch.Tensor = None      # int64 [Np] item_table / id_table rows (None: p_feat given and no id embedding)
+    q_batch: torch.Tensor = None    # int64 [Nq] graph of each query node
+    p_batch: torch.Tensor = None    # int64 [Np] graph of each product node
+    q_feat: torch.Tensor = None     # [Nq, d_in] float features in place of q_ids (prepare)
+    p_feat: torch.Tensor = None     # [Np, d_in] float features in place of (d_id: beside) p_ids (prepare)
+    q_pos: torch.Tensor = None      # int32 [Nq] position id of each query node (prepare_actions)
+    p_cnt: torch.Tensor = None      # int64 [Np] clicks of each product node (prepare_actions)
+    csr_qp: tuple = None            # (rowptr, col, None) by target: queries -> products
+    csr_pq: tuple = None            # (rowptr, col, None) by target: products -> queries
+    csr_pp: tuple = None            # (rowptr, col, edge weight or None) by target: products -> products
+    w_pp: torch.Tensor = None       # float32 [Epp] product-product edge weights, used or not (prepare_actions)
+    src_row: torch.Tensor = None    # int32 [n_clicks + Nq] node of each expanded row, product rows first
+    pos_id: torch.Tensor = None     # int32 [n_clicks + Nq] position id of each expanded row
+    pptr: torch.Tensor = None       # int32 [B + 1] expanded product rows of each graph
+    qptr: torch.Tensor = None       # int32 [B + 1] query nodes of each graph
+    p_ptr: torch.Tensor = None      # int32 [B + 1] product nodes of each graph (prepare_actions)
+    n_self_loop: int = None         # self edges the aggregation kernels add: min(Nq, Np), or 0 (self_loop_rule "none")
+    last_click_mask: torch.Tensor = None    # float32 [Np] 1.0 at each session's last click (prepare: when the batch has one)
+    last_node: torch.Tensor = None  # int32 [B] batch-global product node of that click (prepare_actions)
+    _ws: dict = field(default_factory=dict)     # fused-forward workspace cache, keyed by encoder serial
 
 
 class SessionEncoder:
@@ -172,22 +308,21 @@ class SessionEncoder:
         if not torch.cuda.is_available():
             raise _lib.SssError("no HIP device available: the encoder runs on MI355X only")
         _lib.lib()
-        # use_id_embedding (d_id > 0): internally BOTH node types run at the product width d_p = d_id + d_in -- query
-        # feature rows are zero-padded behind their d_in columns and every weight that reads them gets zero columns
-        # there (`_internal_weights`), which leaves the arithmetic of the reference's mixed-width model unchanged
-        # (a zero column adds exact zeros) and lets every kernel keep ONE input width.
         self.user_cfg = cfg
         self.d_id, self.d_feat = cfg.d_id, cfg.d_in
-        if cfg.d_id:
-            weights = self._internal_weights(cfg, weights)
-            cfg = EncoderConfig(**{**cfg.__dict__, "d_in": cfg.d_p, "d_id": 0})
-        self.cfg = cfg
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.device = model_device(device)
         self.use_edge_weight = use_edge_weight      # the deployed path passes none (model/model.py:317)
         self.debug_nan_checks = debug_nan_checks    # the reference's 3 host-syncing asserts
         self.fused = fused                          # 7-launch fused kernels where the shapes allow (fused_ok)
         self.training = False
-        self._prepare(weights)
+        f = session_fold_weights(cfg, weights)
+        up = lambda block: {k: upload_f32(t, self.device) if torch.is_tensor(t) else t for k, t in block.items()}
+        self.cfg = f["cfg"]                         # single-width: d_in = d_p, d_id = 0
+        tables = up(f["tables"])
+        self.item_table, self.query_table = tables.get("item_table"), tables.get("query_table")
+        self.id_table = tables.get("id_table")      # use_id_embedding: the [V, d_id] NodeAsinEmbedding
+        self.layers = [up(lay) for lay in f["layers"]]
+        self.pool_tab, self.pool = up(f["pool_tab"]), up(f["pool"])
 
     # -- nn.Module-flavoured conveniences the reference scripts call
     def eval(self):
@@ -201,89 +336,6 @@ class SessionEncoder:
 
     def __call__(self, *a, **kw):
         return self.forward(*a, **kw)
-
-    # ------------------------------------------------------------------ weight preparation
-    @staticmethod
-    def _internal_weights(cfg, w):
-        """Reference-shaped weights of a use_id_embedding model -> the single-width internal form: product rows are
-        [id embedding | text features] as the reference concatenates them (model/model.py:289), query rows
-        [text features | d_id zeros]."""
-        dq, did, h = cfg.d_in, cfg.d_id, cfg.h
-        pad_cols = lambda t: torch.cat([t, t.new_zeros(t.shape[0], did)], dim=1)
-        out = dict(w)
-        out["id_table"] = w["item_table"]                           # kept for batches that bring their own text features
-        if "item_text_table" in w:
-            out["item_table"] = torch.cat([w["item_table"], w["item_text_table"]], dim=1)
-        else:
-            del out["item_table"]
-        if "query_table" in w:
-            out["query_table"] = pad_cols(w["query_table"])
-        out["gat_qp.0.lin_src"] = pad_cols(w["gat_qp.0.lin_src"])   # reads query rows
-        out["gat_pq.0.lin_dst"] = pad_cols(w["gat_pq.0.lin_dst"])
-        ql = w["pool.query_lin.w"]
-        out["pool.query_lin.w"] = torch.cat([ql[:, :dq], ql.new_zeros(ql.shape[0], did), ql[:, dq:]], dim=1)
-        return out
-
-    def _prepare(self, w):
-        cfg, dev = self.cfg, self.device
-        h = cfg.h
-        f64 = lambda t: t.detach().to(torch.float64)
-        d = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        self.item_table = d(w["item_table"]) if "item_table" in w else None
-        self.query_table = d(w["query_table"]) if "query_table" in w else None
-        self.id_table = d(w["id_table"]) if "id_table" in w else None      # use_id_embedding: the [V, d_id] NodeAsinEmbedding
-        self.layers = []
-        for l in range(cfg.n_layers):
-            qp = {k: w[f"gat_qp.{l}.{k}"] for k in ("lin_src", "lin_dst", "att_src", "att_dst", "bias")}
-            pq = {k: w[f"gat_pq.{l}.{k}"] for k in ("lin_src", "lin_dst", "att_src", "att_dst", "bias")}
-            # alpha_src[j] = <lin_src x_j, att_src> = x_j . (lin_src^T att_src): one extra output row
-            v = lambda lin, att: (f64(lin).T @ f64(att)).float()
-            din = qp["lin_src"].shape[1]
-            # product-side fused transform: [xs_p (p->q messages) | m = x Wg | gh = W_hh x | a_s(pq) | a_d(qp)]
-            wp = torch.zeros((5 * h + ALPHA_PAD, din))
-            wp[0:h] = pq["lin_src"]
-            wp[h:2 * h, :] = w[f"ggc.{l}.weight"].T[:, :din]     # m = pad(x) @ weight
-            wp[2 * h:5 * h, :] = w[f"ggc.{l}.w_hh"][:, :din]
-            wp[5 * h] = v(pq["lin_src"], pq["att_src"])
-            wp[5 * h + 1] = v(qp["lin_dst"], qp["att_dst"])
-            bp = torch.zeros(5 * h + ALPHA_PAD)
-            bp[2 * h:5 * h] = w[f"ggc.{l}.b_hh"]
-            # query-side fused transform: [xs_q (q->p messages) | a_s(qp) | a_d(pq)]
-            wq = torch.zeros((h + ALPHA_PAD, din))
-            wq[0:h] = qp["lin_src"]
-            wq[h] = v(qp["lin_src"], qp["att_src"])
-            wq[h + 1] = v(pq["lin_dst"], pq["att_dst"])
-            # fused-path product transform (k_layer_update's column layout):
-            #   [xs_p | u = x (W_g W_ih^T) (3h) | gh = W_hh x + b_hh (3h) | a_s(pq) a_d(qp)]
-            # the GRU input transform W_ih is applied BEFORE the neighbour sum (both are linear), so the
-            # layer needs no second GEMM: gi[i] = sum_j u[j] + b_ih.  Product formed in float64.
-            w7 = torch.zeros((7 * h + ALPHA_PAD, din))
-            w7[0:h] = pq["lin_src"]
-            w7[h:4 * h] = (f64(w[f"ggc.{l}.weight"])[:din, :] @ f64(w[f"ggc.{l}.w_ih"]).T).T.float()
-            w7[4 * h:7 * h] = w[f"ggc.{l}.w_hh"][:, :din]
-            w7[7 * h] = v(pq["lin_src"], pq["att_src"])
-            w7[7 * h + 1] = v(qp["lin_dst"], qp["att_dst"])
-            b7 = torch.zeros(7 * h + ALPHA_PAD)
-            b7[4 * h:7 * h] = w[f"ggc.{l}.b_hh"]
-            self.layers.append(dict(
-                wp=d(wp), bp=d(bp), wq=d(wq), w_ih=d(w[f"ggc.{l}.w_ih"]), b_ih=d(w[f"ggc.{l}.b_ih"]),
-                bias_qp=d(qp["bias"]), bias_pq=d(pq["bias"]), din=din, w7=d(w7), b7=d(b7)))
-        # fused pooling (sss_pool_attention_tab): per-position tables and the stacked node-side weights
-        P_, D_ = cfg.max_seq_len, cfg.d_out
-        Dl_ = D_ - P_
-        KT = (Dl_ + 31) // 32 * 32                      # T = tanh(lin) is stored KT wide (zero pad columns): a GEMM K
-        tp = torch.tanh(f64(w["pool.pos_emb"]))
-        wn, wc = f64(w["pool.node_lin.w"]), f64(w["pool.coarse_lin.w"])
-        wnc = torch.zeros((2 * D_, KT), dtype=torch.float64)
-        wnc[:D_, :Dl_] = wn[:, :Dl_]
-        wnc[D_:, :Dl_] = wc[:, :Dl_]
-        self.pool_tab = dict(KT=KT, tanhpos=d(tp.float()), a2=d((tp @ wn[:, Dl_:].T + f64(w["pool.node_lin.b"])).float()),
-                             c2=d((tp @ wc[:, Dl_:].T).float()), wnc=d(wnc.float()))
-        self.pool = dict(
-            wq=d(w["pool.query_lin.w"]), bq=d(w["pool.query_lin.b"]),
-            wp=d(w["pool.product_lin.w"]), bp=d(w["pool.product_lin.b"]),
-            pos=d(w["pool.pos_emb"]), wn=d(w["pool.node_lin.w"]), bn=d(w["pool.node_lin.b"]),
-            wc=d(w["pool.coarse_lin.w"]), watt=d(w["pool.att_lin.w"]))
 
     # ------------------------------------------------------------------ C-ABI call helpers
     def _st(self):
@@ -418,7 +470,6 @@ class SessionEncoder:
         pb.Nq, pb.Np, pb.B, pb.n_clicks = Nq, Np, S_, Xp
         pb.q_ids, pb.q_batch, pb.q_pos = i64(Nq), i64(Nq), i32(Nq)
         pb.p_ids, pb.p_batch, pb.p_cnt = i64(Np), i64(Np), i64(Np)
-        pb.q_feat = pb.p_feat = None
         rp_qp, c_qp, rp_pq, c_pq = i32(Np + 1), i32(E), i32(Nq + 1), i32(E)
         rp_pp, c_pp = i32(Np + 1), i32(Epp)
         w_pp = torch.empty(Epp, dtype=torch.float32, device=dev)
@@ -449,7 +500,7 @@ class SessionEncoder:
             probes += [(pb.pos_id.max(), self.cfg.max_seq_len, False)]
             if check_min_pos:
                 probes += [(pb.pos_id.min(), None, True)]
-        p_table = self.id_table if (self.d_id and getattr(pb, "p_feat", None) is not None) else self.item_table
+        p_table = self.id_table if (self.d_id and pb.p_feat is not None) else self.item_table
         for ids, table in ((pb.p_ids, p_table), (pb.q_ids, self.query_table)):
             if ids is not None and ids.numel() and table is not None:
                 probes += [(ids.max(), int(table.shape[0]), False), (ids.min(), None, True)]
@@ -485,6 +536,25 @@ class SessionEncoder:
             _lib.check(rc, "sss_gather_rows")
         return buf
 
+    def _node_inputs(self, pb, query_node_mask, product_node_mask, NQ=None, NP=None):
+        """Slice 0 of the node buffers ``NQ [Nq, W]`` / ``NP [Np, W]`` (allocated when not given): the input features of
+        both node types, times the optional node masks (model/model.py:293-296; None at inference)."""
+        cfg, dev = self.cfg, self.device
+        NQ = self._features(pb.q_ids, pb.q_feat, self.query_table, pb.Nq, NQ)
+        NP = self._features(pb.p_ids, pb.p_feat, self.item_table, pb.Np, NP, product=True)    # NodeAsinEmbedding's lookup
+        if query_node_mask is not None:
+            NQ[:, :cfg.d_in] *= query_node_mask.to(dev, torch.float32).view(-1, 1)
+        if product_node_mask is not None:
+            NP[:, :cfg.d_in] *= product_node_mask.to(dev, torch.float32).view(-1, 1)
+        return NQ, NP
+
+    def _layer_views(self, l, NQ, NP):
+        """``(din, xin_p, xin_q, out_p, out_q)`` of layer ``l``: it reads the ``din`` columns the layer before it wrote
+        (layer 0: the input features) and writes the next ``h`` columns of the node buffers."""
+        d_in, h, din = self.cfg.d_in, self.cfg.h, self.layers[l]["din"]
+        off, o = (0 if l == 0 else d_in + (l - 1) * h), d_in + l * h
+        return din, NP[:, off:off + din], NQ[:, off:off + din], NP[:, o:o + h], NQ[:, o:o + h]
+
     # ------------------------------------------------------------------ fused path (7 launches)
     def fused_ok(self) -> bool:
         """Shapes the fused kernels cover (one float4 column per lane: h, d_out <= 256); wider
@@ -495,25 +565,18 @@ class SessionEncoder:
         """Intermediate buffers of the fused forward, kept with the prepared batch (no per-forward
         allocation); the node buffers are allocated fresh when the caller asked for them."""
         cfg, dev = self.cfg, self.device
-        h, D, P, W = cfg.h, cfg.d_out, cfg.max_seq_len, cfg.node_width
+        h, D, W = cfg.h, cfg.d_out, cfg.node_width
         # The cache lives with the batch but belongs to THIS encoder: its buffers are sized by this
         # configuration and its argument blocks hold raw pointers to these weights.
-        per_enc = getattr(pb, "_ws", None)
-        if per_enc is None:
-            per_enc = pb._ws = {}
-        ws = per_enc.get(self._serial)
+        e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        ws = pb._ws.get(self._serial)
         if ws is None:
-            e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-            ldl = (D - P + 3) // 4 * 4
-            n_exp = pb.n_clicks + pb.Nq
-            KT = self.pool_tab["KT"]
             ws = dict(NQ=e(pb.Nq, W), NP=e(pb.Np, W), Yp=e(pb.Np, 7 * h + ALPHA_PAD), Yq=e(pb.Nq, h + ALPHA_PAD),
-                      T=torch.zeros((pb.Np + pb.Nq, KT), dtype=torch.float32, device=dev),     # pad columns stay zero
+                      T=torch.zeros((pb.Np + pb.Nq, self.pool_tab["KT"]), dtype=torch.float32, device=dev),     # pad columns stay zero
                       AC=e(pb.Np + pb.Nq, 2 * D), calls={})
-            per_enc[self._serial] = ws
+            pb._ws[self._serial] = ws
         if fresh_nodes:
-            ws = dict(ws, NQ=torch.empty((pb.Nq, W), dtype=torch.float32, device=dev),
-                      NP=torch.empty((pb.Np, W), dtype=torch.float32, device=dev), calls={})
+            ws = dict(ws, NQ=e(pb.Nq, W), NP=e(pb.Np, W), calls={})
         return ws
 
     # Layer 0 over embedding-table features: a node's transforms depend only on its table row, so the
@@ -549,12 +612,10 @@ class SessionEncoder:
         NQ, NP, Yp, Yq = ws["NQ"], ws["NP"], ws["Yp"], ws["Yq"]
         P_, prob = _lib.LinearProblem, _lib.linear_problem
 
-        steps, keep = [], []
+        steps = []
         tabs = self._layer0_tables() if gather else None      # layer-0 transforms of the feature TABLES (weights only)
         for l, lw in enumerate(self.layers):
-            off = 0 if l == 0 else cfg.d_in + (l - 1) * h
-            din = lw["din"]
-            xin_p, xin_q = NP[:, off:off + din], NQ[:, off:off + din]
+            din, xin_p, xin_q, out_p, out_q = self._layer_views(l, NQ, NP)
             table0 = l == 0 and tabs is not None
             if table0:
                 arr = None                                     # no per-batch transform: nodes read their table row's
@@ -566,8 +627,6 @@ class SessionEncoder:
                 pp = prob(xin_p, lw["w7"], lw["b7"], Yp, pb.Np, 7 * h + 2)
                 pq = prob(xin_q, lw["wq"], None, Yq, pb.Nq, h + 2)
                 arr = (P_ * 2)(pp, pq)
-            out_p = NP[:, cfg.d_in + l * h: cfg.d_in + (l + 1) * h]
-            out_q = NQ[:, cfg.d_in + l * h: cfg.d_in + (l + 1) * h]
             rp_qp, c_qp, _ = pb.csr_qp
             rp_pq, c_pq, _ = pb.csr_pq
             rp_pp, c_pp, w_pp = pb.csr_pp
@@ -589,7 +648,6 @@ class SessionEncoder:
             if arr is not None:
                 steps.append(("lin", arr, 2, din))
             steps.append(("layer", la))
-            keep += [arr, la]
         pw, pt = self.pool, self.pool_tab
         Dl = D - P
         T, AC = ws["T"], ws["AC"]
@@ -603,18 +661,13 @@ class SessionEncoder:
 
     def _forward_fused(self, pb, get_node, query_node_mask, product_node_mask, l2_normalize):
         cfg, L, dev = self.cfg, _lib.lib(), self.device
-        h, D, P, W = cfg.h, cfg.d_out, cfg.max_seq_len, cfg.node_width
+        D, P = cfg.d_out, cfg.max_seq_len
         ws = self._workspace(pb, get_node)
         NQ, NP = ws["NQ"], ws["NP"]
         masked = query_node_mask is not None or product_node_mask is not None
         gather = pb.q_feat is None and pb.p_feat is None and not masked
         if not gather:      # features given / masked inputs: materialise slice 0 first (per-op kernels)
-            self._features(pb.q_ids, pb.q_feat, self.query_table, pb.Nq, NQ)
-            self._features(pb.p_ids, pb.p_feat, self.item_table, pb.Np, NP, product=True)
-            if query_node_mask is not None:
-                NQ[:, :cfg.d_in] *= query_node_mask.to(dev, torch.float32).view(-1, 1)
-            if product_node_mask is not None:
-                NP[:, :cfg.d_in] *= product_node_mask.to(dev, torch.float32).view(-1, 1)
+            self._node_inputs(pb, query_node_mask, product_node_mask, NQ, NP)
         elif self.item_table is None or self.query_table is None:
             raise _lib.SssError("no feature table in the weights and no .feat on the batch")
         st = self._st()
@@ -633,48 +686,26 @@ class SessionEncoder:
         _lib.check(rc, "sss_pool_attention_tab")
         return out, NQ, NP
 
-    @torch.no_grad()
-    def forward(self, data, query_node_mask=None, product_node_mask=None, get_node=False, get_token=False,
-                l2_normalize=False):
-        """``l2_normalize=True`` (extension) returns ``normalize(forward(data))`` -- the reference's
-        util_amazon_filtered.normalize -- fused into the last pooling kernel."""
+    # ------------------------------------------------------------------ per-op path (h or d_out > 256, or fused=False)
+    def _forward_per_op(self, pb, query_node_mask, product_node_mask, l2_normalize):
         cfg, L, dev = self.cfg, _lib.lib(), self.device
         h, D, P, W = cfg.h, cfg.d_out, cfg.max_seq_len, cfg.node_width
-        pb = self.prepare(data)
         Nq, Np, B = pb.Nq, pb.Np, pb.B
-        if self.fused_ok():
-            out, NQ, NP = self._forward_fused(pb, get_node, query_node_mask, product_node_mask, l2_normalize)
-            if self.debug_nan_checks and (torch.isnan(NQ).any() or torch.isnan(NP).any()):
-                raise RuntimeError("nan in node embedding")
-            return self._pack(out, NQ, NP, get_node, get_token)
-
-        NQ = self._features(pb.q_ids, pb.q_feat, self.query_table, Nq)   # [Nq, W]; slice 0 = input features
-        NP = self._features(pb.p_ids, pb.p_feat, self.item_table, Np, product=True)    # embedding lookup (NodeAsinEmbedding)
-        if query_node_mask is not None:                   # model/model.py:293-296 (None at inference)
-            NQ[:, :cfg.d_in] *= query_node_mask.to(dev, torch.float32).view(-1, 1)
-        if product_node_mask is not None:
-            NP[:, :cfg.d_in] *= product_node_mask.to(dev, torch.float32).view(-1, 1)
+        NQ, NP = self._node_inputs(pb, query_node_mask, product_node_mask)
         if self.debug_nan_checks and (torch.isnan(NQ[:, :cfg.d_in]).any() or torch.isnan(NP[:, :cfg.d_in]).any()):
             raise RuntimeError("nan in embedding[query]")   # model/model.py:312
 
-        csr_qp, csr_pq, csr_pp = pb.csr_qp, pb.csr_pq, pb.csr_pp
         mp, mq = 5 * h + ALPHA_PAD, h + ALPHA_PAD
-        Yp = torch.empty((Np, mp), dtype=torch.float32, device=dev)
-        Yq = torch.empty((Nq, mq), dtype=torch.float32, device=dev)
-        T1 = torch.empty((Np, h), dtype=torch.float32, device=dev)
-        T2 = torch.empty((Np, h), dtype=torch.float32, device=dev)
-        T3 = torch.empty((Np, 3 * h), dtype=torch.float32, device=dev)
+        e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        Yp, Yq = e(Np, mp), e(Nq, mq)
+        T1, T2, T3 = e(Np, h), e(Np, h), e(Np, 3 * h)
         for l, lw in enumerate(self.layers):
-            off = 0 if l == 0 else cfg.d_in + (l - 1) * h
-            din = lw["din"]
-            xin_p, xin_q = NP[:, off:off + din], NQ[:, off:off + din]
-            out_p = NP[:, cfg.d_in + l * h: cfg.d_in + (l + 1) * h]
-            out_q = NQ[:, cfg.d_in + l * h: cfg.d_in + (l + 1) * h]
+            din, xin_p, xin_q, out_p, out_q = self._layer_views(l, NQ, NP)
             self._linear(xin_p, lw["wp"], lw["bp"], Np, mp, din, Yp)
             self._linear(xin_q, lw["wq"], None, Nq, mq, din, Yq)
             # products <- queries (GAT) ; products <- products (GGC) ; GRU + sum + relu
-            self._gat(Yq[:, :h], Yq[:, h], Yp[:, 5 * h + 1], csr_qp, Np, lw["bias_qp"], 0, T1, pb.n_self_loop)
-            rowptr, col, wv = csr_pp
+            self._gat(Yq[:, :h], Yq[:, h], Yp[:, 5 * h + 1], pb.csr_qp, Np, lw["bias_qp"], 0, T1, pb.n_self_loop)
+            rowptr, col, wv = pb.csr_pp
             rc = L.sss_csr_weighted_sum(Yp[:, h:2 * h].data_ptr(), Yp.stride(0), rowptr.data_ptr(), col.data_ptr(),
                                         0 if wv is None else wv.data_ptr(), Np, h, T2.data_ptr(), T2.stride(0),
                                         self._st())
@@ -685,7 +716,7 @@ class SessionEncoder:
                                    out_p.data_ptr(), NP.stride(0), self._st())
             _lib.check(rc, "sss_gru_combine")
             # queries <- products (GAT) + relu
-            self._gat(Yp[:, :h], Yp[:, 5 * h], Yq[:, h + 1], csr_pq, Nq, lw["bias_pq"], 1, out_q, pb.n_self_loop)
+            self._gat(Yp[:, :h], Yp[:, 5 * h], Yq[:, h + 1], pb.csr_pq, Nq, lw["bias_pq"], 1, out_q, pb.n_self_loop)
         if self.debug_nan_checks and (torch.isnan(NQ).any() or torch.isnan(NP).any()):
             raise RuntimeError("nan in node embedding")
 
@@ -693,32 +724,44 @@ class SessionEncoder:
         pw = self.pool
         Dl = D - P
         ldl = (Dl + 3) // 4 * 4
-        lin_q = torch.empty((Nq, ldl), dtype=torch.float32, device=dev)
-        lin_p = torch.empty((Np, ldl), dtype=torch.float32, device=dev)
+        lin_q, lin_p = e(Nq, ldl), e(Np, ldl)
         self._linear(NQ, pw["wq"], pw["bq"], Nq, Dl, W, lin_q)
         self._linear(NP, pw["wp"], pw["bp"], Np, Dl, W, lin_p)
         n_clicks, n_exp = pb.n_clicks, pb.n_clicks + Nq
-        node = torch.empty((n_exp, D), dtype=torch.float32, device=dev)
+        node = e(n_exp, D)
         rc = L.sss_pool_expand(lin_p.data_ptr(), lin_q.data_ptr(), ldl, pb.src_row.data_ptr(), pb.pos_id.data_ptr(),
                                n_clicks, n_exp, Dl, P, pw["pos"].data_ptr(), node.data_ptr(), node.stride(0),
                                self._st())
         _lib.check(rc, "sss_pool_expand")
         A = self._linear(node, pw["wn"], pw["bn"], n_exp, D, D)
         pptr, qptr = pb.pptr, pb.qptr
-        coarse = torch.empty((B, D), dtype=torch.float32, device=dev)
+        coarse = e(B, D)
         rc = L.sss_segment_pool(node.data_ptr(), node.stride(0), pptr.data_ptr(), qptr.data_ptr(), n_clicks, B, D,
                                 0, 0, 0, 0, 0, coarse.data_ptr(), coarse.stride(0), self._st())
         _lib.check(rc, "sss_segment_pool(mean)")
         Bc = self._linear(coarse, pw["wc"], None, B, D, D)
-        out = torch.empty((B, D), dtype=torch.float32, device=dev)
+        out = e(B, D)
         rc = L.sss_segment_pool(node.data_ptr(), node.stride(0), pptr.data_ptr(), qptr.data_ptr(), n_clicks, B, D,
                                 A.data_ptr(), A.stride(0), Bc.data_ptr(), Bc.stride(0), pw["watt"].data_ptr(),
                                 out.data_ptr(), out.stride(0), self._st())
         _lib.check(rc, "sss_segment_pool(att)")
-
         if l2_normalize:
             from .index import normalize_
             normalize_(out)
+        return out, NQ, NP
+
+    @torch.no_grad()
+    def forward(self, data, query_node_mask=None, product_node_mask=None, get_node=False, get_token=False,
+                l2_normalize=False):
+        """``l2_normalize=True`` (extension) returns ``normalize(forward(data))`` -- the reference's
+        util_amazon_filtered.normalize -- fused into the last pooling kernel."""
+        pb = self.prepare(data)
+        if self.fused_ok():
+            out, NQ, NP = self._forward_fused(pb, get_node, query_node_mask, product_node_mask, l2_normalize)
+            if self.debug_nan_checks and (torch.isnan(NQ).any() or torch.isnan(NP).any()):
+                raise RuntimeError("nan in node embedding")
+        else:           # its two debug_nan_checks reads sit between its launches, as the reference's asserts do
+            out, NQ, NP = self._forward_per_op(pb, query_node_mask, product_node_mask, l2_normalize)
         return self._pack(out, NQ, NP, get_node, get_token)
 
     def _pack(self, out, NQ, NP, get_node, get_token):

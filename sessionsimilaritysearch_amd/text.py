@@ -256,7 +256,7 @@ class NodeTextTransformer(_PackedEncoder):
     Limits: ``ninp % 4 == 0``, ``ninp <= 1024``, head width ``ninp / nhead <= 64``, ``T <= 64``."""
 
     def __init__(self, weights, nhead, pad_rule="compute", device=None, chunk_rows=131072, eps=1e-5):
-        import torch
+        from ._device import model_device, upload_f32
         _check_rule(pad_rule)
         f = text_fold_weights(weights, nhead)                                # raises ValueError when nhead does not divide ninp
         e = f["ninp"]
@@ -267,8 +267,8 @@ class NodeTextTransformer(_PackedEncoder):
         self.pad_rule, self.chunk_rows, self.eps = pad_rule, int(chunk_rows), float(eps)
         self.ninp, self.nhead, self.nhid, self.nlayers = e, f["nhead"], f["nhid"], f["nlayers"]
         self.ntoken, self.scale = int(f["table"].shape[0]), f["scale"]
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        d = lambda t: t.to(device=self.device, dtype=torch.float32).contiguous()
+        self.device = model_device(device)
+        d = lambda t: upload_f32(t, self.device)
         self.table, self.pe = d(f["table"]), d(f["pe"])
         self.layers = [{n: d(v) for n, v in lay.items()} for lay in f["layers"]]
 
@@ -413,7 +413,7 @@ class BertNodeEncoder(_PackedEncoder):
 
     def __init__(self, weights, num_heads, pool="masked", eps=1e-12, device=None, chunk_rows=32768, dedup=True, hidden_act="gelu",
                  position_embedding_type="absolute"):
-        import torch
+        from ._device import model_device, upload_f32
         if pool not in BERT_POOLS:
             raise ValueError(f"pool must be 'masked' or 'mean', got {pool!r}")
         if hidden_act != "gelu":
@@ -434,8 +434,8 @@ class BertNodeEncoder(_PackedEncoder):
         self.pool, self.chunk_rows, self.eps, self.dedup = pool, int(chunk_rows), float(eps), bool(dedup)
         self.ninp, self.nhead, self.inter, self.nlayers = e, f["heads"], f["inter"], f["nlayers"]
         self.n_word, self.n_pos, self.n_type = int(f["word"].shape[0]), int(f["pos"].shape[0]), int(f["type"].shape[0])
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        d = lambda t: t.to(device=self.device, dtype=torch.float32).contiguous()
+        self.device = model_device(device)
+        d = lambda t: upload_f32(t, self.device)
         self.word, self.pos, self.type, self.emb_g, self.emb_b = (d(f[n]) for n in ("word", "pos", "type", "emb_g", "emb_b"))
         self.layers = [{n: d(v) for n, v in lay.items()} for lay in f["layers"]]
         self.lin_w, self.lin_b = (None, None) if f["lin_w"] is None else (d(f["lin_w"]), d(f["lin_b"]))

@@ -30,6 +30,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._device import model_device, upload_f32
 from .sessions import EDGE_PP, EDGE_PQ, EDGE_QP
 
 
@@ -62,17 +63,13 @@ def _pad_cols(w, dev):
     return out
 
 
-def _d(t, dev):
-    return t.detach().to(device=dev, dtype=torch.float32).contiguous()
-
-
 class HeteroSAGE:
     """Three hetero SAGEConv layers + relu; returns the LAST layer's node features
     ``{'query': [Nq, h], 'product': [Np, h]}`` (``GNN.forward``, model/gnn.py:114-121).
     weights: ``sage.{l}.{qp|pq|pp}.lin_l.w [h, d]`` / ``.lin_l.b [h]`` / ``.lin_r.w [h, d]``."""
 
     def __init__(self, weights, n_layers=3, device=None):
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.device = model_device(device)
         self.layers = []
         for l in range(n_layers):
             g = lambda e, n: weights[f"sage.{l}.{e}.{n}"]
@@ -81,7 +78,7 @@ class HeteroSAGE:
             bp = g("qp", "lin_l.b") + g("pp", "lin_l.b")
             wq = torch.cat([g("pq", "lin_l.w"), g("pq", "lin_r.w")], dim=1)
             bq = g("pq", "lin_l.b")
-            self.layers.append(tuple(_d(t, self.device) for t in (wp, bp, wq, bq)))
+            self.layers.append(tuple(upload_f32(t, self.device) for t in (wp, bp, wq, bq)))
 
     @torch.no_grad()
     def forward(self, x_q, x_p, csr_qp, csr_pq, csr_pp):
@@ -175,15 +172,15 @@ class HGT:
     grouped ``a_lin`` GEMM into the next slice of the output, ``sss_hgt_skip`` per type: 1 + 6 L launches."""
 
     def __init__(self, weights, n_heads=4, n_layers=3, device=None):
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.device = model_device(device)
         f = hgt_fold_weights(weights, n_heads, n_layers)
         self.h, self.heads, self.n_layers = f["h"], f["heads"], n_layers
         if self.heads not in (1, 2, 4, 8) or (self.h // self.heads) % 4 or self.h % 32 or self.h > 2048:
             raise ValueError(f"HGT needs n_heads in (1, 2, 4, 8), h / n_heads % 4 == 0, h % 32 == 0 and h <= 2048; "
                              f"got h = {self.h}, n_heads = {n_heads}")
         dev = self.device
-        self.lin = {t: (_pad_cols(w, dev), _d(b, dev)) for t, (w, b) in f["lin"].items()}
-        self.layers = [{t: {n: (v if n == "beta" else _d(v, dev)) for n, v in lay[t].items()} for t in lay} for lay in f["layers"]]
+        self.lin = {t: (_pad_cols(w, dev), upload_f32(b, dev)) for t, (w, b) in f["lin"].items()}
+        self.layers = [{t: {n: (v if n == "beta" else upload_f32(v, dev)) for n, v in lay[t].items()} for t in lay} for lay in f["layers"]]
 
     def _grouped(self, probs, k):
         arr = (_lib.LinearProblem * len(probs))(*probs)
@@ -244,7 +241,7 @@ class GraphPooling:
 
     def __init__(self, pooling_key, weights, device):
         self.pooling_key = pooling_key           # like the reference, the key is only looked at in forward()
-        self.w, self.b = _d(weights["lin.w"], device), _d(weights["lin.b"], device)
+        self.w, self.b = upload_f32(weights["lin.w"], device), upload_f32(weights["lin.b"], device)
 
     @torch.no_grad()
     def forward(self, x, ptr):
@@ -261,7 +258,7 @@ class GraphPooling:
 
 class AttentionPooling:
     def __init__(self, weights, device):
-        self.w, self.b = _d(weights["lin.w"], device), _d(weights["lin.b"], device)
+        self.w, self.b = upload_f32(weights["lin.w"], device), upload_f32(weights["lin.b"], device)
 
     @torch.no_grad()
     def forward(self, x, ptr):
@@ -279,7 +276,7 @@ class SRGNNPooling:
     pass the ``PreparedBatch`` that carries it as ``batch=`` (``SessionEncoder.prepare_actions`` always builds one)."""
 
     def __init__(self, weights, device):
-        g = lambda n: _d(weights[n], device)
+        g = lambda n: upload_f32(weights[n], device)
         self.w1, self.b1, self.w2, self.b2 = g("lin1.w"), g("lin1.b"), g("lin2.w"), g("lin2.b")
         self.w3 = g("lin3.w").view(-1).contiguous()
         self.w4, self.b4 = g("lin4.w"), g("lin4.b")
@@ -324,9 +321,9 @@ class MLPHead:
             # the reference applies relu to EVERY module of layers[:-1], Linear and BatchNorm alike
             # (model/model.py:63-65): relu(bn(relu(lin(x)))).  Both stages are epilogue steps of the Linear's GEMM:
             # act = relu, then the BatchNorm eval affine + relu per output column.
-            self.hidden.append((_pad_cols(weights[f"layers.{i}.w"], device), _d(weights[f"layers.{i}.b"], device),
-                                _d(s.float(), device),
-                                _d((f64(weights[f"bn.{i}.beta"]) - f64(weights[f"bn.{i}.mean"]) * s).float(), device)))
+            self.hidden.append((_pad_cols(weights[f"layers.{i}.w"], device), upload_f32(weights[f"layers.{i}.b"], device),
+                                upload_f32(s.float(), device),
+                                upload_f32((f64(weights[f"bn.{i}.beta"]) - f64(weights[f"bn.{i}.mean"]) * s).float(), device)))
         last = n_hidden_layers + 1
         self.n_in = int(weights["layers.0.w"].shape[1])
         self.n_hidden = int(weights["layers.0.w"].shape[0])
@@ -335,10 +332,10 @@ class MLPHead:
             wl = torch.zeros((self.wl_raw.shape[0], _pad32(self.n_in) + _pad32(self.n_hidden)))
             wl[:, :self.n_in] = self.wl_raw[:, :self.n_in]
             wl[:, _pad32(self.n_in):_pad32(self.n_in) + self.n_hidden] = self.wl_raw[:, self.n_in:]
-            self.wl = _d(wl, device)
+            self.wl = upload_f32(wl, device)
         else:
             self.wl = _pad_cols(self.wl_raw, device)
-        self.bl = _d(weights[f"layers.{last}.b"], device)
+        self.bl = upload_f32(weights[f"layers.{last}.b"], device)
         self.n_out = int(self.wl_raw.shape[0])
 
     def _in_buffer(self, x):
@@ -392,10 +389,10 @@ class BinarizeHead:
             wl = torch.zeros((w.shape[0], _pad32(m_out) + _pad32(self.n_in - m_out)))
             wl[:, :m_out] = w[:, :m_out]
             wl[:, _pad32(m_out):_pad32(m_out) + self.n_in - m_out] = w[:, m_out:]
-            self.w1 = _d(wl, device)
+            self.w1 = upload_f32(wl, device)
         else:
             self.w1 = _pad_cols(w, device)
-        self.b1 = _d(weights["lin1.b"], device)
+        self.b1 = upload_f32(weights["lin1.b"], device)
 
     @torch.no_grad()
     def forward(self, x, pre_sign=False):
