@@ -151,16 +151,34 @@ int launch_range_select(const ThrArgs& a, const float* radius, long* counts, int
 int launch_range_fill(const unsigned* cnt, const unsigned long long* cand, int cap, long nq, const long* lims, long id_offset, float* D,
                       long* I, hipStream_t st);
 
+// What a scanning search entry point was called with (host only: never a kernel argument).  Each extern "C" entry point
+// of ip_topk.hip and scan_long.hip fills one, every field by name, and the checks, the workspace layouts and the kernel
+// argument structs above are made from it.
+enum Family { FAM_IP, FAM_L2, FAM_PAD };       // whose header's rules apply: include/sss.h, sss_l2.h + sss_l2_long.h, sss_pad.h
+struct SearchCall {
+    const char* what = nullptr; Family family = FAM_IP;             // the entry point's name in messages
+    const void* q = nullptr; long nq = 0; const int* qsel = nullptr;   // queries of the exact element type, d wide; threshold forms: nq is nsel, the length of qsel
+    const void* c_exact = nullptr; int exact_dtype = DT_F32;        // the stored rows the candidates are re-scored from ...
+    const void* c_scan = nullptr; int scan_dtype = DT_F32;          // ... and what k_scan reads: the rows themselves or a scan-only image,
+    int corpus_shift = 0; float corpus_resid = 0.f;                 //     a DT_F16 image with its shift and residual
+    const float* bias = nullptr;                // set: an L2 search (keys q.c + bias[row], scores negated distances)
+    long n = 0; int d = 0, d_row = 0, k = 0;    // d: the width of q and c_scan; d_row: of a stored row where it is narrower (sss_pad.h), else 0
+    long id_offset = 0; float corpus_max_norm = 0.f;
+    float* D_out = nullptr; long* I_out = nullptr; int* status = nullptr; int* unproven_count = nullptr;
+    void* state = nullptr; size_t state_bytes = 0; void* ws = nullptr; size_t ws_bytes = 0;
+    hipStream_t st = nullptr;
+};
+
 // What every scanning search entry point checks about its scan source (ip_topk.hip), in this order: the (exact, scan)
 // element-type pairing and row shape (long_rows: long_shape_ok, else the fused scans' shapes), the image pointer and
 // its 16-byte alignment, a DT_F16 image's corpus_shift in [-160, 160] and corpus_resid >= 0, n and nq below 2^31.
-// SSS_EINVAL with a message that starts with `what` on the first failure.
-int check_scan_source(const char* what, int exact_dtype, int scan_dtype, int d, bool long_rows, const void* c_scan, int corpus_shift,
-                      float corpus_resid, long n, long nq);
-// The ThrArgs fields of a threshold-form search that do not depend on its workspace layout (ip_topk.hip); the rest is
-// null / zero until the caller sets thr / cnt / cand, the outputs it writes and the long-row extras.
-ThrArgs thr_args(const void* q, const void* c_exact, int exact_dtype, int scan_dtype, int corpus_shift, float corpus_resid,
-                 float corpus_max_norm, const int* qsel, long nsel, long n, int d, int k, int cap, long id_offset);
+// SSS_EINVAL with a message that starts with c.what on the first failure.
+int check_scan_source(const SearchCall& c, bool long_rows);
+// The buffers the L2 and pad families require (ip_topk.hip), in this order: the row bias 16-byte aligned (bias_required:
+// and there), q / corpus / D_out / I_out / status there, and -- aligned_rows, the pad family -- q and corpus 16-byte aligned.
+int check_buffers(const SearchCall& c, bool bias_required, bool aligned_rows);
+// The ThrArgs of a threshold-form search but for thr / cnt / cand, which the caller sets from its workspace layout.
+ThrArgs thr_args(const SearchCall& c, int cap);
 
 // a float32 [nsel][n] score matrix at the head of a workspace, up to the next 256-byte boundary
 static inline size_t score_matrix_bytes(long nsel, long n) { return al256((size_t)nsel * n * 4); }

@@ -25,6 +25,7 @@
 //   to the final threshold) -- no tile is scanned twice.
 // Two to three passes, the last one dominant; no per-lane list, no shared threshold slots, no bootstrap.
 #include "scan.h"
+#include <algorithm>
 #include <cmath>
 #include "scan_dev.h"
 
@@ -357,54 +358,40 @@ constexpr int LONG_MAX_K = 1024;    // what the exhaustive kernels -- the path o
 // (f32 d > 2560, bf16 d > 5120) leave room for half the capacity only.
 static int long_cap(int d, int exact_dtype) { return d * elem_bytes(exact_dtype) > 10240 ? LONG_CAP / 2 : LONG_CAP; }
 
+// The workspace, written ONCE (offsets in bytes, every array 256-byte aligned): qimg 16-bit [nq][d] the f16 query image |
+// qsel i32 [nq] the identity selection | thr f32 [nq] | cnt u32 [nq] | L2 only: seed f32 [2][2][nq], the seed coefficients
+// for lowered, then for raised keys | qb f64 [nq][2] (error bound, unscale) per query, computed once; L2: + [nq] off = -|q|^2
+// + [nq] the select's bound | cand u64 [nq][LONG_CAP].  cand is sized by LONG_CAP whatever the rows, as the sizing functions
+// always have: a search whose long_cap(d, dtype) is half of it lays its [nq][cap] rows out in the first half of the array.
+struct LongLayout { size_t qimg, qsel, thr, cnt, seed, qb, cand, total; };
+static LongLayout long_layout(long nq, int d, bool l2) {
+    LongLayout l;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t off = at; at += al256(bytes); return off; };
+    l.qimg = take((size_t)nq * d * 2); l.qsel = take((size_t)nq * 4); l.thr = take((size_t)nq * 4); l.cnt = take((size_t)nq * 4);
+    l.seed = l2 ? take((size_t)nq * 16) : 0;
+    l.qb = take((size_t)nq * (l2 ? 32 : 16));
+    l.cand = at; l.total = at + (size_t)nq * LONG_CAP * 8;
+    return l;
+}
+
 extern "C" size_t sss_ip_topk_long_workspace_bytes(int64_t nq, int64_t n, int d, int dtype) {
     if (nq <= 0 || n <= 0 || !long_shape_ok(d, dtype, long_scan_dtype(dtype))) return 0;
-    return al256((size_t)nq * d * 2) + al256((size_t)nq * 4) * 3 + al256((size_t)nq * 16) + (size_t)nq * LONG_CAP * 8;
+    return long_layout(nq, d, false).total;
 }
 
-// L2 (include/sss_l2_long.h): the same arrays, the bound cache two doubles wider (off = -|q|^2 and the select's bound
-// behind the (B, unscale) pairs) and four floats per query more (the seed coefficients of the two kinds of level)
-extern "C" size_t sss_l2_topk_long_workspace_bytes(int64_t nq, int64_t n, int d) {
+extern "C" size_t sss_l2_topk_long_workspace_bytes(int64_t nq, int64_t n, int d) {      // (include/sss_l2_long.h)
     if (nq <= 0 || n <= 0 || !long_shape_ok(d, DT_F32, DT_F16)) return 0;
-    return al256((size_t)nq * d * 2) + al256((size_t)nq * 4) * 3 + al256((size_t)nq * 16) + al256((size_t)nq * 32) +
-           (size_t)nq * LONG_CAP * 8;
+    return long_layout(nq, d, true).total;
 }
 
-// The long-row search of both metrics.  bias == nullptr: inner product (`what` = "ip_topk_long").  bias != nullptr: L2
-// over float32 rows (`what` = "l2_topk_long"; the caller has checked its buffers) -- k_scan_long<DT_F16, 1> seeds every
-// accumulator from its row's bias and norm, the ThrArgs carry metric 1, and everything else -- the level plan,
-// launch_bound_prepare, launch_select_all -- is what the inner product runs.  Two things differ (select_thr.hip: THE
-// PER-ROW BOUND): the sample levels scan keys LOWERED by each row's own error bound and the last level keys RAISED by
-// it, and the levels are never disjoint -- a sample's kept rows carry lowered keys, which the final threshold (made for
-// raised keys) must not prune.
-static int topk_long_impl(const char* what, const float* bias, const void* q, long nq, const void* c_exact, int exact_dtype,
-                          const void* c_scan, int corpus_shift, float corpus_resid, long n, int d, int k, long id_offset,
-                          float corpus_max_norm, float* D_out, long* I_out, int* status, void* ws, size_t ws_bytes, hipStream_t st) {
-    const bool l2 = bias != nullptr;
-    const int scan_dtype = long_scan_dtype(exact_dtype);
-    const bool f16_mfma = scan_dtype != DT_BF16;        // the scaled image and stored f16 rows share k_scan_long<DT_F16>
-    if (nq <= 0 || n <= 0 || k <= 0) { set_error("%s: nq, n, k must be positive", what); return SSS_EINVAL; }
-    int rc = check_scan_source(what, exact_dtype, scan_dtype, d, true, c_scan, corpus_shift, corpus_resid, n, nq);
-    if (rc) return rc;
-    if (k > LONG_MAX_K) { set_error("%s: k too large (max %d)", what, LONG_MAX_K); return SSS_EINVAL; }
-    const int cap = long_cap(d, exact_dtype);
-    if (reinterpret_cast<uintptr_t>(ws) & 255) { set_error("%s: workspace must be 256-byte aligned", what); return SSS_EINVAL; }
-    const size_t need = l2 ? sss_l2_topk_long_workspace_bytes(nq, n, d) : sss_ip_topk_long_workspace_bytes(nq, n, d, exact_dtype);
-    if (ws_bytes < need) { set_error("%s: workspace %zu < %zu", what, ws_bytes, need); return SSS_EWORKSPACE; }
-    char* w = reinterpret_cast<char*>(ws);
-    void* qimg = w;                              w += al256((size_t)nq * d * 2);
-    int* qsel = reinterpret_cast<int*>(w);       w += al256((size_t)nq * 4);
-    float* thr = reinterpret_cast<float*>(w);    w += al256((size_t)nq * 4);
-    unsigned* cnt = reinterpret_cast<unsigned*>(w); w += al256((size_t)nq * 4);
-    float* seed = nullptr;                       // L2: [2][2][nq] seed coefficients: lowered keys, then raised keys
-    if (l2) { seed = reinterpret_cast<float*>(w); w += al256((size_t)nq * 16); }
-    double* qb = reinterpret_cast<double*>(w);   w += al256((size_t)nq * (l2 ? 32 : 16));   // (error bound, unscale) per query, computed once; L2: + [nq] off + [nq] select bound
-    unsigned long long* cand = reinterpret_cast<unsigned long long*>(w);
+// One level of a search: a launch of k_scan_long over tile_count tiles (LongArgs: tile_count, total_tiles, skip_R, S,
+// tiles_per_split, dense) and, behind every level but the last, the bound step with ThrArgs::keep.
+struct LongLevel { int tile_count, total_tiles, skip_R, S, tiles_per_split, dense, keep; };
+struct LongPlan { int levels = 0; LongLevel level[40]; };        // in the order they run: the samples growing, every row last
 
-    // (the f16 query image, the identity selection, D_out at "no bound known", thresholds, counters, status and the
-    //  per-query bound cache are written by ONE launch below, once the ThrArgs are filled: launch_long_setup)
-    const void* q_scan = scan_dtype == DT_F16 ? qimg : q;
-
+// The level schedule of a corpus of total_tiles tiles for G query groups: arithmetic on these integers, nothing else.
+static LongPlan long_plan(int total_tiles, int cap, int k, bool l2, int G) {
     // ---- levels (descending in level_tiles, run in reverse).  The first sample is as large as the capacity allows with
     // the threshold at -inf (cap rows: every sampled row is kept) -- a 32-tile level costs the time of ONE tile, the chip
     // being far from full, and its k-th best score is a much better bound than that of a 2k-row sample.  From there to
@@ -412,11 +399,7 @@ static int topk_long_impl(const char* what, const float* bias, const void* q, lo
     // threshold (2x margin below the capacity at r = fmax), the fewest levels that allows, and the factors balanced so
     // that the last sample is as small as it can be (1M x 1600, K = 100: 32, 353, 3907 tiles -- the samples add ~10 % to
     // the matrix work; it was 1, 24, 488, 3907).  Intermediate levels read no row at all (k_bound_prepare).
-    const int total_tiles = (int)((n + LT_ROWS - 1) / LT_ROWS);
-    int fmax = cap / (4 * k);
-    if (fmax < 2) fmax = 2;
-    int first = cap / LT_ROWS;
-    if (first > total_tiles) first = total_tiles;
+    const int fmax = std::max(cap / (4 * k), 2), first = std::min(cap / LT_ROWS, total_tiles);
     int level_tiles[40];
     int levels = 0;
     level_tiles[levels++] = total_tiles;
@@ -432,24 +415,6 @@ static int topk_long_impl(const char* what, const float* bias, const void* q, lo
         }
         level_tiles[levels++] = first;
     }
-    const size_t lds = LT_LDS_BYTES;
-    rc = l2         ? opt_in_lds(reinterpret_cast<const void*>(&k_scan_long<DT_F16, 1>), "k_scan_long", lds)
-         : f16_mfma ? opt_in_lds(reinterpret_cast<const void*>(&k_scan_long<DT_F16>), "k_scan_long", lds)
-                    : opt_in_lds(reinterpret_cast<const void*>(&k_scan_long<DT_BF16>), "k_scan_long", lds);
-    if (rc) return rc;
-    ThrArgs t = thr_args(q, c_exact, exact_dtype, scan_dtype, corpus_shift, corpus_resid, corpus_max_norm, qsel, nq, n, d, k, cap,
-                         id_offset);
-    t.thr = thr; t.cnt = cnt; t.cand = cand; t.D_out = D_out; t.I_out = I_out; t.status = status;
-    t.qb = qb;
-    t.metric = l2 ? 1 : 0;
-    rc = launch_long_setup(t, qsel, scan_dtype == DT_F16 ? qimg : nullptr, seed, st);
-    if (rc) return rc;
-    t.qb_ready = 1;
-    LongArgs a;
-    a.Qimg = q_scan; a.C = c_scan; a.nq = (int)nq; a.n = (int)n; a.d = d; a.G = (int)((nq + LT_Q - 1) / LT_Q);
-    a.total_tiles = total_tiles; a.cap = cap; a.thr = thr; a.cnt = cnt; a.cand = cand;
-    a.bias = bias;
-    a.gpx = a.G;                    // groups per XCD (block map of k_scan_long): all of them (fewer measured slower, see the kernel)
     // DISJOINT LEVELS (three levels and more).  The last sample used to be scanned twice: once as a sample, once more as
     // part of the whole corpus -- 9 % of the matrix work at 1M x 1600, K = 100.  Now the last sample takes EVERY R-th
     // tile (R = the planned ratio, rounded, >= 2) and the final level only the tiles in between: the rows the sample kept
@@ -457,44 +422,94 @@ static int topk_long_impl(const char* what, const float* bias, const void* q, lo
     // final threshold is the tighter one, so nothing above it was ever dropped), and the final level appends behind
     // them.  Together they are exactly the rows of the whole corpus above the final threshold -- what k_select_all's
     // proof needs -- and there are fewer of them (the sample's rows are filtered by the final threshold now).
+    // Never for L2: a sample's kept rows carry lowered keys, which the final threshold (made for raised keys) must not prune.
     int R = 0;
     if (levels >= 3 && !l2) {
         R = (int)((double)total_tiles / (double)level_tiles[1] + 0.5);
         if (R < 2) R = 0;                              // (ratio below 1.5: the planned sample is most of the corpus -- keep the plain form)
     }
+    LongPlan p;
     for (int lv = levels - 1; lv >= 0; --lv) {
-        int tiles = level_tiles[lv];
-        const bool last = lv == 0;
-        a.total_tiles = total_tiles;
-        a.skip_R = 0;
-        if (R > 0 && lv == 1) {                        // every R-th tile: the proportional map with total = R * count
-            tiles = (total_tiles + R - 1) / R;
-            a.total_tiles = R * tiles;
+        LongLevel& v = p.level[p.levels++];
+        const bool last = lv == 0, last_sample = R > 0 && lv == 1;
+        v.tile_count = level_tiles[lv]; v.total_tiles = total_tiles; v.skip_R = 0;
+        if (last_sample) {                             // every R-th tile: the proportional map with total = R * count
+            v.tile_count = (total_tiles + R - 1) / R;
+            v.total_tiles = R * v.tile_count;
         } else if (R > 0 && last) {                    // the tiles in between
-            tiles = total_tiles - (total_tiles + R - 1) / R;
-            a.skip_R = R;
+            v.tile_count = total_tiles - (total_tiles + R - 1) / R;
+            v.skip_R = R;
         }
-        a.tile_count = tiles;
-        a.seed = l2 ? seed + (last ? 2 * nq : 0) : nullptr;
-        a.dense = last ? 0 : 1;
-        int S = (256 / a.G) & ~7;
-        if (S < 8) S = 8;
-        while (S > 8 && S > tiles) S -= 8;
-        a.S = S;
-        a.tiles_per_split = (tiles + S - 1) / S;
+        v.dense = last ? 0 : 1;
+        v.keep = last_sample ? 1 : 0;                  // the final level keeps this (the last sample's) rows that pass its thresholds
+        v.S = std::max((256 / G) & ~7, 8);
+        while (v.S > 8 && v.S > v.tile_count) v.S -= 8;
+        v.tiles_per_split = (v.tile_count + v.S - 1) / v.S;
+    }
+    return p;
+}
+
+// The long-row search of both metrics.  c.bias == nullptr: inner product.  c.bias != nullptr: L2 over float32 rows (the
+// L2 family's buffers are checked first, as sss_l2_topk_long always has) -- k_scan_long<DT_F16, 1> seeds every accumulator
+// from its row's bias and norm, the ThrArgs carry metric 1, and everything else -- the level plan, launch_bound_prepare,
+// launch_select_all -- is what the inner product runs.  Two things differ (select_thr.hip: THE PER-ROW BOUND): the sample
+// levels scan keys LOWERED by each row's own error bound and the last level keys RAISED by it, and the levels are never
+// disjoint.  All checks come before the first launch.
+static int topk_long_impl(const SearchCall& c) {
+    int rc = c.family == FAM_L2 ? check_buffers(c, true, false) : SSS_OK;
+    if (rc) return rc;
+    const bool l2 = c.bias != nullptr;
+    if (c.nq <= 0 || c.n <= 0 || c.k <= 0) { set_error("%s: nq, n, k must be positive", c.what); return SSS_EINVAL; }
+    rc = check_scan_source(c, true);
+    if (rc) return rc;
+    if (c.k > LONG_MAX_K) { set_error("%s: k too large (max %d)", c.what, LONG_MAX_K); return SSS_EINVAL; }
+    if (reinterpret_cast<uintptr_t>(c.ws) & 255) { set_error("%s: workspace must be 256-byte aligned", c.what); return SSS_EINVAL; }
+    const LongLayout l = long_layout(c.nq, c.d, l2);
+    if (c.ws_bytes < l.total) { set_error("%s: workspace %zu < %zu", c.what, c.ws_bytes, l.total); return SSS_EWORKSPACE; }
+    char* w = reinterpret_cast<char*>(c.ws);
+    void* qimg = w + l.qimg;
+    int* qsel = reinterpret_cast<int*>(w + l.qsel);
+    float* seed = l2 ? reinterpret_cast<float*>(w + l.seed) : nullptr;
+
+    // the scaled image and stored f16 rows share k_scan_long<DT_F16>
+    void (*kernel)(const LongArgs) = l2 ? k_scan_long<DT_F16, 1> : c.scan_dtype != DT_BF16 ? k_scan_long<DT_F16> : k_scan_long<DT_BF16>;
+    const size_t lds = LT_LDS_BYTES;
+    rc = opt_in_lds(reinterpret_cast<const void*>(kernel), "k_scan_long", lds);
+    if (rc) return rc;
+    // the f16 query image, the identity selection, D_out at "no bound known", thresholds, counters, status and the
+    // per-query bound cache are written by ONE launch
+    const int cap = long_cap(c.d, c.exact_dtype);
+    ThrArgs t = thr_args(c, cap);
+    t.qsel = qsel;
+    t.thr = reinterpret_cast<float*>(w + l.thr);
+    t.cnt = reinterpret_cast<unsigned*>(w + l.cnt);
+    t.cand = reinterpret_cast<unsigned long long*>(w + l.cand);
+    t.qb = reinterpret_cast<double*>(w + l.qb);
+    rc = launch_long_setup(t, qsel, c.scan_dtype == DT_F16 ? qimg : nullptr, seed, c.st);
+    if (rc) return rc;
+    t.qb_ready = 1;
+    LongArgs a;
+    a.Qimg = c.scan_dtype == DT_F16 ? qimg : c.q;
+    a.C = c.c_scan; a.nq = (int)c.nq; a.n = (int)c.n; a.d = c.d; a.G = (int)((c.nq + LT_Q - 1) / LT_Q);
+    a.cap = cap; a.thr = t.thr; a.cnt = t.cnt; a.cand = const_cast<unsigned long long*>(t.cand);
+    a.bias = c.bias;
+    a.gpx = a.G;                    // groups per XCD (block map of k_scan_long): all of them (fewer measured slower, see the kernel)
+    const LongPlan plan = long_plan((int)((c.n + LT_ROWS - 1) / LT_ROWS), cap, c.k, l2, a.G);
+    for (int i = 0; i < plan.levels; ++i) {
+        const LongLevel& v = plan.level[i];
+        const bool last = i == plan.levels - 1;
+        a.tile_count = v.tile_count; a.total_tiles = v.total_tiles; a.skip_R = v.skip_R; a.dense = v.dense;
+        a.S = v.S; a.tiles_per_split = v.tiles_per_split;
+        a.seed = l2 ? seed + (last ? 2 * c.nq : 0) : nullptr;
         // (thresholds and counters of this level: written by launch_long_setup -- first level -- or by the previous level's
         //  launch_bound_prepare)
-        if (l2) hipLaunchKernelGGL((k_scan_long<DT_F16, 1>), dim3(a.S * a.G), dim3(LT_THREADS), lds, st, a);
-        else if (f16_mfma) hipLaunchKernelGGL(k_scan_long<DT_F16>, dim3(a.S * a.G), dim3(LT_THREADS), lds, st, a);
-        else hipLaunchKernelGGL(k_scan_long<DT_BF16>, dim3(a.S * a.G), dim3(LT_THREADS), lds, st, a);
+        hipLaunchKernelGGL(kernel, dim3(a.S * a.G), dim3(LT_THREADS), lds, c.st, a);
         rc = check_launch("k_scan_long");
         if (rc) return rc;
-        if (last) rc = launch_select_all(t, st);
+        if (last) rc = launch_select_all(t, c.st);
         else {
-            // bound from this level's kept scan scores -> the next level's thresholds; the final level of a disjoint
-            // schedule keeps this (the last sample's) rows that pass them
-            t.keep = (R > 0 && lv == 1) ? 1 : 0;
-            rc = launch_bound_prepare(t, st);
+            t.keep = v.keep;        // bound from this level's kept scan scores -> the next level's thresholds
+            rc = launch_bound_prepare(t, c.st);
         }
         if (rc) return rc;
     }
@@ -504,22 +519,21 @@ static int topk_long_impl(const char* what, const float* bias, const void* q, lo
 extern "C" int sss_ip_topk_long(const void* q, int64_t nq, const void* corpus, int dtype, const void* scan_image, int corpus_shift,
                                 float corpus_resid_norm, int64_t n, int d, int k, int64_t id_offset, float corpus_max_norm,
                                 float* D_out, int64_t* I_out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return topk_long_impl("ip_topk_long", nullptr, q, nq, corpus, dtype, scan_image, corpus_shift, corpus_resid_norm, n, d, k, id_offset,
-                          corpus_max_norm, D_out, I_out, status, workspace, workspace_bytes, st);
+    return topk_long_impl({.what = "ip_topk_long", .family = FAM_IP, .q = q, .nq = nq, .c_exact = corpus, .exact_dtype = dtype, .c_scan = scan_image,
+                           .scan_dtype = long_scan_dtype(dtype), .corpus_shift = corpus_shift, .corpus_resid = corpus_resid_norm, .n = n, .d = d, .k = k,
+                           .id_offset = id_offset, .corpus_max_norm = corpus_max_norm, .D_out = D_out, .I_out = I_out, .status = status, .ws = workspace,
+                           .ws_bytes = workspace_bytes, .st = static_cast<hipStream_t>(stream)});
 }
 
-// L2 top-k of long float32 rows (include/sss_l2_long.h): the buffers an inner-product call does not have are checked
-// here, the shape / image / k / workspace checks are topk_long_impl's own -- all of them before the first launch.
+// L2 top-k of long float32 rows (include/sss_l2_long.h)
 extern "C" int sss_l2_topk_long(const float* q, int64_t nq, const float* corpus, const void* scan_image, int corpus_shift,
                                 float corpus_resid_norm, const float* bias, int64_t n, int d, int k, int64_t id_offset,
                                 float corpus_max_norm, float* D_out, int64_t* I_out, int32_t* status, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!bias || (reinterpret_cast<uintptr_t>(bias) & 15)) { set_error("l2_topk_long: row bias missing or not 16-byte aligned"); return SSS_EINVAL; }
-    if (!q || !corpus || !D_out || !I_out || !status) { set_error("l2_topk_long: q, corpus, D_out, I_out and status are required"); return SSS_EINVAL; }
-    return topk_long_impl("l2_topk_long", bias, q, nq, corpus, DT_F32, scan_image, corpus_shift, corpus_resid_norm, n, d, k, id_offset, corpus_max_norm,
-                          D_out, I_out, status, workspace, workspace_bytes, st);
+    return topk_long_impl({.what = "l2_topk_long", .family = FAM_L2, .q = q, .nq = nq, .c_exact = corpus, .exact_dtype = DT_F32, .c_scan = scan_image,
+                           .scan_dtype = DT_F16, .corpus_shift = corpus_shift, .corpus_resid = corpus_resid_norm, .bias = bias, .n = n, .d = d, .k = k,
+                           .id_offset = id_offset, .corpus_max_norm = corpus_max_norm, .D_out = D_out, .I_out = I_out, .status = status, .ws = workspace,
+                           .ws_bytes = workspace_bytes, .st = static_cast<hipStream_t>(stream)});
 }
 
 }  // namespace sss
