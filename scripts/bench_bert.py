@@ -14,7 +14,11 @@ Prints one JSON line; per size, pool and dedup setting:
                     rows, walked in chunks of 8192 sequences: hipEvent median
   max_abs_diff      between the two results (a sanity check, not a parity test: tests/test_bert_encoder_gpu.py is that)
   rows, unique      packed token rows that reach the kernels, distinct sequences; gemm_flop what the rows' GEMMs need by
-                    arithmetic: 2 (4 e^2 + 2 e inter) per row and layer"""
+                    arithmetic: 2 (4 e^2 + 2 e inter) per row and layer
+--gemm f32,bf16 builds one encoder per GEMM path (text.BertNodeEncoder(gemm=...)) and times them ALTERNATING in one process,
+one forward of each in turn per repetition, after the same warm-ups (the style of bench_index_dtype.py); each gets a
+result record of its own ("gemm"), a profiler pass of its own, and max_abs_diff_to_f32, the largest difference between its
+output and the f32 encoder's."""
 import argparse
 import json
 import math
@@ -30,7 +34,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench_sparse import event_median_ms, kernel_medians_ms  # noqa: E402
 from sessionsimilaritysearch_amd.text import BertNodeEncoder, bert_pack_rows, unique_rows  # noqa: E402
 
-FAMILIES = ("k_linear_grouped", "k_seq_attention", "k_add_layernorm", "k_bert_embed", "k_segment_reduce")
+GEMM_FAMILY = {"f32": "k_linear_grouped", "bf16": "k_linear_grouped_bf16"}
+OTHER_FAMILIES = ("k_seq_attention", "k_add_layernorm", "k_bert_embed", "k_segment_reduce")
 TORCH_CHUNK = 8192
 LAYER = "encoder.layer.{}."
 
@@ -94,6 +99,21 @@ def make_batch(B, T, vocab, dup, seed):
     return ids[perm], tt[perm], am[perm], B - n_dup
 
 
+def alternating_event_medians_ms(fns, warmup, reps):
+    """{name: hipEvent median of fn()} with the functions run in turn: warm-ups of each, then one timed call of each per
+    repetition.  With one function this is bench_sparse.event_median_ms."""
+    for fn in fns.values():
+        for _ in range(warmup):
+            fn()
+    ts = {name: [] for name in fns}
+    for _ in range(reps):
+        for name, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); fn(); b.record(); b.synchronize()
+            ts[name].append(a.elapsed_time(b))
+    return {name: float(np.median(t)) for name, t in ts.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="3072,32768")
@@ -105,14 +125,18 @@ def main():
     ap.add_argument("--T", type=int, default=20)
     ap.add_argument("--dup", type=float, default=0.5)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--gemm", default="f32", help="f32, bf16 or both separated by a comma: timed alternating in one process")
     a = ap.parse_args()
+    gemms = a.gemm.split(",")
+    if not gemms or any(g not in GEMM_FAMILY for g in gemms) or len(set(gemms)) != len(gemms):
+        raise SystemExit(f"--gemm takes f32, bf16 or f32,bf16; got {a.gemm!r}")
     if not torch.cuda.is_available():
         raise SystemExit("bench_bert.py needs a HIP device; none is visible")
     dev = torch.device("cuda", 0)
     w = seeded_weights(1, a.vocab, a.hidden, a.inter, a.nlayers, 512, dev)
     per_row = a.nlayers * 2 * (4 * a.hidden * a.hidden + 2 * a.hidden * a.inter)
     out = {"vocab": a.vocab, "hidden": a.hidden, "heads": a.heads, "inter": a.inter, "nlayers": a.nlayers, "T": a.T, "dup": a.dup,
-           "reps": a.reps, "launches_per_chunk": 7 * a.nlayers + 2, "results": []}
+           "reps": a.reps, "gemm": gemms, "launches_per_chunk": 7 * a.nlayers + 2, "results": []}
     for B in (int(s) for s in a.sizes.split(",")):
         ids, tt, am, distinct = make_batch(B, a.T, a.vocab, a.dup, B)
         d_ids, d_tt, d_am = (torch.from_numpy(x).to(dev) for x in (ids, tt, am))
@@ -120,33 +144,39 @@ def main():
             base = lambda: torch_forward(w, a.heads, a.nlayers, d_ids, d_tt, d_am, pool)
             torch_ms = None
             for dedup in (True, False):
-                enc = BertNodeEncoder(w, a.heads, pool=pool, device=dev, dedup=dedup)
-                ours = lambda: enc(ids, tt, am)
+                encs = {g: BertNodeEncoder(w, a.heads, pool=pool, device=dev, dedup=dedup, gemm=g) for g in gemms}
+                ours = {g: (lambda enc=enc: enc(ids, tt, am)) for g, enc in encs.items()}
 
                 def host():
                     u = unique_rows(ids, tt, am)[0] if dedup else slice(None)
                     return bert_pack_rows(ids[u], tt[u], am[u], pool)
                 rows = len(host().rows.tok)
-                r = {"B": B, "pool": pool, "dedup": dedup, "unique": distinct if dedup else B, "rows": rows, "gemm_flop": rows * per_row,
-                     "max_abs_diff": float((ours() - base()).abs().max())}
                 ts = []
                 for _ in range(a.reps):
                     t0 = time.perf_counter()
                     host()
                     ts.append((time.perf_counter() - t0) * 1e3)
-                r["host_ms"] = round(float(np.median(ts)), 3)
-                r["forward_ms"] = round(event_median_ms(ours, 2, a.reps), 3)
+                host_ms = round(float(np.median(ts)), 3)
+                ref, exact = base(), (ours["f32"]() if "f32" in ours else None)
+                forward_ms = alternating_event_medians_ms(ours, 2, a.reps)
                 if torch_ms is None:                                    # the restatement does not de-duplicate: once per pool
                     torch_ms = round(event_median_ms(base, 2, a.reps), 3)
-                r["torch_ms"] = torch_ms
-                r["speedup_over_torch"] = round(torch_ms / r["forward_ms"], 3)
-                kern = kernel_medians_ms(ours, 1, min(a.reps, 3))
-                if not all(kern.get(f) for f in FAMILIES):
-                    raise RuntimeError(f"encoder kernels not found in the profile: {sorted(kern)}")
-                r["kernels_ms"] = {f: round(kern[f], 4) for f in FAMILIES}
-                r["other_kernels_ms"] = round(sum(v for k, v in kern.items() if k not in FAMILIES), 4)
-                r["gemm_tflops"] = round(r["gemm_flop"] / (kern["k_linear_grouped"] * 1e-3) / 1e12, 2)
-                out["results"].append(r)
+                for g in gemms:
+                    got = ours[g]()
+                    r = {"B": B, "pool": pool, "dedup": dedup, "gemm": g, "unique": distinct if dedup else B, "rows": rows,
+                         "gemm_flop": rows * per_row, "max_abs_diff": float((got - ref).abs().max())}
+                    if exact is not None and g != "f32":
+                        r["max_abs_diff_to_f32"] = float((got - exact).abs().max())
+                    r["host_ms"], r["forward_ms"], r["torch_ms"] = host_ms, round(forward_ms[g], 3), torch_ms
+                    r["speedup_over_torch"] = round(torch_ms / r["forward_ms"], 3)
+                    kern = kernel_medians_ms(ours[g], 1, min(a.reps, 3))
+                    families = (GEMM_FAMILY[g],) + OTHER_FAMILIES
+                    if not all(kern.get(f) for f in families):
+                        raise RuntimeError(f"encoder kernels not found in the profile: {sorted(kern)}")
+                    r["kernels_ms"] = {f: round(kern[f], 4) for f in families}
+                    r["other_kernels_ms"] = round(sum(v for k, v in kern.items() if k not in families), 4)
+                    r["gemm_tflops"] = round(r["gemm_flop"] / (kern[GEMM_FAMILY[g]] * 1e-3) / 1e12, 2)
+                    out["results"].append(r)
     print(json.dumps(out))
 
 

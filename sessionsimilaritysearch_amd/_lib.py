@@ -1,7 +1,8 @@
 """ctypes binding of libsss.so, read from the C ABI's own declarations: the headers of include/ are the one place where
 an entry point's types and an argument struct's fields are written down (``HEADERS``, ``PARAMS`` and ``STRUCTS`` below
 are what the reader makes of them).  The headers of include/ext/ are read the same way into tables of their own
-(``EXT_HEADERS``, ``EXT_PARAMS``): families added since the listing of include/ was pinned; ``lib()`` binds both.
+(``EXT_HEADERS``, ``EXT_PARAMS``): families added since the listing of include/ was pinned; those of include/lowp/, the
+reduced-precision entry points, into ``LOWP_HEADERS`` and ``LOWP_PARAMS``; ``lib()`` binds all three.
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails, this
 module raises.  ``build()`` compiles the library in-tree with hipcc for gfx950.
@@ -91,6 +92,12 @@ EXT_HEADERS, EXT_PARAMS, _EXT_STRUCT_FIELDS = _read_include(EXT_INCLUDE)
 if _EXT_STRUCT_FIELDS or set(EXT_PARAMS) & set(PARAMS):
     raise ValueError(f"include/ext/ declares a struct or repeats an entry point of include/: "
                      f"{sorted(_EXT_STRUCT_FIELDS) + sorted(set(EXT_PARAMS) & set(PARAMS))}")
+# and for include/lowp/ (its entry points take the structs of include/ by pointer and declare none)
+LOWP_INCLUDE = os.path.join(INCLUDE, "lowp")
+LOWP_HEADERS, LOWP_PARAMS, _LOWP_STRUCT_FIELDS = _read_include(LOWP_INCLUDE)
+if _LOWP_STRUCT_FIELDS or set(LOWP_PARAMS) & (set(PARAMS) | set(EXT_PARAMS)):
+    raise ValueError(f"include/lowp/ declares a struct or repeats an entry point of include/ or include/ext/: "
+                     f"{sorted(_LOWP_STRUCT_FIELDS) + sorted(set(LOWP_PARAMS) & (set(PARAMS) | set(EXT_PARAMS)))}")
 
 
 def header_constant(path, name):
@@ -193,7 +200,7 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C "
                 "sessionsimilaritysearch_amd/csrc`). There is no CPU fallback.")
         h = ctypes.CDLL(LIB_PATH)
-        for table in (*HEADERS.values(), *EXT_HEADERS.values()):
+        for table in (*HEADERS.values(), *EXT_HEADERS.values(), *LOWP_HEADERS.values()):
             for name, (res, args) in table.items():
                 fn = getattr(h, name)      # AttributeError if the .so lacks a declared symbol
                 fn.restype, fn.argtypes = res, args

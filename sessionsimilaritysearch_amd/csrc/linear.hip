@@ -6,21 +6,11 @@
 //                       variants (variants.py) and the four GEMMs of a transformer layer (text.py)
 //   sss_linear          one problem of it;  sss_linear_grouped  the launch as the callers see it (include/sss.h)
 // Dense contractions run on v_mfma_f32_32x32x2_f32 (bit-exact f32 fma chains, the same rate as the f32 VALU peak).
-#include "sss_common.h"
+#include "linear_dev.h"
 
 namespace sss {
 
 constexpr int LT = 64;      // GEMM tile rows (X) and columns (W rows): see k_linear_grouped below
-
-// The kernel's argument: the callers' problems as they are (sss_linear_problem, include/sss.h), each followed by what the
-// launcher adds.  A slot is 128 bytes, so the scalar loads of a problem's fields stay aligned: four bare 120-byte problems
-// with the launcher's tables behind or before them measured 1 - 2 % slower on every shape, 3 - 4 % on the smallest.
-struct LinSlot {
-    sss_linear_problem p;
-    int tiles_m, tile_begin;           // filled by the launcher: the problem's column tiles, its first workgroup
-};
-static_assert(sizeof(LinSlot) == 128, "k_linear_grouped: one problem per 128 bytes of kernel argument");
-struct LinBatch { LinSlot s[4]; int nprob, K; };
 
 template <int KC>
 __global__ __launch_bounds__(256, 2) void k_linear_grouped(const LinBatch B) {
@@ -110,17 +100,7 @@ __global__ __launch_bounds__(256, 2) void k_linear_grouped(const LinBatch B) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const long row = row0 + wr * 32 + (j & 3) + 8 * (j >> 2) + 4 * h;
-            float v = acc[j] + bv;
-            if (act == 1) v = fmaxf(v, 0.f);
-            else if (act == 2) v = tanhf(v);
-            else if (act == 3) v = v > 0.f ? 1.f : v < 0.f ? -1.f : v;     // torch.sign (0 and NaN pass through)
-            else if (act == 4) v = tanhf(tanhf(v));
-            else if (act == 5) v = gelu_erf(v);                             // exact GELU: gelu(0) = 0, NaN passes through
-            if (post_s) {
-#pragma clang fp contract(off)                                               // multiply, round, add, round: no fused fma here
-                v = fmaxf(v * ps + pt, 0.f);                                // bn(x) in eval mode as scale / shift, then relu
-            }
-            if (row < N) Y[row * ldy + col] = v;
+            linear_epilogue(acc[j], bv, act, post_s, ps, pt, row, N, Y, ldy, col);
         }
     }
 }

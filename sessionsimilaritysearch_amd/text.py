@@ -18,8 +18,9 @@ THE TWO PADDING RULES.  The refere
   reach a kernel: a batch of short queries costs only its real tokens.
 
 Every arithmetic step runs in ``libsss.so``: ``sss_text_embed``, ``sss_seq_attention``, ``sss_add_layernorm``
-(include/sss_text.h), ``sss_linear_grouped`` for the four GEMMs of a layer and ``sss_segment_reduce`` for the pooling;
-torch owns memory only.  A layer is 7 launches, a forward ``7 * nlayers + 2`` per chunk of rows.
+(include/sss_text.h), ``sss_linear_grouped`` for the four GEMMs of a layer (``sss_linear_grouped_bf16`` of
+include/lowp/sss_linear_bf16.h under ``gemm="bf16"``) and ``sss_segment_reduce`` for the pooling; torch owns memory only.
+A layer is 7 launches, a forward ``7 * nlayers + 2`` per chunk of rows.
 
 The second half of the module is the deployed model's node text encoder, ``PretrainedQAEAEncoder``
 (``model/NodeEmbedding.py:100-125``): a BERT encoder without its pooling layer, a masked mean over the tokens and an
@@ -45,6 +46,8 @@ from ._lib import pad32 as _pad32
 
 MAX_LEN = 64                                 # rows per sequence sss_seq_attention takes: one lane per query row
 PAD_RULES = ("compute", "zero")
+GEMMS = ("f32", "bf16")                     # what the dense layers run on: sss_linear_grouped / sss_linear_grouped_bf16
+GEMM_WEIGHTS = ("in_w", "out_w", "l1_w", "l2_w")     # the keys of a folded layer that are a GEMM's weight
 
 TokenRows = namedtuple("TokenRows", "tok pos ptr key_ok T")
 TokenRows.__doc__ = """Packed token rows: ``tok`` int64 [n] and ``pos`` int32 [n] per row, ``ptr`` int32 [B + 1] the row range of
@@ -61,6 +64,11 @@ def _host(a):
 def _check_rule(pad_rule):
     if pad_rule not in PAD_RULES:
         raise ValueError(f"pad_rule must be 'compute' or 'zero', got {pad_rule!r}")
+
+
+def _check_gemm(gemm):
+    if gemm not in GEMMS:
+        raise ValueError(f"gemm must be 'f32' or 'bf16', got {gemm!r}")
 
 
 def pack_tokens(src, mask, pad_rule="compute", ntoken=None):
@@ -175,12 +183,32 @@ def split_chunks(ptr, chunk_rows):
 
 class _PackedEncoder:
     """What the two encoders on packed token rows share: the launches of a post-norm transformer layer.  A subclass sets
-    ``device``, ``eps``, ``ninp``, ``nhead`` and ``layers`` (the per-layer dicts of ``text_fold_weights``)."""
+    ``device``, ``gemm``, ``eps``, ``ninp``, ``nhead`` and ``layers`` (the per-layer dicts of ``text_fold_weights``, uploaded
+    with ``_upload_layers``)."""
+
+    def _gemm_weight(self, t):
+        """A GEMM's weight on the device as ``_linear`` takes it: float32, or under ``gemm="bf16"`` its bfloat16 rounding
+        (``sss_f32_to_bf16``, round to nearest even), converted once; the float32 upload is not kept."""
+        import torch
+        from . import _lib
+        from ._device import upload_f32
+        w = upload_f32(t, self.device)
+        if self.gemm == "f32":
+            return w
+        wb = torch.empty(w.shape, dtype=torch.bfloat16, device=self.device)       # K is a multiple of 32: whole groups of 8
+        _lib.check(_lib.lib().sss_f32_to_bf16(w.data_ptr(), w.numel(), wb.data_ptr(), _lib.stream_ptr(self.device)), "sss_f32_to_bf16")
+        return wb
+
+    def _upload_layers(self, layers):
+        from ._device import upload_f32
+        return [{n: self._gemm_weight(v) if n in GEMM_WEIGHTS else upload_f32(v, self.device) for n, v in lay.items()} for lay in layers]
 
     def _linear(self, x, w, b, y, n, act=0):
+        """The one place that picks a GEMM's entry point: every dense layer of the instance goes the same way."""
         from . import _lib
         arr = (_lib.LinearProblem * 1)(_lib.linear_problem(x, w, b, y, n, w.shape[0], act))
-        _lib.check(_lib.lib().sss_linear_grouped(arr, 1, w.shape[1], _lib.stream_ptr(self.device)), "sss_linear_grouped")
+        name = "sss_linear_grouped" if self.gemm == "f32" else "sss_linear_grouped_bf16"
+        _lib.check(getattr(_lib.lib(), name)(arr, 1, w.shape[1], _lib.stream_ptr(self.device)), name)
 
     def _add_layernorm(self, x, res, gamma, beta, n):
         from . import _lib
@@ -253,11 +281,16 @@ class NodeTextTransformer(_PackedEncoder):
     nodes never needs ``rows x nhid`` floats at once.  The default, 131072 rows, keeps the widest buffer (``rows x nhid``)
     at 0.42 GB at the reference's ``nhid = 800`` and all five row buffers together near 1.1 GB.
 
+    ``gemm="bf16"`` (default ``"f32"``, exact): the four GEMMs of a layer round both operands to bfloat16 and sum in float32
+    on the bf16 matrix cores; per GEMM ``|v - (s + bias)| <= K 2^-23 sum|x^ w^| + 2^-23 |s + bias|`` around the exact sum ``s``
+    of the rounded operands (include/lowp/sss_linear_bf16.h; bf16 subnormals not covered), no pointwise bound per forward.
+
     Limits: ``ninp % 4 == 0``, ``ninp <= 1024``, head width ``ninp / nhead <= 64``, ``T <= 64``."""
 
-    def __init__(self, weights, nhead, pad_rule="compute", device=None, chunk_rows=131072, eps=1e-5):
+    def __init__(self, weights, nhead, pad_rule="compute", device=None, chunk_rows=131072, eps=1e-5, gemm="f32"):
         from ._device import model_device, upload_f32
         _check_rule(pad_rule)
+        _check_gemm(gemm)
         f = text_fold_weights(weights, nhead)                                # raises ValueError when nhead does not divide ninp
         e = f["ninp"]
         if e % 4 or e > 1024 or e // f["nhead"] > 64:
@@ -267,10 +300,10 @@ class NodeTextTransformer(_PackedEncoder):
         self.pad_rule, self.chunk_rows, self.eps = pad_rule, int(chunk_rows), float(eps)
         self.ninp, self.nhead, self.nhid, self.nlayers = e, f["nhead"], f["nhid"], f["nlayers"]
         self.ntoken, self.scale = int(f["table"].shape[0]), f["scale"]
-        self.device = model_device(device)
+        self.device, self.gemm = model_device(device), gemm
         d = lambda t: upload_f32(t, self.device)
         self.table, self.pe = d(f["table"]), d(f["pe"])
-        self.layers = [{n: d(v) for n, v in lay.items()} for lay in f["layers"]]
+        self.layers = self._upload_layers(f["layers"])
 
     @classmethod
     def from_torch(cls, module, **kw):
@@ -408,12 +441,18 @@ class BertNodeEncoder(_PackedEncoder):
     at bert-base) at 0.40 GB and the five row buffers together (``rows x 7680`` floats) at 1.0 GB; the result does not
     depend on it.
 
+    ``gemm="bf16"`` (default ``"f32"``, exact): every GEMM, the ``lin`` head included, rounds both operands to bfloat16 and sums
+    in float32 on the bf16 matrix cores; only the bf16 copy of those weights is kept.  Per GEMM ``|v - (s + bias)| <=
+    K 2^-23 sum|x^ w^| + 2^-23 |s + bias|`` around the exact sum ``s`` of the rounded operands (include/lowp/sss_linear_bf16.h;
+    bf16 subnormals not covered); no pointwise bound per forward.
+
     Limits: ``e % 4 == 0``, ``e <= 1024``, head width ``e / num_heads <= 64``, ``T <= 64`` and ``<= max_position_embeddings``.
-    Not here: tokenisation, ELECTRA's ``embeddings_project``, relative position embeddings, a reduced-precision GEMM."""
+    Not here: tokenisation, ELECTRA's ``embeddings_project``, relative position embeddings."""
 
     def __init__(self, weights, num_heads, pool="masked", eps=1e-12, device=None, chunk_rows=32768, dedup=True, hidden_act="gelu",
-                 position_embedding_type="absolute"):
+                 position_embedding_type="absolute", gemm="f32"):
         from ._device import model_device, upload_f32
+        _check_gemm(gemm)
         if pool not in BERT_POOLS:
             raise ValueError(f"pool must be 'masked' or 'mean', got {pool!r}")
         if hidden_act != "gelu":
@@ -434,11 +473,11 @@ class BertNodeEncoder(_PackedEncoder):
         self.pool, self.chunk_rows, self.eps, self.dedup = pool, int(chunk_rows), float(eps), bool(dedup)
         self.ninp, self.nhead, self.inter, self.nlayers = e, f["heads"], f["inter"], f["nlayers"]
         self.n_word, self.n_pos, self.n_type = int(f["word"].shape[0]), int(f["pos"].shape[0]), int(f["type"].shape[0])
-        self.device = model_device(device)
+        self.device, self.gemm = model_device(device), gemm
         d = lambda t: upload_f32(t, self.device)
         self.word, self.pos, self.type, self.emb_g, self.emb_b = (d(f[n]) for n in ("word", "pos", "type", "emb_g", "emb_b"))
-        self.layers = [{n: d(v) for n, v in lay.items()} for lay in f["layers"]]
-        self.lin_w, self.lin_b = (None, None) if f["lin_w"] is None else (d(f["lin_w"]), d(f["lin_b"]))
+        self.layers = self._upload_layers(f["layers"])
+        self.lin_w, self.lin_b = (None, None) if f["lin_w"] is None else (self._gemm_weight(f["lin_w"]), d(f["lin_b"]))
         self.nout = e if self.lin_w is None else int(self.lin_w.shape[0])
 
     @classmethod
