@@ -32,6 +32,10 @@ Drop-in surface of the reference's path:
   ShardedFlatIndex, ShardedBinaryIndex, ShardedSparseIndex, ShardedJaccardIndex, ShardedProductTypeIndex
                                                   (distributed.py: corpus row-sharded over RCCL)
   SessionBatch, build_batch, synthetic_actions    (sessions.py  <- sequence_to_graph + Batch.from_data_list, host side)
+  CatalogueHead, CatalogueLoss, get_next_product_asin_accuracy, get_all_product_asin_accuracy, get_next_product_asin_loss,
+  get_all_product_asin_loss                       (catalogue.py <- train_subsession_embedding.py:271-339 and
+                                                                  train_session_embedding.py:87-: the model's own item
+                                                                  prediction over the catalogue and its validation loss)
 """
 from ._lib import SssError, build, exported_symbols, lib  # noqa: F401
 
@@ -54,6 +58,9 @@ __all__ += list(_TEXT)
 _STRINGS = ("StringTable", "StringSequences", "SequenceParts", "query_sequences", "title_sequences", "sequence_parts",
             "seq_pair_scores", "seq_query_metric", "get_query_metric")
 __all__ += list(_STRINGS)
+_CATALOGUE = ("CatalogueHead", "CatalogueLoss", "get_next_product_asin_accuracy", "get_all_product_asin_accuracy",
+              "get_next_product_asin_loss", "get_all_product_asin_loss")
+__all__ += list(_CATALOGUE)
 
 
 def __getattr__(name):
@@ -82,4 +89,7 @@ def __getattr__(name):
     if name in _STRINGS:                                 # the string metrics of a result: lazily, for the same reason
         from . import strings
         return getattr(strings, name)
+    if name in _CATALOGUE:                               # the catalogue heads: lazily, for the same reason
+        from . import catalogue
+        return getattr(catalogue, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

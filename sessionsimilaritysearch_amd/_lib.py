@@ -2,7 +2,8 @@
 an entry point's types and an argument struct's fields are written down (``HEADERS``, ``PARAMS`` and ``STRUCTS`` below
 are what the reader makes of them).  The headers of include/ext/ are read the same way into tables of their own
 (``EXT_HEADERS``, ``EXT_PARAMS``): families added since the listing of include/ was pinned; those of include/lowp/, the
-reduced-precision entry points, into ``LOWP_HEADERS`` and ``LOWP_PARAMS``; ``lib()`` binds all three.
+reduced-precision entry points, into ``LOWP_HEADERS`` and ``LOWP_PARAMS``; those of include/heads/, the model's catalogue
+heads, into ``HEADS_HEADERS`` and ``HEADS_PARAMS``; ``lib()`` binds all four.
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails, this
 module raises.  ``build()`` compiles the library in-tree with hipcc for gfx950.
@@ -13,7 +14,7 @@ import ctypes
 import os
 import re
 import subprocess
-from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsss.so")
@@ -24,7 +25,8 @@ _lib = None
 
 # ---------------------------------------------------------------------------------------------- the header reader
 # The headers are plain C in one style: no macros in declarations, these scalar types, and everything else a pointer.
-_SCALARS = {"int": c_int, "int32_t": c_int32, "int64_t": c_int64, "size_t": c_size_t, "float": c_float, "double": c_double}
+_SCALARS = {"int": c_int, "int32_t": c_int32, "int64_t": c_int64, "size_t": c_size_t, "float": c_float, "double": c_double,
+            "uint32_t": c_uint32, "uint64_t": c_uint64}
 _DECLARATOR = re.compile(r"\s*(?:const\s+)?(\w+)\s*(\*?)\s*(\w+)\s*(?:\[(\d+)\])?\s*")
 _STRUCT = re.compile(r"typedef\s+struct\s*\{(.*?)\}\s*(sss_\w+)\s*;", re.S)
 _FUNCTION = re.compile(r"\b((?:const\s+)?\w+\s*\*?)\s*\b(sss_\w+)\s*\(([^()]*)\)\s*;")
@@ -98,6 +100,12 @@ LOWP_HEADERS, LOWP_PARAMS, _LOWP_STRUCT_FIELDS = _read_include(LOWP_INCLUDE)
 if _LOWP_STRUCT_FIELDS or set(LOWP_PARAMS) & (set(PARAMS) | set(EXT_PARAMS)):
     raise ValueError(f"include/lowp/ declares a struct or repeats an entry point of include/ or include/ext/: "
                      f"{sorted(_LOWP_STRUCT_FIELDS) + sorted(set(LOWP_PARAMS) & (set(PARAMS) | set(EXT_PARAMS)))}")
+# and for include/heads/ (sss_catalogue.h: no struct)
+HEADS_INCLUDE = os.path.join(INCLUDE, "heads")
+HEADS_HEADERS, HEADS_PARAMS, _HEADS_STRUCT_FIELDS = _read_include(HEADS_INCLUDE)
+if _HEADS_STRUCT_FIELDS or set(HEADS_PARAMS) & (set(PARAMS) | set(EXT_PARAMS) | set(LOWP_PARAMS)):
+    raise ValueError(f"include/heads/ declares a struct or repeats an entry point of include/, include/ext/ or include/lowp/: "
+                     f"{sorted(_HEADS_STRUCT_FIELDS) + sorted(set(HEADS_PARAMS) & (set(PARAMS) | set(EXT_PARAMS) | set(LOWP_PARAMS)))}")
 
 
 def header_constant(path, name):
@@ -107,6 +115,15 @@ def header_constant(path, name):
     if not m:
         raise ValueError(f"include/{path} does not define {name} as an integer")
     return int(m.group(1))
+
+
+def header_float(path, name):
+    """The float32 value a header ``#define``s ``name`` as, written as a hexadecimal float literal with an ``f`` suffix."""
+    with open(os.path.join(INCLUDE, path)) as f:
+        m = re.search(rf"^[ \t]*#[ \t]*define[ \t]+{name}[ \t]+(-?0x[0-9a-fA-F.]+p[-+]?\d+)f\b", f.read(), flags=re.M)
+    if not m:
+        raise ValueError(f"include/{path} does not define {name} as a hexadecimal float32 literal")
+    return float.fromhex(m.group(1))
 
 
 def _c_struct(name):
@@ -200,7 +217,7 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C "
                 "sessionsimilaritysearch_amd/csrc`). There is no CPU fallback.")
         h = ctypes.CDLL(LIB_PATH)
-        for table in (*HEADERS.values(), *EXT_HEADERS.values(), *LOWP_HEADERS.values()):
+        for table in (*HEADERS.values(), *EXT_HEADERS.values(), *LOWP_HEADERS.values(), *HEADS_HEADERS.values()):
             for name, (res, args) in table.items():
                 fn = getattr(h, name)      # AttributeError if the .so lacks a declared symbol
                 fn.restype, fn.argtypes = res, args
