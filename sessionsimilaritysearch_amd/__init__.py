@@ -36,6 +36,8 @@ Drop-in surface of the reference's path:
   get_all_product_asin_loss                       (catalogue.py <- train_subsession_embedding.py:271-339 and
                                                                   train_session_embedding.py:87-: the model's own item
                                                                   prediction over the catalogue and its validation loss)
+  WordPieceTokenizer, TokenTable, Tokens          (wordpiece.py <- util_amazon_filtered.py:19-20, 120-121: the BERT tokenizer
+                                                                  calls of sequence_to_graph, over a StringTable)
 """
 from ._lib import SssError, build, exported_symbols, lib  # noqa: F401
 
@@ -61,6 +63,8 @@ __all__ += list(_STRINGS)
 _CATALOGUE = ("CatalogueHead", "CatalogueLoss", "get_next_product_asin_accuracy", "get_all_product_asin_accuracy",
               "get_next_product_asin_loss", "get_all_product_asin_loss")
 __all__ += list(_CATALOGUE)
+_WORDPIECE = ("WordPieceTokenizer", "TokenTable", "Tokens")
+__all__ += list(_WORDPIECE)
 
 
 def __getattr__(name):
@@ -92,4 +96,7 @@ def __getattr__(name):
     if name in _CATALOGUE:                               # the catalogue heads: lazily, for the same reason
         from . import catalogue
         return getattr(catalogue, name)
+    if name in _WORDPIECE:                               # the tokenizer: lazily, for the same reason
+        from . import wordpiece
+        return getattr(wordpiece, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

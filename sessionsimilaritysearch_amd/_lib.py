@@ -3,7 +3,8 @@ an entry point's types and an argument struct's fields are written down (``HEADE
 are what the reader makes of them).  The headers of include/ext/ are read the same way into tables of their own
 (``EXT_HEADERS``, ``EXT_PARAMS``): families added since the listing of include/ was pinned; those of include/lowp/, the
 reduced-precision entry points, into ``LOWP_HEADERS`` and ``LOWP_PARAMS``; those of include/heads/, the model's catalogue
-heads, into ``HEADS_HEADERS`` and ``HEADS_PARAMS``; ``lib()`` binds all four.
+heads, into ``HEADS_HEADERS`` and ``HEADS_PARAMS``; those of include/tok/, the tokenizer, into ``TOK_HEADERS`` and
+``TOK_PARAMS``; ``lib()`` binds all five.
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails, this
 module raises.  ``build()`` compiles the library in-tree with hipcc for gfx950.
@@ -106,6 +107,13 @@ HEADS_HEADERS, HEADS_PARAMS, _HEADS_STRUCT_FIELDS = _read_include(HEADS_INCLUDE)
 if _HEADS_STRUCT_FIELDS or set(HEADS_PARAMS) & (set(PARAMS) | set(EXT_PARAMS) | set(LOWP_PARAMS)):
     raise ValueError(f"include/heads/ declares a struct or repeats an entry point of include/, include/ext/ or include/lowp/: "
                      f"{sorted(_HEADS_STRUCT_FIELDS) + sorted(set(HEADS_PARAMS) & (set(PARAMS) | set(EXT_PARAMS) | set(LOWP_PARAMS)))}")
+# and for include/tok/ (sss_wordpiece.h: no struct)
+TOK_INCLUDE = os.path.join(INCLUDE, "tok")
+TOK_HEADERS, TOK_PARAMS, _TOK_STRUCT_FIELDS = _read_include(TOK_INCLUDE)
+_OLDER_PARAMS = set(PARAMS) | set(EXT_PARAMS) | set(LOWP_PARAMS) | set(HEADS_PARAMS)
+if _TOK_STRUCT_FIELDS or set(TOK_PARAMS) & _OLDER_PARAMS:
+    raise ValueError(f"include/tok/ declares a struct or repeats an entry point of an older include directory: "
+                     f"{sorted(_TOK_STRUCT_FIELDS) + sorted(set(TOK_PARAMS) & _OLDER_PARAMS)}")
 
 
 def header_constant(path, name):
@@ -217,7 +225,8 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C "
                 "sessionsimilaritysearch_amd/csrc`). There is no CPU fallback.")
         h = ctypes.CDLL(LIB_PATH)
-        for table in (*HEADERS.values(), *EXT_HEADERS.values(), *LOWP_HEADERS.values(), *HEADS_HEADERS.values()):
+        for table in (*HEADERS.values(), *EXT_HEADERS.values(), *LOWP_HEADERS.values(), *HEADS_HEADERS.values(),
+                      *TOK_HEADERS.values()):
             for name, (res, args) in table.items():
                 fn = getattr(h, name)      # AttributeError if the .so lacks a declared symbol
                 fn.restype, fn.argtypes = res, args

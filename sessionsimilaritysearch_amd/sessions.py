@@ -20,8 +20,8 @@ offset form the encoder reads:
 * ``data['query'].batch``        int64 [Nq]
 * ``data.edge_index_dict``       COO int64 [2, E] per edge type, batch-global node ids
 
-Text tokenisation (the reference's BERT tokenizer calls) is out of scope: query nodes carry
-a feature-row id instead of token ids, see DESIGN.md.
+Query nodes carry a string id instead of token ids: the reference's BERT tokenizer calls are
+``wordpiece.TokenTable.rows(data['query'].x)`` over a table encoded once.
 
 Deliberate, documented difference from the reference: distinct items are ordered by *first
 occurrence* in the session.  The reference uses ``list(set(...))`` (hash order,

@@ -447,7 +447,8 @@ class BertNodeEncoder(_PackedEncoder):
     bf16 subnormals not covered); no pointwise bound per forward.
 
     Limits: ``e % 4 == 0``, ``e <= 1024``, head width ``e / num_heads <= 64``, ``T <= 64`` and ``<= max_position_embeddings``.
-    Not here: tokenisation, ELECTRA's ``embeddings_project``, relative position embeddings."""
+    The three inputs are what ``wordpiece.WordPieceTokenizer`` returns (``enc(*tokens)``).  Not here: ELECTRA's
+    ``embeddings_project``, relative position embeddings."""
 
     def __init__(self, weights, num_heads, pool="masked", eps=1e-12, device=None, chunk_rows=32768, dedup=True, hidden_act="gelu",
                  position_embedding_type="absolute", gemm="f32"):
